@@ -8,9 +8,11 @@ on synthetic 256x256 batches, one process per GPU.
 
 A "step" is one full iteration: 3 forward + 3 backward passes over B images each (B source + B target images),
 5 SGD updates, pseudo-labels / losses / PCK bookkeeping on the device.  value = unique images / s over the
-whole job = 2*B*N / t_iter.  Prints ONE JSON line on rank 0 (contract in the task statement):
-metric/value/unit, roofline (MFMA conv family, timed live with HIP events in a second pass over the same
-steps) and cpu_baseline (the CPU oracle = op-for-op restatement of the reference, timed on the host cores).
+whole job = 2*B*N / t_iter.  Prints ONE JSON line on rank 0: metric / value / unit / ms_per_step of the K timed steps.
+A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR), the line.
+--full adds the diagnostics, each a pass of its own after the timed steps: the forward-only eval path, the
+roofline (MFMA conv family, timed live with HIP events in a second pass over the same steps; --launch-log) and
+cpu_baseline (the CPU oracle = op-for-op restatement of the reference, timed on the host cores).
 """
 import argparse
 import json
@@ -48,8 +50,13 @@ def parse():
     ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying HIP graphs')
     ap.add_argument('--graph', action='store_true', help='replay HIP graphs also with more than one rank (default there: eager; '
                     'at B=64 the iteration is GPU-bound either way: 44.72 ms replayed vs 44.75 ms eager)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also run the diagnostics: eval-path throughput, roofline '
+                    'pass, CPU baseline (each can be left out again with --no-eval / --no-roofline / --no-cpu-baseline)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write what the last timed step returned (DAStep.out: losses, '
+                    'heat-maps, PCK distances) as DIR/<name>.npy in float32, at most 64 MB in all: a larger array is written as a '
+                    'fixed, seeded sample of its elements (rank 0)')
     ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--launch-log', default=None, metavar='PATH', help='after the roofline pass run ONE more eager iteration with every logged '
+    ap.add_argument('--launch-log', default=None, metavar='PATH', help='with --full: after the roofline pass run ONE more eager iteration with every logged '
                     'kernel family bracketed by events (conv MFMA, BatchNorm, slab reductions) and write the per-launch list as JSON: '
                     'the input of profiles/insitu_table.py')
     ap.add_argument('--no-eval', action='store_true', help='skip the forward-only (test.py path) section: profiler runs that should see training iterations only')
@@ -58,7 +65,12 @@ def parse():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help='nccl = RCCL over xGMI (default); gloo only to rehearse the '
                     'multi-process path on one GPU (all ranks on device 0)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.launch_log and not args.full:
+        ap.error('--launch-log is part of the roofline pass: it needs --full')
+    return args
 
 
 def log(*a):
@@ -139,6 +151,25 @@ def insitu_top(launches, iters, overhead_us, mfma_tflops, hbm_tbps=6.3, k=10):
     out.sort(key=lambda r: -r['gap_ms_per_step'])
     return {'floor': 'max(FLOP / %.0f TFLOP/s, bytes / %.1f TB/s, 5 us)' % (mfma_tflops, hbm_tbps), 'layers': len(out),
             'table_ms_per_step': round(total * 1e-3, 3), 'top': out[:k]}
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: all files together
+
+
+def dump_outputs(out, path):
+    """The tensors of DAStep.out (what step.run returns) -> path/<name>.npy in float32.  Each gets an equal share of DUMP_BYTES;
+    one larger than its share is written flat, as its elements at a sorted sample of indices drawn with a fixed seed, so that
+    two runs or two builds with the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach() for k, v in sorted(out.items()) if torch.is_tensor(v)}
+    cap = (DUMP_BYTES // len(arrs) - 256) // 4          # elements per file (256 bytes left for the .npy header)
+    for k, v in arrs.items():
+        if v.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), cap, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(path, k + '.npy'), v.float().cpu().numpy())
+    return sorted(arrs)
 
 
 def main():
@@ -245,10 +276,13 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     log('timed region done: %.2f ms/step' % ms_per_step)
     losses = {k: float(step.out[k]) for k in ('loss_s', 'loss_gf', 'loss_gt')}
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(step.out, args.dump_outputs)
+        log('outputs of the last timed step written to %s: %s' % (args.dump_outputs, ', '.join(names)))
 
     # ---- forward-only throughput of the test.py path (eval-mode BatchNorm, main head only, arg-max decode), SURVEY 8(d)
     eval_ms = None
-    if not args.no_eval:
+    if args.full and not args.no_eval:
         model.eval()
         from utils.keypoint_detection import get_max_preds_device
         from mi355.infer import GraphedForward
@@ -269,7 +303,8 @@ def main():
     # ---- roofline of the dominant kernel family (MFMA implicit-GEMM conv: gather + wgrad kernels), rank 0:
     # the same K steps again, eagerly, every conv launch bracketed by hipEvents on its stream.
     roof = None
-    if not args.no_roofline:
+    do_roof = args.full and not args.no_roofline
+    if do_roof:
         # every rank runs these steps (they contain the gradient all-reduces); rank 0's events are the ones reported
         step.graphs = None
         n_prof = min(args.steps, 5)
@@ -287,7 +322,7 @@ def main():
             torch.cuda.synchronize()
         ops.prof_enable(False)
         log('roofline pass: host needs %.0f ms to enqueue one eager iteration' % host_ms)
-    if not args.no_roofline and rank == 0:
+    if do_roof and rank == 0:
         ms, launches, flops, abytes = ops.prof_read()
         log('roofline pass done')
         # executed -> algorithmic FLOPs of the 3-channel stem (K = 147): it runs as a 4x4 conv over the 2x2 space-to-depth image
@@ -377,7 +412,7 @@ def main():
                 if 'conv_mfma' in fam and 'traffic_over_algorithmic' in fam['conv_mfma']:
                     roof['traffic_over_algorithmic'] = fam['conv_mfma']['traffic_over_algorithmic']
             res['roofline'] = roof
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 res['cpu_baseline'] = cpu_baseline(args.arch, S, args.cpu_baseline_batch, args.cpu_baseline_iters)
             except IndexError:

@@ -1,4 +1,4 @@
-"""In-situ layer table: joins the library's per-launch log (bench.py --launch-log: label, algorithmic FLOPs / bytes of every conv-family,
+"""In-situ layer table: joins the library's per-launch log (bench.py --full --launch-log: label, algorithmic FLOPs / bytes of every conv-family,
 BatchNorm and slab-reduce launch of ONE iteration, in launch order) with a rocprofv3 kernel trace of graph-replayed iterations of the
 same configuration (kernel durations in situ, no event overhead).  Launch j of a family in the log is launch j of that family in
 every traced iteration: the iteration is a fixed sequence of launches.
