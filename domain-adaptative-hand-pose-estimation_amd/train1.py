@@ -2,7 +2,8 @@
 """Domain-adaptive hand-pose training on the MI355X kernels — same command line, log / checkpoint layout and
 training schedule as the reference's ``train1.py`` (main :37-275, pretrain :278-325, train :328-492,
 validate :495-536, CLI :591-675).  Additive flags: ``--synthetic`` (seeded synthetic data instead of the
-out-of-scope CPU dataset layer), ``--dtype {bf16,f32}``, ``--no-graph``.
+out-of-scope CPU dataset layer), ``--dtype {bf16,f32}``, ``--no-graph``, ``--device-augment`` (the training
+augmentation chain and its labels on the GPU).
 
     python train1.py data/H3D -t Hand3DStudio --synthetic -a resnet50 -b 64
 
@@ -44,7 +45,7 @@ from mi355.optim import FusedSGD
 from uda.model.loss import JointsKLLoss
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
 from uda.model.regda_7 import PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
-from utils.data import ForeverDataIterator, DevicePrefetcher
+from utils.data import ForeverDataIterator, DevicePrefetcher, DeviceAugmentIterator, ragged_collate
 from utils.keypoint_detection import accuracy
 from utils.logger import CompleteLogger
 from utils.meter import AverageMeter, ProgressMeter, AverageMeterDict
@@ -98,8 +99,11 @@ def build_datasets(args):
     import uda.dataset as datasets                   # RHD / H3D / STB readers + key-point aware augmentation (PIL + numpy)
     import uda.dataset.keypoint_detection as T
     normalize = T.Normalize([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])
-    train_tf = T.Compose([T.RandomRotation(args.rotation), T.RandomResizedCrop(size=args.image_size, scale=args.resize_scale),
-                          T.ColorJitter(brightness=0.25, contrast=0.25, saturation=0.25), T.GaussianBlur(), T.ToTensor(), normalize])
+    if args.device_augment:     # same parameters, drawn on the host; the pixel work and the labels run on the GPU
+        train_tf = T.DeviceAugment(args.rotation, args.image_size, args.resize_scale)
+    else:
+        train_tf = T.Compose([T.RandomRotation(args.rotation), T.RandomResizedCrop(size=args.image_size, scale=args.resize_scale),
+                              T.ColorJitter(brightness=0.25, contrast=0.25, saturation=0.25), T.GaussianBlur(), T.ToTensor(), normalize])
     val_tf = T.Compose([T.Resize(args.image_size), T.ToTensor(), normalize])
     src, tgt = datasets.__dict__[args.source], datasets.__dict__[args.target]
     kw = dict(image_size=image_size, heatmap_size=heatmap_size)
@@ -110,12 +114,15 @@ def build_datasets(args):
 def make_loader(ds, args, train):
     """train: this rank's shard (reshuffled every pass, ForeverDataIterator advances the sampler epoch); validation: the
     strided shard rank::WORLD without padding, so that the counts summed over ranks are exactly the data set's."""
+    # --device-augment: the training sets yield un-augmented ragged sources, packed per batch (utils.data.ragged_collate)
+    collate = ragged_collate if train and getattr(args, 'device_augment', False) and not args.synthetic else None
     if WORLD == 1:
         return DataLoader(ds, batch_size=args.batch_size, shuffle=train, num_workers=args.workers if train else 0,
-                          pin_memory=True, drop_last=train)
+                          pin_memory=True, drop_last=train, collate_fn=collate)
     if train:
         sampler = DistributedSampler(ds, num_replicas=WORLD, rank=RANK, shuffle=True, seed=args.seed or 0, drop_last=True)
-        return DataLoader(ds, batch_size=args.batch_size, sampler=sampler, num_workers=args.workers, pin_memory=True, drop_last=True)
+        return DataLoader(ds, batch_size=args.batch_size, sampler=sampler, num_workers=args.workers, pin_memory=True, drop_last=True,
+                          collate_fn=collate)
     return DataLoader(ds, batch_size=args.batch_size, sampler=list(range(RANK, len(ds), WORLD)), num_workers=0, pin_memory=True)
 
 
@@ -141,8 +148,13 @@ def main(args):
     print("Source train:", len(train_source_loader)); print("Target train:", len(train_target_loader))
     print("Source test:", len(val_source_loader)); print("Target test:", len(val_target_loader))
     train_source_iter, train_target_iter = ForeverDataIterator(train_source_loader), ForeverDataIterator(train_target_loader)
-    # host -> HBM copies of the next batch overlap the current step (pinned, double-buffered, side stream)
-    train_source_iter, train_target_iter = DevicePrefetcher(train_source_iter, device), DevicePrefetcher(train_target_iter, device)
+    if args.device_augment and not args.synthetic:
+        # packed sources -> HBM, augmentation and heat-map labels on the GPU (mi355.augment, utils.labels)
+        dev_aug = lambda it: DeviceAugmentIterator(it, device, args.image_size, args.heatmap_size)
+        train_source_iter, train_target_iter = dev_aug(train_source_iter), dev_aug(train_target_iter)
+    else:
+        # host -> HBM copies of the next batch overlap the current step (pinned, double-buffered, side stream)
+        train_source_iter, train_target_iter = DevicePrefetcher(train_source_iter, device), DevicePrefetcher(train_target_iter, device)
 
     # model (+ the frozen EMA copy the reference builds and checkpoints, train1.py:102-128)
     backbone = models.__dict__[args.arch](pretrained=True)
@@ -409,6 +421,9 @@ _OPTIONS = [
     (('--synthetic',), dict(action='store_true', help='seeded synthetic batches instead of the CPU dataset layer')),
     (('--dtype',), dict(default='bf16', choices=['bf16', 'f32', 'fp8'], help="compute dtype of activations / packed weights ('fp8': bf16 storage, fp8 operands in the K-heavy conv GEMMs)")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
+    (('--device-augment',), dict(action='store_true', help='run the training augmentation chain (rotate, resized crop, colour '
+                                  'jitter, blur, normalisation) and the heat-map labels on the GPU, bit-exact with the CPU chain; '
+                                  'the loader workers only decode, crop (RHD / STB) and draw the parameters')),
 ]
 
 

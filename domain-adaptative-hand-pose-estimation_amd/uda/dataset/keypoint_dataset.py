@@ -65,8 +65,11 @@ class Hand21KeypointDataset(KeypointDataset, ABC):
 
     # ---- shared by the three hand data sets
     def _labels(self, keypoint2d, visible):
-        """(target heat-maps, target weights) as torch tensors."""
+        """(target heat-maps, target weights) as torch tensors -- or, when the transform leaves the labels to the GPU
+        (keypoint_detection.DeviceAugment), (key points (K,2) float64, visibility (K,1) float32) for utils.labels."""
         import torch
+        if getattr(self.transforms, 'labels_on_device', False):
+            return torch.from_numpy(np.asarray(keypoint2d, dtype=np.float64)), torch.from_numpy(np.asarray(visible, dtype=np.float32))
         from .util import generate_target
         target, weight = generate_target(keypoint2d, visible, self.heatmap_size, self.sigma, self.image_size)
         return torch.from_numpy(target), torch.from_numpy(weight)

@@ -33,20 +33,30 @@ def _resize_pil(image, size, interpolation=BILINEAR):
 def resize(image, size, interpolation=BILINEAR, keypoint2d=None, intrinsic_matrix=None):
     width, height = image.size
     assert width == height, 'resize expects the square crops the datasets produce'
-    factor = float(size) / float(width)
     image = _resize_pil(image, size, interpolation)
+    keypoint2d, K = resize_labels(width, size, keypoint2d, intrinsic_matrix)
+    return image, keypoint2d, K
+
+
+def resize_labels(width, size, keypoint2d, intrinsic_matrix):
+    """Key points and camera matrix of a square `width` image resized to `size`."""
+    factor = float(size) / float(width)
     keypoint2d = np.array(keypoint2d, dtype=np.float64, copy=True) * factor
     K = np.array(intrinsic_matrix, dtype=np.float64, copy=True)
     K[0, 0] *= factor; K[0, 2] *= factor; K[1, 1] *= factor; K[1, 2] *= factor
-    return image, keypoint2d, K
+    return keypoint2d, K
 
 
 def crop(image, top, left, height, width, keypoint2d):
     image = image.crop((left, top, left + width, top + height))
+    return image, crop_keypoints(top, left, keypoint2d)
+
+
+def crop_keypoints(top, left, keypoint2d):
     keypoint2d = np.array(keypoint2d, dtype=np.float64, copy=True)
     keypoint2d[:, 0] -= left
     keypoint2d[:, 1] -= top
-    return image, keypoint2d
+    return keypoint2d
 
 
 def resized_crop(img, top, left, height, width, size, interpolation=BILINEAR, keypoint2d=None, intrinsic_matrix=None):
@@ -71,12 +81,15 @@ def hflip(image, keypoint2d):
 def rotate(image, angle, keypoint2d):
     """Counter-clockwise by `angle` degrees about the image centre (PIL convention), same canvas."""
     image = image.rotate(angle)
+    width, height = image.size
+    return image, rotate_keypoints(angle, width, height, keypoint2d)
+
+
+def rotate_keypoints(angle, width, height, keypoint2d):
     a = -np.deg2rad(angle)
     R = np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
-    width, height = image.size
     centre = np.array([width / 2, height / 2])
-    keypoint2d = (np.asarray(keypoint2d, dtype=np.float64) - centre) @ R.T + centre
-    return image, keypoint2d
+    return (np.asarray(keypoint2d, dtype=np.float64) - centre) @ R.T + centre
 
 
 def resize_pad(img, keypoint2d, size, interpolation=BILINEAR):
@@ -274,3 +287,55 @@ class RandomApply:
         for t in self.transforms:
             image, kwargs = t(image, **kwargs)
         return image, kwargs
+
+
+# ------------------------------------------------------------------ the training chain on the GPU (mi355.augment)
+class AugmentSample(tuple):
+    """What ``DeviceAugment`` hands on instead of an image: the un-augmented HWC uint8 RGB pixels and the sample's
+    parameter row (``mi355.augment.PARAM_COLUMNS``).  ``utils.data.ragged_collate`` packs a batch of them."""
+    __slots__ = ()
+
+    def __new__(cls, pixels, params):
+        return tuple.__new__(cls, (pixels, params))
+
+    pixels = property(lambda self: self[0])
+    params = property(lambda self: self[1])
+
+
+class DeviceAugment:
+    """Drop-in for ``Compose([RandomRotation(rotation), RandomResizedCrop(size, scale), ColorJitter(brightness, contrast,
+    saturation), GaussianBlur(*blur), ToTensor(), Normalize(...)])`` whose pixel work runs on the GPU (mi355.augment).
+
+    On the host it makes exactly the RNG calls of that chain, in its order -- ``random.uniform`` for the angle, the
+    ``get_params`` loop of RandomResizedCrop, three ``random.uniform`` and one ``random.shuffle`` for the jitter, then
+    ``np.random.uniform`` for the blur radius -- and moves ``keypoint2d`` / ``intrinsic_matrix`` with the same functions the
+    chain uses.  The image comes back un-augmented as an ``AugmentSample``; the data set's labels are left to the GPU
+    (``labels_on_device``: key points and visibility travel instead of heat-maps)."""
+    labels_on_device = True
+
+    def __init__(self, rotation, size, scale=(0.6, 1.3), brightness=0.25, contrast=0.25, saturation=0.25, blur=(0, 0.8)):
+        self.degrees = RandomRotation(rotation).degrees
+        self.size, self.scale = size, scale
+        self.jitter = ColorJitter(brightness, contrast, saturation)
+        self.blur = GaussianBlur(*blur)
+
+    def __call__(self, image, keypoint2d, intrinsic_matrix, **kwargs):
+        if image.mode != 'RGB':
+            image = image.convert('RGB')
+        width, height = image.size
+        angle = RandomRotation.get_params(self.degrees)
+        keypoint2d = rotate_keypoints(angle, width, height, keypoint2d)
+        top, left, h, w = RandomResizedCrop.get_params(image, self.scale)     # (rotation keeps the canvas size)
+        assert w == h, 'resize expects the square crops the datasets produce'
+        keypoint2d, intrinsic_matrix = resize_labels(w, self.size, crop_keypoints(top, left, keypoint2d), intrinsic_matrix)
+        factors, ops = [0.0, 0.0, 0.0], []
+        for k, rng in enumerate((self.jitter.brightness, self.jitter.contrast, self.jitter.saturation)):
+            if rng:
+                factors[k] = random.uniform(*rng)
+                ops.append(k)
+        random.shuffle(ops)
+        radius = np.random.uniform(low=self.blur.low, high=self.blur.high)
+        order = ops + [-1] * (3 - len(ops))
+        params = np.array([angle, top, left, w] + factors + order + [radius], dtype=np.float64)
+        kwargs.update(keypoint2d=keypoint2d, intrinsic_matrix=intrinsic_matrix)
+        return AugmentSample(np.asarray(image, dtype=np.uint8), params), kwargs

@@ -107,3 +107,69 @@ class DevicePrefetcher:
                 x.record_stream(cur)
         self._preload()
         return batch
+
+
+# ---------------------------------------------------------------- device augmentation (train1.py --device-augment)
+def ragged_collate(samples):
+    """Collate of the ``DeviceAugment`` data sets: (AugmentSample, key points, visibility, meta) per sample ->
+    (packed uint8 (sum of h*w*3,), table int64 (B, 3) of (offset, h, w), params float64 (B, 11), key points float64 (B, K, 2),
+    visibility float32 (B, K, 1), meta).  Ragged sources travel as one flat buffer, so the loader's ``pin_memory`` pins a
+    single tensor per batch; ``image_ema`` (made on the GPU) is dropped from the meta dicts."""
+    from torch.utils.data import default_collate
+    import numpy as np
+    images = [s[0] for s in samples]
+    sizes = [im.pixels.size for im in images]
+    offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    packed = torch.from_numpy(np.concatenate([im.pixels.reshape(-1) for im in images]))
+    table = torch.tensor([[int(o), im.pixels.shape[0], im.pixels.shape[1]] for o, im in zip(offsets, images)], dtype=torch.int64)
+    params = torch.from_numpy(np.stack([im.params for im in images]))
+    keypoints = torch.stack([s[1] for s in samples])
+    visible = torch.stack([s[2] for s in samples])
+    meta = default_collate([{k: v for k, v in s[3].items() if k != 'image_ema'} for s in samples])
+    return packed, table, params, keypoints, visible, meta
+
+
+def snap_keypoints(keypoints, heatmap_size, image_size):
+    """Key points (B, K, 2) float64 -> float32 positions that generate_target_device maps to exactly the heat-map centre the
+    CPU labels use (``int(kp / stride + 0.5)`` in float64, uda/dataset/util.py): the centre times the stride, or far
+    outside when the CPU rule drops the joint."""
+    kp = torch.as_tensor(keypoints, dtype=torch.float64)
+    stride = float(image_size) / float(heatmap_size)
+    v = kp / stride + 0.5
+    centre = torch.trunc(v)
+    snapped = centre * stride
+    return torch.where(v > -1, snapped, torch.full_like(snapped, -1.0e4)).float()
+
+
+class DeviceAugmentIterator:
+    """Batches of ``ragged_collate`` -> the ``(x, target, weight, meta)`` batches the training loops consume, on the GPU:
+    the packed sources are copied to HBM, ``mi355.augment`` produces x (and ``meta['image_ema']`` with want_ema) and
+    ``utils.labels.generate_target_device`` the heat-maps from the key points.  Everything is enqueued on the current
+    stream.  ``out=`` buffers: pass ``out`` (B, 3, S, S) to have x written into a preallocated tensor."""
+
+    def __init__(self, iterator, device, image_size=256, heatmap_size=64, sigma=2, want_ema=False, out=None):
+        self.it = iter(iterator)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ValueError('DeviceAugmentIterator runs the augmentation on a GPU; there is no CPU path')
+        self.image_size, self.heatmap_size, self.sigma, self.want_ema, self.out = image_size, heatmap_size, sigma, want_ema, out
+
+    def __iter__(self):
+        return self
+
+    def __len__(self):
+        return len(self.it)
+
+    def __next__(self):
+        from mi355.augment import augment
+        from utils.labels import generate_target_device
+        packed, table, params, keypoints, visible, meta = next(self.it)
+        packed = packed.to(self.device, non_blocking=True)
+        res = augment(packed, table, params, out=self.out, want_ema=self.want_ema, size=self.image_size)
+        x = res[0] if self.want_ema else res
+        if self.want_ema:
+            meta = dict(meta, image_ema=res[1])
+        kp = snap_keypoints(keypoints, self.heatmap_size, self.image_size).to(self.device, non_blocking=True)
+        target, weight = generate_target_device(kp, visible.to(self.device, non_blocking=True), self.heatmap_size, self.sigma,
+                                                self.image_size)
+        return x, target, weight, meta

@@ -381,6 +381,39 @@ int mi355_sgd_nesterov(float* p, const float* g, float* buf, long n, const float
                        float wd, int nesterov, void* p_lowp, void* stream);
 int mi355_cast_f32(const float* in, void* out, long n, int dtype, void* stream);
 
+/* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
+ * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
+ * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
+ * ragged HWC uint8 RGB sources packed into one buffer, bit-exact with Pillow's arithmetic:
+ *   rotate    Image.rotate NEAREST as Pillow's 16.16 fixed-point affine (or its copy / transpose shortcuts);
+ *   crop      square (top, left, side) of the rotated image, resized to S x S by Image.resize BILINEAR
+ *             (22-bit coefficients from double math, horizontal pass to uint8, then the vertical pass);
+ *   jitter    ImageEnhance brightness / contrast / saturation as float32 Image.blend, in the drawn order; contrast
+ *             blends with int(mean(L) + 0.5) of the image it is applied to (exact integer sum over the image);
+ *   blur      ImagingGaussianBlur with integer box radius 0: 3 horizontal then 3 vertical 3-tap passes,
+ *             (ww * centre + fw * (left + right) + 2^23) >> 24 with edge clamp;
+ *   output    out[b][c][y][x] = (v / 255 - mean[c]) / std[c] fp32 NCHW; ema (nullable): the same normalisation of the
+ *             geometry image (before jitter and blur).
+ * Unlike the rest of this header, the records are passed twice: `rec_host` (host memory) is what the argument checks read
+ * before anything is enqueued, `rec_dev` (device memory, an identical copy) is what the kernels read.  Two launches. */
+typedef struct {
+  int64_t offset;           /* byte offset of the source image (h x w x 3, row-major) in the packed buffer */
+  int32_t h, w;             /* source size */
+  int32_t rot;              /* 0 affine a[], 1 copy, 2 rotate 180, 3 rotate 90 (square), 4 rotate 270 (square) */
+  int32_t a[6];             /* 16.16 fixed point: xs = (a2 + y*a1 + x*a0) >> 16, ys = (a5 + y*a4 + x*a3) >> 16 */
+  int32_t top, left, side;  /* square crop of the rotated image (inside it), resized to S x S */
+  float factor[3];          /* blend factors: brightness, contrast, saturation */
+  int32_t order[3];         /* op ids (0 brightness, 1 contrast, 2 saturation) in application order, -1 = no op */
+  int32_t blur;             /* 0 none, 1 the 3 + 3 box passes with weights ww, fw */
+  uint32_t ww, fw;
+  int32_t reserved;
+} mi355_aug_rec;
+/* workspace bytes of mi355_augment for B images of S x S */
+size_t mi355_augment_workspace(int B, int S);
+/* norm: host pointer to 6 floats (mean[3], std[3]); out: fp32 [B][3][S][S]; ema (nullable): fp32 [B][3][S][S] */
+int mi355_augment(const uint8_t* src, int64_t src_bytes, const mi355_aug_rec* rec_host, const mi355_aug_rec* rec_dev,
+                  int B, int S, const float* norm, float* out, float* ema, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- in-library kernel timing (bench.py roofline)
  * on = 1: every launch of the MFMA conv family is bracketed by hipEvents on its stream; on = 2: the BatchNorm kernels and
  * the weight-gradient slab reductions as well (family 1 / 2; they never enter the totals below).  mi355_prof_read
