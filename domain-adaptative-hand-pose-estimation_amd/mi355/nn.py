@@ -19,9 +19,20 @@ from . import ops
 
 
 # ---------------------------------------------------------------- parameter-gradient bookkeeping
+def _same_layout(g, p):
+    """g and p address their elements alike (the strides of every extent > 1 agree)."""
+    return all(n == 1 or a == b for n, a, b in zip(p.shape, g.stride(), p.stride()))
+
+
 def grad_slot(p):
     """Return (tensor to write the gradient into, accumulate?) for parameter `p`."""
     p._mi_slot = True              # this gradient is written by the kernels, not by autograd's AccumulateGrad
+    if p.grad is not None and not _same_layout(p.grad, p):
+        # a gradient the caller created in another memory order (p.grad = torch.zeros(p.shape)): the kernels write the
+        # parameter's own order ([Co][kh][kw][Ci] for conv weights), so the values move into a tensor laid out like p
+        g = torch.empty_strided(p.shape, p.stride(), dtype=p.dtype, device=p.device)
+        g.copy_(p.grad)
+        p.grad = g
     if p.grad is None:
         p.grad = torch.empty_strided(p.shape, p.stride(), dtype=p.dtype, device=p.device)
         p._mi_fresh = False
@@ -428,16 +439,28 @@ def _take_partial(mod, y):
 
 def _zero_grad_once(g):
     """g (the gradient buffer of a bias) <- 0, skipped when this very tensor object still holds the zeros this function wrote last
-    time: nothing but this module's bias-gradient code writes non-zeros into it (the optimizer and the gradient exchange read it; a
-    mean of zeros is zero; zero_grad only marks it fresh), and a re-created gradient tensor (flattening by FusedSGD, set_to_none)
-    is a new object without the mark.  An iteration's ~20 zero-fill launches become none (none is captured into the HIP graphs)."""
+    time.  A stand-alone gradient tensor proves that by its version counter: any torch op that wrote into it since moved the
+    counter.  Views of FusedSGD's flat buffer share the buffer's counter (every neighbour's write moves it) and may be written by
+    anything that holds the buffer (clipping, a manual weight decay, scaled flat gradients), invisibly to this function: there
+    FusedSGD.zero_grad puts the zeros back before the next backward, one launch per flat group for all the ranges registered here
+    (the offset table in g._mi_flat), and the mark decides.  An iteration's ~20 zero-fill launches become one per flat group and
+    zero_grad."""
     mark = getattr(g, '_mi_zeroed', None)
-    # a stand-alone gradient tensor also proves by its version counter that no torch op touched it since; views of FusedSGD's flat
-    # buffer share the buffer's counter (every neighbour's zero_ moves it), there the mark alone decides
-    if mark is not None and mark is not False and (g._base is not None or mark == g._version):
+    flat = getattr(g, '_mi_flat', None)
+    if mark is not None and mark is not False and (mark == g._version or flat is not None):
         return
     g.zero_()
     g._mi_zeroed = g._version
+    if flat is not None:
+        flat[0][flat[1]] = flat[2]
+
+
+def _unmark_zeroed(g):
+    """g is about to receive values other than zeros (column sum): _zero_grad_once must fill it again next time."""
+    g._mi_zeroed = False
+    flat = getattr(g, '_mi_flat', None)
+    if flat is not None:
+        flat[0].pop(flat[1], None)
 
 
 def _bias_grad(ctx, bias, dy):
@@ -455,7 +478,7 @@ def _bias_grad(ctx, bias, dy):
         if not acc:
             _zero_grad_once(g)
         return
-    g._mi_zeroed = False
+    _unmark_zeroed(g)
     ops.colsum(dy, g, acc)
 
 
@@ -839,6 +862,7 @@ class _PwC2KFn(torch.autograd.Function):
                 ops.pw_wgrad(x, dy, g, True, acc)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             g, acc = grad_slot(bias)
+            _unmark_zeroed(g)
             ops.hm_rowsum(dy, g, acc)
         return dx, None, None, None, None
 
@@ -932,7 +956,7 @@ class _ConvCatFn(torch.autograd.Function):
                     if not acc:
                         _zero_grad_once(g)
                 else:
-                    g._mi_zeroed = False
+                    _unmark_zeroed(g)
                     ops.colsum(dout, g, acc)
         if ctx.needs_input_grad[2]:
             _conv_wgrad(ctx, x, dout, wf)
@@ -1115,8 +1139,9 @@ class Conv2d(_FastSlots, nn.Module):
                 dst.add_(t) if acc else dst.copy_(t)
         else:   # stem: kernel works on the padded channel count; un-pad into the (Co,3,7,7) gradient
             k = self.kernel_size[0]
-            if self._stem_tmp is None or self._stem_tmp.device != x.device:
-                self._stem_tmp = torch.empty(self.out_channels, k, k, desc.Ci, dtype=torch.float32, device=x.device)
+            shape = (self.out_channels, k, k, desc.Ci)      # (the folded form leaves a flat buffer; Ci is 4 in f32, 8 in bf16)
+            if self._stem_tmp is None or self._stem_tmp.device != x.device or tuple(self._stem_tmp.shape) != shape:
+                self._stem_tmp = torch.empty(shape, dtype=torch.float32, device=x.device)
             ops.conv_wgrad(desc, x, dy, self._stem_tmp, False)
             src = self._stem_tmp[..., :self.in_channels]
             dst = g.permute(0, 2, 3, 1)

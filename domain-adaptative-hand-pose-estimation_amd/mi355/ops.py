@@ -20,6 +20,13 @@ def is_nhwc(x):
     return x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous()
 
 
+def _chk_room(what, t, need):
+    """Raise before any launch when the caller-provided buffer `t` holds fewer than `need` elements: the kernels index it
+    from the problem size alone and would write past its end."""
+    if t is not None and t.numel() < need:
+        raise Mi355Error('%s: buffer of %d elements, the launch writes %d' % (what, t.numel(), need))
+
+
 def _chk_dev(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
@@ -74,6 +81,7 @@ def stem_s2d_pack(w, dtype, out=None):
     Co = w.numel() // 147
     if out is None:
         out = torch.empty(Co * 256, dtype=dtype, device=w.device)
+    _chk_room('stem_s2d_pack out', out, Co * 256)
     call('mi355_stem_s2d_pack', ptr(w), ptr(out), Co, dtype_code(dtype), stream_ptr())
     return out
 
@@ -81,6 +89,9 @@ def stem_s2d_pack(w, dtype, out=None):
 def stem_s2d_unpack_grad(gs, g, accumulate):
     """gs: fp32 [Co][4][4][16] weight gradient of the folded stem; g: fp32 gradient in [Co][7][7][3] memory order (= / +=)."""
     _chk_dev(gs, g)
+    if g.numel() % 147:
+        raise Mi355Error('stem_s2d_unpack_grad: g is not a (Co, 3, 7, 7) gradient (%d elements)' % g.numel())
+    _chk_room('stem_s2d_unpack_grad gs', gs, g.numel() // 147 * 256)
     call('mi355_stem_s2d_unpack_grad', ptr(gs), ptr(g), g.numel() // 147, int(bool(accumulate)), stream_ptr())
 
 
@@ -169,6 +180,7 @@ def conv_dgrad_bnbwd(desc, dy, wT, bn, scale_dev=None, out=None, accumulate=Fals
     """conv_dgrad whose result is the dy of the BatchNorm described by `bn`; also returns that BatchNorm's backward
     reduction partials (buffer, nslices) from the epilogue, or None when the launch could not fuse them."""
     _chk_dev(dy, wT)
+    _chk_room('conv_dgrad_bnbwd out', out, desc.N * desc.Ci * desc.Hi * desc.Wi)
     dx = out if out is not None else nhwc_empty(desc.N, desc.Ci, desc.Hi, desc.Wi, dy.dtype, dy.device)
     partial, nbytes = _stats_buf(desc.N * desc.Hi * desc.Wi, desc.Ci, dy.device)
     ns = ctypes.c_int(0)
@@ -192,6 +204,7 @@ def conv_fwd_bnbwd(desc, x, w, bn):
 
 def conv_dgrad(desc, dy, wT, scale_dev=None, out=None, accumulate=False):
     _chk_dev(dy, wT)
+    _chk_room('conv_dgrad out', out, desc.N * desc.Ci * desc.Hi * desc.Wi)
     dx = out if out is not None else nhwc_empty(desc.N, desc.Ci, desc.Hi, desc.Wi, dy.dtype, dy.device)
     call('mi355_conv_dgrad', ctypes.byref(desc), ptr(dy), ptr(wT), 0, ptr(scale_dev), int(accumulate), ptr(dx),
          stream_ptr())
@@ -201,6 +214,9 @@ def conv_dgrad(desc, dy, wT, scale_dev=None, out=None, accumulate=False):
 def conv_dgrad_masked_acc(desc, dy, wT, out, acc_mask, scale_dev=None):
     """out <- conv_dgrad(dy) + (bit of acc_mask set ? out : 0), in place; returns out."""
     _chk_dev(dy, wT, out, acc_mask)
+    n = desc.N * desc.Ci * desc.Hi * desc.Wi
+    _chk_room('conv_dgrad_masked_acc out', out, n)
+    _chk_room('conv_dgrad_masked_acc acc_mask', acc_mask, n // (8 if out.dtype == torch.bfloat16 else 4))
     call('mi355_conv_dgrad_masked_acc', ctypes.byref(desc), ptr(dy), ptr(wT), ptr(scale_dev), ptr(out), ptr(acc_mask), stream_ptr())
     return out
 
@@ -209,6 +225,7 @@ def apply_relu_mask(g, mask):
     """g <- bit of mask set ? g : 0, in place (g channels_last bf16 / fp32, mask from bn_relu_mask); returns g."""
     _chk_dev(g, mask)
     N, C, H, W = g.shape
+    _chk_room('apply_relu_mask mask', mask, g.numel() // (8 if g.dtype == torch.bfloat16 else 4))
     call('mi355_apply_relu_mask', ptr(g), ptr(mask), N * H * W, C, dtype_code(g.dtype), stream_ptr())
     return g
 
@@ -216,6 +233,7 @@ def apply_relu_mask(g, mask):
 def conv_wgrad(desc, x, dy, dw, accumulate, ws_tag='main'):
     """dw: fp32 buffer in [Co][kh][kw][Ci] memory order (Ci = desc.Ci, i.e. padded for the stem)."""
     _chk_dev(x, dy, dw)
+    _chk_room('conv_wgrad dw', dw, desc.Co * desc.kh * desc.kw * desc.Ci)
     need = load().mi355_conv_wgrad_workspace(ctypes.byref(desc))
     ws = workspace(need, x.device, ws_tag)
     call('mi355_conv_wgrad', ctypes.byref(desc), ptr(x), ptr(dy), ptr(dw), int(accumulate), ptr(ws), ws.numel(),
@@ -228,6 +246,7 @@ def conv_wgrad_grouped(items, ws_tag='main'):
     arr = (WgradItem * n)()
     for i, (desc, x, dy, dw, acc) in enumerate(items):
         _chk_dev(x, dy, dw)
+        _chk_room('conv_wgrad_grouped dw', dw, desc.Co * desc.kh * desc.kw * desc.Ci)
         arr[i].d = desc
         arr[i].x, arr[i].dy, arr[i].dw, arr[i].accumulate = ptr(x), ptr(dy), ptr(dw), int(acc)
     need = load().mi355_conv_wgrad_grouped_workspace(arr, n)
@@ -257,6 +276,7 @@ def pack_weights_into(w_master, wf, wt, O, T, I, Ipad, dtype):
 def colsum(dy, out, accumulate):
     """out[C] (=|+=) column sums of the channels_last tensor dy."""
     N, C, H, W = dy.shape
+    _chk_room('colsum out', out, C)
     rows = N * H * W
     ws = workspace(load().mi355_colsum_workspace(rows, C), dy.device)
     call('mi355_colsum', ptr(dy), ptr(out), rows, C, dtype_code(dy.dtype), int(accumulate), ptr(ws), ws.numel(),
@@ -345,6 +365,7 @@ def conv_fwd_fp8(desc, x8, x_state, w8, w_state, bias=None, residual=None, want_
 def conv_dgrad_fp8(desc, dy8, dy_state, wT8, w_state, scale_dev=None, out=None, accumulate=False, want_stats=False, dy_fmt=E5M2):
     """dx (bf16) = dgrad(dy8, wT8) * descale_dy * descale_w (* *scale_dev) (+ dx when accumulate)."""
     _chk_dev(dy8, wT8)
+    _chk_room('conv_dgrad_fp8 out', out, desc.N * desc.Ci * desc.Hi * desc.Wi)
     dx = out if out is not None else nhwc_empty(desc.N, desc.Ci, desc.Hi, desc.Wi, torch.bfloat16, dy8.device)
     partial, nbytes, ns = None, 0, ctypes.c_int(0)
     if want_stats:
@@ -360,6 +381,7 @@ def conv_wgrad_fp8(desc, x8, x_state, dy8, dy_state, dw, accumulate, dy_fmt=E5M2
     """dw (fp32, [Co][kh][kw][Ci]) (+)= wgrad(x8, dy8) * descale_x * descale_dy for the 3x3 / stride-1 and the 3x3 / 4x4 /
     stride-2 layers: both operands are the fp8 copies the forward / input-gradient launches of the layer already made."""
     _chk_dev(x8, dy8, dw)
+    _chk_room('conv_wgrad_fp8 dw', dw, desc.Co * desc.kh * desc.kw * desc.Ci)
     need = load().mi355_conv_wgrad_fp8_workspace(ctypes.byref(desc))
     ws = workspace(need, x8.device, ws_tag)
     call('mi355_conv_wgrad_fp8', ctypes.byref(desc), ptr(x8), int(x_fmt), ptr(dy8), int(dy_fmt), ptr(x_state[1:2]),
@@ -540,6 +562,7 @@ def pw_k2c_stats(y, w, bias, C, dtype, residual=None):
 def pw_wgrad(x, y, dw, kc_layout, accumulate):
     N, C, H, W = x.shape
     K = y.shape[1]
+    _chk_room('pw_wgrad dw', dw, C * K)
     ws = workspace(load().mi355_pw_wgrad_workspace(N, H * W, C, K), x.device)
     call('mi355_pw_wgrad', ptr(x), ptr(y), ptr(dw), int(kc_layout), int(accumulate), N, H * W, C, K,
          dtype_code(x.dtype), ptr(ws), ws.numel(), stream_ptr())
@@ -547,6 +570,7 @@ def pw_wgrad(x, y, dw, kc_layout, accumulate):
 
 def hm_rowsum(y, out, accumulate):
     N, K, H, W = y.shape
+    _chk_room('hm_rowsum out', out, K)
     ws = workspace(N * K * 4, y.device)
     call('mi355_hm_rowsum', ptr(y), ptr(out), int(accumulate), N, K, H * W, ptr(ws), ws.numel(), stream_ptr())
 
@@ -639,6 +663,7 @@ def bilinear_up(x, size, alpha=1.0, out=None):
     x = _hm(x)
     B, K, h, w = x.shape
     acc = out is not None
+    _chk_room('bilinear_up out', out, B * K * size * size)
     if out is None:
         out = torch.empty((B, K, size, size), dtype=torch.float32, device=x.device)
     call('mi355_bilinear_up', ptr(x), ptr(out), B * K, h, w, size, size, float(alpha), int(acc), stream_ptr())
@@ -655,11 +680,14 @@ def pck_dists(pred_xy, tgt_xy, norm_x, norm_y):
 
 # ---------------------------------------------------------------- optimiser
 def sgd_nesterov(p, g, buf, lr_dev, momentum, wd, nesterov, p_lowp=None):
+    for what, t in (('g', g), ('buf', buf), ('p_lowp', p_lowp)):
+        _chk_room('sgd_nesterov ' + what, t, p.numel())
     call('mi355_sgd_nesterov', ptr(p), ptr(g), ptr(buf), p.numel(), ptr(lr_dev), float(momentum), float(wd),
          int(nesterov), ptr(p_lowp), stream_ptr())
 
 
 def cast_f32(src, dst):
+    _chk_room('cast_f32 dst', dst, src.numel())
     call('mi355_cast_f32', ptr(src), ptr(dst), src.numel(), dtype_code(dst.dtype), stream_ptr())
 
 

@@ -47,6 +47,7 @@ class FusedSGD(Optimizer):
             P = torch.zeros(total, dtype=torch.float32, device=dev)
             G = torch.zeros(total, dtype=torch.float32, device=dev)
             M = torch.zeros(total, dtype=torch.float32, device=dev)
+            zeroed = {}              # offset -> length of the bias gradients nn._zero_grad_once holds at zero (see zero_grad)
             for p, o in zip(ps, offs):
                 n = p.numel()
                 if p.dtype != torch.float32:
@@ -61,10 +62,11 @@ class FusedSGD(Optimizer):
                     mv.copy_(st['momentum_buffer'])
                 p.data = pv
                 p.grad = gv
+                gv._mi_flat = (zeroed, o, n)
                 st['momentum_buffer'] = mv
                 p._mi_epoch = getattr(p, '_mi_epoch', 0) + 1     # packed copies must be rebuilt (storage moved)
             lr_dev = torch.zeros((), dtype=torch.float32, device=dev)
-            flat.append(dict(P=P, G=G, M=M, params=ps, lr_dev=lr_dev, gi=gi,
+            flat.append(dict(P=P, G=G, M=M, params=ps, lr_dev=lr_dev, gi=gi, zeroed=zeroed, zero_idx=(None, None),
                              offs={id(p): (o, (p.numel() + 3) // 4 * 4) for p, o in zip(ps, offs)}))
         self._flat = flat
         self.sync_lr(force=True)
@@ -112,7 +114,15 @@ class FusedSGD(Optimizer):
         gradient before the next step() is skipped by it (no weight decay, no momentum update), exactly like a parameter
         whose ``grad is None``.  Gradients written by the mi355 kernels are simply overwritten by the next backward (no
         memset, the flat buffers stay in place); gradients accumulated by autograd itself (torch-native modules in the
-        same optimizer) are zeroed here and recognised as untouched by their version counter."""
+        same optimizer) are zeroed here and recognised as untouched by their version counter.
+
+        The bias gradients whose backward writes zeros (a conv in front of a training-mode BatchNorm: nn._zero_grad_once) are
+        zeroed here, with one launch per flat group, instead of one fill per bias in the backward: clipping, a manual weight
+        decay or scaled flat gradients may have written into them since, which no version counter of the flat views shows."""
+        if self._flat is not None:
+            for f in self._flat:
+                if f is not None and f['zeroed']:
+                    self._refill_zeros(f)
         for group in self.param_groups:
             ps = group['params']
             mark_grads_fresh([p for p in ps if getattr(p, '_mi_slot', False)])
@@ -120,6 +130,18 @@ class FusedSGD(Optimizer):
                 if p.grad is not None and not getattr(p, '_mi_slot', False):
                     p.grad.zero_()
                     p._mi_zero_ver = p.grad._version
+
+    @staticmethod
+    def _refill_zeros(f):
+        key = tuple(sorted(f['zeroed'].items()))
+        if f['zero_idx'][0] != key:
+            if torch.cuda.is_current_stream_capturing():      # (no index yet: one fill per range, captured as they are)
+                for o, n in key:
+                    f['G'][o:o + n].zero_()
+                return
+            idx = torch.cat([torch.arange(o, o + n, dtype=torch.long) for o, n in key])
+            f['zero_idx'] = (key, idx.to(f['G'].device))
+        f['G'].index_fill_(0, f['zero_idx'][1], 0.0)
 
     @staticmethod
     def _stale(p):
