@@ -1598,7 +1598,8 @@ static int check_bnb(const mi355_bn_bwd_src* bn, const float* partial, const int
   return MI355_OK;
 }
 // fp8 operand launches: device scalars undoing the operand scales, and the format of the gathered operand
-struct Fp8Extra { const float* descale_a; const float* descale_b; int a_fmt; };
+// (MX: block scales sa / sb instead of the descales, e4m3 operands; mx_fp8.hip)
+struct Fp8Extra { const float* descale_a; const float* descale_b; int a_fmt; const void* sa = nullptr; const void* sb = nullptr; };
 struct CatExtra { const void* x2; const void* w2; const float* bias2; int c2; };
 static int conv_fwd_impl(const mi355_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
                          float* partial, size_t partial_bytes, int* nslices, void* stream, const mi355_bn_bwd_src* bn = nullptr,
@@ -1607,7 +1608,7 @@ static int conv_fwd_impl(const mi355_conv_desc* d, const void* x, const void* w,
   if ((d->dtype == MI355_FP8) != (f8 != nullptr)) MI_FAIL(MI355_EINVAL, "fp8 descriptors go through the *_fp8 entry points (and only they)");
   if (relu && (bn || f8 || partial)) MI_FAIL(MI355_EINVAL, "conv_fwd: the fused ReLU is an inference epilogue (no statistics / BatchNorm-backward / fp8 variant)");
   GatherArgs a; memset(&a, 0, sizeof(a));
-  if (prof_on()) prof_set_tag("fwd%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? "8" : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
+  if (prof_on()) prof_set_tag("fwd%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? "mx" : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
                               residual ? " +res" : "", cat ? " +cat" : "");
   a.relu = relu ? 1 : 0;
   a.A = x; a.B = w; a.D = y; a.bias = bias; a.residual = residual; a.scale = nullptr;
@@ -1625,7 +1626,7 @@ static int conv_fwd_impl(const mi355_conv_desc* d, const void* x, const void* w,
   for (int i = 0; i < d->kh; ++i)
     for (int j = 0; j < d->kw; ++j) { Tap& t = a.taps[i * d->kw + j]; t.dy = (int8_t)(i - d->pad); t.dx = (int8_t)(j - d->pad); t.widx = (int16_t)(i * d->kw + j); }
   int e;
-  if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; e = dispatch_gather_fp8(a, as_stream(stream)); }
+  if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; a.mx_sa = f8->sa; a.mx_sb = f8->sb; e = dispatch_gather_fp8(a, as_stream(stream)); }
   else e = d->dtype == MI355_BF16 ? dispatch_gather<bf16_t>(a, as_stream(stream)) : dispatch_gather<float>(a, as_stream(stream));
   if (nslices) *nslices = a.stat_slices;
   return e;
@@ -1636,6 +1637,19 @@ extern "C" int mi355_conv_fwd_fp8(const mi355_conv_desc* d, const void* x8, int 
   if (!descale_x || !descale_w || (x_fmt != 0 && x_fmt != 1)) MI_FAIL(MI355_EINVAL, "conv_fwd_fp8: descale scalars / format missing");
   if (nslices) *nslices = 0;
   Fp8Extra f8{descale_x, descale_w, x_fmt};
+  return conv_fwd_impl(d, x8, w8, bias, residual, y, partial, partial_bytes, nslices, stream, nullptr, &f8);
+}
+// MX operands (mx_fp8.hip): e4m3 x8 [N][Hi][Wi][Ci] with scales sx [N][Hi][Wi][Ci/32], w8 [Co][T][Ci] with sw [Co][T][Ci/32]
+extern "C" int mi355_conv_fwd_mx(const mi355_conv_desc* d, const void* x8, const void* sx, const void* w8, const void* sw,
+                                 const float* bias, const void* residual, void* y, float* partial, size_t partial_bytes,
+                                 int* nslices, void* stream) {
+  if (nslices) *nslices = 0;
+  if (!d || !x8 || !sx || !w8 || !sw || !y) MI_FAIL(MI355_EINVAL, "conv_fwd_mx: null descriptor, operand, scale or output");
+  if (d->dtype != MI355_FP8) MI_FAIL(MI355_EINVAL, "conv_fwd_mx: the descriptor's dtype must be MI355_FP8");
+  if (d->Ci < 128 || d->Ci % 128 || (d->Ci & (d->Ci - 1))) MI_FAIL(MI355_EINVAL, "conv_fwd_mx: Ci=%d (contracted) must be a power-of-two multiple of 128", d->Ci);
+  if (d->Co < 8 || d->Co % 8) MI_FAIL(MI355_EINVAL, "conv_fwd_mx: Co=%d must be a multiple of 8", d->Co);
+  if ((partial == nullptr) != (nslices == nullptr)) MI_FAIL(MI355_EINVAL, "conv_fwd_mx: partial and nslices go together");
+  Fp8Extra f8{nullptr, nullptr, 0, sx, sw};
   return conv_fwd_impl(d, x8, w8, bias, residual, y, partial, partial_bytes, nslices, stream, nullptr, &f8);
 }
 extern "C" int mi355_conv_fwd(const mi355_conv_desc* d, const void* x, const void* w, const float* bias,
@@ -1717,6 +1731,21 @@ extern "C" int mi355_conv_dgrad_fp8(const mi355_conv_desc* d, const void* dy8, i
   Fp8Extra f8{descale_dy, descale_w, dy_fmt};
   return conv_dgrad_impl(d, dy8, wT8, nullptr, scale_dev, accumulate, dx, partial, partial_bytes, nslices, stream, nullptr, &f8);
 }
+// MX operands: e4m3 dy8 [N][Ho][Wo][Co] with sdy [N][Ho][Wo][Co/32], wT8 [Ci][T][Co] with swT [Ci][T][Co/32]
+extern "C" int mi355_conv_dgrad_mx(const mi355_conv_desc* d, const void* dy8, const void* sdy, const void* wT8, const void* swT,
+                                   const float* scale_dev, int accumulate, void* dx, float* partial, size_t partial_bytes,
+                                   int* nslices, void* stream) {
+  if (nslices) *nslices = 0;
+  if (!d || !dy8 || !sdy || !wT8 || !swT || !dx) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx: null descriptor, operand, scale or output");
+  if (d->dtype != MI355_FP8) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx: the descriptor's dtype must be MI355_FP8");
+  if (d->Co < 128 || d->Co % 128 || (d->Co & (d->Co - 1))) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx: Co=%d (contracted) must be a power-of-two multiple of 128", d->Co);
+  if (d->Ci < 8 || d->Ci % 8) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx: Ci=%d must be a multiple of 8", d->Ci);
+  if ((partial == nullptr) != (nslices == nullptr)) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx: partial and nslices go together");
+  if (accumulate != 0 && accumulate != 1) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx: accumulate %d", accumulate);
+  if (int e = check_desc(d)) return e;       // (before the zero fill of a phase without taps)
+  Fp8Extra f8{nullptr, nullptr, 0, sdy, swT};
+  return conv_dgrad_impl(d, dy8, wT8, nullptr, scale_dev, accumulate, dx, partial, partial_bytes, nslices, stream, nullptr, &f8);
+}
 // conv input gradient that is the dy of a BatchNorm: that BatchNorm's backward reduction in the epilogue
 extern "C" int mi355_conv_dgrad_bnbwd(const mi355_conv_desc* d, const void* dy, const void* wT, const float* scale_dev, int accumulate,
                                       void* dx, const mi355_bn_bwd_src* bn, float* partial, size_t partial_bytes, int* nslices,
@@ -1774,7 +1803,7 @@ static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void*
     MI_CHECK_LAUNCH("zero_fill");
   }
   GatherArgs a; memset(&a, 0, sizeof(a));
-  if (prof_on()) prof_set_tag("dgrad%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? "8" : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
+  if (prof_on()) prof_set_tag("dgrad%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? "mx" : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
                               accumulate ? (acc_mask ? " +macc" : " +acc") : "", bn ? " +bnb" : "");
   a.A = dy; a.B = wT; a.D = dx; a.bias = bias; a.residual = nullptr; a.scale = scale_dev;
   a.Hi = d->Ho; a.Wi = d->Wo; a.Ci = d->Co;
@@ -1809,7 +1838,7 @@ static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void*
     if (bn) set_bnb(a, bn, partial, partial_bytes);   // (zero-filled phases carry dy = 0: they add nothing to the sums)
     else if (partial && !need_zero && a.nphase == s * s) { a.stat_partial = partial; a.stat_bytes = partial_bytes; }
     int e;
-    if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; e = dispatch_gather_fp8(a, st); }
+    if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; a.mx_sa = f8->sa; a.mx_sb = f8->sb; e = dispatch_gather_fp8(a, st); }
     else e = d->dtype == MI355_BF16 ? dispatch_gather<bf16_t>(a, st) : dispatch_gather<float>(a, st);
     if (nslices) *nslices = a.stat_slices;
     return e;

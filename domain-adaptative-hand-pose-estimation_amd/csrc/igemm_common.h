@@ -45,8 +45,15 @@ struct GatherArgs {
   // Concatenated-K forward (CAT builds of the gather kernel): D += A2 * B2^T as ONE more K tile behind the conv's own taps --
   // A2 [M][c2] lives at the OUTPUT resolution (row m = output pixel m: single phase, unit output stride), B2 [Nout][c2],
   // c2 <= one K tile.  `heatmap_conv(y) + feature_conv(f)` of the multiscale-fusion heads as one GEMM (regda_7.py:4573-4581).
-  const void* A2; const void* B2; const float* bias2;
-  int c2; unsigned a2_bytes, b2_bytes;
+  // MX build of the fp8 gather kernel (igemm_fp8.hip, mx_fp8.hip), which has no CAT form and shares these slots: the E8M0 scale
+  // arrays of A and B (one byte per 32 contracted elements, laid out like the operand with its contiguous axis divided by 32 --
+  // the scale dword of a 128-channel K tile sits at (byte offset of the tile's first element) / 32) and their sizes.
+  union { const void* A2; const void* mx_sa; };
+  union { const void* B2; const void* mx_sb; };
+  const float* bias2;
+  int c2;
+  union { unsigned a2_bytes; unsigned mx_sa_bytes; };
+  union { unsigned b2_bytes; unsigned mx_sb_bytes; };
   int pg_nadd;                 // (pgemm.hip, ADD build) slots of the addend ring
 };
 
@@ -85,6 +92,9 @@ __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t rs, int byte_
   u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0);
   return make_uint4(v[0], v[1], v[2], v[3]);
 }
+__device__ __forceinline__ unsigned buf_load4(__amdgpu_buffer_rsrc_t rs, int byte_off) {
+  return __builtin_amdgcn_raw_buffer_load_b32(rs, byte_off, 0, 0);
+}
 
 
 // Persistent pipelined GEMM for 1x1 / unit-stride convs (pgemm.hip): `a` filled exactly as for dispatch_gather.
@@ -92,6 +102,7 @@ bool pgemm_eligible(const GatherArgs& a, int elem_size);
 int dispatch_pgemm(GatherArgs& a, hipStream_t st);
 
 // fp8-operand build of the gather GEMM (igemm_fp8.hip).  `a` is filled exactly as for the bf16 kernel (element = byte).
+// mx_sa / mx_sb set (both e4m3): the block-scaled (MX) build; the per-tensor scale2 / scale3 are then null.
 int dispatch_gather_fp8(GatherArgs& a, hipStream_t st);
 
 // out[i] (+)= sum over S fp32 slabs of n elements, `stride` elements apart (igemm.hip; also used by wgrad_fp8.hip)

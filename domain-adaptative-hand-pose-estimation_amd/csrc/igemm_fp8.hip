@@ -165,13 +165,14 @@ extern "C" int mi355_pack_weights_fp8(const float* w_master, void* wf, void* wt,
 }
 
 // ------------------------------------------------------------------------------------ gather GEMM, fp8 operands
-template <int BM, int BN, bool KW3 = false>
+template <int BM, int BN, bool KW3 = false, bool MX = false>
 struct Fp8Smem {
   static constexpr int kARows = KW3 ? BM + 4 * (BM / 8) + 4 : BM;        // KW3: segmented A image with spare rows (as GatherSmem)
   static constexpr int kStage = (kARows + BN) * 128;
+  static constexpr int kScales = MX ? (BM + BN) * 4 : 0;     // MX: one scale dword per A row and per B row, behind the stage
   static constexpr int kOutStride = BN * 2 + 16;             // bf16 output tile rows
   static constexpr int kOut = BM * kOutStride;
-  static constexpr int kBytes = (kStage > kOut ? kStage : kOut) + BM * 4;
+  static constexpr int kBytes = (kStage + kScales > kOut ? kStage + kScales : kOut) + BM * 4;
 };
 
 // 4 waves (2 x 2), each a (BM/2) x (BN/2) sub-tile of 32x32 MFMA blocks.  K-tile = 128 channels of one tap
@@ -181,14 +182,21 @@ struct Fp8Smem {
 // -1 / 0 / +1, so one staged A tile per (kernel row, 128-channel chunk) serves three K sub-steps -- the construction of the bf16
 // kernel's KW3 path (igemm.hip), whose 128-byte rows carry 64 bf16 channels where these carry 128 fp8 channels: same LDS image,
 // same shifted fragment reads.  With the K=64 MFMA these layers are bounded by the tile fills; this takes a third of them away.
-template <int BM, int BN, bool A_BF8, int EPI, bool KW3 = false>
+// MX: block-scaled e4m3 operands (mx_fp8.hip): one E8M0 scale per 32 contracted elements of every A row and B row.  A K tile
+// (one tap, 128 channels) is four such blocks per row, so with each tile thread t < BM also fetches the scale dword of A row t
+// (same pixel / tap / OOB predicate as that row's data) and BM <= t < BM + BN the one of B row t - BM; they are staged next to
+// the tile.  The instruction applies lane half hi's scale to its K block hi, which spans both halves (see the fragment
+// reads); the fragments are read so that this block is MX block 2u + hi of the row: the lane shifts its row's dword right by
+// 8 hi and the MFMA's wave-uniform byte select takes byte 2u.  Plain (non-KW3) path only.
+template <int BM, int BN, bool A_BF8, int EPI, bool KW3 = false, bool MX = false>
 __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
+  static_assert(!(MX && (KW3 || A_BF8)), "MX: e4m3 operands on the plain path");
   constexpr int CHI = 16;                                     // fp8 elements per 16-byte chunk
   constexpr int CHO = 8;                                      // bf16 output elements per chunk
   constexpr int NTHR = 256, RPP = 32;
   constexpr int WM = BM / 2, WN = BN / 2, MT = WM / 32, NT = WN / 32;
   constexpr int RA = BM / RPP, RB = BN / RPP;
-  using SM = Fp8Smem<BM, BN, KW3>;
+  using SM = Fp8Smem<BM, BN, KW3, MX>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int* row_off = reinterpret_cast<int*>(smem + SM::kBytes - BM * 4);
 
@@ -223,6 +231,18 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
     row_off[t] = off;
   }
   const int cmask = (1 << p.cshift) - 1;
+  [[maybe_unused]] int s_iy = -(1 << 20), s_ix = 0, s_pix = 0, s_n = 0;     // MX: this thread's scale row (see above)
+  [[maybe_unused]] unsigned rsc = 0;                                          // MX: its scale dword for the next K tile
+  if constexpr (MX) {
+    if (t < BM) {
+      const int m = m0 + t;
+      if (m < pM) {
+        const int ox = m % pOWp, r = m / pOWp, oy = r % pOHp, n = r / pOHp;
+        s_iy = oy * p.in_sy; s_ix = ox * p.in_sx;
+        s_pix = (n * p.Hi * p.Wi + s_iy * p.Wi + s_ix) * p.Ci;
+      }
+    } else s_n = n0 + t - BM;
+  }
   uint4 ra0[RA], rb0[RB];
   auto load_tile = [&](int kt, uint4 (&ra)[RA], uint4 (&rb)[RB]) {
     const Tap tp = ptaps[(kt * 8) >> p.cshift];
@@ -239,6 +259,16 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
     for (int i = 0; i < RB; ++i) {
       const int n = n0 + lr + RPP * i;
       rb[i] = buf_load16(rsB, n < p.Nout ? n * p.ldb + koff : OOB_OFF);
+    }
+    if constexpr (MX) {
+      const int c0 = ((kt * 8) & cmask) * CHI;                // first channel of the tile: scale offset = data offset / 32
+      if (t < BM) {
+        const int iy = s_iy + tp.dy, ix = s_ix + tp.dx;
+        const bool ok = (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
+        rsc = buf_load4(make_rsrc(p.mx_sa, p.mx_sa_bytes), ok ? (s_pix + ((int)tp.dy * p.Wi + (int)tp.dx) * p.Ci + c0) >> 5 : OOB_OFF);
+      } else if (t < BM + BN) {
+        rsc = buf_load4(make_rsrc(p.mx_sb, p.mx_sb_bytes), s_n < p.Nout ? (s_n * p.ldb + (int)tp.widx * p.Ci + c0) >> 5 : OOB_OFF);
+      }
     }
   };
   char* as = smem;
@@ -335,7 +365,16 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
     for (int i = 0; i < RA; ++i) *reinterpret_cast<uint4*>(as + swz128(lr + RPP * i, lc)) = ra0[i];
 #pragma unroll
     for (int i = 0; i < RB; ++i) *reinterpret_cast<uint4*>(bs + swz128(lr + RPP * i, lc)) = rb0[i];
+    if constexpr (MX) { if (t < BM + BN) reinterpret_cast<unsigned*>(smem + SM::kStage)[t] = rsc; }
     __syncthreads();
+    [[maybe_unused]] unsigned sa[MT], sb[NT];               // MX: this lane's row scales, its block's byte moved to 2u
+    if constexpr (MX) {
+      const unsigned* sc = reinterpret_cast<const unsigned*>(smem + SM::kStage);
+#pragma unroll
+      for (int i = 0; i < MT; ++i) sa[i] = sc[wm0 + i * 32 + r31] >> (8 * hi);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) sb[j] = sc[BM + wn0 + j * 32 + r31] >> (8 * hi);
+    }
     if (kt + 1 < nk) load_tile(kt + 1, ra0, rb0);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -344,15 +383,18 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
       // 4u + 2hi + 1 of the 128-byte row).  The K=64 instruction does the work of four 32x32x16 fp8 MFMAs in the cycles of two
       // (16 passes against 4 x 8; profiles/mx_mfma_probe.hip: same bits, 3.8 against 1.9 PFLOP/s).  It is the block-scaled
       // instruction with both scale operands the literal 0, which the compiler emits as the unscaled opcode.
+      // MX: the instruction's K index of (lane half hi, byte j) is 16 (j / 8) + 8 hi + j % 8 (profiles/mx_mfma_probe.hip), so its
+      // scale block 0 / 1 is bytes 0-15 / 16-31 of BOTH halves: half hi reads chunks 4u + hi and 4u + 2 + hi, which puts the
+      // 32 channels of MX block 2u in the first and those of 2u + 1 in the second; half hi supplies the scale of block 2u + hi.
       uint4 a[MT][2], b[NT][2];
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) a[i][c] = *reinterpret_cast<const uint4*>(as + swz128(wm0 + i * 32 + r31, 4 * u + 2 * hi + c));
+        for (int c = 0; c < 2; ++c) a[i][c] = *reinterpret_cast<const uint4*>(as + swz128(wm0 + i * 32 + r31, MX ? 4 * u + hi + 2 * c : 4 * u + 2 * hi + c));
 #pragma unroll
       for (int j = 0; j < NT; ++j)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) b[j][c] = *reinterpret_cast<const uint4*>(bs + swz128(wn0 + j * 32 + r31, 4 * u + 2 * hi + c));
+        for (int c = 0; c < 2; ++c) b[j][c] = *reinterpret_cast<const uint4*>(bs + swz128(wn0 + j * 32 + r31, MX ? 4 * u + hi + 2 * c : 4 * u + 2 * hi + c));
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -361,7 +403,12 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
           const i32x8_t bv = {(int)b[j][0].x, (int)b[j][0].y, (int)b[j][0].z, (int)b[j][0].w, (int)b[j][1].x, (int)b[j][1].y, (int)b[j][1].z, (int)b[j][1].w};
           // operands swapped (weights first): acc holds D^T, lane = output pixel, registers = runs of 4 channels.
           // cbsz / blgp = formats of the first / second operand: 0 = e4m3, 1 = e5m2
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bv, av, acc[i][j], 0, A_BF8 ? 1 : 0, 0, 0, 0, 0);
+          if constexpr (MX) {     // scales: the weight row's first, then the pixel row's; byte select 2u (a constant)
+            if (u == 0) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bv, av, acc[i][j], 0, 0, 0, (int)sb[j], 0, (int)sa[i]);
+            else acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bv, av, acc[i][j], 0, 0, 2, (int)sb[j], 2, (int)sa[i]);
+          } else {
+            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bv, av, acc[i][j], 0, A_BF8 ? 1 : 0, 0, 0, 0, 0);
+          }
         }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -460,9 +507,9 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
   }
 }
 
-template <int BM, int BN, bool KW3 = false>
+template <int BM, int BN, bool KW3 = false, bool MX = false>
 static void launch_fp8(GatherArgs& a, hipStream_t st) {
-  constexpr int smem = Fp8Smem<BM, BN, KW3>::kBytes;
+  constexpr int smem = Fp8Smem<BM, BN, KW3, MX>::kBytes;
   a.ntn = cdiv(a.Nout, BN);
   int mx = 0;
   for (int i = 0; i < a.nphase; ++i) { a.ph[i].ntm = cdiv(a.ph[i].M, BM); if (a.ph[i].ntm > mx) mx = a.ph[i].ntm; }
@@ -474,10 +521,11 @@ static void launch_fp8(GatherArgs& a, hipStream_t st) {
     if (even && (size_t)a.nphase * mx * a.Nout * 3 * sizeof(float) <= a.stat_bytes) a.stat_slices = a.nphase * mx;
     else a.stat_partial = nullptr;
   }
-#define MI_L(BF8, EPI) do { auto kern = gather_fp8_kernel<BM, BN, BF8, EPI, KW3>; static bool set_ = false; \
+#define MI_L(BF8, EPI) do { auto kern = gather_fp8_kernel<BM, BN, BF8, EPI, KW3, MX>; static bool set_ = false; \
     if (!set_) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); set_ = true; } \
     hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(256), smem, st, a); } while (0)
-  if (a.a_fmt) { if (a.stat_partial) MI_L(true, 1); else MI_L(true, 0); }
+  if constexpr (MX) { if (a.stat_partial) MI_L(false, 1); else MI_L(false, 0); }
+  else if (a.a_fmt) { if (a.stat_partial) MI_L(true, 1); else MI_L(true, 0); }
   else { if (a.stat_partial) MI_L(false, 1); else MI_L(false, 0); }
 #undef MI_L
 }
@@ -504,7 +552,10 @@ int dispatch_gather_fp8(GatherArgs& a, hipStream_t st) {
   if (abytes >= (1L << 31) || bbytes >= (1L << 31) || Mtot * a.Nout * 2 >= (1L << 31))
     MI_FAIL(MI355_EINVAL, "fp8 gather: tensor too large for 32-bit byte offsets");
   a.a_bytes = (unsigned)abytes; a.b_bytes = (unsigned)bbytes;
-  ProfScope ps(st, flops, (double)abytes + (double)bbytes * ntaps_tot / (a.ldb / a.Ci) + (double)Mtot * a.Nout * 2);
+  const bool mx = a.mx_sa != nullptr;
+  if (mx && (!a.mx_sb || a.a_fmt || a.scale2 || a.scale3)) MI_FAIL(MI355_EINVAL, "fp8 gather: MX takes two scale arrays, e4m3 operands, no per-tensor descales");
+  if (mx) { a.mx_sa_bytes = a.a_bytes / 32; a.mx_sb_bytes = a.b_bytes / 32; }
+  ProfScope ps(st, flops, ((double)abytes + (double)bbytes * ntaps_tot / (a.ldb / a.Ci)) * (mx ? 33.0 / 32.0 : 1.0) + (double)Mtot * a.Nout * 2);
   static const int force = getenv("MI355_FP8_TILE") ? atoi(getenv("MI355_FP8_TILE")) : -1;
   const long t128 = cdiv(Mtot, 128L) * cdiv(a.Nout, 128);
   // 3x3 / unit stride / same-size maps of a power-of-two width <= 128: the A-tile-sharing variant (KW3 above; conditions as in
@@ -522,7 +573,12 @@ int dispatch_gather_fp8(GatherArgs& a, hipStream_t st) {
     for (int k = 0; k < 3; ++k) { if (tp[k].dy != tp[0].dy || tp[k].dx < -1 || tp[k].dx > 1) kw3 = false; else seen |= 1 << (tp[k].dx + 1); }
     if (seen != 7 || tp[0].dy < -1 || tp[0].dy > 1) kw3 = false;
   }
-  if (kw3) { a.lw = ilog2x(a.Wi); launch_fp8<128, 128, true>(a, st); }
+  if (mx) {      // (the KW3 row-sharing variant has no MX build)
+    if (force == 0 || (force < 0 && t128 >= 512 && a.Nout > 64)) launch_fp8<128, 128, false, true>(a, st);
+    else if (force == 1 || (force < 0 && a.Nout > 64 && cdiv(Mtot, 64L) * cdiv(a.Nout, 128) >= 256)) launch_fp8<64, 128, false, true>(a, st);
+    else launch_fp8<64, 64, false, true>(a, st);
+  }
+  else if (kw3) { a.lw = ilog2x(a.Wi); launch_fp8<128, 128, true>(a, st); }
   else if (force == 0 || (force < 0 && t128 >= 512 && a.Nout > 64)) launch_fp8<128, 128>(a, st);
   else if (force == 1 || (force < 0 && a.Nout > 64 && cdiv(Mtot, 64L) * cdiv(a.Nout, 128) >= 256)) launch_fp8<64, 128>(a, st);
   else launch_fp8<64, 64>(a, st);

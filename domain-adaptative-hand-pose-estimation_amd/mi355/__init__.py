@@ -60,6 +60,11 @@ SIGNATURES = {
     'mi355_pack_weights_fp8_batched': (_I, [_P, _I, _I, _P]),
     'mi355_conv_fwd_fp8': (_I, [_D, _P, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P]),
     'mi355_conv_dgrad_fp8': (_I, [_D, _P, _I, _P, _P, _P, _P, _I, _P, _P, _Z, _P, _P]),
+    'mi355_mx_quantize': (_I, [_P, _P, _P, _L, _I, _I, _P]),
+    'mi355_pack_weights_mx': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'mi355_pack_weights_mx_batched': (_I, [_P, _I, _I, _P]),
+    'mi355_conv_fwd_mx': (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P]),
+    'mi355_conv_dgrad_mx': (_I, [_D, _P, _P, _P, _P, _P, _I, _P, _P, _Z, _P, _P]),
     'mi355_conv_wgrad_workspace': (_Z, [_D]),
     'mi355_conv_wgrad_fp8_workspace': (_Z, [_D]),
     'mi355_conv_wgrad_fp8': (_I, [_D, _P, _I, _P, _I, _P, _P, _P, _I, _P, _Z, _P]),
@@ -179,22 +184,30 @@ _compute_dtype = torch.bfloat16
 
 
 _fp8_convs = False
+_mx_convs = False
 
 
 def set_compute_dtype(dt):
-    """'bf16' (default, throughput path), 'f32' (exact-fp32 MFMA parity path) or 'fp8': bf16 storage and kernels
-    everywhere, except that the forward and input-gradient GEMMs of the K-heavy convolutions (3x3 / 4x4, channel counts
-    that are multiples of 128) run on fp8 operands (e4m3 activations and weights, e5m2 gradients, per-tensor delayed
-    scaling, fp32 accumulate); weight gradients stay bf16."""
-    global _compute_dtype, _fp8_convs
+    """'bf16' (default, throughput path), 'f32' (exact-fp32 MFMA parity path), 'fp8' or 'mxfp8'.
+
+    'fp8': bf16 storage and kernels everywhere, except that the forward and input-gradient GEMMs of the K-heavy convolutions
+    (3x3 / 4x4, channel counts that are multiples of 128) run on fp8 operands (e4m3 activations and weights, e5m2 gradients,
+    per-tensor delayed scaling, fp32 accumulate); weight gradients stay bf16.
+
+    'mxfp8': the same convolutions -- the 4x4 transposed convs of the neck included -- on MX operands instead: e4m3 for every
+    operand, gradients included, with one E8M0 scale per 32 contracted elements (mx_fp8.hip), no scaling state; weight
+    gradients stay bf16, eval-mode modules take the BatchNorm-folded bf16 path, the MI355_FP8_* switches do not apply."""
+    global _compute_dtype, _fp8_convs, _mx_convs
     if dt in ('bf16', torch.bfloat16):
-        _compute_dtype, _fp8_convs = torch.bfloat16, False
+        _compute_dtype, _fp8_convs, _mx_convs = torch.bfloat16, False, False
     elif dt in ('f32', 'fp32', torch.float32):
-        _compute_dtype, _fp8_convs = torch.float32, False
+        _compute_dtype, _fp8_convs, _mx_convs = torch.float32, False, False
     elif dt in ('fp8', 'f8'):
-        _compute_dtype, _fp8_convs = torch.bfloat16, True
+        _compute_dtype, _fp8_convs, _mx_convs = torch.bfloat16, True, False
+    elif dt in ('mxfp8', 'mx'):
+        _compute_dtype, _fp8_convs, _mx_convs = torch.bfloat16, False, True
     else:
-        raise ValueError('compute dtype must be bf16, f32 or fp8, got %r' % (dt,))
+        raise ValueError('compute dtype must be bf16, f32, fp8 or mxfp8, got %r' % (dt,))
 
 
 def graph_capture_mode():
@@ -220,6 +233,11 @@ def compute_dtype():
 
 def fp8_convs():
     return _fp8_convs
+
+
+def mx_convs():
+    """True in 'mxfp8' mode: the K-heavy convs run their forward and input gradient on MX (block-scaled e4m3) operands."""
+    return _mx_convs
 
 
 # ---------------------------------------------------------------- fp8 scaling states (delayed scaling)

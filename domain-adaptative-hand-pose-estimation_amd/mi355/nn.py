@@ -298,6 +298,46 @@ class _Fp8Stream:
         return q, q._mi_rec
 
 
+class _PackedMx:
+    """'mxfp8' mode: MX copies of one conv-form weight -- e4m3 [O][T][I] with its E8M0 scales [O][T][I/32] (forward operand) and
+    e4m3 [I][T][O] with scales [I][T][O/32] (input-gradient operand), both quantised from the fp32 master -- refreshed when the
+    master changes.  Keyed by parameter version, shape and device; not a state_dict entry."""
+
+    def __init__(self):
+        self.key = None
+        self.wf = self.sf = self.wt = self.st = None
+
+    def get(self, weight, O, T, I):
+        key = (_param_version(weight), O, T, I, weight.device)
+        if key != self.key:
+            n = O * T * I
+            if self.wf is None or self.wf.numel() != n or self.wf.device != weight.device:
+                if torch.cuda.is_current_stream_capturing():
+                    raise Mi355Error('MX weight copies are created on first use: run one eager iteration before capturing')
+                self.wf, self.wt = (torch.empty(n, dtype=torch.uint8, device=weight.device) for _ in range(2))
+                self.sf, self.st = (torch.empty(n // ops.MX_BLOCK, dtype=torch.uint8, device=weight.device) for _ in range(2))
+            ops.pack_weights_mx(weight.detach(), O, T, I, self.wf, self.sf, self.wt, self.st)
+            self.key = key
+            weight._mi_packmx = (self, O, T, I)          # lets the optimizer refresh all MX copies of a group in one launch
+        return self.wf, self.sf, self.wt, self.st
+
+
+def _mx_copy(t):
+    """(e4m3 copy, E8M0 scales) of a bf16 NHWC activation / gradient, quantised once however many MX GEMMs consume it: the
+    copy rides on the tensor (like _mi_q8) and is valid while the tensor's version is unchanged."""
+    hit = getattr(t, '_mi_mx', None)
+    if hit is not None and hit[2] == t._version:
+        return hit[0], hit[1]
+    q, sc = ops.mx_quantize(t)
+    t._mi_mx = (q, sc, t._version)
+    return q, sc
+
+
+def _mx_eligible(cin, cout):
+    """channel counts the MX GEMMs take as contracted axes: power-of-two multiples of the 128-channel K tile"""
+    return all(c >= 128 and c % 128 == 0 and (c & (c - 1)) == 0 for c in (cin, cout))
+
+
 _PACK_BATCHED = __import__('os').environ.get('MI355_PACK_BATCHED', '1') == '1'
 
 
@@ -354,6 +394,32 @@ def repack_params_fp8(params, cache):
     ops.pack_weights_fp8_batched(cache['tab8'], len(ents), cache['blocks8'])
     for p, (pk, O, T, I) in ents:
         pk.key = (_param_version(p), O, T, I)
+
+
+def repack_params_mx(params, cache):
+    """'mxfp8' mode: the MX copies of every conv weight in `params` refreshed by ONE kernel right after the optimizer step, so
+    that the forward and input gradient of the next pass -- replayed graphs included -- read packs of the new weights."""
+    if not _PACK_BATCHED or not _rt.mx_convs():
+        return
+    ents = [(p, p._mi_packmx) for p in params if getattr(p, '_mi_packmx', None) is not None and p._mi_packmx[0].wf is not None]
+    if not ents:
+        return
+    sig = tuple((p.data_ptr(), e[0].wf.data_ptr(), e[0].sf.data_ptr(), e[0].wt.data_ptr(), e[0].st.data_ptr()) for p, e in ents)
+    if cache.get('sigmx') != sig:
+        if torch.cuda.is_current_stream_capturing():
+            return                                     # table not built yet: the convs repack lazily
+        import numpy as np
+        rec = np.zeros(len(ents), dtype=[('w', '<u8'), ('wf', '<u8'), ('sf', '<u8'), ('wt', '<u8'), ('st', '<u8'), ('O', '<i4'),
+                                         ('T', '<i4'), ('I', '<i4'), ('blk0', '<i4')])
+        blk = 0
+        for i, (p, (pk, O, T, I)) in enumerate(ents):
+            rec[i] = (p.data_ptr(), pk.wf.data_ptr(), pk.sf.data_ptr(), pk.wt.data_ptr(), pk.st.data_ptr(), O, T, I, blk)
+            blk += (O // 32) * (I // 32) * T
+        cache['tabmx'] = torch.from_numpy(rec.view(np.uint8).copy()).to(ents[0][0].device)
+        cache['blocksmx'], cache['sigmx'] = blk, sig
+    ops.pack_weights_mx_batched(cache['tabmx'], len(ents), cache['blocksmx'])
+    for p, (pk, O, T, I) in ents:
+        pk.key = (_param_version(p), O, T, I, p.device)
 
 
 def _chk_convform(weight):
@@ -486,10 +552,17 @@ def _conv_forward(ctx, mod, x, bias, residual, stats_ok=True):
     """conv forward on the bf16 / fp32 kernels or, in 'fp8' mode, on fp8 operands; leaves the plan on ctx."""
     want = stats_ok and mod._want_stats() and residual is None
     ok8 = mod._fp8_ok(x)
+    ctx.mx = mod._mx_ok(x)                                       # ('mxfp8' mode: forward and input gradient on MX operands)
     ctx.fp8 = ok8 and 'd' in _FP8_PARTS                          # (input gradient on fp8 operands)
     if ok8:
         desc, ctx.desc8, wf8, _, sw = mod._plan_fp8(x)
-    if ok8 and 'f' in _FP8_PARTS:
+    if ctx.mx:
+        desc, ctx.desc8, wfm, sfm, _, _ = mod._plan_mx(x)
+        xm, sxm = _mx_copy(x)
+        y = ops.conv_fwd_mx(ctx.desc8, xm, sxm, wfm, sfm, bias, residual, want_stats=want)
+        if want:
+            y, mod._last_partial = y
+    elif ok8 and 'f' in _FP8_PARTS:
         x8, sx = mod._q_in.quantize(x)
         ctx.x8 = (x8, sx) if mod._fp8_wgrad_ok(x) else None      # the weight gradient reads the same e4m3 copy
         y = ops.conv_fwd_fp8(ctx.desc8, x8, sx, wf8, sw, bias, residual, want_stats=want)
@@ -536,12 +609,17 @@ def _conv_wgrad(ctx, x, dy, weight):
 
 def _conv_dgrad(ctx, x, dy, scale_dev=None, out=None, accumulate=False, acc_mask=None):
     mod = ctx.mod
+    mx = getattr(ctx, 'mx', False)
     if acc_mask is not None:
-        if ctx.fp8 or ctx.bn_src is not None or not accumulate:
+        if ctx.fp8 or mx or ctx.bn_src is not None or not accumulate:
             ops.apply_relu_mask(out, acc_mask)          # (paths without the masked epilogue: mask first, then accumulate)
         else:
             _, _, wt = mod._plan(x)
             return ops.conv_dgrad_masked_acc(ctx.desc, dy, wt, out, acc_mask, scale_dev=scale_dev)
+    if mx:
+        _, _, _, _, wtm, stm = mod._plan_mx(x)
+        dym, sdym = _mx_copy(dy)
+        return ops.conv_dgrad_mx(ctx.desc8, dym, sdym, wtm, stm, scale_dev=scale_dev, out=out, accumulate=accumulate)
     if ctx.fp8:
         _, _, _, wt8, sw = mod._plan_fp8(x)
         dy8, sdy = mod._q_dy.quantize(dy)
@@ -619,7 +697,15 @@ class _DeconvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, mod):
         ctx.fp8 = mod._fp8_ok(x)
-        if ctx.fp8:      # conv-form dgrad with the deconv input as the gathered (e4m3) operand
+        ctx.mx = mod._mx_ok(x)
+        if ctx.mx:       # 'mxfp8' mode: conv-form dgrad on MX operands (the deconv input, blocks along its channels)
+            desc, desc8, _, _, wtm, stm = mod._plan_mx(x)
+            xm, sxm = _mx_copy(x)
+            y = ops.conv_dgrad_mx(desc8, xm, sxm, wtm, stm, want_stats=mod._want_stats())
+            if mod._want_stats():
+                y, mod._last_partial = y
+            ctx.desc8 = desc8
+        elif ctx.fp8:    # conv-form dgrad with the deconv input as the gathered (e4m3) operand
             desc, desc8, _, wt8, sw = mod._plan_fp8(x)
             x8, sx = mod._q_in.quantize(x)
             ctx.x8 = (x8, sx) if mod._fp8_wgrad_ok(x) else None      # the weight gradient reads the same e4m3 copy
@@ -658,7 +744,11 @@ class _DeconvFn(torch.autograd.Function):
                 _rt.group_wgrad(desc, dy, x, g, acc)
             else:
                 ops.conv_wgrad(desc, dy, x, g, acc)      # conv-form input = dy, conv-form output = x
-        if ctx.needs_input_grad[0] and ctx.fp8:
+        if ctx.needs_input_grad[0] and ctx.mx:
+            _, _, wfm, sfm, _, _ = mod._plan_mx(x)
+            dym, sdym = _mx_copy(dy)
+            dx = ops.conv_fwd_mx(ctx.desc8, dym, sdym, wfm, sfm)
+        elif ctx.needs_input_grad[0] and ctx.fp8:
             _, _, wf8, _, sw = mod._plan_fp8(x)
             dy8, sdy = mod._q_dy.quantize(dy)
             dx = ops.conv_fwd_fp8(ctx.desc8, dy8, sdy, wf8, sw, x_fmt=_GRAD_FMT)
@@ -1011,6 +1101,7 @@ class Conv2d(_FastSlots, nn.Module):
         self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
         self._packed = _PackedWeights()
         self._packed8, self._q_in, self._q_dy = _PackedFp8(), _Fp8Stream(ops.E4M3), _Fp8Stream(_GRAD_FMT)
+        self._packedmx = _PackedMx()
         self._cast = _CastCopy()
         self._cast_t = _CastCopy(transposed=True)
         self._folded = _FoldedBn()
@@ -1084,6 +1175,21 @@ class Conv2d(_FastSlots, nn.Module):
             return False
         # a 1x1 conv is HBM-bound: worth it only when its producer already wrote the fp8 copy of x (BatchNorm side output)
         return self.kernel_size[0] >= 3 or _cached_q8(x, ops.E4M3) is not None
+
+    def _mx_ok(self, x):
+        """MX operands for this conv's forward and input gradient?  'mxfp8' compute mode, training mode, a 3x3 / 4x4 kernel,
+        groups 1 and channel counts the 128-channel K tile divides (eligibility as _fp8_ok; no 1x1 side-output route)."""
+        return (_rt.mx_convs() and self.training and self.mode == 'mfma' and self.groups == 1 and x.dtype == torch.bfloat16 and
+                self.kernel_size[0] in (3, 4) and not self._s2d_ok(x) and _mx_eligible(self.in_channels, self.out_channels))
+
+    def _plan_mx(self, x):
+        N, C, H, W = x.shape
+        k = self.kernel_size[0]
+        _chk_convform(self.weight)
+        desc = ops.make_desc(N, H, W, C, self.out_channels, k, k, self.stride[0], self.padding[0], x.dtype)
+        desc8 = ops.make_desc_fp8(N, H, W, C, self.out_channels, k, k, self.stride[0], self.padding[0])
+        wf, sf, wt, st = self._packedmx.get(self.weight, self.out_channels, k * k, self.in_channels)
+        return desc, desc8, wf, sf, wt, st
 
     def _fp8_wgrad_ok(self, x):
         """weight gradient from the fp8 copies too?  The 3x3 / pad-1 layers the two kernels of mi355_conv_wgrad_fp8 take:
@@ -1212,8 +1318,8 @@ class Conv2d(_FastSlots, nn.Module):
             return None
         x, scale = _claim_gl(x, dtype)
         x = _as_feature(x, dtype)
-        if self._fp8_ok(x):
-            return None                      # ('fp8' mode: the 3x3 feature conv runs on fp8 operands, which have no concat-K build)
+        if self._fp8_ok(x) or self._mx_ok(x):
+            return None                      # ('fp8' / 'mxfp8' mode: the 3x3 feature conv runs on fp8 operands, which have no concat-K build)
         if hm.dtype != torch.float32 or not hm.is_contiguous():
             hm = hm.float().contiguous()
         fan = getattr(x, '_mi_fan', None) if torch.is_grad_enabled() and x.requires_grad else None
@@ -1251,6 +1357,7 @@ class ConvTranspose2d(_FastSlots, nn.Module):
         self._packed = _PackedWeights()
         self._folded = _FoldedBn()
         self._packed8, self._q_in, self._q_dy = _PackedFp8(), _Fp8Stream(ops.E4M3), _Fp8Stream(_GRAD_FMT)
+        self._packedmx = _PackedMx()
         self._last_partial = None
         self._in_bn_src = None
         self.bn_follows = False
@@ -1259,6 +1366,22 @@ class ConvTranspose2d(_FastSlots, nn.Module):
     def _fp8_ok(self, x):
         return (_FP8_DECONV and _rt.fp8_convs() and (self.training or _FP8_EVAL) and x.dtype == torch.bfloat16 and
                 self.in_channels % 128 == 0 and self.out_channels % 128 == 0)
+
+    def _mx_ok(self, x):
+        """MX operands for the forward and input gradient?  'mxfp8' compute mode, training mode and channel counts the
+        128-channel K tile divides (unlike 'fp8' mode, no opt-in: block scales keep the neck's precision)."""
+        return (_rt.mx_convs() and self.training and x.dtype == torch.bfloat16 and self.kernel_size[0] in (3, 4) and
+                _mx_eligible(self.in_channels, self.out_channels))
+
+    def _plan_mx(self, x):
+        N, C, H, W = x.shape          # conv-form output side
+        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        Hi, Wi = (H - 1) * s - 2 * p + k, (W - 1) * s - 2 * p + k
+        _chk_convform(self.weight)
+        desc = ops.make_desc(N, Hi, Wi, self.out_channels, self.in_channels, k, k, s, p, x.dtype)
+        desc8 = ops.make_desc_fp8(N, Hi, Wi, self.out_channels, self.in_channels, k, k, s, p)
+        wf, sf, wt, st = self._packedmx.get(self.weight, self.in_channels, k * k, self.out_channels)
+        return desc, desc8, wf, sf, wt, st
 
     def _fp8_wgrad_ok(self, x):
         """weight gradient from the fp8 copies too?  The 4x4 / stride-2 / pad-1 layers whose input width (the conv-form's

@@ -388,6 +388,98 @@ def conv_wgrad_fp8(desc, x8, x_state, dy8, dy_state, dw, accumulate, dy_fmt=E5M2
          ptr(dy_state[1:2]), ptr(dw), int(accumulate), ptr(ws), ws.numel(), stream_ptr())
 
 
+# ---------------------------------------------------------------- MX (block-scaled) fp8 operand path ('mxfp8' mode)
+MX_BLOCK = 32
+
+
+def mx_quantize(x, q=None, scales=None):
+    """bf16 / fp32 device tensor whose last memory axis (C, a multiple of 32) is contiguous -- an NHWC feature map or any
+    [rows][C] array -> (q, scales): e4m3 bytes shaped and strided like x, and one E8M0 byte per 32 consecutive elements of
+    a row, a uint8 tensor of x.numel() / 32 elements ([rows][C/32]).  No state (mx_fp8.hip has the scale rule)."""
+    _chk_dev(x)
+    if x.dim() == 4 and is_nhwc(x):
+        C = x.shape[1]
+    elif x.is_contiguous():
+        C = x.shape[-1] if x.dim() else 1
+    else:
+        raise Mi355Error('mx_quantize needs a contiguous or channels_last tensor')
+    if C % MX_BLOCK or C < MX_BLOCK:
+        raise Mi355Error('mx_quantize: the contiguous axis (%d) must be a multiple of %d' % (C, MX_BLOCK))
+    n = x.numel()
+    _chk_room('mx_quantize q', q, n)
+    _chk_room('mx_quantize scales', scales, n // MX_BLOCK)
+    q = q if q is not None else torch.empty_strided(x.shape, x.stride(), dtype=torch.uint8, device=x.device)
+    scales = scales if scales is not None else torch.empty(n // MX_BLOCK, dtype=torch.uint8, device=x.device)
+    _chk_dev(q, scales)
+    call('mi355_mx_quantize', ptr(x), ptr(q), ptr(scales), n // C, C, dtype_code(x.dtype), stream_ptr())
+    return q, scales
+
+
+def pack_weights_mx(w_master, O, T, I, wf=None, sf=None, wt=None, st=None):
+    """fp32 master in [O][T][I] memory order -> (wf e4m3 [O][T][I], sf [O][T][I/32], wt e4m3 [I][T][O], st [I][T][O/32]),
+    flat uint8 tensors; both packs quantised from the master."""
+    _chk_dev(w_master)
+    if w_master.dtype != torch.float32:
+        raise Mi355Error('pack_weights_mx: the master must be fp32')
+    n = O * T * I
+    _chk_room('pack_weights_mx master', w_master, n)
+    dev = w_master.device
+    for what, t, need in (('wf', wf, n), ('sf', sf, n // MX_BLOCK), ('wt', wt, n), ('st', st, n // MX_BLOCK)):
+        _chk_room('pack_weights_mx ' + what, t, need)
+    wf = torch.empty(n, dtype=torch.uint8, device=dev) if wf is None else wf
+    wt = torch.empty(n, dtype=torch.uint8, device=dev) if wt is None else wt
+    sf = torch.empty(n // MX_BLOCK, dtype=torch.uint8, device=dev) if sf is None else sf
+    st = torch.empty(n // MX_BLOCK, dtype=torch.uint8, device=dev) if st is None else st
+    _chk_dev(wf, sf, wt, st)
+    call('mi355_pack_weights_mx', ptr(w_master), ptr(wf), ptr(sf), ptr(wt), ptr(st), int(O), int(T), int(I), stream_ptr())
+    return wf, sf, wt, st
+
+
+def pack_weights_mx_batched(table, nitems, total_blocks):
+    """table: uint8 device tensor holding `nitems` mi355_packmx_item records."""
+    _chk_dev(table)
+    _chk_room('pack_weights_mx_batched table', table, nitems * 56)
+    call('mi355_pack_weights_mx_batched', ptr(table), int(nitems), int(total_blocks), stream_ptr())
+
+
+def conv_fwd_mx(desc, x8, sx, w8, sw, bias=None, residual=None, want_stats=False, out=None):
+    """y (bf16, channels_last) = conv(x8 * 2^sx, w8 * 2^sw) + bias (+ residual) on MX operands (desc from make_desc_fp8);
+    optionally the BatchNorm statistics partials of y.  Returns y or (y, (partial, nslices) | None)."""
+    _chk_dev(x8, sx, w8, sw)
+    nx, nw = desc.N * desc.Hi * desc.Wi * desc.Ci, desc.Co * desc.kh * desc.kw * desc.Ci
+    for what, t, need in (('x8', x8, nx), ('sx', sx, nx // MX_BLOCK), ('w8', w8, nw), ('sw', sw, nw // MX_BLOCK),
+                          ('residual', residual, desc.N * desc.Ho * desc.Wo * desc.Co), ('bias', bias, desc.Co),
+                          ('out', out, desc.N * desc.Ho * desc.Wo * desc.Co)):
+        _chk_room('conv_fwd_mx ' + what, t, need)
+    y = out if out is not None else nhwc_empty(desc.N, desc.Co, desc.Ho, desc.Wo, torch.bfloat16, x8.device)
+    partial, nbytes, ns = None, 0, ctypes.c_int(0)
+    if want_stats:
+        partial, nbytes = _stats_buf(desc.N * desc.Ho * desc.Wo, desc.Co, x8.device)
+    call('mi355_conv_fwd_mx', ctypes.byref(desc), ptr(x8), ptr(sx), ptr(w8), ptr(sw), ptr(bias), ptr(residual), ptr(y),
+         ptr(partial), nbytes, ctypes.byref(ns) if want_stats else None, stream_ptr())
+    if want_stats:
+        return y, ((partial, ns.value) if ns.value > 0 else None)
+    return y
+
+
+def conv_dgrad_mx(desc, dy8, sdy, wT8, swT, scale_dev=None, out=None, accumulate=False, want_stats=False):
+    """dx (bf16) = dgrad(dy8 * 2^sdy, wT8 * 2^swT) (* *scale_dev) (+ dx when accumulate) on MX operands."""
+    _chk_dev(dy8, sdy, wT8, swT)
+    ndy, nw = desc.N * desc.Ho * desc.Wo * desc.Co, desc.Co * desc.kh * desc.kw * desc.Ci
+    for what, t, need in (('dy8', dy8, ndy), ('sdy', sdy, ndy // MX_BLOCK), ('wT8', wT8, nw), ('swT', swT, nw // MX_BLOCK),
+                          ('out', out, desc.N * desc.Ci * desc.Hi * desc.Wi)):
+        _chk_room('conv_dgrad_mx ' + what, t, need)
+    dx = out if out is not None else nhwc_empty(desc.N, desc.Ci, desc.Hi, desc.Wi, torch.bfloat16, dy8.device)
+    partial, nbytes, ns = None, 0, ctypes.c_int(0)
+    if want_stats:
+        partial, nbytes = _stats_buf(desc.N * desc.Hi * desc.Wi, desc.Ci, dy8.device)
+    call('mi355_conv_dgrad_mx', ctypes.byref(desc), ptr(dy8), ptr(sdy), ptr(wT8), ptr(swT), ptr(scale_dev), int(accumulate),
+         ptr(dx), ptr(partial), nbytes, ctypes.byref(ns) if want_stats else None, stream_ptr())
+    if want_stats:
+        return dx, ((partial, ns.value) if ns.value > 0 else None)
+    return dx
+
+
 # ---------------------------------------------------------------- batch norm
 def bn_relu_mask(x):
     """uint8 buffer for the ReLU bit mask of a BatchNorm over x: one byte per 16-byte chunk of every row."""

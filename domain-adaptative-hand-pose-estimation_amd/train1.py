@@ -2,7 +2,7 @@
 """Domain-adaptive hand-pose training on the MI355X kernels — same command line, log / checkpoint layout and
 training schedule as the reference's ``train1.py`` (main :37-275, pretrain :278-325, train :328-492,
 validate :495-536, CLI :591-675).  Additive flags: ``--synthetic`` (seeded synthetic data instead of the
-out-of-scope CPU dataset layer), ``--dtype {bf16,f32}``, ``--no-graph``, ``--device-augment`` (the training
+out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--no-graph``, ``--device-augment`` (the training
 augmentation chain and its labels on the GPU).
 
     python train1.py data/H3D -t Hand3DStudio --synthetic -a resnet50 -b 64
@@ -419,7 +419,7 @@ _OPTIONS = [
     (('--ema-decay',), dict(default=0.999, type=float, metavar='ALPHA', help='unused (reference CLI parity)')),
     # additive
     (('--synthetic',), dict(action='store_true', help='seeded synthetic batches instead of the CPU dataset layer')),
-    (('--dtype',), dict(default='bf16', choices=['bf16', 'f32', 'fp8'], help="compute dtype of activations / packed weights ('fp8': bf16 storage, fp8 operands in the K-heavy conv GEMMs)")),
+    (('--dtype',), dict(default='bf16', choices=['bf16', 'f32', 'fp8', 'mxfp8'], help="compute dtype of activations / packed weights ('fp8': bf16 storage, fp8 operands in the K-heavy conv GEMMs; 'mxfp8': the same convs and the neck's transposed convs on block-scaled MX e4m3 operands)")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--device-augment',), dict(action='store_true', help='run the training augmentation chain (rotate, resized crop, colour '
                                   'jitter, blur, normalisation) and the heat-map labels on the GPU, bit-exact with the CPU chain; '

@@ -156,6 +156,38 @@ int mi355_conv_fwd_fp8(const mi355_conv_desc* d, const void* x8, int x_fmt, cons
 int mi355_conv_dgrad_fp8(const mi355_conv_desc* d, const void* dy8, int dy_fmt, const void* wT8, const float* descale_dy,
                          const float* descale_w, const float* scale_dev, int accumulate, void* dx, float* partial,
                          size_t partial_bytes, int* nslices, void* stream);
+/* ---- MX (block-scaled) fp8 operand path ('mxfp8' compute mode; the same reference layers as the fp8 path: the K-heavy
+ * 3x3 convs of uda/model/regda_7.py:4906-4929, the torchvision Bottleneck conv2 (resnet.py:92-107, stride 1 and 2) and the
+ * 4x4 transposed convs of pose_resnet2.py:33-41).  Elements e4m3 (format 0) for every operand, gradients included; one E8M0
+ * scale byte per block of 32 consecutive elements along the contracted axis; no scaling state.
+ * Scale rule (NOT OCP MX v1.0's floor(log2 amax) - 8, which saturates the top of a block): amax = m * 2^E (m in [1, 2)),
+ * e = E - 8 + (m > 1.75), clamped to [-127, 127]; byte = e + 127; element = RNE_e4m3(x * 2^-e).  All-zero block: 0x00;
+ * a block holding NaN or Inf: 0xFF (E8M0 NaN), its elements quantised with the e of its finite values.
+ *
+ * mi355_mx_quantize: x [rows][C] (bf16 or fp32, C a multiple of 32) -> q e4m3 [rows][C] and scales [rows][C/32].  x and q
+ *   16-byte aligned.
+ * mi355_pack_weights_mx: fp32 master [O][T][I] (O, I multiples of 32) -> wf e4m3 [O][T][I] + sf [O][T][I/32] (forward operand)
+ *   and wt e4m3 [I][T][O] + st [I][T][O/32] (input-gradient operand, blocks along O), both quantised from the master.
+ * mi355_pack_weights_mx_batched: the same for many weights in one launch: items in DEVICE memory, blk0 = first block of the
+ *   item = sum over earlier items of (O/32)*(I/32)*T. */
+int mi355_mx_quantize(const void* x, void* q, void* scales, long rows, int C, int src_dtype, void* stream);
+int mi355_pack_weights_mx(const float* w, void* wf, void* sf, void* wt, void* st, int O, int T, int I, void* stream);
+typedef struct mi355_packmx_item { const float* w; void* wf; void* sf; void* wt; void* st; int O, T, I, blk0; } mi355_packmx_item;
+int mi355_pack_weights_mx_batched(const mi355_packmx_item* items_dev, int nitems, int total_blocks, void* stream);
+/* mi355_conv_fwd / mi355_conv_dgrad on MX operands (d->dtype = MI355_FP8; the contracted channel count -- Ci forward, Co input
+ * gradient -- a power-of-two multiple of 128; the other a multiple of 8):
+ *   y  (bf16) = conv(x8 * 2^sx, w8 * 2^sw) + bias [+ residual]           x8 [N][Hi][Wi][Ci], sx [N][Hi][Wi][Ci/32],
+ *                                                                         w8 [Co][T][Ci],     sw [Co][T][Ci/32]
+ *   dx (bf16) = dgrad(dy8 * 2^sdy, wT8 * 2^swT) * (*scale_dev, optional) [+ dx when accumulate]
+ *                                                                         dy8 [N][Ho][Wo][Co], sdy [N][Ho][Wo][Co/32],
+ *                                                                         wT8 [Ci][T][Co],     swT [Ci][T][Co/32]
+ * (2^s: the E8M0 block scale).  fp32 accumulate; partial / nslices (nullable, together): BatchNorm statistics of the result
+ * from the epilogue, as mi355_conv_fwd_stats.  Null pointers and misaligned channel counts fail before any launch. */
+int mi355_conv_fwd_mx(const mi355_conv_desc* d, const void* x8, const void* sx, const void* w8, const void* sw, const float* bias,
+                      const void* residual, void* y, float* partial, size_t partial_bytes, int* nslices, void* stream);
+int mi355_conv_dgrad_mx(const mi355_conv_desc* d, const void* dy8, const void* sdy, const void* wT8, const void* swT,
+                        const float* scale_dev, int accumulate, void* dx, float* partial, size_t partial_bytes, int* nslices,
+                        void* stream);
 /* The 3x3 / unit-stride fp8 launches (forward and input gradient) use the variant that stages one operand tile per kernel ROW
  * and reads it shifted for the three taps (a third fewer bytes per MFMA) from `min_tiles` 128x128 output tiles on: 0 never,
  * 1 wherever the shape allows (tests), -1 back to the environment's choice (MI355_FP8_KW3, default 1024).  Returns the previous
