@@ -25,6 +25,7 @@ VARIANTS = [
     ({'MI355_WGRAD_KW': '0', 'MI355_WGRAD_KW2': '0', 'MI355_KW3': '0', 'MI355_DMA': '0'}, G8),      # generic kernels everywhere
     ({'MI355_BN_LAZY_DRES': '0', 'MI355_SKIP_FUSE': '0'}, G8),                                        # host-side fusions off
     ({'MI355_ZERO_BN_BIAS_GRAD': '0'}, G8),   # bias gradients in front of a BatchNorm as column sums (rounding noise instead of an exact zero)
+    ({'MI355_ROW_REG': '0'}, G8),            # heat-map row kernels (arg-max, soft-arg-max, KL, pseudo labels) in their loop forms at every size
 ]
 
 
