@@ -36,7 +36,7 @@ extern "C" size_t mi355_bn_workspace(long rows, int C) {
     if (q.nslices > ns) ns = q.nslices;
   }
   size_t n = (size_t)ns * C * 3;
-  if (n < 32768) n = 32768;              // the resident backward's partials: <= 256 blocks x 64 channels x 2 sums
+  if (n < 32768) n = 32768;              // (the floor the resident backward's partials needed while they lived here; callers size by it)
   return (n + 4 * (size_t)C) * sizeof(float);
 }
 extern "C" size_t mi355_colsum_workspace(long rows, int C) { return mi355_bn_workspace(rows, C); }
@@ -436,56 +436,59 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 // reduce + finalize + apply: a block per CU holds its [rows / R][64 or 32 channels] tile of x and dy in LDS between the
 // reduction and the apply pass, so both tensors are read from HBM once (3 tensor passes instead of 5) and two launch
 // boundaries disappear.  The R blocks of a channel group exchange their partial sums through device memory inside the launch
-// (guide, Guideline 16 counter form: write-through `sc1` partial stores drained by every storing wave, one agent-scope
-// arrive add per block, one relaxed poller per block with a bounded spin, `sc1` loads of the partials; the sums are folded
-// in a fixed order: bitwise reproducible).  All blocks must be resident together: the grid never exceeds the CU count.
+// as data-tagged granules (guide, Guideline 16 form R2): every partial sum travels as ONE naturally aligned 8-byte
+// {float sum, 32-bit tag} written by one write-through `sc1` store, so the data is its own flag -- nothing is drained, no block
+// arrives on a counter and nobody polls a flag word.  Every wave of a block sweeps its share of the group's R x 2 GC granules
+// with `sc1` 8-byte buffer loads and re-reads only that share (bounded) until every tag is this launch's; the sums are then
+// folded in a fixed order: bitwise reproducible.  All blocks must be resident together: the grid never exceeds the CU count.
 struct BnResArgs {
   const void* dy; const void* x; const float* mean; const float* invstd; const float* gamma; const float* beta;
   void* dx; void* dres; float* dgamma; float* dbeta; const unsigned char* mask;
-  float* partial;                       // [G][R][2 * channels per group]
   long rows; int C, G, R, rpb, keep, accumulate; float inv_rows;      // keep: rows of a block's tile that stay in LDS
-  unsigned spin_limit;                  // grid-barrier poll iterations before a block gives up (and poisons its outputs)
+  unsigned spin_limit;                  // re-reads of a wave's granules before its block gives up (and poisons its outputs)
 };
-// One 64-bit arrival counter per grid size, never reset: a launch of n blocks moves it from one multiple of n to the next, so
-// a block that drew ticket v waits for the counter to reach (v / n + 1) * n (64 bits: no wrap within the life of a process;
-// the 32-bit form would have wrapped after ~1e5 training iterations and broken every grid size that is not a power of two).
-// Launches of this kernel on one device must not overlap in time (this library issues them on one stream;
-// MI355_BN_RESIDENT=0 otherwise).  A block whose spin gives up (a co-resident kernel kept one of the grid's blocks off the chip
-// for longer than the limit) FAILS LOUDLY: it counts the event in bn_res_err[0] (sticky until mi355_bn_resident_reset) and
-// poisons everything it writes -- its dx rows, and dgamma / dbeta if it owns them -- with NaN instead of continuing on
-// incomplete sums; the host side raises on the counter (mi355.ops.bn_resident_check: train1.py once per epoch, DAStep.check_health,
-// bench.py, smoke).
-#define BN_RES_MAXBLK 1024
+// The granules live in a buffer of the library's own (block b of a launch owns slots [b][0 .. 2 GC)): nothing else ever writes
+// there, so a slot holds a tag only because some launch of this kernel put it there.  The tag of a launch is made of DEVICE state,
+// not of a kernel argument (an argument is frozen when a graph is captured): bn_res_done[kind][n] is the completion count of
+// the n-block launches of one kind (kind = granules per block: 128 bf16 / 64 fp32).  Every block reads it at entry and adds to
+// it (no value returned) as its last act: block 0 adds 257 - n, every other block 1, so a whole launch moves the word by
+// exactly 256 and every proper subset of its blocks by less.  Whatever the order in which blocks enter and leave, a block of the
+// k-th launch therefore reads a value in [256 k, 256 k + 255]: v >> 8 is the same k in every block, k + 1 in the next launch.
+//   tag = 1 << 31 | kind << 30 | (n - 1) << 22 | ((v >> 8) & 0x3fffff)          (n <= 256)
+// Why a stale slot never matches: the tag names (kind, n), so a slot last written by a launch of another kind or grid size
+// cannot match; a launch of (kind, n) rewrites EVERY slot that launches of (kind, n) read, so the newest tag of that (kind, n) in
+// any slot is the previous such launch's, k - 1.  Only neighbours must differ, so wrap-around is harmless: the 32-bit word
+// wraps at a multiple of 256 (v >> 8 simply continues modulo 2^24), and the 22 bits kept of it wrap after 4 M launches from k
+// to 0, which still differs from k.  Tag 0 is never formed; mi355_bn_resident_reset zeroes the counts AND every slot, so no
+// slot can match afterwards.
+// Launches of this kernel on one device must not overlap in time: two launches in flight would share slots and, at equal (kind,
+// n), the tag (this library issues them on one stream; MI355_BN_RESIDENT=0 otherwise).  A block one of whose waves gives up (a
+// co-resident kernel kept one of the grid's blocks off the chip for longer than the limit) FAILS LOUDLY: it counts the event in
+// bn_res_err[0] (sticky until mi355_bn_resident_reset) and poisons everything it writes -- its dx rows, and dgamma / dbeta if it
+// owns them -- with NaN instead of continuing on incomplete sums; the host side raises on the counter
+// (mi355.ops.bn_resident_check: train1.py once per epoch, DAStep.check_health, bench.py, smoke).
+#define BN_RES_MAXBLK 256  // blocks of a launch (one per CU)
+#define BN_RES_GRAN 128    // granule slots per block: 2 sums x 64 channels (bf16); fp32 blocks use the first 64
+#define BN_RES_SW 8        // granule loads a lane keeps in flight per sweep
 #define BN_RES_KR 0        // tile rows per thread held in registers (8 VGPRs each)
 #define BN_RES_NT 1024     // threads per block
-__device__ unsigned long long bn_res_sync[BN_RES_MAXBLK + 1];     // [n] arrivals of the n-block launches
-__device__ unsigned bn_res_err[4];                                // [0]: spins that gave up since load / reset
+__device__ unsigned long long bn_res_gran[BN_RES_MAXBLK * BN_RES_GRAN];     // {sum: low word, tag: high word}
+__device__ unsigned bn_res_done[2][BN_RES_MAXBLK + 1];                      // [kind][n] blocks of the n-block launches that have ended
+__device__ unsigned bn_res_err[4];                                          // [0]: blocks that gave up since load / reset
+static_assert(BN_RES_MAXBLK == 256, "a launch adds 256 to its completion count and the tag keeps 8 bits of n - 1");
 
-// returns false (in every thread of the block) when the spin gave up
-__device__ __forceinline__ bool bn_res_grid_barrier(unsigned nblk, int t, unsigned spin_limit, int* ok_lds) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave: its sc1 partial stores have left
-  __syncthreads();
-  if (t == 0) {
-    int ok = 1;
-    unsigned long long* st = bn_res_sync + nblk;
-    const unsigned long long v = __hip_atomic_fetch_add(st, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long target = (v / nblk + 1ull) * nblk;
-    if (v + 1ull != target) {             // (the last arriver has nothing to wait for)
-      unsigned spins = 0;
-      while (__hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        __builtin_amdgcn_s_sleep(4);
-        if (++spins > spin_limit) {       // default ~0.3 s: a block that never became resident
-          __hip_atomic_fetch_add(bn_res_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = 0;
-          break;
-        }
-      }
-    }
-    *ok_lds = ok;
-  }
-  __syncthreads();
-  return *ok_lds != 0;
+// In-kernel time stamps for profiles/bn_exchange_anatomy.py: compiled in only with -DBN_RES_STAMPS (build.py --variant), never
+// in the default library.  Thread 0 of every block stores the 100 MHz wall clock at six points (ordinary vector stores).
+#ifdef BN_RES_STAMPS
+__device__ unsigned long long bn_res_stamp[BN_RES_MAXBLK * 8];
+#define BN_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (t == 0) bn_res_stamp[blockIdx.x * 8 + (k)] = wall_clock64(); \
+                         __builtin_amdgcn_sched_barrier(0); } while (0)
+extern "C" int mi355_bn_resident_stamps(unsigned long long* out) {      // out[BN_RES_MAXBLK][8]; synchronises the device
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(bn_res_stamp), sizeof(unsigned long long) * BN_RES_MAXBLK * 8) == hipSuccess ? MI355_OK : MI355_ELAUNCH;
 }
+#else
+#define BN_STAMP(k) do {} while (0)
+#endif
 
 // A block's tile, by row: the first KR * NT / 8 rows live in REGISTERS (row ty + k NT / 8 in slot k of its thread), the
 // next `keep` rows in LDS, the rest is streamed from HBM in both passes.  Built with KR = 0, NT = 1024: 512 threads with
@@ -503,12 +506,19 @@ __global__ __launch_bounds__(NT) void bn_bwd_resident_kernel(BnResArgs p) {
   const int keep = p.keep;
   uint4* xs = reinterpret_cast<uint4*>(smem);
   uint4* ds = xs + (size_t)keep * 8;
-  float* red = reinterpret_cast<float*>(ds + (size_t)keep * 8);      // [NW][GC][2], later [NL][GC*2]
-  float* tot = red + NW * GC * 2;                                    // [GC*2]
-  int* bar_ok = reinterpret_cast<int*>(tot + GC * 2);                // the grid barrier's verdict, broadcast to the block
+  float* red = reinterpret_cast<float*>(ds + (size_t)keep * 8);      // [NW][GC][2]: the block's own fold
+  float* grp = red + NW * GC * 2;                                    // [NL][GC*2]: the group's fold (the waves that sweep do not wait for the ones that still read `red`)
+  float* tot = grp + NL * GC * 2;                                    // [GC*2]
+  int* bar_ok = reinterpret_cast<int*>(tot + GC * 2);                // the exchange's verdict, broadcast to the block
   const T* __restrict__ X = reinterpret_cast<const T*>(p.x);
   const T* __restrict__ DY = reinterpret_cast<const T*>(p.dy);
   const int C = p.C, cpr = C / CH, c0 = g * GC + tx * CH, chunk = c0 / CH;
+  BN_STAMP(0);
+  // this launch's tag (see bn_res_done): read at entry, needed only when the block publishes
+  const unsigned nblk = (unsigned)(p.G * p.R);
+  unsigned* done = &bn_res_done[GC * 2 == BN_RES_GRAN ? 1 : 0][nblk];
+  const unsigned tag = 0x80000000u | (GC * 2 == BN_RES_GRAN ? 0x40000000u : 0u) | ((nblk - 1u) << 22) |
+                       ((__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 8) & 0x3fffffu);
   float mu[CH], is[CH], sc[CH], sft[CH], s1[CH], s2[CH];
 #pragma unroll
   for (int e = 0; e < CH; ++e) {
@@ -572,41 +582,58 @@ __global__ __launch_bounds__(NT) void bn_bwd_resident_kernel(BnResArgs p) {
 #pragma unroll
     for (int e = 0; e < CH; ++e) { red[(wave * GC + tx * CH + e) * 2] = s1[e]; red[(wave * GC + tx * CH + e) * 2 + 1] = s2[e]; }
   }
+  if (t == 0) *bar_ok = 1;
+  BN_STAMP(1);
   __syncthreads();
-  float* part = p.partial + ((size_t)g * p.R) * (GC * 2);
+  // ---- publish: one granule per partial sum, the data is the flag (nothing to drain, nobody to tell)
   if (t < GC * 2) {
     float a = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) a += red[w * GC * 2 + t];
-    __hip_atomic_store(part + (size_t)r * (GC * 2) + t, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // sc1: write-through
+    __hip_atomic_store(bn_res_gran + (size_t)blockIdx.x * BN_RES_GRAN + t, ((unsigned long long)tag << 32) | __float_as_uint(a),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ONE aligned 8-byte sc1 (write-through) store
   }
-  const bool exchanged = bn_res_grid_barrier((unsigned)(p.G * p.R), t, p.spin_limit, bar_ok);
-  // ---- the group's totals: NL lanes per value over the R blocks (fixed order), then the lanes in order
+  BN_STAMP(2);
+  // ---- the group's totals: NL lanes per value over the R blocks (fixed order), then the lanes in order.  Lane s of value i
+  // takes the granules of rows s, s + NL, ...: BN_RES_SW sc1 buffer loads (aux 16) in flight, re-read until each carries this
+  // launch's tag (the rows of a batch beyond R count as 0, which leaves the bits of the sum as they are: it is never -0).
   {
-    // sc1 buffer loads (aux 16), eight in flight per thread: atomic loads would be waited for one at a time
-    const int i = t % (GC * 2), s = t / (GC * 2);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(part, 0, (unsigned)(p.R * GC * 2 * 4), 0x00020000);
+    const int i = t % (GC * 2), s = t / (GC * 2);      // (s is the same in all lanes of a wave: GC * 2 >= 64)
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(bn_res_gran, 0, (unsigned)sizeof(bn_res_gran), 0x00020000);
     float a = 0.f;
-    for (int rr0 = s; rr0 < p.R; rr0 += 8 * NL) {
-      float q[8];
+    bool arrived = true;
+    for (int rr0 = s; rr0 < p.R && arrived; rr0 += BN_RES_SW * NL) {
+      float q[BN_RES_SW];
+      for (unsigned spins = 0;;) {
+        asm volatile("" ::: "memory");      // every sweep loads anew
+        bool ok = true;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int rr = rr0 + k * NL;
-        q[k] = rr < p.R ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (rr * (GC * 2) + i) * 4, 0, 16)) : 0.f;
+        for (int k = 0; k < BN_RES_SW; ++k) {
+          const int rr = rr0 + k * NL;      // no branch around a load (they would be waited for one by one): a row beyond R is
+          const auto gv = __builtin_amdgcn_raw_buffer_load_b64(rs, rr < p.R ? ((rr * p.G + g) * BN_RES_GRAN + i) * 8 : 0x7ffffff0, 0, 16);
+          q[k] = rr < p.R ? __uint_as_float(gv[0]) : 0.f; ok &= (gv[1] == tag) | (rr >= p.R);      // read out of the buffer's range (no access)
+        }
+        if (__all(ok)) break;
+        if (++spins > p.spin_limit) { arrived = false; break; }      // default: a block that never became resident
+        __builtin_amdgcn_s_sleep(4);
       }
 #pragma unroll
-      for (int k = 0; k < 8; ++k) a += q[k];
+      for (int k = 0; k < BN_RES_SW; ++k) a += q[k];
     }
-    red[s * GC * 2 + i] = a;
+    grp[s * GC * 2 + i] = a;
+    if (!arrived && lane == 0) *bar_ok = 0;
   }
   __syncthreads();
+  const bool exchanged = *bar_ok != 0;
+  if (!exchanged && t == 0) __hip_atomic_fetch_add(bn_res_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (t < GC * 2) {
     float a = 0.f;
 #pragma unroll
-    for (int s = 0; s < NL; ++s) a += red[s * GC * 2 + t];
+    for (int s = 0; s < NL; ++s) a += grp[s * GC * 2 + t];
     tot[t] = a;
   }
   __syncthreads();
+  BN_STAMP(3);
   float k1[CH], k2[CH];
 #pragma unroll
   for (int e = 0; e < CH; ++e) {
@@ -625,6 +652,9 @@ __global__ __launch_bounds__(NT) void bn_bwd_resident_kernel(BnResArgs p) {
   // the residual branch)
   T* __restrict__ DX = reinterpret_cast<T*>(p.dx);
   T* __restrict__ DR = reinterpret_cast<T*>(p.dres);
+#ifdef BN_RES_STAMPS
+  bool stamped = false;
+#endif
   auto finish = [&](int lr, const uint4& qxv, const uint4& qdv, unsigned mb) {
     const size_t off = (size_t)(row0 + lr) * C + c0;
     float v[CH], gq[CH]; Chunk<T>::unpack(qxv, v); Chunk<T>::unpack(qdv, gq);
@@ -637,6 +667,9 @@ __global__ __launch_bounds__(NT) void bn_bwd_resident_kernel(BnResArgs p) {
 #pragma unroll
     for (int e = 0; e < CH; ++e) v[e] = sc[e] * (gq[e] - k1[e] - (v[e] - mu[e]) * is[e] * k2[e]);
     Chunk<T>::store(DX + off, v);
+#ifdef BN_RES_STAMPS
+    if (!stamped) { BN_STAMP(4); stamped = true; }
+#endif
   };
 #pragma unroll
   for (int k = 0; k < KR; ++k) {
@@ -661,6 +694,9 @@ __global__ __launch_bounds__(NT) void bn_bwd_resident_kernel(BnResArgs p) {
       if (lr < nrows) finish(lr, qx[k], qd[k], mk[k]);
     }
   }
+  // the block's share of the 256 a launch adds to its completion count (see bn_res_done); no value comes back
+  if (t == 0) __hip_atomic_fetch_add(done, blockIdx.x == 0 ? (unsigned)BN_RES_MAXBLK + 1u - nblk : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  BN_STAMP(5);
 }
 
 // g <- bit of mask set ? g : 0, in place (the stand-alone form of the masking the consumers of a residual block's fork
@@ -889,7 +925,7 @@ static bool bn_resident_plan(long rows, int C, int CH, BnResPlan* q) {
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return false;
     max_lds = (size_t)v;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-    ncu = v > 256 ? 256 : v;      // mi355_bn_workspace reserves partials for at most 256 blocks x 64 channels x 2 sums
+    ncu = v > BN_RES_MAXBLK ? BN_RES_MAXBLK : v;      // bn_res_gran has slots for BN_RES_MAXBLK blocks, and a launch's count adds up to 256
   }
   const int GC = 8 * CH;
   if (C % GC) return false;
@@ -902,7 +938,7 @@ static bool bn_resident_plan(long rows, int C, int CH, BnResPlan* q) {
   q->R = (int)((rows + q->rpb - 1) / q->rpb);
   static const long max_bytes = getenv("MI355_BN_RESIDENT_MAX") ? atol(getenv("MI355_BN_RESIDENT_MAX")) : (1L << 62);
   if (rows * C * (16 / CH) > max_bytes) return false;
-  const size_t scratch = (size_t)(BN_RES_NT / 64 * GC * 2 + GC * 2 + 4) * sizeof(float);      // sums, totals, barrier verdict
+  const size_t scratch = (size_t)(BN_RES_NT / 64 * GC * 2 + BN_RES_NT + GC * 2 + 4) * sizeof(float);      // block sums, group sums, totals, verdict
   long keep = (long)((max_lds - scratch) / 256);        // tile rows (128 B of x + 128 B of dy each) that fit beside the scratch
   const long reg_rows = (long)BN_RES_KR * (BN_RES_NT / 8);
   const long rest = q->rpb > reg_rows ? q->rpb - reg_rows : 0;
@@ -912,7 +948,7 @@ static bool bn_resident_plan(long rows, int C, int CH, BnResPlan* q) {
   q->max_lds = max_lds;
   return (size_t)q->G * q->R <= (size_t)ncu && q->G * q->R <= BN_RES_MAXBLK;
 }
-static unsigned g_bn_res_spin = 1u << 19;      // grid-barrier poll iterations (~0.3 s) before a block gives up
+static unsigned g_bn_res_spin = 1u << 19;      // re-reads of a wave's granules (a fraction of a second) before its block gives up
 // Test hook: shrink (or restore, 0 = default) the spin bound so that a give-up can be provoked on purpose.
 extern "C" int mi355_bn_resident_set_spin_limit(unsigned limit) {
   g_bn_res_spin = limit ? limit : (1u << 19);
@@ -934,7 +970,7 @@ static int bn_resident_launch(const BnResArgs& a, size_t lds, size_t max_lds, hi
   hipLaunchKernelGGL(kern, dim3(a.G * a.R), dim3(BN_RES_NT), lds, st, a);
   return MI355_OK;
 }
-// Number of grid-barrier spins that gave up since the library was loaded or mi355_bn_resident_reset (0 unless a block of a
+// Number of blocks whose exchange gave up since the library was loaded or mi355_bn_resident_reset (0 unless a block of a
 // one-launch backward was kept off the chip).  Every such launch has poisoned its outputs with NaN.  Synchronises the device.
 extern "C" int mi355_bn_resident_timeouts(unsigned* out) {
   unsigned v[4] = {0, 0, 0, 0};
@@ -943,13 +979,17 @@ extern "C" int mi355_bn_resident_timeouts(unsigned* out) {
   *out = v[0];
   return MI355_OK;
 }
-// Clears the give-up count and the arrival counters (after a give-up has been reported and handled).  Synchronises the device.
+// Clears the give-up count, the completion counts and every granule slot (after a give-up has been reported and handled): the
+// counts start again at 0, and no slot keeps a tag a later launch could form (tag 0 is never formed).  Synchronises the device.
 extern "C" int mi355_bn_resident_reset(void) {
-  static const unsigned long long zeros[BN_RES_MAXBLK + 1] = {0};
+  static const unsigned zdone[2][BN_RES_MAXBLK + 1] = {{0}};
   static const unsigned zerr[4] = {0, 0, 0, 0};
+  void* gran = nullptr;
   if (hipDeviceSynchronize() != hipSuccess) MI_FAIL(MI355_ELAUNCH, "bn_resident_reset: device synchronize failed");
-  if (hipMemcpyToSymbol(HIP_SYMBOL(bn_res_sync), zeros, sizeof(zeros)) != hipSuccess ||
+  if (hipGetSymbolAddress(&gran, HIP_SYMBOL(bn_res_gran)) != hipSuccess || hipMemset(gran, 0, sizeof(bn_res_gran)) != hipSuccess ||
+      hipMemcpyToSymbol(HIP_SYMBOL(bn_res_done), zdone, sizeof(zdone)) != hipSuccess ||
       hipMemcpyToSymbol(HIP_SYMBOL(bn_res_err), zerr, sizeof(zerr)) != hipSuccess) MI_FAIL(MI355_ELAUNCH, "bn_resident_reset: copy failed");
+  if (hipDeviceSynchronize() != hipSuccess) MI_FAIL(MI355_ELAUNCH, "bn_resident_reset: device synchronize failed");
   return MI355_OK;
 }
 
@@ -980,10 +1020,9 @@ extern "C" int mi355_bn_bwd(const void* dy, const void* x, const void* y, const 
   hipStream_t st = as_stream(stream);
   BnResPlan rp;
   if (relu != 1 && !q8_out && bn_resident_plan(rows, C, CH, &rp)) {
-    if (ws_bytes < (size_t)rp.G * rp.R * (8 * CH) * 2 * sizeof(float)) MI_FAIL(MI355_EWORKSPACE, "bn_bwd: workspace too small for the one-launch partials");
     BnResArgs a;
     a.dy = dy; a.x = x; a.mean = save_mean; a.invstd = save_invstd; a.gamma = gamma; a.beta = beta; a.dx = dx; a.dres = dresidual;
-    a.dgamma = dgamma; a.dbeta = dbeta; a.mask = mk; a.partial = reinterpret_cast<float*>(ws); a.rows = rows; a.C = C;
+    a.dgamma = dgamma; a.dbeta = dbeta; a.mask = mk; a.rows = rows; a.C = C;
     a.G = rp.G; a.R = rp.R; a.rpb = rp.rpb; a.keep = rp.keep; a.accumulate = accumulate; a.inv_rows = 1.0f / (float)rows;
     a.spin_limit = g_bn_res_spin;
     int e;

@@ -584,7 +584,7 @@ def bn_resident_set_spin_limit(limit):
 
 def bn_resident_check(where=''):
     """Raise when a one-launch BatchNorm backward could not get all its blocks onto the chip since the last check: its gradients
-    are NaN (csrc/bn.hip bn_res_grid_barrier).  The one-launch form is switched off for the rest of the process and the counters
+    are NaN (csrc/bn.hip bn_bwd_resident_kernel).  The one-launch form is switched off for the rest of the process and the counters
     are cleared, so a caller that catches the error can redo the step on the three-launch path.  Synchronises the device: call it
     where the host waits anyway (train1.py: once per epoch; bench.py / smoke: at the end)."""
     n = bn_resident_timeouts()

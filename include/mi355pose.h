@@ -281,10 +281,11 @@ int mi355_bn_bwd(const void* dy, const void* x, const void* y, const float* gamm
  * mi355_bn_resident_reset.  Synchronises.  Callers poll it where they synchronise anyway (train1.py: once per epoch;
  * mi355.ops.bn_resident_check raises). */
 int mi355_bn_resident_timeouts(unsigned* out);
-/* Clears the give-up count and the arrival counters after a give-up has been handled.  Synchronises the device. */
+/* Clears the give-up count and the exchange's device state (completion counts, granule slots) after a give-up has been
+ * handled.  Synchronises the device. */
 int mi355_bn_resident_reset(void);
-/* TEST HOOK: grid-barrier poll iterations before a block gives up (0 restores the default, 1 << 19 ~ 0.3 s).  Used by the
- * tests to provoke a give-up and check that it is loud. */
+/* TEST HOOK: how often a wave re-reads its share of the exchanged sums before its block gives up (0 restores the default,
+ * 1 << 19: a fraction of a second).  Used by the tests to provoke a give-up and check that it is loud. */
 int mi355_bn_resident_set_spin_limit(unsigned limit);
 /* Run-time switch of the one-launch backward (1 on, 0 off, -1 back to the environment's choice); returns the previous value.
  * Switch it off while another kernel runs beside the backward on the same device (e.g. a collective overlapped with it): all
