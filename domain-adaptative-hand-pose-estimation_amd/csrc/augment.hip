@@ -6,6 +6,8 @@
 // from the fixed-point closed form (no rotated image is stored); the horizontal BILINEAR pass writes the band's rows of
 // the uint8 intermediate to LDS, the vertical pass reads them.  Writes the uint8 geometry image to the workspace, the
 // optional normalised image_ema, and the integer luminance sum of the image as it stands right before contrast.
+// mi355_resize_normalize is this launch alone, instantiated without the uint8 image and the luminance sum (FULL = false):
+// the normalised geometry image is its output.
 // Launch 2 (aug_photometric): one block per tile of TILE output rows with a 3-row halo: jitter recomputed pointwise,
 // the 3 + 3 box-blur passes in LDS (ping-pong, edge clamp), then the normalisation to fp32 NCHW.
 #include "common.h"
@@ -19,7 +21,7 @@ constexpr int KMAX = 9;           // BILINEAR taps for crop side <= 4 * S (suppo
 constexpr int TMAX = 9 * 4 + 5;   // intermediate rows per band: <= (BAND - 1) * scale + 2 * support + 2 at scale 4
 constexpr int TILE = 16;          // output rows per photometric block
 constexpr int HALO = 3;           // one row per vertical box pass
-constexpr int SMAX = 256;
+constexpr int SMAX = 512;          // dynamic LDS at SMAX: 85 504 B (geometry), 67 584 B (photometric); the cap is raised on demand
 constexpr int PREC = 22;          // Resample.c PRECISION_BITS for 8-bit images
 
 struct Norm { float mean[3], stdv[3]; };
@@ -99,6 +101,8 @@ __device__ inline void bilinear_coeffs(int side, int S, int i, int* xmin_out, in
   *xmin_out = xmin; *n_out = xmax;
 }
 
+// FULL: the first launch of mi355_augment.  !FULL: mi355_resize_normalize -- `ema` is the output, geo / lsum are not touched
+template <bool FULL>
 __global__ __launch_bounds__(NT) void aug_geometry(const uint8_t* __restrict__ src, const mi355_aug_rec* __restrict__ recs,
                                                    int S, uint8_t* __restrict__ geo, float* __restrict__ ema, Norm nm,
                                                    unsigned long long* __restrict__ lsum) {
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(NT) void aug_geometry(const uint8_t* __restrict__ s
   const mi355_aug_rec r = recs[b];
   const uint8_t* img = src + r.offset;
   const bool resize = r.side != S;
-  if (tid == 0) red = 0;
+  if (FULL && tid == 0) red = 0;
 
   int rmin = 0, nrows = BAND;
   if (resize) {
@@ -147,7 +151,8 @@ __global__ __launch_bounds__(NT) void aug_geometry(const uint8_t* __restrict__ s
   __syncthreads();
 
   bool contrast = false;
-  for (int j = 0; j < 3; ++j) contrast |= r.order[j] == 1;
+  if (FULL)
+    for (int j = 0; j < 3; ++j) contrast |= r.order[j] == 1;
   unsigned lum = 0;
   const size_t plane = (size_t)S * S;
   for (int e = tid; e < BAND * S; e += NT) {         // vertical pass, outputs, pre-contrast jitter
@@ -167,8 +172,10 @@ __global__ __launch_bounds__(NT) void aug_geometry(const uint8_t* __restrict__ s
       px[0] = t[0]; px[1] = t[1]; px[2] = t[2];
     }
     const size_t pix = (size_t)yy * S + xx;
-    uint8_t* g = geo + ((size_t)b * plane + pix) * 3;
-    g[0] = (uint8_t)px[0]; g[1] = (uint8_t)px[1]; g[2] = (uint8_t)px[2];
+    if (FULL) {
+      uint8_t* g = geo + ((size_t)b * plane + pix) * 3;
+      g[0] = (uint8_t)px[0]; g[1] = (uint8_t)px[1]; g[2] = (uint8_t)px[2];
+    }
     if (ema) {
       float* o = ema + (size_t)b * 3 * plane + pix;
 #pragma unroll
@@ -294,32 +301,71 @@ static int check_rec(const mi355_aug_rec& r, int i, int64_t src_bytes, int S) {
   return MI355_OK;
 }
 
-extern "C" int mi355_augment(const uint8_t* src, int64_t src_bytes, const mi355_aug_rec* rec_host, const mi355_aug_rec* rec_dev,
-                             int B, int S, const float* norm, float* out, float* ema, void* ws, size_t ws_bytes, void* stream) {
+// argument checks shared by mi355_augment (ws_needed: its workspace) and mi355_resize_normalize, all before anything is enqueued
+static int check_batch(const uint8_t* src, int64_t src_bytes, const mi355_aug_rec* rec_host, const mi355_aug_rec* rec_dev, int B, int S,
+                       const float* norm, const float* out, bool ws_needed, const void* ws, size_t ws_bytes, Norm* nm) {
   if (B < 1 || B > 65535) MI_FAIL(MI355_EINVAL, "augment: batch %d outside 1..65535", B);
   if (S < TILE || S > SMAX || S % TILE) MI_FAIL(MI355_EINVAL, "augment: output side %d (multiple of %d, at most %d)", S, TILE, SMAX);
-  if (!src || src_bytes < 3 || !rec_host || !rec_dev || !norm || !out || !ws) MI_FAIL(MI355_EINVAL, "augment: null argument");
+  if (!src || src_bytes < 3 || !rec_host || !rec_dev || !norm || !out || (ws_needed && !ws)) MI_FAIL(MI355_EINVAL, "augment: null argument");
   if ((size_t)B * 3 * S * S > (size_t)INT32_MAX) MI_FAIL(MI355_EINVAL, "augment: output exceeds the 32-bit index range");
-  if (ws_bytes < mi355_augment_workspace(B, S)) MI_FAIL(MI355_EWORKSPACE, "augment: workspace %zu < %zu", ws_bytes, mi355_augment_workspace(B, S));
-  Norm nm;
+  // names the two arguments the requirement follows from: a workspace sized for side 256 is refused at 512 by this message
+  if (ws_needed && ws_bytes < mi355_augment_workspace(B, S))
+    MI_FAIL(MI355_EWORKSPACE, "augment: workspace %zu < %zu for batch %d, output side %d", ws_bytes, mi355_augment_workspace(B, S), B, S);
   for (int c = 0; c < 3; ++c) {
-    nm.mean[c] = norm[c]; nm.stdv[c] = norm[3 + c];
-    if (!(nm.stdv[c] != 0.0f)) MI_FAIL(MI355_EINVAL, "augment: std[%d] = 0", c);
+    nm->mean[c] = norm[c]; nm->stdv[c] = norm[3 + c];
+    if (!(nm->stdv[c] != 0.0f)) MI_FAIL(MI355_EINVAL, "augment: std[%d] = 0", c);
   }
   for (int i = 0; i < B; ++i) {
     const int rc = check_rec(rec_host[i], i, src_bytes, S);
     if (rc) return rc;
   }
+  return MI355_OK;
+}
+
+// dynamic LDS above the 64 KB default (S > 384 geometry, S > 496 photometric): raise the kernel's cap, once per size reached.
+// The caps the callers keep are per process and unguarded, like the attribute flags of igemm.hip / pgemm.hip: one GPU and one
+// calling thread per process (train1.py starts one rank per GPU).
+template <typename K>
+static int raise_lds(K kern, size_t lds, size_t* cap, const char* what) {
+  if (lds <= *cap) return MI355_OK;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    MI_FAIL(MI355_ELAUNCH, "augment: cannot raise the dynamic LDS limit of the %s kernel to %zu bytes", what, lds);
+  *cap = lds;
+  return MI355_OK;
+}
+constexpr size_t LDS_DEFAULT = 64 * 1024;
+static size_t geometry_lds(int S) { return (size_t)S * (2 + KMAX) * sizeof(int) + (size_t)TMAX * S * 3; }
+
+extern "C" int mi355_augment(const uint8_t* src, int64_t src_bytes, const mi355_aug_rec* rec_host, const mi355_aug_rec* rec_dev,
+                             int B, int S, const float* norm, float* out, float* ema, void* ws, size_t ws_bytes, void* stream) {
+  Norm nm;
+  int rc = check_batch(src, src_bytes, rec_host, rec_dev, B, S, norm, out, true, ws, ws_bytes, &nm);
+  if (rc) return rc;
+  const size_t lds_a = geometry_lds(S), lds_b = 2 * (size_t)(TILE + 2 * HALO) * S * 3;
+  static size_t cap_a = LDS_DEFAULT, cap_b = LDS_DEFAULT;
+  if ((rc = raise_lds(aug_geometry<true>, lds_a, &cap_a, "geometry")) || (rc = raise_lds(aug_photometric, lds_b, &cap_b, "photometric"))) return rc;
   hipStream_t st = as_stream(stream);
   unsigned long long* lsum = reinterpret_cast<unsigned long long*>(ws);
   uint8_t* geo = reinterpret_cast<uint8_t*>(ws) + align256((size_t)B * sizeof(unsigned long long));
   if (hipMemsetAsync(lsum, 0, (size_t)B * sizeof(unsigned long long), st) != hipSuccess)
     MI_FAIL(MI355_ELAUNCH, "augment: memset failed");
-  const size_t lds_a = (size_t)S * (2 + KMAX) * sizeof(int) + (size_t)TMAX * S * 3;
-  hipLaunchKernelGGL(aug_geometry, dim3(S / BAND, B), dim3(NT), lds_a, st, src, rec_dev, S, geo, ema, nm, lsum);
+  hipLaunchKernelGGL(aug_geometry<true>, dim3(S / BAND, B), dim3(NT), lds_a, st, src, rec_dev, S, geo, ema, nm, lsum);
   MI_CHECK_LAUNCH("augment geometry");
-  const size_t lds_b = 2 * (size_t)(TILE + 2 * HALO) * S * 3;
   hipLaunchKernelGGL(aug_photometric, dim3(S / TILE, B), dim3(NT), lds_b, st, geo, rec_dev, S, lsum, nm, out);
   MI_CHECK_LAUNCH("augment photometric");
+  return MI355_OK;
+}
+
+extern "C" int mi355_resize_normalize(const uint8_t* src, int64_t src_bytes, const mi355_aug_rec* rec_host, const mi355_aug_rec* rec_dev,
+                                      int B, int S, const float* norm, float* out, void* stream) {
+  Norm nm;
+  int rc = check_batch(src, src_bytes, rec_host, rec_dev, B, S, norm, out, false, nullptr, 0, &nm);
+  if (rc) return rc;
+  const size_t lds = geometry_lds(S);
+  static size_t cap = LDS_DEFAULT;
+  if ((rc = raise_lds(aug_geometry<false>, lds, &cap, "resize")) != MI355_OK) return rc;
+  hipLaunchKernelGGL(aug_geometry<false>, dim3(S / BAND, B), dim3(NT), lds, as_stream(stream), src, rec_dev, S,
+                     (uint8_t*)nullptr, out, nm, (unsigned long long*)nullptr);
+  MI_CHECK_LAUNCH("resize_normalize");
   return MI355_OK;
 }

@@ -119,6 +119,7 @@ SIGNATURES = {
     'mi355_cast_f32': (_I, [_P, _P, _L, _I, _P]),
     'mi355_augment_workspace': (_Z, [_I, _I]),
     'mi355_augment': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    'mi355_resize_normalize': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P]),
     'mi355_prof_enable': (_I, [_I]),
     'mi355_spin_us': (_I, [_L, _P]),
     'mi355_prof_read_split': (_I, [ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),

@@ -97,12 +97,11 @@ def _workspace(device, B, S):
     return buf
 
 
-def augment(packed_u8, table, params, out=None, want_ema=False, size=256, mean=MEAN, std=STD):
-    """packed_u8: flat uint8 CUDA tensor of the HWC RGB sources; table: (B, 3) (offset, h, w) and params: (B, 11)
-    (``PARAM_COLUMNS``), both host tensors / arrays.  Returns x (B, 3, size, size) fp32 -- written into `out` when given --
-    and, with want_ema, (x, image_ema)."""
+def _prepare(name, packed_u8, table, params, out, size):
+    """The argument contract augment and resize_normalize share: (packed, records on the host (pinned) and on the device,
+    out (B, 3, size, size) fp32)."""
     if not (torch.is_tensor(packed_u8) and packed_u8.is_cuda and packed_u8.dtype == torch.uint8):
-        raise Mi355Error('augment: the packed sources must be a uint8 CUDA tensor (no CPU path)')
+        raise Mi355Error('%s: the packed sources must be a uint8 CUDA tensor (no CPU path)' % name)
     packed_u8 = packed_u8.contiguous()
     dev = packed_u8.device
     table = table.numpy() if torch.is_tensor(table) else table
@@ -113,12 +112,33 @@ def augment(packed_u8, table, params, out=None, want_ema=False, size=256, mean=M
         out = torch.empty(B, 3, size, size, dtype=torch.float32, device=dev)
     elif (tuple(out.shape) != (B, 3, size, size) or out.dtype != torch.float32 or out.device != dev
           or not out.is_contiguous()):
-        raise Mi355Error('augment: out must be a contiguous fp32 (%d, 3, %d, %d) tensor on %s' % (B, size, size, dev))
-    ema = torch.empty(B, 3, size, size, dtype=torch.float32, device=dev) if want_ema else None
+        raise Mi355Error('%s: out must be a contiguous fp32 (%d, 3, %d, %d) tensor on %s' % (name, B, size, size, dev))
     rec_host = torch.from_numpy(rec.view(np.uint8)).pin_memory()
     rec_dev = rec_host.to(dev, non_blocking=True)
+    return packed_u8, rec_host, rec_dev, out
+
+
+def augment(packed_u8, table, params, out=None, want_ema=False, size=256, mean=MEAN, std=STD):
+    """packed_u8: flat uint8 CUDA tensor of the HWC RGB sources; table: (B, 3) (offset, h, w) and params: (B, 11)
+    (``PARAM_COLUMNS``), both host tensors / arrays.  Returns x (B, 3, size, size) fp32 -- written into `out` when given --
+    and, with want_ema, (x, image_ema).  size: a multiple of 16 up to 512."""
+    packed_u8, rec_host, rec_dev, out = _prepare('augment', packed_u8, table, params, out, size)
+    B, dev = out.shape[0], out.device
+    ema = torch.empty(B, 3, size, size, dtype=torch.float32, device=dev) if want_ema else None
     ws = _workspace(dev, B, size)
     norm = np.array(list(mean) + list(std), dtype=np.float32)
     call('mi355_augment', ptr(packed_u8), packed_u8.numel(), rec_host.data_ptr(), ptr(rec_dev), B, size,
          norm.ctypes.data, ptr(out), ptr(ema), ptr(ws), ws.numel(), stream_ptr())
     return (out, ema) if want_ema else out
+
+
+def resize_normalize(packed_u8, table, params, out=None, size=256, mean=MEAN, std=STD):
+    """The geometry stage of ``augment`` alone (``mi355_resize_normalize``, one launch, no workspace): what ``augment`` returns
+    as image_ema for the same arguments.  With the identity rows of ``DeviceResize`` (angle 0, the whole image as the crop)
+    it is the validation chain Resize -> ToTensor -> Normalize, bit-identical with Pillow.  Same arguments and errors as
+    ``augment``; returns x (B, 3, size, size) fp32, written into `out` when given."""
+    packed_u8, rec_host, rec_dev, out = _prepare('resize_normalize', packed_u8, table, params, out, size)
+    norm = np.array(list(mean) + list(std), dtype=np.float32)
+    call('mi355_resize_normalize', ptr(packed_u8), packed_u8.numel(), rec_host.data_ptr(), ptr(rec_dev), out.shape[0], size,
+         norm.ctypes.data, ptr(out), stream_ptr())
+    return out

@@ -3,7 +3,7 @@
 training schedule as the reference's ``train1.py`` (main :37-275, pretrain :278-325, train :328-492,
 validate :495-536, CLI :591-675).  Additive flags: ``--synthetic`` (seeded synthetic data instead of the
 out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--no-graph``, ``--device-augment`` (the training
-augmentation chain and its labels on the GPU).
+augmentation chain, the validation resize and the labels of both on the GPU).
 
     python train1.py data/H3D -t Hand3DStudio --synthetic -a resnet50 -b 64
 
@@ -46,7 +46,7 @@ from uda.model.loss import JointsKLLoss
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
 from uda.model.regda_7 import PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
 from utils.data import ForeverDataIterator, DevicePrefetcher, DeviceAugmentIterator, ragged_collate
-from utils.keypoint_detection import accuracy
+from utils.keypoint_detection import accuracy, accuracy_from_preds, get_max_preds_device
 from utils.logger import CompleteLogger
 from utils.meter import AverageMeter, ProgressMeter, AverageMeterDict
 
@@ -104,7 +104,10 @@ def build_datasets(args):
     else:
         train_tf = T.Compose([T.RandomRotation(args.rotation), T.RandomResizedCrop(size=args.image_size, scale=args.resize_scale),
                               T.ColorJitter(brightness=0.25, contrast=0.25, saturation=0.25), T.GaussianBlur(), T.ToTensor(), normalize])
-    val_tf = T.Compose([T.Resize(args.image_size), T.ToTensor(), normalize])
+    if args.device_augment:     # the test sets hand over their sources as well: Resize / ToTensor / Normalize on the GPU
+        val_tf = T.DeviceResize(args.image_size)
+    else:
+        val_tf = T.Compose([T.Resize(args.image_size), T.ToTensor(), normalize])
     src, tgt = datasets.__dict__[args.source], datasets.__dict__[args.target]
     kw = dict(image_size=image_size, heatmap_size=heatmap_size)
     return (src(root=args.source_root, transforms=train_tf, **kw), src(root=args.source_root, split='test', transforms=val_tf, **kw),
@@ -114,16 +117,20 @@ def build_datasets(args):
 def make_loader(ds, args, train):
     """train: this rank's shard (reshuffled every pass, ForeverDataIterator advances the sampler epoch); validation: the
     strided shard rank::WORLD without padding, so that the counts summed over ranks are exactly the data set's."""
-    # --device-augment: the training sets yield un-augmented ragged sources, packed per batch (utils.data.ragged_collate)
-    collate = ragged_collate if train and getattr(args, 'device_augment', False) and not args.synthetic else None
+    # --device-augment: the data sets yield their sources ragged and unprocessed, packed per batch (utils.data.ragged_collate);
+    # the validation loaders then only decode, so they get the workers too
+    ragged = getattr(args, 'device_augment', False) and not args.synthetic
+    collate = ragged_collate if ragged else None
+    val_workers = args.workers if ragged else 0
     if WORLD == 1:
-        return DataLoader(ds, batch_size=args.batch_size, shuffle=train, num_workers=args.workers if train else 0,
+        return DataLoader(ds, batch_size=args.batch_size, shuffle=train, num_workers=args.workers if train else val_workers,
                           pin_memory=True, drop_last=train, collate_fn=collate)
     if train:
         sampler = DistributedSampler(ds, num_replicas=WORLD, rank=RANK, shuffle=True, seed=args.seed or 0, drop_last=True)
         return DataLoader(ds, batch_size=args.batch_size, sampler=sampler, num_workers=args.workers, pin_memory=True, drop_last=True,
                           collate_fn=collate)
-    return DataLoader(ds, batch_size=args.batch_size, sampler=list(range(RANK, len(ds), WORLD)), num_workers=0, pin_memory=True)
+    return DataLoader(ds, batch_size=args.batch_size, sampler=list(range(RANK, len(ds), WORLD)), num_workers=val_workers, pin_memory=True,
+                      collate_fn=collate)
 
 
 def main(args):
@@ -348,26 +355,55 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
         end = time.time()
 
 
+def validate_batch_metrics(y, label, weight, criterion):
+    """The per-batch metric step of validate(): (0-d loss, predicted (B,K,2) and labelled (B,K,2) heat-map maxima), all on the
+    device -- three launches and no host synchronisation."""
+    return criterion(y, label, weight).detach(), get_max_preds_device(y)[0], get_max_preds_device(label)[0]
+
+
 def validate(val_loader, model, criterion, args):
+    """The host reads the metrics only when a progress line is due and at the end, so the printed Time field is the mean over
+    the batches since the last read (time since then / batches metered), not the time of the single last batch."""
     batch_time, losses = AverageMeter('Time', ':6.3f'), AverageMeter('Loss', ':.2e')
-    acc = AverageMeterDict(val_loader.dataset.keypoints_group.keys(), ":3.2f")
+    dataset = val_loader.dataset
+    acc = AverageMeterDict(dataset.keypoints_group.keys(), ":3.2f")
     progress = ProgressMeter(len(val_loader), [batch_time, losses, acc['all']], prefix='Test: ')
     model.eval()
     from mi355.infer import GraphedForward
     forward = GraphedForward(model)          # full batches replay one HIP graph; the ragged last batch runs eagerly
+    batches = val_loader
+    if getattr(getattr(dataset, 'transforms', None), 'labels_on_device', False):
+        # DeviceResize data set: packed sources -> HBM, resize + normalisation and the heat-map labels on the GPU
+        batches = DeviceAugmentIterator(val_loader, device, dataset.image_size[0], dataset.heatmap_size[0], dataset.sigma,
+                                        geometry_only=True)
+    pending = []                             # (loss, pred, label pred, batch size, heat-map h, w) of the batches not yet metered
+
+    def meter(since):
+        # one stack and one copy per kind, then the meters replayed batch by batch (reference arithmetic, train1.py:505-524)
+        if not pending:
+            return
+        loss_h = torch.stack([p[0] for p in pending]).cpu().tolist()
+        pred_h = torch.cat([p[1] for p in pending]).cpu().numpy()
+        tgt_h = torch.cat([p[2] for p in pending]).cpu().numpy()
+        per_batch, o = (time.time() - since) / len(pending), 0
+        for (_, _, _, n, h, w), loss_i in zip(pending, loss_h):
+            losses.update(loss_i, n)
+            acc.update(dataset.group_accuracy(accuracy_from_preds(pred_h[o:o + n], tgt_h[o:o + n], h, w)[0]), n)
+            batch_time.update(per_batch)
+            o += n
+        pending.clear()
+
     with torch.no_grad():
         end = time.time()
-        for i, (x, label, weight, meta) in enumerate(val_loader):
-            x, label, weight = x.to(device), label.to(device), weight.to(device)
+        for i, (x, label, weight, meta) in enumerate(batches):
+            x, label, weight = x.to(device, non_blocking=True), label.to(device, non_blocking=True), weight.to(device, non_blocking=True)
             y = forward(x)
-            loss = criterion(y, label, weight)
-            losses.update(loss.item(), x.size(0))
-            acc_per_points, avg_acc, cnt, pred = accuracy(y, label)
-            acc.update(val_loader.dataset.group_accuracy(acc_per_points), x.size(0))
-            batch_time.update(time.time() - end)
-            end = time.time()
-            if i % args.print_freq == 0:
+            pending.append(validate_batch_metrics(y, label, weight, criterion) + (x.size(0), y.shape[2], y.shape[3]))
+            if i % args.print_freq == 0:     # the host reads only when something is printed, and once at the end
+                meter(end)
+                end = time.time()
                 progress.display(i)
+        meter(end)
     if WORLD > 1:                                        # sums and counts over all shards (train1.py:505-524 per shard)
         keys = list(acc.dict.keys())
         t = torch.tensor([v for k in keys for v in (acc[k].sum, acc[k].count)] + [losses.sum, losses.count],
@@ -422,8 +458,9 @@ _OPTIONS = [
     (('--dtype',), dict(default='bf16', choices=['bf16', 'f32', 'fp8', 'mxfp8'], help="compute dtype of activations / packed weights ('fp8': bf16 storage, fp8 operands in the K-heavy conv GEMMs; 'mxfp8': the same convs and the neck's transposed convs on block-scaled MX e4m3 operands)")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--device-augment',), dict(action='store_true', help='run the training augmentation chain (rotate, resized crop, colour '
-                                  'jitter, blur, normalisation) and the heat-map labels on the GPU, bit-exact with the CPU chain; '
-                                  'the loader workers only decode, crop (RHD / STB) and draw the parameters')),
+                                  'jitter, blur, normalisation), the validation resize + normalisation and the heat-map labels '
+                                  'of both on the GPU, bit-exact with the CPU chains; the loader workers (validation included) '
+                                  'only decode, crop (RHD / STB) and draw the parameters')),
 ]
 
 

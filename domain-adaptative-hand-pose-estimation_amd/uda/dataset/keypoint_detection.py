@@ -339,3 +339,26 @@ class DeviceAugment:
         params = np.array([angle, top, left, w] + factors + order + [radius], dtype=np.float64)
         kwargs.update(keypoint2d=keypoint2d, intrinsic_matrix=intrinsic_matrix)
         return AugmentSample(np.asarray(image, dtype=np.uint8), params), kwargs
+
+
+class DeviceResize:
+    """Drop-in for ``Compose([Resize(size), ToTensor(), Normalize(...)])`` -- the validation chain -- whose pixel work runs on
+    the GPU (mi355.augment.resize_normalize).  No random draw is made: the parameter row is the identity of the training
+    chain (angle 0, the whole image as the crop, no jitter, no blur), so ``utils.data.ragged_collate`` and
+    ``mi355.augment.records`` take it as they take ``DeviceAugment``'s.  ``keypoint2d`` / ``intrinsic_matrix`` move with
+    ``resize_labels`` as in ``Resize``; the labels are left to the GPU."""
+    labels_on_device = True
+
+    def __init__(self, size):
+        assert isinstance(size, int)
+        self.size = size
+
+    def __call__(self, image, keypoint2d, intrinsic_matrix, **kwargs):
+        if image.mode != 'RGB':
+            image = image.convert('RGB')
+        width, height = image.size
+        assert width == height, 'resize expects the square crops the datasets produce'
+        keypoint2d, intrinsic_matrix = resize_labels(width, self.size, keypoint2d, intrinsic_matrix)
+        params = np.array([0.0, 0, 0, width, 0.0, 0.0, 0.0, -1, -1, -1, 0.0], dtype=np.float64)
+        kwargs.update(keypoint2d=keypoint2d, intrinsic_matrix=intrinsic_matrix)
+        return AugmentSample(np.asarray(image, dtype=np.uint8), params), kwargs

@@ -111,7 +111,7 @@ class DevicePrefetcher:
 
 # ---------------------------------------------------------------- device augmentation (train1.py --device-augment)
 def ragged_collate(samples):
-    """Collate of the ``DeviceAugment`` data sets: (AugmentSample, key points, visibility, meta) per sample ->
+    """Collate of the ``DeviceAugment`` / ``DeviceResize`` data sets: (AugmentSample, key points, visibility, meta) per sample ->
     (packed uint8 (sum of h*w*3,), table int64 (B, 3) of (offset, h, w), params float64 (B, 11), key points float64 (B, K, 2),
     visibility float32 (B, K, 1), meta).  Ragged sources travel as one flat buffer, so the loader's ``pin_memory`` pins a
     single tensor per batch; ``image_ema`` (made on the GPU) is dropped from the meta dicts."""
@@ -145,14 +145,20 @@ class DeviceAugmentIterator:
     """Batches of ``ragged_collate`` -> the ``(x, target, weight, meta)`` batches the training loops consume, on the GPU:
     the packed sources are copied to HBM, ``mi355.augment`` produces x (and ``meta['image_ema']`` with want_ema) and
     ``utils.labels.generate_target_device`` the heat-maps from the key points.  Everything is enqueued on the current
-    stream.  ``out=`` buffers: pass ``out`` (B, 3, S, S) to have x written into a preallocated tensor."""
+    stream.  ``out=`` buffers: pass ``out`` (B, 3, S, S) to have x written into a preallocated tensor.
 
-    def __init__(self, iterator, device, image_size=256, heatmap_size=64, sigma=2, want_ema=False, out=None):
+    ``geometry_only`` (validation, ``DeviceResize`` data sets): x is ``mi355.augment.resize_normalize`` of the batch -- rotate /
+    crop / resize / normalise in one launch, no jitter, no blur, no ``image_ema``."""
+
+    def __init__(self, iterator, device, image_size=256, heatmap_size=64, sigma=2, want_ema=False, out=None, geometry_only=False):
         self.it = iter(iterator)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ValueError('DeviceAugmentIterator runs the augmentation on a GPU; there is no CPU path')
+        if geometry_only and want_ema:
+            raise ValueError('DeviceAugmentIterator: the geometry-only mode has no image_ema (x is that image)')
         self.image_size, self.heatmap_size, self.sigma, self.want_ema, self.out = image_size, heatmap_size, sigma, want_ema, out
+        self.geometry_only = geometry_only
 
     def __iter__(self):
         return self
@@ -161,11 +167,14 @@ class DeviceAugmentIterator:
         return len(self.it)
 
     def __next__(self):
-        from mi355.augment import augment
+        from mi355.augment import augment, resize_normalize
         from utils.labels import generate_target_device
         packed, table, params, keypoints, visible, meta = next(self.it)
         packed = packed.to(self.device, non_blocking=True)
-        res = augment(packed, table, params, out=self.out, want_ema=self.want_ema, size=self.image_size)
+        if self.geometry_only:
+            res = resize_normalize(packed, table, params, out=self.out, size=self.image_size)
+        else:
+            res = augment(packed, table, params, out=self.out, want_ema=self.want_ema, size=self.image_size)
         x = res[0] if self.want_ema else res
         if self.want_ema:
             meta = dict(meta, image_ema=res[1])

@@ -49,15 +49,12 @@ def dist_acc(dists, thr=0.5):
     return -1
 
 
-def accuracy(output, target, hm_type='gaussian', thr=0.5):
-    """PCK on heat-maps (ground-truth heat-map arg-max as the label), reference :63-92.
-    Returns (per-keypoint acc, average acc, count, pred (B,K,2))."""
-    pred, _ = get_max_preds(output)
-    tgt, _ = get_max_preds(target)
-    h, w = output.shape[2], output.shape[3]
+def accuracy_from_preds(pred, target_pred, h, w, thr=0.5):
+    """PCK from decoded coordinates: pred / target_pred (B,K,2) numpy arg-max positions of the h x w heat-maps.
+    Returns (per-keypoint acc, average acc, count, pred) -- the arithmetic of ``accuracy`` after its two decodes."""
     norm = np.ones((pred.shape[0], 2)) * np.array([h, w]) / 10
-    dists = calc_dists(pred, tgt, norm)
-    K = output.shape[1]
+    dists = calc_dists(pred, target_pred, norm)
+    K = pred.shape[1]
     acc = np.zeros(K)
     avg_acc, cnt = 0, 0
     for i in range(K):
@@ -67,6 +64,14 @@ def accuracy(output, target, hm_type='gaussian', thr=0.5):
             cnt += 1
     avg_acc = avg_acc / cnt if cnt != 0 else 0
     return acc, avg_acc, cnt, pred
+
+
+def accuracy(output, target, hm_type='gaussian', thr=0.5):
+    """PCK on heat-maps (ground-truth heat-map arg-max as the label), reference :63-92.
+    Returns (per-keypoint acc, average acc, count, pred (B,K,2))."""
+    pred, _ = get_max_preds(output)
+    tgt, _ = get_max_preds(target)
+    return accuracy_from_preds(pred, tgt, output.shape[2], output.shape[3], thr)
 
 
 def compute_uv_from_heatmaps3(heatmap: torch.Tensor) -> torch.Tensor:

@@ -428,7 +428,10 @@ int mi355_cast_f32(const float* in, void* out, long n, int dtype, void* stream);
  *   output    out[b][c][y][x] = (v / 255 - mean[c]) / std[c] fp32 NCHW; ema (nullable): the same normalisation of the
  *             geometry image (before jitter and blur).
  * Unlike the rest of this header, the records are passed twice: `rec_host` (host memory) is what the argument checks read
- * before anything is enqueued, `rec_dev` (device memory, an identical copy) is what the kernels read.  Two launches. */
+ * before anything is enqueued, `rec_dev` (device memory, an identical copy) is what the kernels read.  Two launches.
+ * S: a multiple of 16 from 16 to 512; sources up to 4096 x 4096; crop side <= 4 S; box radius 0.  Above S = 384 the
+ * kernels need more than the default 64 KB of dynamic LDS (85 504 B and 67 584 B at 512): the cap is raised on first use,
+ * MI355_ELAUNCH when the runtime refuses. */
 typedef struct {
   int64_t offset;           /* byte offset of the source image (h x w x 3, row-major) in the packed buffer */
   int32_t h, w;             /* source size */
@@ -446,6 +449,14 @@ size_t mi355_augment_workspace(int B, int S);
 /* norm: host pointer to 6 floats (mean[3], std[3]); out: fp32 [B][3][S][S]; ema (nullable): fp32 [B][3][S][S] */
 int mi355_augment(const uint8_t* src, int64_t src_bytes, const mi355_aug_rec* rec_host, const mi355_aug_rec* rec_dev,
                   int B, int S, const float* norm, float* out, float* ema, void* ws, size_t ws_bytes, void* stream);
+/* The validation chain (train1.py:67-71: Resize, ToTensor, Normalize) and, in general, the geometry stage of mi355_augment
+ * alone: out[b][c][y][x] is bit for bit what mi355_augment writes to `ema` for the same records (rotate, crop, BILINEAR
+ * resize to S x S, normalisation).  Reads offset, h, w, rot, a[], top, left, side of every record; the photometric fields are
+ * checked like mi355_augment checks them and otherwise ignored.  A validation sample is the identity record: rot 1 (copy),
+ * top = left = 0, side = w = h.  Same argument checks, limits and rec_host / rec_dev convention as mi355_augment.
+ * ONE launch: no workspace, no memset, no uint8 intermediate in memory. */
+int mi355_resize_normalize(const uint8_t* src, int64_t src_bytes, const mi355_aug_rec* rec_host, const mi355_aug_rec* rec_dev,
+                           int B, int S, const float* norm, float* out, void* stream);
 
 /* ---------------------------------------------------------------- in-library kernel timing (bench.py roofline)
  * on = 1: every launch of the MFMA conv family is bracketed by hipEvents on its stream; on = 2: the BatchNorm kernels and
