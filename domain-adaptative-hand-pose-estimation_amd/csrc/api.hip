@@ -23,20 +23,33 @@ struct ProfState {
 };
 ProfState& P() { static ProfState s; return s; }
 thread_local char g_tag[160] = "";
+thread_local long g_last = -1;      // launch index of the entry this thread opened last (prof_amend_label)
 }
 bool prof_on() { return P().on; }
 void prof_set_tag(const char* fmt, ...) {
   if (!P().on) return;
   va_list ap; va_start(ap, fmt); vsnprintf(g_tag, sizeof(g_tag), fmt, ap); va_end(ap);
 }
+// Appends " <text>" to the label of the entry the calling thread opened last: the launchers name the kernel build they chose
+// ("[g128x128 dma kg2 epi1]") after the scope of the launch was opened with the layer's label.  Callers test prof_on() first.
+void prof_amend_label(const char* fmt, ...) {
+  ProfState& p = P();
+  if (!p.on || g_last < 0) return;
+  char buf[96];
+  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
+  std::lock_guard<std::mutex> lk(p.mu);
+  if ((size_t)g_last >= p.used / 2) return;          // (the log was reset in between)
+  p.llabel[g_last] += ' '; p.llabel[g_last] += buf;
+}
 ProfScope::ProfScope(hipStream_t st, double flops, double bytes, int family, const char* label) : s(st), on(false), slot(-1) {
   ProfState& p = P();
+  g_last = -1;
   if (!p.on || (family != 0 && p.level < 2)) return;
   std::lock_guard<std::mutex> lk(p.mu);
   if (p.used + 2 > p.ev.size()) {
     for (int i = 0; i < 2; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; p.ev.push_back(e); }
   }
-  slot = (int)p.used; p.used += 2; on = true;
+  slot = (int)p.used; p.used += 2; on = true; g_last = slot / 2;
   if (family == 0) { p.flops += flops; p.bytes += bytes; p.launches += 1; }
   if (p.lflops.size() < p.used / 2) { p.lflops.resize(p.used / 2); p.lbytes.resize(p.used / 2); p.lfam.resize(p.used / 2); p.llabel.resize(p.used / 2); }
   p.lflops[slot / 2] = flops; p.lbytes[slot / 2] = bytes; p.lfam[slot / 2] = family;

@@ -145,7 +145,11 @@ __device__ inline unsigned fd_div(unsigned n, const FastDiv& f) {
 // family 1 = BatchNorm kernels, 2 = everything else that is logged.  Each scope brackets exactly ONE kernel launch; its label is
 // the explicit one or, when that is null, the thread's pending tag (prof_set_tag: "fwd k3s1 256>256 @64x64 n64" ...), so that the
 // launches of one iteration can be listed layer by layer (mi355_prof_read_launch) and joined, in launch order, with a rocprofv3
-// kernel trace of the same iteration (profiles/insitu_table.py).
+// kernel trace of the same iteration (profiles/insitu_table.py).  The conv-family launchers then append the kernel build they
+// chose, in brackets (prof_amend_label): "[g128x128 dma kg2 epi1]" = gather kernel, 128 x 128 tile, LDS-DMA ring, two K groups,
+// statistics epilogue; further words: "f32" (fp32 build; bf16 otherwise), "small" (small-channel tile), "kw3" (shared A tile),
+// "cat" in front (concat-K), "hm" (heat-map output), "epi2" (BatchNorm-backward epilogue); "[pgemm bm64 bn128 ns8 add]" = the
+// persistent GEMM with its ring depth and addend ring; "[f8 g64x128 bf8]" / "[mx g64x64]" = the fp8 / MX kernels (bf8: e5m2 operand).
 struct ProfScope {
   hipStream_t s; bool on; int slot;
   ProfScope(hipStream_t st, double flops, double bytes = 0.0, int family = 0, const char* label = nullptr);
@@ -153,3 +157,4 @@ struct ProfScope {
 };
 bool prof_on();
 void prof_set_tag(const char* fmt, ...);
+void prof_amend_label(const char* fmt, ...);

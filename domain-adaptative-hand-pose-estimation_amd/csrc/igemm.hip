@@ -1393,6 +1393,12 @@ static void launch_gather_epi(const GatherArgs& a, hipStream_t st) {
   auto kern = gather_gemm_kernel<T, BM, BN, SMALL_C, WGM, WGN, HM_OUT, DMA, EPI, KW3, CAT, KG>;
   static bool attr_set = false;   // raise the dynamic-LDS cap once per instantiation
   if (!attr_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr_set = true; }
+  if (prof_on()) {
+    char epi[8] = "";
+    if (EPI) snprintf(epi, sizeof(epi), " epi%d", EPI);
+    prof_amend_label("[%sg%dx%d%s%s%s%s%s%s%s]", CAT ? "cat " : "", BM, BN, sizeof(T) == 4 ? " f32" : "", SMALL_C ? " small" : "", HM_OUT ? " hm" : "",
+                     DMA ? " dma" : "", KW3 ? " kw3" : "", KG == 2 ? " kg2" : "", epi);
+  }
   hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(64 * WGM * WGN * KG), smem, st, a);
 }
 
@@ -1803,8 +1809,11 @@ static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void*
     MI_CHECK_LAUNCH("zero_fill");
   }
   GatherArgs a; memset(&a, 0, sizeof(a));
-  if (prof_on()) prof_set_tag("dgrad%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? "mx" : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
-                              accumulate ? (acc_mask ? " +macc" : " +acc") : "", bn ? " +bnb" : "");
+  auto tag = [&]() {      // (a launch consumes the pending tag: the per-phase launches below set it once each)
+    if (prof_on()) prof_set_tag("dgrad%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? "mx" : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
+                                accumulate ? (acc_mask ? " +macc" : " +acc") : "", bn ? " +bnb" : "");
+  };
+  tag();
   a.A = dy; a.B = wT; a.D = dx; a.bias = bias; a.residual = nullptr; a.scale = scale_dev;
   a.Hi = d->Ho; a.Wi = d->Wo; a.Ci = d->Co;
   a.in_sy = a.in_sx = 1; a.Ho = d->Hi; a.Wo = d->Wi; a.out_sy = a.out_sx = s;
@@ -1847,6 +1856,7 @@ static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void*
   const int np = a.nphase;
   for (int i = 0; i < np; ++i) {
     GatherArgs b = a; b.nphase = 1; b.ph[0] = a.ph[i];
+    if (i) tag();
     int e = d->dtype == MI355_BF16 ? dispatch_gather<bf16_t>(b, st) : dispatch_gather<float>(b, st);
     if (e) return e;
   }

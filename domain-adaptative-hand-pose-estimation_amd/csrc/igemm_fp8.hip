@@ -523,6 +523,7 @@ static void launch_fp8(GatherArgs& a, hipStream_t st) {
   }
 #define MI_L(BF8, EPI) do { auto kern = gather_fp8_kernel<BM, BN, BF8, EPI, KW3, MX>; static bool set_ = false; \
     if (!set_) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); set_ = true; } \
+    if (prof_on()) prof_amend_label("[%s g%dx%d%s%s%s]", MX ? "mx" : "f8", BM, BN, KW3 ? " kw3" : "", BF8 ? " bf8" : "", EPI ? " epi1" : ""); \
     hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(256), smem, st, a); } while (0)
   if constexpr (MX) { if (a.stat_partial) MI_L(false, 1); else MI_L(false, 0); }
   else if (a.a_fmt) { if (a.stat_partial) MI_L(true, 1); else MI_L(true, 0); }

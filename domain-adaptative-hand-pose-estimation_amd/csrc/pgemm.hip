@@ -567,6 +567,7 @@ static void launch_pgemm_epi(GatherArgs& a, int ncu, int ntm, int smem, hipStrea
   // every block owns one column tile: the grid is a whole number of (row group, column tile) pairs, at most one per row tile
   int groups = ncu * per_cu / a.ntn; if (groups < 1) groups = 1;
   if (groups > ntm) groups = ntm;
+  if (prof_on()) prof_amend_label("[pgemm bm%d bn%d ns%d%s%s]", BM, BN, NS, EPI == 1 ? " epi1" : "", ADD ? " add" : "");
   if (EPI == 1) a.stat_slices = groups;      // one statistics record per block and channel (slice = row group; groups <= ntm fits, checked by the caller)
   hipLaunchKernelGGL(kern, dim3(groups * a.ntn), dim3(256), smem, st, a);
 }

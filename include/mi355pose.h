@@ -465,7 +465,12 @@ int mi355_resize_normalize(const uint8_t* src, int64_t src_bytes, const mi355_au
 int mi355_prof_enable(int on);
 /* The launches logged since the last reset, one by one in launch order: family (0 conv MFMA, 1 BatchNorm, 2 other), event-timed
  * duration in microseconds (contains the dispatch latency mi355_prof_event_overhead_us measures), algorithmic FLOPs and bytes,
- * and a label naming the layer ("fwd k3s1 256>256 @64x64 n64 +stats", "bn_bwd_res rows262144 C256 ...").  Each entry is ONE
+ * and a label naming the layer ("fwd k3s1 256>256 @64x64 n64 +stats", "bn_bwd_res rows262144 C256 ...").  The launches of the
+ * implicit-GEMM convolutions also name the kernel build that ran, in brackets at the end of the label: "[g128x128 dma kg2 epi1]"
+ * (gather kernel, 128 x 128 tile, LDS-DMA ring, two K groups, statistics epilogue; "f32", "small", "hm", "kw3", a leading "cat"
+ * and "epi2" name the fp32, small-channel, heat-map-output, shared-A-tile and concat-K builds and the BatchNorm-backward
+ * epilogue), "[pgemm bm64 bn128 ns8 add]" (persistent GEMM: tile, ring depth, addend ring), "[f8 g64x128 bf8]" / "[mx g64x64]"
+ * (fp8 / MX kernels; bf8: e5m2 operand).  Consumers match labels by prefix.  Each entry is ONE
  * kernel launch, so the list joins in order with a rocprofv3 kernel trace of the same iteration (profiles/insitu_table.py). */
 int mi355_prof_launch_count(long* n);
 int mi355_prof_read_launch(long i, int* family, double* us, double* flops, double* bytes, char* label, int label_cap);

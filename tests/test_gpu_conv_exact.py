@@ -1,0 +1,563 @@
+"""Every conv GEMM build against the float64 reference BIT FOR BIT, on exact integer operands (tests/conv_exact_ref.py).
+
+The operands are small integers for which every product and partial sum is exact in fp32 and every result exact in bf16
+(the range condition, asserted on the reference before a kernel result is looked at), so a correct kernel returns the
+reference's bits whatever its tile, staging, split-K or slab reduction: the tolerance is zero.  Each launch is also held to
+the kernel build named in its launch-log label ("[g128x128 dma kg2 epi1]", csrc/common.h) through the expected-build tables
+below, so a case that silently moves to another kernel when a dispatch threshold changes fails instead of testing something
+else.  The tables are read from dispatch_gather / dispatch_pgemm / dispatch_gather_fp8 / plan_wgrad at this commit;
+profiles/conv_exact_labels.txt holds the full labels of one run for diffing.
+
+Builds behind switches that are read once per process (MI355_DMA, MI355_KW3, MI355_PHASES, MI355_T256D_*, MI355_FP8_TILE)
+run in child processes, one per entry of GROUPS, strictly one after another, each with its own timeout and no retry.
+
+Instantiations no case reaches, and why:
+  * gather 256x256 register-staged (MI355_T256 experiment switch) and the MI355_TILE-forced tiles: not dispatched by default,
+    the forced tiles are the same instantiations the shapes here reach;
+  * concat-K tiles behind MI355_CAT_TILE: the same instantiations are reached by shape (64x64, 64x128, 128x128) or through
+    MI355_DMA=2 (LDS-DMA ring) and the forced 256x256 group;
+  * pgemm at K = 1024 (named by the issue): pg_bn refuses it -- a 64-wide weight slice of more than 512 channels exceeds the 64 KB
+    the kernel keeps for it -- so under mi355_set_pgemm(2) such a launch stays on the gather kernel; K = 512 is the longest K run;
+  * a second full-size case for a partial column tile on the 256x128 shared-A-tile build (4096 tiles of 128x128 cost 40 GFLOP
+    in the float64 reference at any channel count): its column tail is the code the 128x128 shared-A-tile build runs at Co = 136;
+  * pgemm bm128 (MI355_PG_BM=128) and the ring depths only MI355_PG_RING selects (128-wide columns with a ring of 5 and no
+    addend ring, 64-wide columns with a ring of 4): experiment switches, never dispatched by default;
+  * the EPI = 2 (BatchNorm-backward) epilogue on the 256-row, shared-A-tile, split-K and concat-K builds: it does not exist
+    (dispatch falls to a regular tile, which the 'bnb' column asserts)."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import conv_exact_ref as R
+from mx_ref import mx_dequantize
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+GROUPS = {
+    'dma_kw3':   {'MI355_DMA': '2', 'MI355_KW3': '2', 'MI355_PHASES': '0'},
+    't256d':     {'MI355_T256D_MIN': '1', 'MI355_T256D_KMIN': '1'},
+    'fp8_tile0': {'MI355_FP8_TILE': '0'},
+    'fp8_tile1': {'MI355_FP8_TILE': '1'},
+}
+GROUP = os.environ.get('MI355_CONV_EXACT_GROUP', 'default')      # set by the parent for its child processes
+DT = {'bf16': torch.bfloat16, 'f32': torch.float32}
+
+# name: (bf16, f32) x (forward, input gradient, accumulating input gradient, input gradient + BatchNorm-backward epilogue,
+# weight gradient with its slab count).  'build *4': four launches (one per phase, MI355_PHASES=0).
+EXPECT = {
+    'small7':         (('g128x64 small', 'g64x64', 'g64x64', 'g64x64', 'wgrad S9'), ('g128x64 f32 small', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S17')),
+    'small7_co72':    (('g128x64 small', None, None, None, 'wgrad S9'), ('g128x64 f32 small', None, None, None, 'wgrad S17')),
+    'stem4_crop':     (('g128x64 small', None, None, None, 'wgrad S9'), ('g128x64 f32 small', None, None, None, 'wgrad S17')),
+    'small_dgrad':    (('g64x64', 'g128x64 small', 'g128x64 small', 'g128x64 small', 'wgrad S6'), ('g64x64 f32', 'g128x64 f32 small', 'g128x64 f32 small', 'g128x64 f32 small', 'wgrad S11')),
+    't64_co72':       (('g64x64', None, None, None, 'wgrad S2'), ('g64x64 f32', None, None, None, 'wgrad S4')),
+    't64_s2':         (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S6')),
+    't64x128':        (('g64x128', 'g64x64', 'g64x64', 'g64x64', 'wgrad S94'), ('g64x128 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S113')),
+    't64x128_co136':  (('g64x128', None, None, None, 'wgrad S94'), ('g64x128 f32', None, None, None, 'wgrad S113')),
+    't64x128_dgrad':  (('g64x64', 'g64x128', 'g64x128', 'g64x128', 'wgrad S94'), ('g64x64 f32', 'g64x128 f32', 'g64x128 f32', 'g64x128 f32', 'wgrad S113')),
+    't128x64':        (('g128x64', 'g128x64', 'g128x64', 'g128x64', 'wgrad S61'), ('g128x64 f32', 'g128x64 f32', 'g128x64 f32', 'g128x64 f32', 'wgrad S121')),
+    't128x128':       (('g128x128', None, None, None, 'wgrad S31'), ('g128x128 f32 dma', None, None, None, 'wgrad S62')),
+    't128x128_dgrad': (('g128x64', 'g128x128', 'g128x128', 'g128x128', 'wgrad S61'), ('g128x64 f32', 'g128x128 f32 dma', 'g128x128 f32 dma', 'g128x128 f32 dma', 'wgrad S86')),
+    't128x128_f32_dgrad': (('g128x64', 'g128x64 small', 'g128x64 small', 'g128x64 small', 'wgrad S61'), ('g128x64 f32', 'g128x128 f32', 'g128x128 f32', 'g128x128 f32', 'wgrad S86')),
+    'kg2_64_co136':   (('g64x128 dma kg2', None, None, None, 'wgrad_kw S22'), ('g64x128 f32 dma kg2', None, None, None, 'wgrad S15')),
+    'kg2_128_co136':  (('g128x128 dma kg2', None, None, None, 'wgrad_kw S21'), ('g128x128 f32 dma kg2', None, None, None, 'wgrad S25')),
+    'kg2_64':         (('g64x128 dma kg2', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S22'), ('g64x128 f32 dma kg2', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S15')),
+    'kg2_128':        (('g128x128 dma kg2', 'g64x128 dma kg2', 'g64x128 dma kg2', 'g64x64', 'wgrad_kw S21'), ('g128x128 f32 dma kg2', 'g64x128 f32 dma kg2', 'g64x128 f32 dma kg2', 'g64x64 f32', 'wgrad S25')),
+    't256d':          (('g256x256 dma', 'g128x128 dma kg2', 'g128x128 dma kg2', 'g64x64', 'wgrad S15'), ('g128x128 f32', 'g128x128 f32 dma kg2', 'g128x128 f32 dma kg2', 'g64x64 f32', 'wgrad S23')),
+    's2_3x3_odd':     (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S5')),
+    's2_4x4_odd':     (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S4')),
+    'wkw_w8':         (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S6')),
+    'wkw_w16':        (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S5')),
+    'wkw_w32':        (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S6')),
+    'wkw_w64':        (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S5'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S10')),
+    'wkw_w128':       (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S6'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S12')),
+    'wkw_direct':     (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S1'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S2')),
+    'wkw2_wo8':       (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S3')),
+    'wkw2_wo16':      (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S3')),
+    'wkw2_wo32':      (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S3')),
+    'wkw2_wo64':      (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S4')),
+    'wkw2_direct':    (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S1'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S2')),
+    'wgen_direct':    (('g64x64', None, None, None, 'wgrad S1'), ('g64x64 f32', None, None, None, 'wgrad S2')),
+    'kw3_256x128':    (('g256x128 kw3', 'g128x64 kw3', 'g128x64 kw3', 'g128x64', 'wgrad_kw S128'), ('g128x128 f32 dma', 'g128x64 f32', 'g128x64 f32', 'g128x64 f32', 'wgrad S77')),
+    'dma_co136':      (('g128x128 dma', None, None, None, 'wgrad S4'), ('g128x128 f32 dma', None, None, None, 'wgrad S8')),
+    'dma_s2':         (('g128x128 dma', 'g128x128 dma *4', 'g128x128 dma *4', 'g128x128 dma *4', 'wgrad S2'), ('g128x128 f32 dma', 'g128x128 f32 dma *4', 'g128x128 f32 dma *4', 'g128x128 f32 dma *4', 'wgrad S4')),
+    'dma_s2_4x4':     (('g128x128 dma', 'g128x128 dma *4', 'g128x128 dma *4', 'g128x128 dma *4', 'wgrad S2'), ('g128x128 f32 dma', 'g128x128 f32 dma *4', 'g128x128 f32 dma *4', 'g128x128 f32 dma *4', 'wgrad S4')),
+    'kw3_w8':         (('g128x128 kw3', 'g128x64 kw3', 'g128x64 kw3', 'g64x64', 'wgrad_kw S2'), ('g128x128 f32 dma', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S4')),
+    'kw3_w16_co136':  (('g128x128 kw3', None, None, None, 'wgrad_kw S2'), ('g128x128 f32 dma', None, None, None, 'wgrad S3')),
+    'kw3_w32':        (('g128x64 kw3', 'g128x64 kw3', 'g128x64 kw3', 'g64x64', 'wgrad_kw S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S3')),
+    'kw3_w64':        (('g128x128 kw3', 'g128x64 kw3', 'g128x64 kw3', 'g64x64', 'wgrad_kw S3'), ('g128x128 f32 dma', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S6')),
+    'kw3_w128':       (('g128x64 kw3', 'g128x128 kw3', 'g128x128 kw3', 'g128x128 dma', 'wgrad_kw S6'), ('g64x64 f32', 'g128x128 f32 dma', 'g128x128 f32 dma', 'g128x128 f32 dma', 'wgrad S12')),
+    'phase_s2_odd':   (('g64x64', 'g64x64 *4', 'g64x64 *4', 'g64x64 *4', 'wgrad S3'), ('g64x64 f32', 'g64x64 f32 *4', 'g64x64 f32 *4', 'g64x64 f32 *4', 'wgrad S5')),
+    't256d_m300':     (('g256x256 dma', 'g64x64', 'g64x64', 'g64x64', 'wgrad S5'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S10')),
+    't256d_co512':    (('g256x256 dma', 'g64x64', 'g64x64', 'g64x64', 'wgrad S5'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S10')),
+    't256d_s2':       (('g64x64', 'g256x256 dma', 'g64x64', 'g64x64', 'wgrad S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S4')),
+}
+CAT_EXPECT = {      # name: (bf16, f32)
+    'cat_64x64':    ('cat g64x64', 'cat g64x64 f32'),
+    'cat_64x64_s2': ('cat g64x64', 'cat g64x64 f32'),
+    'cat_64x128':   ('cat g64x128', 'cat g64x128 f32'),
+    'cat_128x128':  ('cat g128x128', 'cat g128x128 f32 dma'),
+    'cat_dma':      ('cat g128x128 dma', 'cat g128x128 f32 dma'),
+    'cat_256x256':  ('cat g256x256 dma', 'cat g64x64 f32'),
+}
+FP8_EXPECT = {      # name: (forward / input-gradient tile, the same with mi355_set_fp8_kw3(1) or None where the shape has no such build)
+    'f8_3x3_w8':   ('g64x64', 'g128x128 kw3'),
+    'f8_3x3_w16':  ('g64x64', 'g128x128 kw3'),
+    'f8_s2_3x3':   ('g64x64', None),
+    'f8_s2_4x4':   ('g64x64', None),
+    'f8_64x128':   (('g64x128', 'g64x64'), 'g128x128 kw3'),      # (forward, input gradient: 128 output columns are one column tile)
+    'f8_t128_w8':  ('g128x128', 'g128x128 kw3'),
+    'f8_t128_s2':  ('g128x128', None),
+    'f8_t64x128_w8': ('g64x128', 'g128x128 kw3'),
+    'f8_t64x128_s2': ('g64x128', None),
+}
+
+
+def _names(table):
+    return [n for n in table if table[n][0] == GROUP]
+
+
+def _ops():
+    import mi355
+    from mi355 import ops
+    mi355.load()
+    return ops
+
+
+@pytest.fixture(scope='module', autouse=True)
+def launch_log(gpu):
+    ops = _ops()
+    ops.prof_enable(1)
+    yield
+    ops.prof_enable(0)
+
+
+def _run(ops, fn):
+    """fn() with the labels of the conv-family launches it made."""
+    ops.prof_reset()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, [l['label'] for l in ops.prof_launches() if l['family'] == 0]
+
+
+def _build(label):
+    m = re.search(r'\[([^\]]*)\]$', label)
+    assert m, 'launch label without a build: %r' % label
+    return m.group(1)
+
+
+def _check_builds(what, labels, expect):
+    """Every launch of one call ran the expected build; returns the epilogue index the launches carry (0, 1 or 2)."""
+    n = 1
+    if ' *' in expect:
+        expect, n = expect.split(' *')[0], int(expect.split(' *')[1])
+    print('\nLABEL %s %s' % (what, ' | '.join(labels)))
+    assert all(l.split(' [')[0].strip() for l in labels), '%s: a launch without its layer label: %r' % (what, labels)
+    builds = [_build(l) for l in labels]
+    bare = [re.sub(r' epi\d$', '', b) for b in builds]
+    assert bare == [expect] * n, '%s: launched %r, expected %d x [%s]' % (what, labels, n, expect)
+    epis = set(int(b[-1]) if re.search(r' epi\d$', b) else 0 for b in builds)
+    assert len(epis) == 1
+    return epis.pop()
+
+
+def _same(what, got, ref, dtype):
+    assert R.same_bits(got, ref, dtype), '%s: %s' % (what, R.first_mismatch(got, ref, dtype))
+
+
+def _dev(t, dtype, gpu):
+    return _ops().to_nhwc(t.to(gpu), dtype)
+
+
+def _check_stats(what, part, C, ref, rows):
+    """(n, mean, M2) slices of a statistics epilogue, folded in float64, against float64 statistics of the exact output: n exact,
+    mean and 1 / sqrt(var + eps) within the tolerances of test_conv_epilogue_bn_statistics (1e-5 / 2e-5 relative, 1e-6 absolute)."""
+    assert part is not None and part[1] >= 1, what
+    tot, mean, m2 = R.fold_stats(part[0], part[1], C)
+    n, rmean, rm2 = R.bn_stats(ref)
+    assert n == rows and torch.equal(tot, torch.full((C,), float(rows), dtype=torch.float64)), what
+    inv, rinv = 1.0 / torch.sqrt(m2 / tot + 1e-5), 1.0 / torch.sqrt(rm2 / n + 1e-5)
+    print('\nSTATS %s: max |mean err| %.3e (max |mean| %.3e), max rel invstd err %.3e' % (
+        what, float((mean - rmean).abs().max()), float(rmean.abs().max()), float(((inv - rinv) / rinv).abs().max())))
+    assert torch.allclose(mean, rmean, rtol=1e-5, atol=1e-6), what
+    assert torch.allclose(inv, rinv, rtol=2e-5, atol=1e-6), what
+
+
+# ---------------------------------------------------------------------------------------------- forward / dgrad / wgrad
+_CONV = [(n, dt) for n in _names(R.CASES) for dt in ('bf16', 'f32')]
+if _CONV:
+    @pytest.mark.parametrize('name,dt', _CONV, ids=['%s-%s' % p for p in _CONV])
+    def test_conv_builds_return_the_reference_bits(gpu, name, dt):
+        ops = _ops()
+        c = R.build_case(name)
+        dtype, per = DT[dt], (8 if dt == 'bf16' else 4)
+        R.assert_exact_in(dtype, *c.fwd_values)
+        R.assert_exact_in(dtype, *c.dgrad_values)
+        R.assert_exact_in(torch.float32, c.dw, c.dw_acc)
+        e_fwd, e_dgrad, e_acc, e_bnb, e_wgrad = EXPECT[name][0 if dt == 'bf16' else 1]
+        N, Ci, H, W, Co, k, s, p = c.shape
+        desc = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype, out_hw=c.out_hw)
+        xd, dyd = _dev(c.x, dtype, gpu), _dev(c.dy, dtype, gpu)
+        wf, wt = ops.pack_weights(c.w.permute(0, 2, 3, 1).contiguous().to(gpu), Co, k * k, Ci, Ci, dtype)
+        bias, res = c.bias.to(gpu), _dev(c.res, dtype, gpu)
+        tag = '%s/%s ' % (name, dt)
+
+        for what, fn, ref in (('fwd', lambda: ops.conv_fwd(desc, xd, wf), c.y),
+                              ('fwd+bias', lambda: ops.conv_fwd(desc, xd, wf, bias), c.y_b),
+                              ('fwd+bias+res', lambda: ops.conv_fwd(desc, xd, wf, bias, res), c.y_br),
+                              ('fwd+bias+res+relu', lambda: ops.conv_fwd(desc, xd, wf, bias, res, relu=True), c.y_brr)):
+            y, labels = _run(ops, fn)
+            assert _check_builds(tag + what, labels, e_fwd) == 0
+            _same(tag + what, y, ref, dtype)
+        (y, part), labels = _run(ops, lambda: ops.conv_fwd_stats(desc, xd, wf, bias))
+        assert _check_builds(tag + 'fwd+stats', labels, e_fwd) == 1
+        _same(tag + 'fwd+stats', y, c.y_b, dtype)
+        _check_stats(tag + 'fwd+stats', part, Co, c.y_b, N * c.Ho * c.Wo)
+
+        if c.has_dgrad:
+            sc = torch.tensor(0.25, device=gpu)
+            base, mask, bias_i = _dev(c.base, dtype, gpu), c.mask[per].to(gpu), c.bias_i.to(gpu)
+            for what, fn, ref, exp in (
+                    ('dgrad', lambda: ops.conv_dgrad(desc, dyd, wt), c.dx, e_dgrad),
+                    ('dgrad*scale', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc), c.dx_q, e_dgrad),
+                    ('dgrad*scale+acc', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc, out=base.clone(), accumulate=True), c.dx_acc, e_acc),
+                    ('dgrad+macc', lambda: ops.conv_dgrad_masked_acc(desc, dyd, wt, base.clone(), mask), c.dx_macc[per], e_acc),
+                    ('deconv+bias', lambda: ops.deconv_fwd_act(desc, dyd, wt, bias_i), c.dx_b, e_dgrad),
+                    ('deconv+bias+relu', lambda: ops.deconv_fwd_act(desc, dyd, wt, bias_i, relu=True), c.dx_br, e_dgrad)):
+                dx, labels = _run(ops, fn)
+                assert _check_builds(tag + what, labels, exp) == 0
+                _same(tag + what, dx, ref, dtype)
+            (dx, part), labels = _run(ops, lambda: ops.conv_dgrad_stats(desc, dyd, wt))
+            epi = _check_builds(tag + 'dgrad+stats', labels, e_dgrad)
+            _same(tag + 'dgrad+stats', dx, c.dx, dtype)
+            assert (epi == 1) == (part is not None)          # the statistics are fused, or refused (uneven phases), never half done
+            if s == 1:
+                assert epi == 1
+            if part is not None:
+                _check_stats(tag + 'dgrad+stats', part, Ci, c.dx, N * H * W)
+            # the input gradient as the dy of a BatchNorm: exact dx, that BatchNorm's reduction partials against its own passes
+            xb = _dev(c.base, dtype, gpu)
+            gamma, beta = (1 + c.bias_i / 64).to(gpu), (c.bias_i / 32).to(gpu)
+            rm, rv, nbt = torch.zeros(Ci, device=gpu), torch.ones(Ci, device=gpu), torch.zeros((), dtype=torch.int64, device=gpu)
+            _, mean, invstd = ops.bn_train_fwd(xb, None, gamma, beta, rm, rv, nbt, 1e-5, 0.1, False)
+            bn = (xb, None, gamma, beta, mean, invstd, False)
+            (dx, part), labels = _run(ops, lambda: ops.conv_dgrad_bnbwd(desc, dyd, wt, bn))
+            epi = _check_builds(tag + 'dgrad+bnb', labels, e_bnb)
+            _same(tag + 'dgrad+bnb', dx, c.dx, dtype)
+            assert (epi == 2) == (part is not None)
+            if s == 1:
+                assert epi == 2
+            if part is not None:
+                sums = []
+                for pp in (None, part):
+                    dg, db = torch.zeros(Ci, device=gpu), torch.zeros(Ci, device=gpu)
+                    ops.bn_bwd(dx, xb, None, gamma, mean, invstd, dg, db, False, False, False, beta=beta, partial=pp)
+                    sums.append((dg, db))
+                (dga, dba), (dgb, dbb) = sums
+                tol = 2e-5 * (float(dga.abs().max()) + float(dba.abs().max()) + 1.0)     # as test_gemm_epilogue_bn_backward_reduction
+                assert float((dga - dgb).abs().max()) <= tol and float((dba - dbb).abs().max()) <= tol
+
+        kind, slabs = e_wgrad.split(' ')
+        dw = torch.full((Co, k, k, Ci), 7.0, dtype=torch.float32, device=gpu)
+        _, labels = _run(ops, lambda: ops.conv_wgrad(desc, xd, dyd, dw, accumulate=False))
+        print('\nLABEL %swgrad %s' % (tag, ' | '.join(labels)))
+        assert len(labels) == 1 and labels[0].split(' ')[0] == kind and labels[0].split(' ')[-1] == slabs, (labels, e_wgrad)
+        _same(tag + 'wgrad', dw, c.dw, torch.float32)
+        dw = c.dw0.to(gpu).contiguous()
+        _, labels = _run(ops, lambda: ops.conv_wgrad(desc, xd, dyd, dw, accumulate=True))
+        assert len(labels) == 1 and labels[0].split(' ')[0] == kind and labels[0].split(' ')[-1] == slabs, (labels, e_wgrad)
+        _same(tag + 'wgrad+acc', dw, c.dw_acc, torch.float32)
+        if dt == 'f32':
+            R._cache.pop(name, None)          # both formats done: drop the float64 references of this case
+
+
+# ---------------------------------------------------------------------------------------------- concat-K forward
+_CAT = [(n, dt) for n in _names(R.CAT_CASES) for dt in ('bf16', 'f32')]
+if _CAT:
+    @pytest.mark.parametrize('name,dt', _CAT, ids=['%s-%s' % p for p in _CAT])
+    def test_concat_k_builds_return_the_reference_bits(gpu, name, dt):
+        ops = _ops()
+        c = R.build_cat_case(name)
+        dtype = DT[dt]
+        expect = CAT_EXPECT[name][0 if dt == 'bf16' else 1]
+        N, Ci, H, W, Co, k, s, p = c.shape
+        desc = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype)
+        xd = _dev(c.x, dtype, gpu)
+        wf, _ = ops.pack_weights(c.w.permute(0, 2, 3, 1).contiguous().to(gpu), Co, k * k, Ci, Ci, dtype)
+        b1, b2 = c.b1.to(gpu), c.b2.to(gpu)
+        for n2 in R.CAT_C2[dtype]:          # one 16-byte chunk of second-operand channels, and three
+            R.assert_exact_in(dtype, c.y[n2], c.y_b[n2])
+            x2d, w2 = _dev(c.x2[n2], dtype, gpu), c.w2[n2].to(gpu).to(dtype).contiguous()
+            tag = '%s/%s c2=%d ' % (name, dt, n2)
+            y, labels = _run(ops, lambda: ops.conv_fwd_cat(desc, xd, wf, None, x2d, w2, None))
+            assert _check_builds(tag + 'cat', labels, expect) == 0
+            _same(tag + 'cat', y, c.y[n2], dtype)
+            y, labels = _run(ops, lambda: ops.conv_fwd_cat(desc, xd, wf, b1, x2d, w2, b2))
+            assert _check_builds(tag + 'cat+bias', labels, expect) == 0
+            _same(tag + 'cat+bias', y, c.y_b[n2], dtype)
+            (y, part), labels = _run(ops, lambda: ops.conv_fwd_cat(desc, xd, wf, b1, x2d, w2, b2, want_stats=True))
+            assert _check_builds(tag + 'cat+stats', labels, expect) == 1
+            _same(tag + 'cat+stats', y, c.y_b[n2], dtype)
+            _check_stats(tag + 'cat+stats', part, Co, c.y_b[n2], N * c.Ho * c.Wo)
+
+
+# ---------------------------------------------------------------------------------------------- rounding of the store path
+ROUNDING_EXPECT = {     # the builds of R.ROUNDING_CASES, in order
+    'default': ['g64x64', 'g64x128', 'g128x64', 'pgemm bm64 bn64 ns8', 'pgemm bm64 bn128 ns6'],
+    'dma_kw3': ['g128x128 dma'],
+    't256d': ['g256x256 dma'],
+}
+ROUNDING = {g: [c + (e,) for c, e in zip(R.ROUNDING_CASES[g], ROUNDING_EXPECT[g])] for g in R.ROUNDING_CASES}
+if GROUP in ROUNDING:
+    @pytest.mark.parametrize('case', ROUNDING[GROUP], ids=lambda c: '%s-%dx%dx%dx%d' % ((c[5].replace(' ', '_'),) + c[:4]))
+    def test_bf16_store_rounds_to_nearest_even(gpu, case):
+        """The exact tests never round; this one pins the one rounding they do not see.  Sums of 256 .. 384 in magnitude, where
+        bf16 is spaced by 2: odd sums are ties.  Expected: float64 -> fp32 -> bf16, i.e. round to nearest even."""
+        import mi355
+        ops = _ops()
+        lib = mi355.load()
+        N, H, W, Co, pg, expect = case
+        x, w, sums = R.rounding_case(N, H, W, Co)
+        ref = R.conv_fwd(x, w, 1, 0)
+        assert set(int(v) for v in ref.unique()) == set(sums)
+        assert not torch.equal(R.to_dtype(ref, torch.bfloat16).double(), ref)         # the case does round
+        desc = ops.make_desc(N, H, W, 64, Co, 1, 1, 1, 0, torch.bfloat16)
+        wf, _ = ops.pack_weights(w.permute(0, 2, 3, 1).contiguous().to(gpu), Co, 1, 64, 64, torch.bfloat16)
+        xd = _dev(x, torch.bfloat16, gpu)
+        prev = lib.mi355_set_pgemm(pg) if pg is not None else None
+        try:
+            y, labels = _run(ops, lambda: ops.conv_fwd(desc, xd, wf))
+        finally:
+            if pg is not None:
+                lib.mi355_set_pgemm(prev)
+        assert _check_builds('rounding %s' % (case,), labels, expect) == 0
+        _same('rounding', y, ref, torch.bfloat16)
+
+
+if GROUP == 'default':
+    # ------------------------------------------------------------------------------------------ persistent GEMM
+    PGEMM = {       # name: (forward builds (plain, addend ring), input-gradient builds (plain, addend ring)) of R.PGEMM_CASES
+        'pg_k64':   (('pgemm bm64 bn128 ns6', 'pgemm bm64 bn128 ns4 add'), ('pgemm bm64 bn64 ns5', 'pgemm bm64 bn64 ns8 add')),
+        'pg_k128':  (('pgemm bm64 bn64 ns6', 'pgemm bm64 bn64 ns8 add'), ('pgemm bm64 bn128 ns6', 'pgemm bm64 bn128 ns4 add')),
+        'pg_k256':  (('pgemm bm64 bn128 ns8', 'pgemm bm64 bn128 ns4 add'), ('pgemm bm64 bn128 ns4', 'pgemm bm64 bn128 ns5 add')),
+        'pg_k512':  (('pgemm bm64 bn64 ns8', 'pgemm bm64 bn64 ns8 add'), ('pgemm bm64 bn128 ns4', 'pgemm bm64 bn128 ns5 add')),
+        'pg_co72':  (('pgemm bm64 bn128 ns6', 'pgemm bm64 bn128 ns4 add'), None),
+    }
+
+    @pytest.mark.parametrize('name', sorted(PGEMM))
+    def test_pgemm_builds_return_the_reference_bits(gpu, name):
+        """mi355_set_pgemm(2): the persistent GEMM wherever the launch fits it -- 351 rows (the last of six row tiles holds 31),
+        K = 64 .. 512 (the longest K whose weight slice fits LDS; every ring depth the defaults choose), 64- and 128-wide column tiles,
+        72 live columns, every epilogue."""
+        import mi355
+        ops = _ops()
+        lib = mi355.load()
+        c = R.build_pgemm_case(name)
+        N, Ci, H, W, Co = c.shape
+        has_dgrad, (e_fwd, e_dgrad) = c.has_dgrad, PGEMM[name]
+        dtype = torch.bfloat16
+        R.assert_exact_in(dtype, *c.values)
+        x, w, bias, res, y, y_b, y_brr = c.x, c.w, c.bias, c.res, c.y, c.y_b, c.y_brr
+        desc = ops.make_desc(N, H, W, Ci, Co, 1, 1, 1, 0, dtype)
+        wf, wt = ops.pack_weights(w.permute(0, 2, 3, 1).contiguous().to(gpu), Co, 1, Ci, Ci, dtype)
+        xd, resd, biasd = _dev(x, dtype, gpu), _dev(res, dtype, gpu), bias.to(gpu)
+        prev = lib.mi355_set_pgemm(2)
+        try:
+            for what, fn, ref, exp in (('fwd', lambda: ops.conv_fwd(desc, xd, wf), y, e_fwd[0]),
+                                       ('fwd+bias', lambda: ops.conv_fwd(desc, xd, wf, biasd), y_b, e_fwd[0]),
+                                       ('fwd+bias+res+relu', lambda: ops.conv_fwd(desc, xd, wf, biasd, resd, relu=True), y_brr, e_fwd[1])):
+                got, labels = _run(ops, fn)
+                assert _check_builds('%s %s' % (name, what), labels, exp) == 0
+                _same('%s %s' % (name, what), got, ref, dtype)
+            (got, part), labels = _run(ops, lambda: ops.conv_fwd_stats(desc, xd, wf, biasd))
+            assert _check_builds(name + ' fwd+stats', labels, e_fwd[0]) == 1
+            _same(name + ' fwd+stats', got, y_b, dtype)
+            _check_stats(name + ' fwd+stats', part, Co, y_b, N * H * W)
+            if has_dgrad:
+                dy, base, mask, dx, dx_acc, dx_macc = c.dy, c.base, c.mask, c.dx, c.dx_acc, c.dx_macc
+                dyd, based, sc = _dev(dy, dtype, gpu), _dev(base, dtype, gpu), torch.tensor(0.25, device=gpu)
+                for what, fn, ref, exp in (
+                        ('dgrad', lambda: ops.conv_dgrad(desc, dyd, wt), dx, e_dgrad[0]),
+                        ('dgrad*scale+acc', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc, out=based.clone(), accumulate=True), dx_acc, e_dgrad[1]),
+                        ('dgrad+macc', lambda: ops.conv_dgrad_masked_acc(desc, dyd, wt, based.clone(), mask.to(gpu)), dx_macc, e_dgrad[1])):
+                    got, labels = _run(ops, fn)
+                    assert _check_builds('%s %s' % (name, what), labels, exp) == 0
+                    _same('%s %s' % (name, what), got, ref, dtype)
+        finally:
+            lib.mi355_set_pgemm(prev)
+
+    # ------------------------------------------------------------------------------------------ 21-channel heat-map conv
+    @pytest.mark.parametrize('dt', ['bf16', 'f32'])
+    @pytest.mark.parametrize('name', sorted(R.HM_CASES))
+    def test_heatmap_conv_returns_the_reference_bits(gpu, dt, name):
+        """conv1x1_heatmap (128 x 32 tile, NCHW fp32 output): HW = 120 (row tiles that straddle images and a partial last one) and
+        4096, K = 21."""
+        ops = _ops()
+        dtype = DT[dt]
+        N, C, K, H, W = R.HM_CASES[name]
+        c = R.build_hm_case(name)
+        R.assert_exact_in(torch.float32, c.ref)
+        y, labels = _run(ops, lambda: ops.conv1x1_heatmap(_dev(c.x, dtype, gpu), c.w.view(K, C).to(gpu).to(dtype).contiguous(), c.b.to(gpu), K))
+        assert _check_builds('%s/%s' % (name, dt), labels, 'g128x32 hm' if dt == 'bf16' else 'g128x32 f32 hm') == 0
+        assert y.is_contiguous()
+        _same(name, y, c.ref, torch.float32)
+
+    # ------------------------------------------------------------------------------------------ grouped weight gradients
+    GROUPED = {     # form: the launches R.GROUPED_CASES[form] must make (kernel and items per launch), in order
+        'wgrad_group':    ['wgrad_group x3', 'wgrad_group x1'],
+        'wgrad_group256': ['wgrad_group256 x2', 'wgrad_group256 x1'],
+        'wgrad_kw_group': ['wgrad_kw_group x1', 'wgrad_kw_group x2', 'wgrad_kw_group x1'],
+    }
+    _GROUPED = [(f, dt) for f in sorted(GROUPED) for dt in R.GROUPED_CASES[f][0]]
+
+    @pytest.mark.parametrize('form,dt', _GROUPED, ids=['%s-%s' % p for p in _GROUPED])
+    def test_grouped_weight_gradients_return_the_reference_bits(gpu, form, dt):
+        """The three grouped weight-gradient kernels on mixed items: overwriting and accumulating ones, a strided 1x1, a 3x3 the
+        specialised kernels do not take, and an item that accumulates onto the gradient an earlier item of the call wrote."""
+        ops = _ops()
+        dtype = DT[dt]
+        heads = GROUPED[form]
+        cases, refs = R.build_grouped_case(form)
+        items = []
+        for (N, H, W, Ci, Co, k, s, p, acc, share), x, dy, dw0 in cases:
+            if share is not None:
+                dw = items[share][3]
+            elif acc:
+                dw = dw0.to(gpu).contiguous()
+            else:
+                dw = torch.full((Co, k, k, Ci), float('nan'), device=gpu)
+            items.append((ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype), _dev(x, dtype, gpu), _dev(dy, dtype, gpu), dw, acc))
+        R.assert_exact_in(torch.float32, *[r for r in refs if r is not None])
+        _, labels = _run(ops, lambda: ops.conv_wgrad_grouped(items))
+        print('\nLABEL %s/%s %s' % (form, dt, ' | '.join(labels)))
+        assert [' '.join(l.split(' ')[:2]) for l in labels] == heads, labels
+        for i, ref in enumerate(refs):
+            if ref is not None:
+                _same('%s item %d' % (form, i), items[i][3], ref, torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- fp8 and MX operands
+_FP8 = _names(R.FP8_CASES)
+if _FP8:
+    @pytest.mark.parametrize('name', _FP8)
+    def test_fp8_and_mx_builds_return_the_reference_bits(gpu, name):
+        """The same integers through the fp8 quantisers (just-in-time power-of-two scales) and the MX quantiser (E8M0 block
+        scales): quantise -> dequantise must return them unchanged -- a test of the quantisers and the precondition for exactness
+        -- and then every fp8 / MX convolution must return the reference's bits."""
+        import mi355
+        ops = _ops()
+        lib = mi355.load()
+        c = R.build_fp8_case(name)
+        bf16 = torch.bfloat16
+        R.assert_exact_in(bf16, c.y, c.y_b, c.dx, c.dx_q, c.dx_acc)
+        R.assert_exact_in(torch.float32, c.dw, c.dw_acc)
+        N, Ci, H, W, Co, k, s, p = c.shape
+        e_plain, e_kw3 = FP8_EXPECT[name]
+        e_fwd, e_dgrad = e_plain if isinstance(e_plain, tuple) else (e_plain, e_plain)
+        desc = ops.make_desc_fp8(N, H, W, Ci, Co, k, k, s, p)
+        xd, dyd, based = _dev(c.x, bf16, gpu), _dev(c.dy, bf16, gpu), _dev(c.base, bf16, gpu)
+        w_conv = c.w.permute(0, 2, 3, 1).contiguous().to(gpu)
+        bias, sc = c.bias.to(gpu), torch.tensor(0.25, device=gpu)
+        sx, sw, sd = ops.fp8_state(gpu), ops.fp8_state(gpu), ops.fp8_state(gpu)
+        x8 = ops.fp8_quantize(xd, sx, ops.E4M3, jit=True)
+        dy8 = ops.fp8_quantize(dyd, sd, ops.E5M2, jit=True)
+        wf8, wt8 = ops.pack_weights_fp8(w_conv, Co, k * k, Ci, sw)
+        torch.cuda.synchronize()
+        assert torch.equal((x8.view(torch.float8_e4m3fn).float() * sx[1]).cpu(), c.x)
+        assert torch.equal((dy8.view(torch.float8_e5m2).float() * sd[1]).cpu(), c.dy)
+        assert torch.equal((wf8.view(torch.float8_e4m3fn).float() * sw[1]).view(Co, k, k, Ci).cpu(), c.w.permute(0, 2, 3, 1))
+        assert torch.equal((wt8.view(torch.float8_e4m3fn).float() * sw[1]).view(Ci, k, k, Co).cpu(), c.w.permute(1, 2, 3, 0))
+        prev = lib.mi355_set_fp8_kw3(0)
+        try:
+            for mode, ef, ed in ((0, e_fwd, e_dgrad), (1, e_kw3, e_kw3)):
+                if ef is None:
+                    continue
+                lib.mi355_set_fp8_kw3(mode)
+                tag = '%s kw3=%d ' % (name, mode)
+                (y, part), labels = _run(ops, lambda: ops.conv_fwd_fp8(desc, x8, sx, wf8, sw, bias, want_stats=True))
+                assert _check_builds(tag + 'fwd8', labels, 'f8 ' + ef) == 1
+                _same(tag + 'fwd8', y, c.y_b, bf16)
+                _check_stats(tag + 'fwd8', part, Co, c.y_b, N * c.Ho * c.Wo)
+                y, labels = _run(ops, lambda: ops.conv_fwd_fp8(desc, x8, sx, wf8, sw))
+                assert _check_builds(tag + 'fwd8 plain', labels, 'f8 ' + ef) == 0
+                _same(tag + 'fwd8 plain', y, c.y, bf16)
+                dx, labels = _run(ops, lambda: ops.conv_dgrad_fp8(desc, dy8, sd, wt8, sw))
+                assert _check_builds(tag + 'dgrad8', labels, 'f8 ' + ed + ' bf8') == 0
+                _same(tag + 'dgrad8', dx, c.dx, bf16)
+                (dx, part), labels = _run(ops, lambda: ops.conv_dgrad_fp8(desc, dy8, sd, wt8, sw, want_stats=True))
+                epi = _check_builds(tag + 'dgrad8+stats', labels, 'f8 ' + ed + ' bf8')
+                _same(tag + 'dgrad8+stats', dx, c.dx, bf16)
+                assert (epi == 1) == (part is not None) and (epi == 1 or s != 1)
+                if part is not None:
+                    _check_stats(tag + 'dgrad8+stats', part, Ci, c.dx, N * H * W)
+                dx, labels = _run(ops, lambda: ops.conv_dgrad_fp8(desc, dy8, sd, wt8, sw, scale_dev=sc, out=based.clone(), accumulate=True))
+                assert _check_builds(tag + 'dgrad8*scale+acc', labels, 'f8 ' + ed + ' bf8') == 0
+                _same(tag + 'dgrad8*scale+acc', dx, c.dx_acc, bf16)
+        finally:
+            lib.mi355_set_fp8_kw3(prev)
+        dw = torch.full((Co, k, k, Ci), float('nan'), device=gpu)
+        _, labels = _run(ops, lambda: ops.conv_wgrad_fp8(desc, x8, sx, dy8, sd, dw, False))
+        print('\nLABEL %s wgrad8 %s' % (name, ' | '.join(labels)))
+        assert len(labels) == 1 and labels[0].startswith('wgrad8 '), labels
+        _same(name + ' wgrad8', dw, c.dw, torch.float32)
+        dw = c.dw0.to(gpu).contiguous()
+        ops.conv_wgrad_fp8(desc, x8, sx, dy8, sd, dw, True)
+        _same(name + ' wgrad8+acc', dw, c.dw_acc, torch.float32)
+
+        # MX: e4m3 elements, one E8M0 scale per 32 contracted channels
+        xq, xs = ops.mx_quantize(xd)
+        dyq, dys = ops.mx_quantize(dyd)
+        wf, sf, wt, st = ops.pack_weights_mx(w_conv, Co, k * k, Ci)
+        torch.cuda.synchronize()
+        nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().cpu()
+        assert torch.equal(mx_dequantize(nhwc(xq), xs.view(N, H, W, Ci // 32).cpu()), c.x.permute(0, 2, 3, 1))
+        assert torch.equal(mx_dequantize(nhwc(dyq), dys.view(N, c.Ho, c.Wo, Co // 32).cpu()), c.dy.permute(0, 2, 3, 1))
+        assert torch.equal(mx_dequantize(wf.view(Co, k, k, Ci).cpu(), sf.view(Co, k, k, Ci // 32).cpu()), c.w.permute(0, 2, 3, 1))
+        assert torch.equal(mx_dequantize(wt.view(Ci, k, k, Co).cpu(), st.view(Ci, k, k, Co // 32).cpu()), c.w.permute(1, 2, 3, 0))
+        (y, part), labels = _run(ops, lambda: ops.conv_fwd_mx(desc, xq, xs, wf, sf, bias, want_stats=True))
+        assert _check_builds(name + ' fwdmx', labels, 'mx ' + e_fwd) == 1
+        _same(name + ' fwdmx', y, c.y_b, bf16)
+        _check_stats(name + ' fwdmx', part, Co, c.y_b, N * c.Ho * c.Wo)
+        dx, labels = _run(ops, lambda: ops.conv_dgrad_mx(desc, dyq, dys, wt, st))
+        assert _check_builds(name + ' dgradmx', labels, 'mx ' + e_dgrad) == 0
+        _same(name + ' dgradmx', dx, c.dx, bf16)
+        (dx, part), labels = _run(ops, lambda: ops.conv_dgrad_mx(desc, dyq, dys, wt, st, want_stats=True))
+        epi = _check_builds(name + ' dgradmx+stats', labels, 'mx ' + e_dgrad)
+        _same(name + ' dgradmx+stats', dx, c.dx, bf16)
+        assert (epi == 1) == (part is not None) and (epi == 1 or s != 1)
+        if part is not None:
+            _check_stats(name + ' dgradmx+stats', part, Ci, c.dx, N * H * W)
+        y, labels = _run(ops, lambda: ops.conv_fwd_mx(desc, xq, xs, wf, sf))
+        assert _check_builds(name + ' fwdmx plain', labels, 'mx ' + e_fwd) == 0
+        _same(name + ' fwdmx plain', y, c.y, bf16)
+        dx, labels = _run(ops, lambda: ops.conv_dgrad_mx(desc, dyq, dys, wt, st, scale_dev=sc, out=based.clone(), accumulate=True))
+        assert _check_builds(name + ' dgradmx*scale+acc', labels, 'mx ' + e_dgrad) == 0
+        _same(name + ' dgradmx*scale+acc', dx, c.dx_acc, bf16)
+
+
+# ---------------------------------------------------------------------------------------------- the forced builds, in children
+if GROUP == 'default':
+    _abnormal = []          # a child that ended by a signal, an abort or its timeout: nothing more is started on the GPU
+
+    @pytest.mark.parametrize('group', sorted(GROUPS))
+    def test_forced_builds_in_a_child_process(gpu, group):
+        """This module once more under the switches of GROUPS[group] (read once per process, hence a child): the cases of that
+        group only.  One child at a time, each with its own timeout, no retry."""
+        if _abnormal:
+            pytest.fail('not started after an abnormal exit (%s)' % _abnormal[0])
+        env = dict(os.environ, MI355_CONV_EXACT_GROUP=group, **GROUPS[group])
+        cmd = [sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-x', '-q', '-s', '-m', 'gpu', '-p', 'no:cacheprovider']
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
+        except subprocess.TimeoutExpired:
+            _abnormal.append('%s: timeout' % group)
+            pytest.fail('child %s ran into its timeout' % group)
+        if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
+            _abnormal.append('%s: exit status %d' % (group, r.returncode))
+        print('\n' + '\n'.join(l for l in r.stdout.splitlines() if l.startswith(('LABEL ', 'STATS '))))
+        assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+        assert ' passed' in r.stdout and 'failed' not in r.stdout, r.stdout[-2000:]
