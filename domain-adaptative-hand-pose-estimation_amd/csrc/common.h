@@ -1,10 +1,16 @@
 // Shared device/host helpers for libmi355pose (gfx950 only; wave = 64).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 #include "../../include/mi355pose.h"
+
+// ---- plain C++ (conv_plan.h and its CPU probe include this part with a host compiler) --
+static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline int ilog2_exact(int v) { int s = 0; while ((1 << s) < v) ++s; return ((1 << s) == v) ? s : -1; }   // log2 of a power of two, else -1
+
+#ifdef __HIP__
+#include <hip/hip_runtime.h>
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;   // MFMA A/B fragment (8 bf16)
@@ -20,7 +26,6 @@ void mi355_set_error(const char* fmt, ...);
   if (e_ != hipSuccess) MI_FAIL(MI355_ELAUNCH, "%s: %s", (name), hipGetErrorString(e_)); } while (0)
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- element traits -------------------------------------------------------------------
 template <typename T> struct Elem;
@@ -158,3 +163,4 @@ struct ProfScope {
 bool prof_on();
 void prof_set_tag(const char* fmt, ...);
 void prof_amend_label(const char* fmt, ...);
+#endif  // __HIP__

@@ -1384,68 +1384,63 @@ __global__ void zero_fill_kernel(uint4* __restrict__ p, size_t n16) {
 }
 
 // ------------------------------------------------------------------------------------ host side
-static int ilog2_exact(int v) { int s = 0; while ((1 << s) < v) ++s; return ((1 << s) == v) ? s : -1; }
-
+// describe, choose, launch: the first two are conv_plan.h; what follows maps a chosen ConvBuild to its instantiation.
 template <typename T, int BM, int BN, bool SMALL_C, int WGM, int WGN, bool HM_OUT, bool DMA, int EPI, bool KW3 = false, bool CAT = false, int KG = 1>
-static void launch_gather_epi(const GatherArgs& a, hipStream_t st) {
+static void launch_gather_epi(const GatherArgs& a, const ConvBuild& b, hipStream_t st) {
   using SM = GatherSmem<T, BM, BN, DMA ? 2 : 1, KW3>;
   constexpr int smem = SM::kBytes + (KG - 1) * 2 * SM::kStage;
   auto kern = gather_gemm_kernel<T, BM, BN, SMALL_C, WGM, WGN, HM_OUT, DMA, EPI, KW3, CAT, KG>;
   static bool attr_set = false;   // raise the dynamic-LDS cap once per instantiation
   if (!attr_set) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr_set = true; }
-  if (prof_on()) {
-    char epi[8] = "";
-    if (EPI) snprintf(epi, sizeof(epi), " epi%d", EPI);
-    prof_amend_label("[%sg%dx%d%s%s%s%s%s%s%s]", CAT ? "cat " : "", BM, BN, sizeof(T) == 4 ? " f32" : "", SMALL_C ? " small" : "", HM_OUT ? " hm" : "",
-                     DMA ? " dma" : "", KW3 ? " kw3" : "", KG == 2 ? " kg2" : "", epi);
-  }
+  if (prof_on()) { char text[64]; conv_build_text(b, text, sizeof(text)); prof_amend_label("[%s]", text); }
   hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(64 * WGM * WGN * KG), smem, st, a);
 }
 
+// `b` names this instantiation (launch_gather_build, heatmap_conv): its tile grid and epilogue, then the launch
 template <typename T, int BM, int BN, bool SMALL_C, int WGM = 2, int WGN = 2, bool HM_OUT = false, bool DMA = false, bool KW3 = false, bool CAT = false, int KG = 1>
-static void launch_gather(GatherArgs& a, hipStream_t st) {
-  a.ntn = cdiv(a.Nout, BN);
-  int mx = 0;
-  for (int i = 0; i < a.nphase; ++i) { a.ph[i].ntm = cdiv(a.ph[i].M, BM); if (a.ph[i].ntm > mx) mx = a.ph[i].ntm; }
-  a.ntiles = a.nphase * mx * a.ntn;
-  a.stat_slices = 0;
-  if (a.stat_partial) {
-    bool even = !HM_OUT && !a.residual && !a.accumulate;        // phases of unequal tile count would leave unwritten slices
-    for (int i = 0; i < a.nphase; ++i) even = even && a.ph[i].ntm == mx;
-    if (even && (size_t)a.nphase * mx * a.Nout * 3 * sizeof(float) <= a.stat_bytes) a.stat_slices = a.nphase * mx;
-    else a.stat_partial = nullptr;
+static void launch_gather(GatherArgs& a, ConvBuild b, hipStream_t st) {
+  plan_gather_launch(a, b, conv_knobs());
+  if constexpr (gather_has_bnb(BM, HM_OUT, KW3, CAT, KG)) {
+    if (b.epi == 2) { launch_gather_epi<T, BM, BN, SMALL_C, WGM, WGN, HM_OUT, DMA, 2>(a, b, st); return; }
   }
-  if (a.bnb_partial) {
-    bool even = !HM_OUT && !a.stat_partial;
-    for (int i = 0; i < a.nphase; ++i) even = even && a.ph[i].ntm == mx;
-    if (even && (size_t)a.nphase * mx * a.Nout * 2 * sizeof(float) <= a.stat_bytes) a.stat_slices = a.nphase * mx;
-    else a.bnb_partial = nullptr;
+  if constexpr (gather_has_stats(BM, BN, HM_OUT, DMA)) {
+    if (b.epi == 1) { launch_gather_epi<T, BM, BN, SMALL_C, WGM, WGN, HM_OUT, DMA, 1, KW3, CAT, KG>(a, b, st); return; }
   }
-  constexpr bool EXTRAS = !HM_OUT && BM <= 128 && !CAT && KG == 1;     // the BatchNorm-backward epilogue exists for the regular tiles only
-  constexpr bool STATS = !HM_OUT && (BM <= 128 || (BM == 256 && BN == 128) || (BM == 256 && BN == 256 && DMA));   // statistics: also the 256x128 macro tile and the 256x256 LDS-DMA build
-  if (!EXTRAS && a.bnb_partial) a.bnb_partial = nullptr;
-  static const bool stats256 = !(getenv("MI355_STATS_256") && atoi(getenv("MI355_STATS_256")) == 0);      // A/B switch
-  if ((!STATS || (BM == 256 && !stats256)) && a.stat_partial) { a.stat_partial = nullptr; a.stat_slices = 0; }
-  if (!a.stat_partial && !a.bnb_partial) a.stat_slices = 0;
-  if constexpr (EXTRAS) {
-    if (a.bnb_partial) { launch_gather_epi<T, BM, BN, SMALL_C, WGM, WGN, HM_OUT, DMA, 2>(a, st); return; }     // (EPI 2 has no KW3 build)
-  }
-  if constexpr (STATS) {
-    if (a.stat_partial) { launch_gather_epi<T, BM, BN, SMALL_C, WGM, WGN, HM_OUT, DMA, 1, KW3, CAT, KG>(a, st); return; }
-  }
-  launch_gather_epi<T, BM, BN, SMALL_C, WGM, WGN, HM_OUT, DMA, 0, KW3, CAT, KG>(a, st);
+  launch_gather_epi<T, BM, BN, SMALL_C, WGM, WGN, HM_OUT, DMA, 0, KW3, CAT, KG>(a, b, st);
 }
 
-// Do the 256 x 256 tiles of this launch fill whole rounds of 256 CUs (one 8-wave block per CU)?  mode 1: exactly one round of
-// >= tmin tiles; mode 2 (experiment): up to four rounds, the last one with >= tmin tiles, phases of a strided launch counted separately.
-static bool t256_fits(const GatherArgs& a, long Mtot, int mode, long tmin) {
-  (void)Mtot;
-  long t = 0;
-  for (int i = 0; i < a.nphase; ++i) t += cdiv(a.ph[i].M, 256L) * (a.Nout / 256);
-  if (mode < 2) return t >= tmin && t <= 256;
-  const long rem = t % 256;
-  return t >= tmin && t <= 1024 && (rem == 0 || rem >= tmin);
+// Every build of the gather kernel the chooser can name (the heat-map build has its own entry point, heatmap_conv):
+//   BM, BN, small-channel, waves along M, waves along N, LDS-DMA, shared A tile, concat-K, K groups, bf16 only
+#define GATHER_BUILDS(X) \
+  X(128,  64, true,  2, 2, false, false, false, 1, false) \
+  X(128, 128, false, 2, 2, false, false, false, 1, false) \
+  X( 64, 128, false, 2, 2, false, false, false, 1, false) \
+  X(128,  64, false, 2, 2, false, false, false, 1, false) \
+  X( 64,  64, false, 2, 2, false, false, false, 1, false) \
+  X(128, 128, false, 2, 2, true,  false, false, 1, false) \
+  X( 64, 128, false, 2, 2, true,  false, false, 2, false) \
+  X(128, 128, false, 2, 2, true,  false, false, 2, false) \
+  X(256, 256, false, 2, 4, false, false, false, 1, false) \
+  X(256, 256, false, 2, 4, true,  false, false, 1, true)  \
+  X(128,  64, false, 2, 2, false, true,  false, 1, true)  \
+  X(128, 128, false, 2, 2, false, true,  false, 1, true)  \
+  X(256, 128, false, 2, 2, false, true,  false, 1, true)  \
+  X( 64,  64, false, 2, 2, false, false, true,  1, false) \
+  X( 64, 128, false, 2, 2, false, false, true,  1, false) \
+  X(128, 128, false, 2, 2, false, false, true,  1, false) \
+  X(128, 128, false, 2, 2, true,  false, true,  1, false) \
+  X(256, 256, false, 2, 4, true,  false, true,  1, true)
+template <typename T>
+static bool launch_gather_build(GatherArgs& a, const ConvBuild& b, hipStream_t st) {
+#define X(BM, BN, SMALL_C, WGM, WGN, DMA, KW3, CAT, KG, BF16_ONLY) \
+  if (b.bm == BM && b.bn == BN && b.small_c == SMALL_C && b.dma == DMA && b.kw3 == KW3 && b.cat == CAT && b.kg == KG) { \
+    if constexpr (!BF16_ONLY || sizeof(T) == 2) { launch_gather<T, BM, BN, SMALL_C, WGM, WGN, false, DMA, KW3, CAT, KG>(a, b, st); return true; } \
+  }
+  GATHER_BUILDS(X)
+#undef X
+  return false;
 }
+
 template <typename T>
 static int dispatch_gather(GatherArgs& a, hipStream_t st) {
   constexpr int CH = MmaTraits<T>::CH;
@@ -1454,10 +1449,9 @@ static int dispatch_gather(GatherArgs& a, hipStream_t st) {
   if (a.cshift < 0) MI_FAIL(MI355_EINVAL, "gather: Ci/%d must be a power of two (Ci=%d)", CH, a.Ci);
   if (a.Nout % CH) MI_FAIL(MI355_EINVAL, "gather: Nout=%d not a multiple of %d", a.Nout, CH);
   if (a.nphase < 1 || a.nphase > 4) MI_FAIL(MI355_EINVAL, "gather: nphase=%d", a.nphase);
-  long Mtot = 0, ntaps_tot = 0; int kchunks = 0; double flops = 0.0;
+  long Mtot = 0, ntaps_tot = 0; double flops = 0.0;
   for (int i = 0; i < a.nphase; ++i) {
     Mtot += a.ph[i].M; ntaps_tot += a.ph[i].ntaps;
-    if ((a.ph[i].ntaps << a.cshift) > kchunks) kchunks = a.ph[i].ntaps << a.cshift;
     flops += 2.0 * a.ph[i].M * (double)a.Nout * a.ph[i].ntaps * a.Ci;
   }
   {
@@ -1466,108 +1460,19 @@ static int dispatch_gather(GatherArgs& a, hipStream_t st) {
     a.a_bytes = (unsigned)(imgs * a.Hi * a.Wi * a.Ci * (long)sizeof(T));
     a.b_bytes = (unsigned)((long)a.Nout * a.ldb * (long)sizeof(T));
   }
-  const bool small = (a.Ci / CH) < 8;
-  const long kavg = (ntaps_tot << a.cshift) / a.nphase;   // phases of a strided dgrad differ in length
-  (void)kchunks;
   // algorithmic bytes: every input element, weight and output element once
   if (a.A2) flops += 2.0 * Mtot * (double)a.Nout * a.c2;
   ProfScope ps(st, flops, (double)a.a_bytes + (double)a.b_bytes * ntaps_tot / (a.ldb / a.Ci) + (double)Mtot * a.Nout * sizeof(T) +
                               (a.A2 ? (double)a.a2_bytes + a.b2_bytes : 0.0));
-  static const int force = getenv("MI355_TILE") ? atoi(getenv("MI355_TILE")) : -1;   // experiment switch
-  static const int dma_mode = getenv("MI355_DMA") ? atoi(getenv("MI355_DMA")) : 1;
   if (a.A2) {
-    // concatenated-K forward: the tile choices of the plain path that matter for the two layers that use it (1x1 and 3x3 / stride 2,
-    // 256 -> 256 channels), register-staged or LDS-DMA ring
-    if (small || a.nphase != 1 || a.out_sx != 1 || a.out_sy != 1 || a.bnb_partial || a.residual || a.accumulate)
+    if ((a.Ci / CH) < 8 || a.nphase != 1 || a.out_sx != 1 || a.out_sy != 1 || a.bnb_partial || a.residual || a.accumulate)
       MI_FAIL(MI355_EINVAL, "concat-K forward: plain single-phase forward conv with >= 8 input chunks only");
     if (a.c2 < CH || a.c2 % CH || a.c2 > MmaTraits<T>::BK) MI_FAIL(MI355_EINVAL, "concat-K forward: c2=%d must be a multiple of %d and <= %d", a.c2, CH, MmaTraits<T>::BK);
-    const long t128 = cdiv(Mtot, 128L) * cdiv(a.Nout, 128);
-    static const int cat_tile = getenv("MI355_CAT_TILE") ? atoi(getenv("MI355_CAT_TILE")) : 0;     // experiment switch
-    static const int t256d_cat = getenv("MI355_T256D") ? atoi(getenv("MI355_T256D")) : 2;
-    static const long t256d_cmin = getenv("MI355_T256D_MIN") ? atol(getenv("MI355_T256D_MIN")) : 192;
-    if (t256d_cat >= 2 && sizeof(T) == 2 && a.Nout % 256 == 0 && dma_mode == 1 && t256_fits(a, Mtot, t256d_cat, t256d_cmin)) {
-      if constexpr (sizeof(T) == 2) launch_gather<T, 256, 256, false, 2, 4, false, true, false, true>(a, st);
-    }
-    else if (cat_tile == 1 && a.Nout > 64) launch_gather<T, 128, 128, false, 2, 2, false, false, false, true>(a, st);
-    else if (cat_tile == 2 && a.Nout > 64) launch_gather<T, 128, 128, false, 2, 2, false, true, false, true>(a, st);
-    else if (cat_tile == 3 && a.Nout > 64) launch_gather<T, 64, 128, false, 2, 2, false, false, false, true>(a, st);
-    else if (a.Nout <= 64) launch_gather<T, 64, 64, false, 2, 2, false, false, false, true>(a, st);
-    else if ((dma_mode == 2) || (dma_mode == 1 && ((t128 >= 512 && kavg >= 128) || (t128 >= 256 && kavg >= 256)))) launch_gather<T, 128, 128, false, 2, 2, false, true, false, true>(a, st);
-    else if (t128 >= 512 && kavg <= 32 && sizeof(T) == 2) launch_gather<T, 64, 128, false, 2, 2, false, false, false, true>(a, st);
-    else if (t128 >= 512) launch_gather<T, 128, 128, false, 2, 2, false, false, false, true>(a, st);
-    else if (cdiv(Mtot, 64L) * cdiv(a.Nout, 128) >= 512) launch_gather<T, 64, 128, false, 2, 2, false, false, false, true>(a, st);
-    else launch_gather<T, 64, 64, false, 2, 2, false, false, false, true>(a, st);
-    MI_CHECK_LAUNCH("gather_gemm_cat");
-    return MI355_OK;
   }
-  if constexpr (sizeof(T) == 2) {
-    if (pgemm_eligible(a, 2)) return dispatch_pgemm(a, st);       // 1x1 / unit stride: the persistent pipelined GEMM (pgemm.hip)
-  }
-  if (small) { launch_gather<T, 128, 64, true>(a, st); }
-  else if (force == 0) launch_gather<T, 128, 128, false>(a, st);
-  else if (force == 1) launch_gather<T, 64, 128, false>(a, st);
-  else if (force == 2) launch_gather<T, 128, 64, false>(a, st);
-  else if (force == 3) launch_gather<T, 64, 64, false>(a, st);
-  else {
-    const long t128 = cdiv(Mtot, 128L) * cdiv(a.Nout, 128);
-    // 3x3 / unit stride / same-size maps of a power-of-two width <= 128: the A-tile-sharing variant (see KW3 above)
-    static const int kw3_on = getenv("MI355_KW3") ? atoi(getenv("MI355_KW3")) : 1;
-    // A/B switch: 256 x 256 LDS-DMA tiles.  1: launches of ONE round of tiles (30.41 / 30.42 -> 30.15 / 30.18 ms; with 128 .. 191 tiles too:
-    // slower); 2 (default): also up to four full rounds, the phases of strided input gradients / transposed convs, the concat-K forward
-    static const int t256d = getenv("MI355_T256D") ? atoi(getenv("MI355_T256D")) : 2;
-    static const long t256d_min = getenv("MI355_T256D_MIN") ? atol(getenv("MI355_T256D_MIN")) : 192;
-    static const long t256d_kmin = getenv("MI355_T256D_KMIN") ? atol(getenv("MI355_T256D_KMIN")) : 32;
-    static const int splitk_on = getenv("MI355_SPLITK") ? atoi(getenv("MI355_SPLITK")) : 2;                 // A/B switch (1: 128 x 128 tiles only)
-    const long t64 = cdiv(Mtot, 64L) * cdiv(a.Nout, 128);
-    static const long splitk_min = getenv("MI355_SPLITK_MIN") ? atol(getenv("MI355_SPLITK_MIN")) : 128;
-    static const long splitk_max = getenv("MI355_SPLITK_MAX") ? atol(getenv("MI355_SPLITK_MAX")) : 320;
-    static const long splitk_kmin = getenv("MI355_SPLITK_KMIN") ? atol(getenv("MI355_SPLITK_KMIN")) : 128;      // shortest K taken, in 16-byte chunks (128: the 1x1 convs with K = 1024 at 16x16 too, 30.88 / 30.81 -> 30.76 / 30.76 ms)
-    static const int kw3_n64 = getenv("MI355_KW3_N64") ? atoi(getenv("MI355_KW3_N64")) : 1;      // A/B switch: the variant for 64 output channels
-    bool kw3 = kw3_on && sizeof(T) == 2 && a.nphase == 1 && a.ph[0].ntaps == 9 && a.in_sx == 1 && a.in_sy == 1 && a.out_sx == 1 &&
-               a.out_sy == 1 && a.ph[0].OWp == a.Wi && a.ph[0].OHp == a.Hi && a.Wo == a.Wi && a.Ho == a.Hi && a.Wi >= 8 &&
-               a.Wi <= 128 && ilog2_exact(a.Wi) >= 0 && (a.Nout > 64 || (kw3_n64 && a.Nout == 64)) && a.Ci % 64 == 0 && !a.bnb_partial;
-    for (int g = 0; g < 3 && kw3; ++g) {
-      const Tap* tp = a.taps + a.ph[0].tap0 + 3 * g;
-      int seen = 0;
-      for (int k = 0; k < 3; ++k) { if (tp[k].dy != tp[0].dy || tp[k].dx < -1 || tp[k].dx > 1) kw3 = false; else seen |= 1 << (tp[k].dx + 1); }
-      if (seen != 7 || tp[0].dy < -1 || tp[0].dy > 1) kw3 = false;
-    }
-    if (kw3) a.lw = ilog2_exact(a.Wi);
-    if (a.Nout <= 64) {
-      // 3x3 64 -> 64 on the large maps (layer1 of the ResNets: 2048 tiles of 128 x 64): the shared-A-tile variant here too -- two
-      // thirds of what a 128 x 64 tile stages per tap is the A tile
-      if (kw3 && (cdiv(Mtot, 128L) >= 2048 || kw3_on == 2)) { if constexpr (sizeof(T) == 2) launch_gather<T, 128, 64, false, 2, 2, false, false, true>(a, st); }
-      else if (cdiv(Mtot, 128L) >= 512) launch_gather<T, 128, 64, false>(a, st); else launch_gather<T, 64, 64, false>(a, st);
-    } else if (sizeof(T) == 2 && getenv("MI355_T256") && a.Nout % 256 == 0 && cdiv(Mtot, 256L) * (a.Nout / 256) >= 256) launch_gather<T, 256, 256, false, 2, 4>(a, st);
-    // one 256 x 256 tile per CU on the LDS-DMA ring (8 waves, 128 accumulators each): half the bytes through L1 per MFMA of the 128 x 128
-    // tiles, for launches that offer one round of such tiles
-    // (not the accumulating epilogues: their read-modify-write of a 128-KB tile has no second block on the CU to hide behind --
-    //  1x1 1024 -> 256 @16x16 input gradient + masked accumulate 20.8 -> 25.2 us, 256 -> 256 @64x64 + accumulate 93 -> 112 us)
-    else if (t256d && sizeof(T) == 2 && (a.nphase == 1 || t256d >= 2) && a.Nout % 256 == 0 && dma_mode == 1 && !a.bnb_partial && !a.accumulate &&
-             t256_fits(a, Mtot, t256d, t256d_min) && kavg >= t256d_kmin && !(kw3 && t128 >= 2048)) {      // (the big 3x3 layers keep the shared-A-tile kernels: 309.7 vs 312.7 us)
-      if constexpr (sizeof(T) == 2) launch_gather<T, 256, 256, false, 2, 4, false, true>(a, st);
-    }
-    // LDS-DMA ring for K-heavy layers (>= 16 K-tiles): +9..12 % on the 3x3 / 4x4 convs, but -15 % on short-K 1x1 convs
-    // (2 blocks/CU instead of 3), so those keep the register-staged form.  MI355_DMA=0 disables, =2 forces (tests).
-    // (measured: 334 -> 310 us forward, 324 -> 312 us dgrad on 256->256 @64x64; at 1024 tiles the LDS-DMA ring still wins)
-    // 256x128 macro tile (128 accumulators per wave, 2 blocks/CU, 0.21 KB of L1 traffic per MFMA): 313 -> 302 us on the 64x64 layers
-    else if (kw3 && t128 >= 4096 && kw3_on != 2 && kw3_on != 4) { if constexpr (sizeof(T) == 2) launch_gather<T, 256, 128, false, 2, 2, false, false, true>(a, st); }
-    else if (kw3 && (t128 >= 2048 || kw3_on == 2)) { if constexpr (sizeof(T) == 2) launch_gather<T, 128, 128, false, 2, 2, false, false, true>(a, st); }
-    // (also the K-heavy mid-size layers, 256 .. 511 tiles with K >= 2048: 3x3 256->256 @16x16 36.2 -> 32.7 us; a 3-stage ring with
-    //  two tiles in flight and counted vmcnt measured 33.5 us there: the per-CU fill rate, not latency, bounds these layers)
-    // one 128 x 128 tile per CU or fewer and a long K: two K groups per workgroup (KG above) -- 3x3 256 -> 256 @16x16 and kin
-    // fewer 128 x 128 tiles than CUs (the 8x8 maps: 128 of them would leave half the chip idle): 64-row tiles, two K groups each
-    else if (splitk_on >= 2 && dma_mode == 1 && t128 < 256 && t64 >= splitk_min && t64 <= 384 && kavg >= splitk_kmin && !a.bnb_partial) launch_gather<T, 64, 128, false, 2, 2, false, true, false, false, 2>(a, st);
-    else if (splitk_on && dma_mode == 1 && t128 >= splitk_min && t128 <= splitk_max && kavg >= splitk_kmin && !a.bnb_partial) launch_gather<T, 128, 128, false, 2, 2, false, true, false, false, 2>(a, st);
-    else if ((dma_mode == 2 && a.Nout > 64) || (dma_mode == 1 && ((t128 >= 512 && kavg >= 128) || (t128 >= 256 && kavg >= 256)))) launch_gather<T, 128, 128, false, 2, 2, false, true>(a, st);
-    // short-K 1x1 convs at large M are all prologue / epilogue and HBM-bound: more, smaller blocks in flight win
-    // (64->256 @64x64: 54.5 -> 47.0 us, 256->256: 79.6 -> 68.9 us)
-    else if (t128 >= 512 && kavg <= 32 && sizeof(T) == 2) launch_gather<T, 64, 128, false>(a, st);
-    else if (t128 >= 512) launch_gather<T, 128, 128, false>(a, st);   // (128x256 tile with 8 waves measured slower: 687 vs 755 TFLOP/s)
-    else if (cdiv(Mtot, 64L) * cdiv(a.Nout, 128) >= 512) launch_gather<T, 64, 128, false>(a, st);
-    else launch_gather<T, 64, 64, false>(a, st);
-  }
-  MI_CHECK_LAUNCH("gather_gemm");
+  const ConvBuild b = choose_conv(a, (int)sizeof(T), conv_knobs());
+  if (b.family == CONV_PGEMM) return launch_pgemm_build(a, b, st);
+  if (!launch_gather_build<T>(a, b, st)) MI_FAIL(MI355_EINVAL, "gather: no such build (%dx%d)", b.bm, b.bn);
+  MI_CHECK_LAUNCH(b.cat ? "gather_gemm_cat" : "gather_gemm");
   return MI355_OK;
 }
 
@@ -1607,6 +1512,10 @@ static int check_bnb(const mi355_bn_bwd_src* bn, const float* partial, const int
 // (MX: block scales sa / sb instead of the descales, e4m3 operands; mx_fp8.hip)
 struct Fp8Extra { const float* descale_a; const float* descale_b; int a_fmt; const void* sa = nullptr; const void* sb = nullptr; };
 struct CatExtra { const void* x2; const void* w2; const float* bias2; int c2; };
+static int dispatch_conv(GatherArgs& a, const mi355_conv_desc* d, const Fp8Extra* f8, hipStream_t st) {
+  if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; a.mx_sa = f8->sa; a.mx_sb = f8->sb; return dispatch_gather_fp8(a, st); }
+  return d->dtype == MI355_BF16 ? dispatch_gather<bf16_t>(a, st) : dispatch_gather<float>(a, st);
+}
 static int conv_fwd_impl(const mi355_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
                          float* partial, size_t partial_bytes, int* nslices, void* stream, const mi355_bn_bwd_src* bn = nullptr,
                          const Fp8Extra* f8 = nullptr, int relu = 0, const CatExtra* cat = nullptr) {
@@ -1617,11 +1526,8 @@ static int conv_fwd_impl(const mi355_conv_desc* d, const void* x, const void* w,
   if (prof_on()) prof_set_tag("fwd%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? "mx" : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
                               residual ? " +res" : "", cat ? " +cat" : "");
   a.relu = relu ? 1 : 0;
-  a.A = x; a.B = w; a.D = y; a.bias = bias; a.residual = residual; a.scale = nullptr;
-  a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.in_sy = a.in_sx = d->stride;
-  a.Ho = d->Ho; a.Wo = d->Wo; a.out_sy = a.out_sx = 1;
-  a.Nout = d->Co; a.ldd = d->Co; a.ldb = d->kh * d->kw * d->Ci; a.accumulate = 0;
-  a.nphase = 1; a.ph[0].OHp = d->Ho; a.ph[0].OWp = d->Wo; a.ph[0].M = d->N * d->Ho * d->Wo; a.ph[0].ntaps = d->kh * d->kw;
+  a.A = x; a.B = w; a.D = y; a.bias = bias; a.residual = residual; a.scale = nullptr; a.accumulate = 0;
+  describe_fwd(a, d);
   if (bn) set_bnb(a, bn, partial, partial_bytes);
   else { a.stat_partial = partial; a.stat_bytes = partial_bytes; }
   if (cat) {
@@ -1629,11 +1535,7 @@ static int conv_fwd_impl(const mi355_conv_desc* d, const void* x, const void* w,
     a.A2 = cat->x2; a.B2 = cat->w2; a.bias2 = cat->bias2; a.c2 = cat->c2;
     a.a2_bytes = (unsigned)((long)d->N * d->Ho * d->Wo * cat->c2 * esz); a.b2_bytes = (unsigned)((long)d->Co * cat->c2 * esz);
   }
-  for (int i = 0; i < d->kh; ++i)
-    for (int j = 0; j < d->kw; ++j) { Tap& t = a.taps[i * d->kw + j]; t.dy = (int8_t)(i - d->pad); t.dx = (int8_t)(j - d->pad); t.widx = (int16_t)(i * d->kw + j); }
-  int e;
-  if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; a.mx_sa = f8->sa; a.mx_sb = f8->sb; e = dispatch_gather_fp8(a, as_stream(stream)); }
-  else e = d->dtype == MI355_BF16 ? dispatch_gather<bf16_t>(a, as_stream(stream)) : dispatch_gather<float>(a, as_stream(stream));
+  const int e = dispatch_conv(a, d, f8, as_stream(stream));
   if (nslices) *nslices = a.stat_slices;
   return e;
 }
@@ -1692,7 +1594,7 @@ extern "C" int mi355_conv_fwd_bnbwd(const mi355_conv_desc* d, const void* x, con
   return conv_fwd_impl(d, x, w, nullptr, nullptr, y, partial, partial_bytes, nslices, stream, bn);
 }
 // capacity that always suffices for the fused statistics of a conv output / deconv output (smallest tile = 64 rows)
-extern "C" size_t mi355_conv_stats_bytes(long rows, int C) { return (size_t)(rows / 64 + 8) * C * 3 * sizeof(float); }
+extern "C" size_t mi355_conv_stats_bytes(long rows, int C) { return conv_stats_bytes(rows, C); }
 
 // 1x1 conv C -> K (K <= 32) written as NCHW fp32 heat-maps: y[n][k][p] = bias[k] + sum_c x[n*HW+p][c] * w[k][c]
 template <typename T>
@@ -1711,7 +1613,9 @@ static int heatmap_conv(const void* x, const void* w, const float* bias, float* 
   a.b_bytes = (unsigned)((long)K * C * (long)sizeof(T));
   if (prof_on()) prof_set_tag("hm1x1 %d>%d hw%d n%d", C, K, HW, N);
   ProfScope ps(st, 2.0 * N * HW * (double)K * C, (double)a.a_bytes + a.b_bytes + 4.0 * N * HW * K);
-  launch_gather<T, 128, 32, false, 4, 1, true>(a, st);
+  ConvBuild b;
+  b.bm = 128; b.bn = 32; b.f32 = sizeof(T) == 4; b.hm = true;
+  launch_gather<T, 128, 32, false, 4, 1, true>(a, b, st);
   MI_CHECK_LAUNCH("conv1x1_heatmap");
   return MI355_OK;
 }
@@ -1724,8 +1628,7 @@ extern "C" int mi355_conv1x1_heatmap(const void* x, const void* w, const float* 
        : (mi355_set_error("bad dtype"), MI355_EINVAL);
 }
 
-// conv-form dgrad: dx[n][iy][ix][ci] = sum_{kh,kw,co} dy[n][(iy+p-kh)/s][(ix+p-kw)/s][co] * w[co][kh][kw][ci]
-// decomposed into stride^2 phases (iy%s, ix%s), each a unit-stride gather over its own tap subset.
+// conv-form dgrad (describe_dgrad): stride^2 phases in one launch
 static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void* wT, const float* bias, const float* scale_dev,
                            int accumulate, void* dx, float* partial, size_t partial_bytes, int* nslices, void* stream,
                            const mi355_bn_bwd_src* bn = nullptr, const Fp8Extra* f8 = nullptr, const void* acc_mask = nullptr,
@@ -1792,63 +1695,29 @@ static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void*
   if (f8 && bn) MI_FAIL(MI355_EINVAL, "fp8 dgrad: no BatchNorm-backward epilogue");
   hipStream_t st = as_stream(stream);
   const int s = d->stride;
-  const size_t esz = d->dtype == MI355_F32 ? 4 : 2;        // dx element size (bf16 for fp8 operands)
-  bool need_zero = false;
-  for (int py = 0; py < s && !need_zero; ++py) {
-    int cnt = 0; for (int kh = 0; kh < d->kh; ++kh) if ((py + d->pad - kh) % s == 0) ++cnt;
-    if (!cnt) need_zero = true;
-  }
-  for (int px = 0; px < s && !need_zero; ++px) {
-    int cnt = 0; for (int kw = 0; kw < d->kw; ++kw) if ((px + d->pad - kw) % s == 0) ++cnt;
-    if (!cnt) need_zero = true;
-  }
+  GatherArgs a; memset(&a, 0, sizeof(a));
+  const bool need_zero = describe_dgrad(a, d);
   if (need_zero && !accumulate) {
+    const size_t esz = d->dtype == MI355_F32 ? 4 : 2;        // dx element size (bf16 for fp8 operands)
     const size_t n16 = (size_t)d->N * d->Hi * d->Wi * d->Ci * esz / 16;   // Ci*esz is a multiple of 16
     int grid = (int)((n16 + 255) / 256); if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(zero_fill_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<uint4*>(dx), n16);
     MI_CHECK_LAUNCH("zero_fill");
   }
-  GatherArgs a; memset(&a, 0, sizeof(a));
   auto tag = [&]() {      // (a launch consumes the pending tag: the per-phase launches below set it once each)
     if (prof_on()) prof_set_tag("dgrad%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? "mx" : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
                                 accumulate ? (acc_mask ? " +macc" : " +acc") : "", bn ? " +bnb" : "");
   };
   tag();
   a.A = dy; a.B = wT; a.D = dx; a.bias = bias; a.residual = nullptr; a.scale = scale_dev;
-  a.Hi = d->Ho; a.Wi = d->Wo; a.Ci = d->Co;
-  a.in_sy = a.in_sx = 1; a.Ho = d->Hi; a.Wo = d->Wi; a.out_sy = a.out_sx = s;
-  a.Nout = d->Ci; a.ldd = d->Ci; a.ldb = d->kh * d->kw * d->Co;
   a.accumulate = accumulate ? 1 : 0;
   a.acc_mask = reinterpret_cast<const unsigned char*>(acc_mask);
   a.relu = relu ? 1 : 0;
-  int nt = 0;
-  for (int py = 0; py < s; ++py)
-    for (int px = 0; px < s; ++px) {
-      Phase& P = a.ph[a.nphase];
-      P.OHp = (d->Hi - py + s - 1) / s; P.OWp = (d->Wi - px + s - 1) / s;
-      if (P.OHp <= 0 || P.OWp <= 0) continue;
-      P.out_oy = py; P.out_ox = px; P.M = d->N * P.OHp * P.OWp; P.tap0 = nt;
-      for (int kh = 0; kh < d->kh; ++kh) {
-        if ((py + d->pad - kh) % s != 0) continue;
-        for (int kw = 0; kw < d->kw; ++kw) {
-          if ((px + d->pad - kw) % s != 0) continue;
-          Tap& t = a.taps[nt++]; t.dy = (int8_t)((py + d->pad - kh) / s); t.dx = (int8_t)((px + d->pad - kw) / s);
-          t.widx = (int16_t)(kh * d->kw + kw);
-        }
-      }
-      P.ntaps = nt - P.tap0;
-      if (P.ntaps == 0) continue;   // region already zeroed (or left untouched when accumulating)
-      ++a.nphase;
-    }
   if (a.nphase == 0) return MI355_OK;
-  static const int merge = getenv("MI355_PHASES") ? atoi(getenv("MI355_PHASES")) : 1;   // 0: one launch per phase (A/B)
-  if (merge || a.nphase == 1) {
-    // statistics only when every output pixel is produced by this launch (no zero-filled phase)
+  if (conv_knobs().phases || a.nphase == 1) {      // (MI355_PHASES=0: one launch per phase, A/B)
     if (bn) set_bnb(a, bn, partial, partial_bytes);   // (zero-filled phases carry dy = 0: they add nothing to the sums)
-    else if (partial && !need_zero && a.nphase == s * s) { a.stat_partial = partial; a.stat_bytes = partial_bytes; }
-    int e;
-    if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; a.mx_sa = f8->sa; a.mx_sb = f8->sb; e = dispatch_gather_fp8(a, st); }
-    else e = d->dtype == MI355_BF16 ? dispatch_gather<bf16_t>(a, st) : dispatch_gather<float>(a, st);
+    else if (partial && dgrad_fuses_stats(a, s, need_zero)) { a.stat_partial = partial; a.stat_bytes = partial_bytes; }
+    const int e = dispatch_conv(a, d, f8, st);
     if (nslices) *nslices = a.stat_slices;
     return e;
   }
@@ -1857,53 +1726,47 @@ static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void*
   for (int i = 0; i < np; ++i) {
     GatherArgs b = a; b.nphase = 1; b.ph[0] = a.ph[i];
     if (i) tag();
-    int e = d->dtype == MI355_BF16 ? dispatch_gather<bf16_t>(b, st) : dispatch_gather<float>(b, st);
-    if (e) return e;
+    if (int e = dispatch_conv(b, d, nullptr, st)) return e;
   }
   return MI355_OK;
 }
 
-struct WgradPlan { int S, rows_per_split, nto, nti, ldw, kw3, mt, kw2; };
-static int ilog2_exact(int v);
-static const int g_wgrad_blocks = getenv("MI355_WG_BLOCKS") ? atoi(getenv("MI355_WG_BLOCKS")) : 768;
-static WgradPlan plan_wgrad(const mi355_conv_desc* d) {
-  WgradPlan w; w.ldw = d->kh * d->kw * d->Ci;
-  const int bkm = d->dtype == MI355_BF16 ? 64 : 32;
-  const long M = (long)d->N * d->Ho * d->Wo;
-  // 3x3 / stride 1 / pad 1 in bf16 with a power-of-two width: the kw-shared kernel (see wgrad_kw_kernel)
-  static const int kw3_on = getenv("MI355_WGRAD_KW") ? atoi(getenv("MI355_WGRAD_KW")) : 1;
-  w.kw3 = kw3_on && d->dtype == MI355_BF16 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 &&
-          d->Ho == d->Hi && d->Wo == d->Wi &&              // (not a cropped output: the shifted-row trick needs same-size maps)
-          d->Wi >= 8 && ilog2_exact(d->Wi) >= 0;
-  w.mt = d->Co <= 64 ? 1 : 2;
-  // 3x3 / 4x4, stride 2, pad 1 in bf16, output width a power of two in [8, 64]: the parity-image kernel (wgrad_kw2_kernel)
-  static const int kw2_on = getenv("MI355_WGRAD_KW2") ? atoi(getenv("MI355_WGRAD_KW2")) : 1;
-  w.kw2 = kw2_on && d->dtype == MI355_BF16 && d->kh == d->kw && (d->kh == 3 || d->kh == 4) && d->stride == 2 && d->pad == 1 &&
-          d->Hi % 2 == 0 && d->Wi % 2 == 0 && d->Ho == d->Hi / 2 && d->Wo == d->Wi / 2 && d->Wo >= 8 && d->Wo <= 64 &&
-          ilog2_exact(d->Wo) >= 0;
-  long tiles;
-  if (w.kw2) { w.nto = cdiv(d->Co, 64 * w.mt); w.nti = cdiv(d->Ci, 64); tiles = (long)w.nto * d->kh * w.nti; }
-  else if (w.kw3) { w.nto = cdiv(d->Co, 64 * w.mt); w.nti = cdiv(d->Ci, 64); tiles = (long)w.nto * 3 * w.nti; }
-  else { w.nto = cdiv(d->Co, 128); w.nti = cdiv(w.ldw, 128); tiles = (long)w.nto * w.nti; }
-  // split count: fill the chip (3 blocks per CU), but keep >= 16 reduction steps per block while at least one block
-  // per CU remains -- short blocks are all prologue / epilogue and every split costs a full fp32 slab write + read.
-  // (measured per layer, B=64 @256x256: see DESIGN.md)
-  const long ksteps = (M + bkm - 1) / bkm;
-  long S = (g_wgrad_blocks + tiles - 1) / tiles;
-  long S16 = ksteps / 16, S256 = (256 + tiles - 1) / tiles;
-  long lo = S16 > S256 ? S16 : S256;
-  if (S > lo) S = lo;
-  if (tiles >= 384) S = 1;                       // enough tiles on their own: direct write, no slab pass
-  if (S > ksteps) S = ksteps;
-  if (S < 1) S = 1;
-  long rps = (M + S - 1) / S; rps = ((rps + bkm - 1) / bkm) * bkm;
-  S = (M + rps - 1) / rps;
-  w.S = (int)S; w.rows_per_split = (int)rps;
-  return w;
+// argument blocks of the three weight-gradient kernels: `out` is dw or the item's slabs, `rows` the rows per split
+template <typename Args>
+static void fill_wgrad_common(Args& a, const mi355_conv_desc* d, const WgradPlan& w, const void* x, const void* dy, float* out, int rows) {
+  memset(&a, 0, sizeof(a));
+  a.X = x; a.DY = dy; a.out = out; a.Ci = d->Ci; a.Co = d->Co;
+  a.M = d->N * d->Ho * d->Wo; a.rows_per_split = rows; a.ldw = w.ldw; a.slab_stride = (long)d->Co * w.ldw; a.nto = w.nto;
+  const long esz = d->dtype == MI355_BF16 ? 2 : 4;
+  a.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * d->Ci * esz); a.dy_bytes = (unsigned)((long)a.M * d->Co * esz);
+}
+static void fill_wgrad_args(WgradArgs& a, const mi355_conv_desc* d, const WgradPlan& w, const void* x, const void* dy, float* out, int rows) {
+  fill_wgrad_common(a, d, w, x, dy, out, rows);
+  a.Hi = d->Hi; a.Wi = d->Wi; a.Ho = d->Ho; a.Wo = d->Wo; a.nti = w.nti;
+  a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.cshift = ilog2_exact(d->Ci / (d->dtype == MI355_BF16 ? 8 : 4));
+  a.dWo = make_fastdiv(d->Wo); a.dHo = make_fastdiv(d->Ho);
+}
+static void fill_wgrad_args(WgradKwArgs& k, const mi355_conv_desc* d, const WgradPlan& w, const void* x, const void* dy, float* out, int rows) {
+  fill_wgrad_common(k, d, w, x, dy, out, rows);
+  k.H = d->Hi; k.W = d->Wi; k.nci = w.nti;
+  k.lwf = ilog2_exact(d->Wi); k.lw = k.lwf > 6 ? 6 : k.lwf; k.halo = d->Wi > 64;
+  k.dH = make_fastdiv(d->Hi);
+}
+static void fill_wgrad_args(WgradKw2Args& k, const mi355_conv_desc* d, const WgradPlan& w, const void* x, const void* dy, float* out, int rows) {
+  fill_wgrad_common(k, d, w, x, dy, out, rows);
+  k.H = d->Hi; k.W = d->Wi; k.Ho = d->Ho; k.nci = w.nti;
+  k.lwo = ilog2_exact(d->Wo); k.lw = k.lwo > 6 ? 6 : k.lwo;
+  k.dHo = make_fastdiv(d->Ho);
+}
+static int check_wgrad_channels(const mi355_conv_desc* d) {
+  const int CH = d->dtype == MI355_BF16 ? 8 : 4;
+  if (d->Ci % CH || d->Co % CH) MI_FAIL(MI355_EINVAL, "wgrad: channels must be multiples of %d", CH);
+  if (ilog2_exact(d->Ci / CH) < 0) MI_FAIL(MI355_EINVAL, "wgrad: Ci/%d must be a power of two", CH);
+  return MI355_OK;
 }
 
 extern "C" size_t mi355_conv_wgrad_workspace(const mi355_conv_desc* d) {
-  WgradPlan w = plan_wgrad(d);
+  WgradPlan w = plan_wgrad(d, conv_knobs());
   return (size_t)w.S * d->Co * w.ldw * sizeof(float);
 }
 
@@ -1911,77 +1774,37 @@ extern "C" int mi355_conv_wgrad(const mi355_conv_desc* d, const void* x, const v
                                 void* ws, size_t ws_bytes, void* stream) {
   if (int e = check_desc(d, true)) return e;
   hipStream_t st = as_stream(stream);
-  const int CH = d->dtype == MI355_BF16 ? 8 : 4;
-  if (d->Ci % CH || d->Co % CH) MI_FAIL(MI355_EINVAL, "wgrad: channels must be multiples of %d", CH);
-  int cshift = ilog2_exact(d->Ci / CH);
-  if (cshift < 0) MI_FAIL(MI355_EINVAL, "wgrad: Ci/%d must be a power of two", CH);
-  WgradPlan w = plan_wgrad(d);
+  if (int e = check_wgrad_channels(d)) return e;
+  const WgradPlan w = plan_wgrad(d, conv_knobs());
   const size_t need = (size_t)w.S * d->Co * w.ldw * sizeof(float);
   const bool direct = (w.S == 1 && !accumulate);
   if (!direct && (ws == nullptr || ws_bytes < need)) MI_FAIL(MI355_EWORKSPACE, "wgrad workspace %zu < %zu", ws_bytes, need);
-  if (w.kw2) {
-    WgradKw2Args k; memset(&k, 0, sizeof(k));
-    k.X = x; k.DY = dy; k.out = direct ? dw : reinterpret_cast<float*>(ws);
-    k.H = d->Hi; k.W = d->Wi; k.Ho = d->Ho; k.Ci = d->Ci; k.Co = d->Co;
-    k.lwo = ilog2_exact(d->Wo); k.lw = k.lwo > 6 ? 6 : k.lwo;
-    k.M = d->N * d->Ho * d->Wo; k.rows_per_split = w.rows_per_split; k.ldw = w.ldw;
-    k.slab_stride = (long)d->Co * w.ldw; k.nto = w.nto; k.nci = w.nti;
-    k.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * d->Ci * 2); k.dy_bytes = (unsigned)((long)k.M * d->Co * 2);
-    k.dHo = make_fastdiv(d->Ho);
-    {
-      if (prof_on()) prof_set_tag("wgrad_kw2 k%ds%d %d>%d @%dx%d n%d S%d", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, w.S);
-      ProfScope ps(st, 2.0 * k.M * (double)d->Co * w.ldw, (double)k.x_bytes + (double)k.dy_bytes + 4.0 * d->Co * w.ldw);
+  float* out = direct ? dw : reinterpret_cast<float*>(ws);
+  const long M = (long)d->N * d->Ho * d->Wo, slab = (long)d->Co * w.ldw, esz = d->dtype == MI355_BF16 ? 2 : 4;
+  const unsigned x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * d->Ci * esz), dy_bytes = (unsigned)(M * d->Co * esz);
+  {
+    if (prof_on()) prof_set_tag("%s k%ds%d %d>%d @%dx%d n%d S%d", wgrad_kernel_name(w), d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, w.S);
+    ProfScope ps(st, 2.0 * M * (double)d->Co * w.ldw, (double)x_bytes + (double)dy_bytes + 4.0 * d->Co * w.ldw);
+    if (w.kw2) {
+      WgradKw2Args k; fill_wgrad_args(k, d, w, x, dy, out, w.rows_per_split);
       dim3 grid(w.nto * d->kh * w.nti * w.S);
       if (d->kh == 3) { if (w.mt == 1) hipLaunchKernelGGL((wgrad_kw2_kernel<1, 3>), grid, dim3(256), 0, st, k); else hipLaunchKernelGGL((wgrad_kw2_kernel<2, 3>), grid, dim3(256), 0, st, k); }
       else { if (w.mt == 1) hipLaunchKernelGGL((wgrad_kw2_kernel<1, 4>), grid, dim3(256), 0, st, k); else hipLaunchKernelGGL((wgrad_kw2_kernel<2, 4>), grid, dim3(256), 0, st, k); }
-      MI_CHECK_LAUNCH("wgrad_kw2");
-    }
-    if (!direct) launch_slab_reduce(reinterpret_cast<const float*>(ws), dw, k.slab_stride, w.S, k.slab_stride, accumulate, st);
-    return MI355_OK;
-  }
-  if (w.kw3) {
-    WgradKwArgs k; memset(&k, 0, sizeof(k));
-    k.X = x; k.DY = dy; k.out = direct ? dw : reinterpret_cast<float*>(ws);
-    k.H = d->Hi; k.W = d->Wi; k.Ci = d->Ci; k.Co = d->Co;
-    k.lwf = ilog2_exact(d->Wi); k.lw = k.lwf > 6 ? 6 : k.lwf; k.halo = d->Wi > 64;
-    k.M = d->N * d->Ho * d->Wo; k.rows_per_split = w.rows_per_split; k.ldw = w.ldw;
-    k.slab_stride = (long)d->Co * w.ldw; k.nto = w.nto; k.nci = w.nti;
-    k.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * d->Ci * 2); k.dy_bytes = (unsigned)((long)k.M * d->Co * 2);
-    k.dH = make_fastdiv(d->Hi);
-    {
-      if (prof_on()) prof_set_tag("wgrad_kw k%ds%d %d>%d @%dx%d n%d S%d", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, w.S);
-      ProfScope ps(st, 2.0 * k.M * (double)d->Co * w.ldw, (double)k.x_bytes + (double)k.dy_bytes + 4.0 * d->Co * w.ldw);
+    } else if (w.kw3) {
+      WgradKwArgs k; fill_wgrad_args(k, d, w, x, dy, out, w.rows_per_split);
       dim3 grid(w.nto * 3 * w.nti * w.S);
       if (w.mt == 1) hipLaunchKernelGGL(wgrad_kw_kernel<1>, grid, dim3(256), 0, st, k);
       else hipLaunchKernelGGL(wgrad_kw_kernel<2>, grid, dim3(256), 0, st, k);
-      MI_CHECK_LAUNCH("wgrad_kw");
+    } else {
+      WgradArgs a; fill_wgrad_args(a, d, w, x, dy, out, w.rows_per_split);
+      dim3 grid(w.nto * w.nti * w.S);
+      if (d->dtype == MI355_BF16) hipLaunchKernelGGL(wgrad_gemm_kernel<bf16_t>, grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(wgrad_gemm_kernel<float>, grid, dim3(256), 0, st, a);
     }
-    if (!direct) {
-      long n = k.slab_stride;
-      launch_slab_reduce(reinterpret_cast<const float*>(ws), dw, n, w.S, k.slab_stride, accumulate, st);
-      MI_CHECK_LAUNCH("slab_reduce");
-    }
-    return MI355_OK;
-  }
-  WgradArgs a; memset(&a, 0, sizeof(a));
-  a.X = x; a.DY = dy; a.out = direct ? dw : reinterpret_cast<float*>(ws);
-  a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co;
-  a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.cshift = cshift;
-  a.M = d->N * d->Ho * d->Wo; a.rows_per_split = w.rows_per_split; a.ldw = w.ldw;
-  a.slab_stride = (long)d->Co * w.ldw; a.nto = w.nto; a.nti = w.nti;
-  a.dWo = make_fastdiv(d->Wo); a.dHo = make_fastdiv(d->Ho);
-  { const long esz = d->dtype == MI355_BF16 ? 2 : 4; a.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * d->Ci * esz); a.dy_bytes = (unsigned)((long)a.M * d->Co * esz); }
-  {
-    if (prof_on()) prof_set_tag("wgrad k%ds%d %d>%d @%dx%d n%d S%d", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, w.S);
-    ProfScope ps(st, 2.0 * a.M * (double)d->Co * w.ldw, (double)a.x_bytes + (double)a.dy_bytes + 4.0 * d->Co * w.ldw);
-    dim3 grid(w.nto * w.nti * w.S);
-    if (d->dtype == MI355_BF16) hipLaunchKernelGGL(wgrad_gemm_kernel<bf16_t>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(wgrad_gemm_kernel<float>, grid, dim3(256), 0, st, a);
-    MI_CHECK_LAUNCH("wgrad_gemm");
+    MI_CHECK_LAUNCH(wgrad_kernel_name(w));
   }
   if (!direct) {
-    long n = a.slab_stride;
-    launch_slab_reduce(reinterpret_cast<const float*>(ws), dw, n, w.S, a.slab_stride, accumulate, st);
+    launch_slab_reduce(reinterpret_cast<const float*>(ws), dw, slab, w.S, slab, accumulate, st);
     MI_CHECK_LAUNCH("slab_reduce");
   }
   return MI355_OK;
@@ -1992,135 +1815,72 @@ extern "C" int mi355_conv_wgrad(const mi355_conv_desc* d, const void* x, const v
 // items: HOST array.  Problems the specialised kernels take (3x3 stride 1 -> wgrad_kw, 3x3 / 4x4 stride 2 -> wgrad_kw2), and
 // any problem that fills the chip on its own, run through mi355_conv_wgrad one by one; the rest -- the generic kernel's
 // small problems -- are launched in groups of up to WG_MAX with a split count chosen for the GROUP.
+// (`kind` below: the launch kinds of walk_wgrad_groups.)
 static bool group_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
   return !w.kw2 && !w.kw3 && (long)w.nto * w.nti < 384;
 }
 // ... and of those, the ones the 256 x 256-tile kernel takes (wgrad_group256_kernel): bf16, whole 256-wide tiles both ways
 static bool group256_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
-  static const bool on = !(getenv("MI355_WGRAD_GROUP256") && atoi(getenv("MI355_WGRAD_GROUP256")) == 0);      // A/B switch
-  return on && d->dtype == MI355_BF16 && d->kh == 1 && d->kw == 1 && d->pad == 0 && d->Co % 256 == 0 && d->Ci % 256 == 0;
+  return conv_knobs().wgrad_group256 && d->dtype == MI355_BF16 && d->kh == 1 && d->kw == 1 && d->pad == 0 && d->Co % 256 == 0 && d->Ci % 256 == 0;
+}
+// 3x3 / stride-1 problems (wgrad_kw_kernel) small enough to share a launch: fewer than 24 K steps per block at 768 blocks
+static bool kw_group_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
+  if (!conv_knobs().wgrad_kw_group || !w.kw3) return false;
+  const long M = (long)d->N * d->Ho * d->Wo, ksteps = (M + 63) / 64;
+  return (long)w.nto * 3 * w.nti * ksteps < 768L * 24;
+}
+static long group_tiles(int kind, const mi355_conv_desc* d, const WgradPlan& w) {
+  return kind == 3 ? (long)(d->Co / 256) * (w.ldw / 256) : kind == 2 ? (long)w.nto * 3 * w.nti : (long)w.nto * w.nti;
 }
 struct GroupPlan { int S, rps; size_t ws_off; };
-// tile: 128 (wgrad_group_kernel) or 256 (wgrad_group256_kernel)
-static long group_plan(const mi355_wgrad_item* items, const int* idx, int n, GroupPlan* gp, size_t* ws_bytes, int tile = 128) {
+// Split counts and slab offsets of the items of one grouped launch of `kind`; returns its blocks.
+static long group_plan(const mi355_wgrad_item* items, const int* idx, int n, GroupPlan* gp, size_t* ws_bytes, int kind) {
+  const ConvKnobs& kn = conv_knobs();
+  const int target = kind == 3 ? kn.wg_group256_blocks : kind == 2 ? kn.wg_kw_group_blocks : kn.wg_group_blocks;
+  auto rows = [](const mi355_conv_desc* d) { return (long)d->N * d->Ho * d->Wo; };
+  auto kstep = [](const mi355_conv_desc* d) { return d->dtype == MI355_BF16 ? 64 : 32; };
   // equal work per block: block-steps W = sum tiles_i * ksteps_i; aim at 3 blocks per CU, never fewer than 16 K-steps per block
   // (256-wide tiles: one 8-wave block per CU)
   double W = 0;
   for (int k = 0; k < n; ++k) {
-    const mi355_conv_desc* d = &items[idx[k]].d; WgradPlan w = plan_wgrad(d);
-    const int bkm = d->dtype == MI355_BF16 ? 64 : 32;
-    const long tiles = tile == 256 ? (long)(d->Co / 256) * (w.ldw / 256) : (long)w.nto * w.nti;
-    W += (double)tiles * (((long)d->N * d->Ho * d->Wo + bkm - 1) / bkm);
+    const mi355_conv_desc* d = &items[idx[k]].d;
+    W += (double)group_tiles(kind, d, plan_wgrad(d, kn)) * ((rows(d) + kstep(d) - 1) / kstep(d));
   }
-  static const int group_blocks = getenv("MI355_WG_GROUP_BLOCKS") ? atoi(getenv("MI355_WG_GROUP_BLOCKS")) : 512;     // (768 -> 512: -0.09 ms / iteration, three same-box pairs)
-  static const int group256_blocks = getenv("MI355_WG_GROUP256_BLOCKS") ? atoi(getenv("MI355_WG_GROUP256_BLOCKS")) : 256;
-  long per = (long)(W / (tile == 256 ? group256_blocks : group_blocks)) + 1; if (per < 16) per = 16;
-  long blocks = 0; size_t off = 0;
+  long per = (long)(W / target) + 1; if (per < 16) per = 16;
+  auto plan_at = [&](long per, GroupPlan* out, size_t* ws_end) {      // blocks of the group when every block runs `per` K steps
+    long blocks = 0; size_t off = 0;
+    for (int k = 0; k < n; ++k) {
+      const mi355_wgrad_item& it = items[idx[k]]; const mi355_conv_desc* d = &it.d; const WgradPlan w = plan_wgrad(d, kn);
+      const WgradSplit s = wgrad_split(rows(d), kstep(d), ((rows(d) + kstep(d) - 1) / kstep(d) + per - 1) / per);
+      if (out) { out[k].S = s.S; out[k].rps = s.rows; out[k].ws_off = off; }
+      if (s.S > 1 || it.accumulate) off += (size_t)s.S * d->Co * w.ldw * sizeof(float);
+      blocks += group_tiles(kind, d, w) * s.S;
+    }
+    if (ws_end) *ws_end = off;
+    return blocks;
+  };
   // 256-wide tiles run one block per CU: a grid of 294 blocks on 256 CUs would take two rounds, the second nearly empty -- lengthen
   // the blocks until the group fits the target (rounding the split counts up is what overshoots it)
-  for (int trial = 0; tile == 256 && trial < 64; ++trial) {
-    long b = 0;
-    for (int k = 0; k < n; ++k) {
-      const mi355_conv_desc* d = &items[idx[k]].d; WgradPlan w = plan_wgrad(d);
-      const long M = (long)d->N * d->Ho * d->Wo, ksteps = (M + 63) / 64;
-      long S = (ksteps + per - 1) / per; if (S < 1) S = 1;
-      long rps = (M + S - 1) / S; rps = ((rps + 63) / 64) * 64;
-      S = (M + rps - 1) / rps;
-      b += (long)(d->Co / 256) * (w.ldw / 256) * S;
-    }
-    if (b <= group256_blocks) break;
+  for (int trial = 0; kind == 3 && trial < 64; ++trial) {
+    if (plan_at(per, nullptr, nullptr) <= target) break;
     per += per / 16 + 1;
   }
-  for (int k = 0; k < n; ++k) {
-    const mi355_wgrad_item& it = items[idx[k]]; const mi355_conv_desc* d = &it.d; WgradPlan w = plan_wgrad(d);
-    const int bkm = d->dtype == MI355_BF16 ? 64 : 32;
-    const long M = (long)d->N * d->Ho * d->Wo, ksteps = (M + bkm - 1) / bkm;
-    long S = (ksteps + per - 1) / per; if (S < 1) S = 1;
-    long rps = (M + S - 1) / S; rps = ((rps + bkm - 1) / bkm) * bkm;
-    S = (M + rps - 1) / rps;
-    gp[k].S = (int)S; gp[k].rps = (int)rps; gp[k].ws_off = off;
-    if (S > 1 || it.accumulate) off += (size_t)S * d->Co * w.ldw * sizeof(float);
-    blocks += (tile == 256 ? (long)(d->Co / 256) * (w.ldw / 256) : (long)w.nto * w.nti) * S;
-  }
-  if (ws_bytes) *ws_bytes = off;
-  return blocks;
+  return plan_at(per, gp, ws_bytes);
 }
-// 3x3 / stride-1 problems (wgrad_kw_kernel) small enough to share a launch: fewer than 24 K steps per block at 768 blocks
-static bool kw_group_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
-  static const bool on = !(getenv("MI355_WGRAD_KW_GROUP") && atoi(getenv("MI355_WGRAD_KW_GROUP")) == 0);      // A/B switch
-  if (!on || !w.kw3) return false;
-  const long M = (long)d->N * d->Ho * d->Wo, ksteps = (M + 63) / 64;
-  return (long)w.nto * 3 * w.nti * ksteps < 768L * 24;
+// The slab reductions of a grouped launch, one launch for all of them.
+static void slab_group_add(SlabGroupArgs& sg, int& nblocks, const float* slabs, float* out, long slab_stride, int S, int accumulate) {
+  SlabItem& q = sg.it[sg.n];
+  q.slabs = slabs; q.out = out; q.n4 = slab_stride / 4; q.stride = slab_stride; q.S = S; q.accumulate = accumulate;
+  sg.bstart[sg.n] = nblocks; nblocks += cdiv(q.n4, 256); ++sg.n;
 }
-static long kw_group_plan(const mi355_wgrad_item* items, const int* idx, int n, GroupPlan* gp, size_t* ws_bytes) {
-  double W = 0;
-  for (int k = 0; k < n; ++k) {
-    const mi355_conv_desc* d = &items[idx[k]].d; WgradPlan w = plan_wgrad(d);
-    W += (double)w.nto * 3 * w.nti * (((long)d->N * d->Ho * d->Wo + 63) / 64);
-  }
-  static const int group_blocks = getenv("MI355_WG_KW_GROUP_BLOCKS") ? atoi(getenv("MI355_WG_KW_GROUP_BLOCKS")) : 512;      // (512 / 768 / 1024: 32.47 / 32.55 / 32.64 ms per iteration, same box)
-  long per = (long)(W / group_blocks) + 1; if (per < 16) per = 16;
-  long blocks = 0; size_t off = 0;
-  for (int k = 0; k < n; ++k) {
-    const mi355_wgrad_item& it = items[idx[k]]; const mi355_conv_desc* d = &it.d; WgradPlan w = plan_wgrad(d);
-    const long M = (long)d->N * d->Ho * d->Wo, ksteps = (M + 63) / 64;
-    long S = (ksteps + per - 1) / per; if (S < 1) S = 1;
-    long rps = (M + S - 1) / S; rps = ((rps + 63) / 64) * 64;
-    S = (M + rps - 1) / rps;
-    gp[k].S = (int)S; gp[k].rps = (int)rps; gp[k].ws_off = off;
-    if (S > 1 || it.accumulate) off += (size_t)S * d->Co * w.ldw * sizeof(float);
-    blocks += (long)w.nto * 3 * w.nti * S;
-  }
-  if (ws_bytes) *ws_bytes = off;
-  return blocks;
-}
-static int launch_wgrad_kw_group(const mi355_wgrad_item* items, const int* idx, int n, void* ws, size_t ws_bytes, hipStream_t st) {
-  GroupPlan gp[WGK_MAX]; size_t need = 0;
-  kw_group_plan(items, idx, n, gp, &need);
-  if (need && (!ws || ws_bytes < need)) MI_FAIL(MI355_EWORKSPACE, "wgrad kw group workspace %zu < %zu", ws_bytes, need);
-  WgradKwGroupArgs g; memset(&g, 0, sizeof(g));
-  SlabGroupArgs sg; memset(&sg, 0, sizeof(sg));
-  int nb = 0, nsb = 0;
-  double flops = 0, bytes = 0;
-  const int mt = plan_wgrad(&items[idx[0]].d).mt;
-  for (int k = 0; k < n; ++k) {
-    const mi355_wgrad_item& it = items[idx[k]]; const mi355_conv_desc* d = &it.d;
-    WgradPlan w = plan_wgrad(d);
-    const bool direct = gp[k].S == 1 && !it.accumulate;
-    WgradKwArgs& a = g.p[k];
-    a.X = it.x; a.DY = it.dy; a.out = direct ? it.dw : reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + gp[k].ws_off);
-    a.H = d->Hi; a.W = d->Wi; a.Ci = d->Ci; a.Co = d->Co;
-    a.lwf = ilog2_exact(d->Wi); a.lw = a.lwf > 6 ? 6 : a.lwf; a.halo = d->Wi > 64;
-    a.M = d->N * d->Ho * d->Wo; a.rows_per_split = gp[k].rps; a.ldw = w.ldw;
-    a.slab_stride = (long)d->Co * w.ldw; a.nto = w.nto; a.nci = w.nti;
-    a.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * d->Ci * 2); a.dy_bytes = (unsigned)((long)a.M * d->Co * 2);
-    a.dH = make_fastdiv(d->Hi);
-    g.bstart[k] = nb; nb += w.nto * 3 * w.nti * gp[k].S;
-    flops += 2.0 * a.M * (double)d->Co * w.ldw; bytes += (double)a.x_bytes + a.dy_bytes + 4.0 * d->Co * w.ldw;
-    if (!direct) {
-      SlabItem& q = sg.it[sg.n];
-      q.slabs = a.out; q.out = it.dw; q.n4 = a.slab_stride / 4; q.stride = a.slab_stride; q.S = gp[k].S; q.accumulate = it.accumulate;
-      sg.bstart[sg.n] = nsb; nsb += cdiv(q.n4, 256); ++sg.n;
-    }
-  }
-  g.bstart[n] = nb; g.n = n; sg.bstart[sg.n] = nsb;
-  {
-    if (prof_on()) {
-      const mi355_conv_desc* d0 = &items[idx[0]].d;
-      prof_set_tag("wgrad_kw_group x%d blocks%d first k%ds%d %d>%d @%dx%d", n, nb, d0->kh, d0->stride, d0->Ci, d0->Co, d0->Hi, d0->Wi);
-    }
-    ProfScope ps(st, flops, bytes);
-    if (mt == 1) hipLaunchKernelGGL(wgrad_kw_group_kernel<1>, dim3(nb), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(wgrad_kw_group_kernel<2>, dim3(nb), dim3(256), 0, st, g);
-    MI_CHECK_LAUNCH("wgrad_kw_group");
-  }
-  if (sg.n) {
-    double sb = 0; for (int k = 0; k < sg.n; ++k) sb += 16.0 * sg.it[k].n4 * (sg.it[k].S + 1);
-    char lab[64];
-    if (prof_on()) snprintf(lab, sizeof(lab), "slab_reduce_group x%d", sg.n);
-    ProfScope ps(st, 0.0, sb, 2, prof_on() ? lab : nullptr);
-    hipLaunchKernelGGL(slab_reduce_group_kernel, dim3(nsb), dim3(256), 0, st, sg); MI_CHECK_LAUNCH("slab_reduce_group");
-  }
+static int launch_slab_reduce_group(SlabGroupArgs& sg, int nblocks, hipStream_t st) {
+  sg.bstart[sg.n] = nblocks;
+  if (!sg.n) return MI355_OK;
+  double sb = 0; for (int k = 0; k < sg.n; ++k) sb += 16.0 * sg.it[k].n4 * (sg.it[k].S + 1);
+  char lab[64];
+  if (prof_on()) snprintf(lab, sizeof(lab), "slab_reduce_group x%d", sg.n);
+  ProfScope ps(st, 0.0, sb, 2, prof_on() ? lab : nullptr);
+  hipLaunchKernelGGL(slab_reduce_group_kernel, dim3(nblocks), dim3(256), 0, st, sg); MI_CHECK_LAUNCH("slab_reduce_group");
   return MI355_OK;
 }
 // The launches mi355_conv_wgrad_grouped makes of `items`, in order, handed to `fn(kind, idx, m)`: kind 0 = one item through
@@ -2136,14 +1896,14 @@ static int walk_wgrad_groups(const mi355_wgrad_item* items, int n, F&& fn) {
   auto flush_b = [&]() -> int { if (!bm) return 0; int e = fn(3, bi, bm); bm = 0; return e; };
   for (int i = 0; i < n; ++i) {
     const mi355_wgrad_item& it = items[i];
-    WgradPlan w = plan_wgrad(&it.d);
+    WgradPlan w = plan_wgrad(&it.d, conv_knobs());
     bool shares = false;
     for (int k = 0; k < gm; ++k) shares = shares || items[gi[k]].dw == it.dw;
     for (int k = 0; k < km; ++k) shares = shares || items[ki[k]].dw == it.dw;
     for (int k = 0; k < bm; ++k) shares = shares || items[bi[k]].dw == it.dw;
     if (shares) { if (int e = flush_g()) return e; if (int e = flush_k()) return e; if (int e = flush_b()) return e; }
     if (kw_group_eligible(&it.d, w)) {
-      if (km && (km == WGK_MAX || plan_wgrad(&items[ki[0]].d).mt != w.mt)) { if (int e = flush_k()) return e; }
+      if (km && (km == WGK_MAX || plan_wgrad(&items[ki[0]].d, conv_knobs()).mt != w.mt)) { if (int e = flush_k()) return e; }
       ki[km++] = i;
     } else if (group_eligible(&it.d, w) && group256_eligible(&it.d, w)) {
       if (bm == WG_MAX) { if (int e = flush_b()) return e; }
@@ -2166,73 +1926,58 @@ extern "C" size_t mi355_conv_wgrad_grouped_workspace(const mi355_wgrad_item* ite
   (void)walk_wgrad_groups(items, n, [&](int kind, const int* idx, int m) -> int {
     size_t b = 0;
     if (kind == 0) b = mi355_conv_wgrad_workspace(&items[idx[0]].d);
-    else if (kind == 1) { GroupPlan gp[WG_MAX]; group_plan(items, idx, m, gp, &b); }
-    else if (kind == 3) { GroupPlan gp[WG_MAX]; group_plan(items, idx, m, gp, &b, 256); }
-    else { GroupPlan gp[WGK_MAX]; kw_group_plan(items, idx, m, gp, &b); }
+    else { static_assert(WGK_MAX <= WG_MAX, "one plan array for every kind"); GroupPlan gp[WG_MAX]; group_plan(items, idx, m, gp, &b, kind); }
     if (b > need) need = b;
     return 0;
   });
   return need;
 }
-static int launch_wgrad_group(const mi355_wgrad_item* items, const int* idx, int n, void* ws, size_t ws_bytes, hipStream_t st, int tile = 128) {
+// the kernel of a grouped launch of `kind`, d0 its first item
+static void launch_group_kernel(const WgradGroupArgs& g, int nb, int kind, const mi355_conv_desc* d0, hipStream_t st) {
+  if (kind == 3) {
+    static bool attr_set = false;
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)wgrad_group256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WG256_SMEM); attr_set = true; }
+    hipLaunchKernelGGL(wgrad_group256_kernel, dim3(nb), dim3(512), WG256_SMEM, st, g);
+  }
+  else if (d0->dtype == MI355_BF16) hipLaunchKernelGGL(wgrad_group_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, g);
+  else hipLaunchKernelGGL(wgrad_group_kernel<float>, dim3(nb), dim3(256), 0, st, g);
+}
+static void launch_group_kernel(const WgradKwGroupArgs& g, int nb, int, const mi355_conv_desc* d0, hipStream_t st) {
+  if (plan_wgrad(d0, conv_knobs()).mt == 1) hipLaunchKernelGGL(wgrad_kw_group_kernel<1>, dim3(nb), dim3(256), 0, st, g);
+  else hipLaunchKernelGGL(wgrad_kw_group_kernel<2>, dim3(nb), dim3(256), 0, st, g);
+}
+// One grouped launch (Group = WgradKwGroupArgs for kind 2, WgradGroupArgs for kinds 1 and 3) and the slab reductions of its items.
+template <typename Group>
+static int launch_wgrad_group(const mi355_wgrad_item* items, const int* idx, int n, void* ws, size_t ws_bytes, hipStream_t st, int kind) {
+  const char* name = kind == 3 ? "wgrad_group256" : kind == 2 ? "wgrad_kw_group" : "wgrad_group";
   GroupPlan gp[WG_MAX]; size_t need = 0;
-  group_plan(items, idx, n, gp, &need, tile);
-  if (need && (!ws || ws_bytes < need)) MI_FAIL(MI355_EWORKSPACE, "wgrad group workspace %zu < %zu", ws_bytes, need);
-  WgradGroupArgs g; memset(&g, 0, sizeof(g));
+  group_plan(items, idx, n, gp, &need, kind);
+  if (need && (!ws || ws_bytes < need)) MI_FAIL(MI355_EWORKSPACE, "%s workspace %zu < %zu", name, ws_bytes, need);
+  Group g; memset(&g, 0, sizeof(g));
   SlabGroupArgs sg; memset(&sg, 0, sizeof(sg));
   int nb = 0, nsb = 0;
+  double flops = 0, bytes = 0;
   for (int k = 0; k < n; ++k) {
     const mi355_wgrad_item& it = items[idx[k]]; const mi355_conv_desc* d = &it.d;
-    if (int e = check_desc(d)) return e;
-    const int CH = d->dtype == MI355_BF16 ? 8 : 4;
-    if (d->Ci % CH || d->Co % CH) MI_FAIL(MI355_EINVAL, "wgrad: channels must be multiples of %d", CH);
-    const int cshift = ilog2_exact(d->Ci / CH);
-    if (cshift < 0) MI_FAIL(MI355_EINVAL, "wgrad: Ci/%d must be a power of two", CH);
-    WgradPlan w = plan_wgrad(d);
+    if (kind != 2) { if (int e = check_wgrad_channels(d)) return e; }
+    WgradPlan w = plan_wgrad(d, conv_knobs());
+    if (kind == 3) { w.nto = d->Co / 256; w.nti = w.ldw / 256; }
     const bool direct = gp[k].S == 1 && !it.accumulate;
-    WgradArgs& a = g.p[k];
-    a.X = it.x; a.DY = it.dy; a.out = direct ? it.dw : reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + gp[k].ws_off);
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co;
-    a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.cshift = cshift;
-    a.M = d->N * d->Ho * d->Wo; a.rows_per_split = gp[k].rps; a.ldw = w.ldw;
-    a.slab_stride = (long)d->Co * w.ldw; a.nto = w.nto; a.nti = w.nti;
-    if (tile == 256) { a.nto = d->Co / 256; a.nti = w.ldw / 256; }
-    a.dWo = make_fastdiv(d->Wo); a.dHo = make_fastdiv(d->Ho);
-    const long esz = d->dtype == MI355_BF16 ? 2 : 4;
-    a.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * d->Ci * esz); a.dy_bytes = (unsigned)((long)a.M * d->Co * esz);
-    g.bstart[k] = nb; nb += a.nto * a.nti * gp[k].S;
-    if (!direct) {
-      SlabItem& q = sg.it[sg.n];
-      q.slabs = a.out; q.out = it.dw; q.n4 = a.slab_stride / 4; q.stride = a.slab_stride; q.S = gp[k].S; q.accumulate = it.accumulate;
-      sg.bstart[sg.n] = nsb; nsb += cdiv(q.n4, 256); ++sg.n;
-    }
+    auto& a = g.p[k];
+    fill_wgrad_args(a, d, w, it.x, it.dy, direct ? it.dw : reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + gp[k].ws_off), gp[k].rps);
+    g.bstart[k] = nb; nb += (int)group_tiles(kind, d, w) * gp[k].S;
+    flops += 2.0 * a.M * (double)d->Co * w.ldw; bytes += (double)a.x_bytes + a.dy_bytes + 4.0 * d->Co * w.ldw;
+    if (!direct) slab_group_add(sg, nsb, a.out, it.dw, a.slab_stride, gp[k].S, it.accumulate);
   }
-  g.bstart[n] = nb; g.n = n; sg.bstart[sg.n] = nsb;
+  g.bstart[n] = nb; g.n = n;
   {
-    double flops = 0, bytes = 0;
-    for (int k = 0; k < n; ++k) { const WgradArgs& a = g.p[k]; flops += 2.0 * a.M * (double)a.Co * a.ldw; bytes += (double)a.x_bytes + a.dy_bytes + 4.0 * a.Co * a.ldw; }
-    if (prof_on()) {
-      const mi355_conv_desc* d0 = &items[idx[0]].d;
-      prof_set_tag("wgrad_group%s x%d blocks%d first k%ds%d %d>%d @%dx%d", tile == 256 ? "256" : "", n, nb, d0->kh, d0->stride, d0->Ci, d0->Co, d0->Hi, d0->Wi);
-    }
+    const mi355_conv_desc* d0 = &items[idx[0]].d;
+    if (prof_on()) prof_set_tag("%s x%d blocks%d first k%ds%d %d>%d @%dx%d", name, n, nb, d0->kh, d0->stride, d0->Ci, d0->Co, d0->Hi, d0->Wi);
     ProfScope ps(st, flops, bytes);
-    if (tile == 256) {
-      static bool attr_set = false;
-      if (!attr_set) { (void)hipFuncSetAttribute((const void*)wgrad_group256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WG256_SMEM); attr_set = true; }
-      hipLaunchKernelGGL(wgrad_group256_kernel, dim3(nb), dim3(512), WG256_SMEM, st, g);
-    }
-    else if (items[idx[0]].d.dtype == MI355_BF16) hipLaunchKernelGGL(wgrad_group_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(wgrad_group_kernel<float>, dim3(nb), dim3(256), 0, st, g);
-    MI_CHECK_LAUNCH("wgrad_group");
+    launch_group_kernel(g, nb, kind, d0, st);
+    MI_CHECK_LAUNCH(name);
   }
-  if (sg.n) {
-    double sb = 0; for (int k = 0; k < sg.n; ++k) sb += 16.0 * sg.it[k].n4 * (sg.it[k].S + 1);
-    char lab[64];
-    if (prof_on()) snprintf(lab, sizeof(lab), "slab_reduce_group x%d", sg.n);
-    ProfScope ps(st, 0.0, sb, 2, prof_on() ? lab : nullptr);
-    hipLaunchKernelGGL(slab_reduce_group_kernel, dim3(nsb), dim3(256), 0, st, sg); MI_CHECK_LAUNCH("slab_reduce_group");
-  }
-  return MI355_OK;
+  return launch_slab_reduce_group(sg, nsb, st);
 }
 extern "C" int mi355_conv_wgrad_grouped(const mi355_wgrad_item* items, int n, void* ws, size_t ws_bytes, void* stream) {
   if (!items || n < 1) MI_FAIL(MI355_EINVAL, "wgrad_grouped: no items");
@@ -2243,9 +1988,8 @@ extern "C" int mi355_conv_wgrad_grouped(const mi355_wgrad_item* items, int n, vo
   }
   return walk_wgrad_groups(items, n, [&](int kind, const int* idx, int m) -> int {
     if (kind == 0) { const mi355_wgrad_item& it = items[idx[0]]; return mi355_conv_wgrad(&it.d, it.x, it.dy, it.dw, it.accumulate, ws, ws_bytes, stream); }
-    if (kind == 1) return launch_wgrad_group(items, idx, m, ws, ws_bytes, st);
-    if (kind == 3) return launch_wgrad_group(items, idx, m, ws, ws_bytes, st, 256);
-    return launch_wgrad_kw_group(items, idx, m, ws, ws_bytes, st);
+    if (kind == 2) return launch_wgrad_group<WgradKwGroupArgs>(items, idx, m, ws, ws_bytes, st, kind);
+    return launch_wgrad_group<WgradGroupArgs>(items, idx, m, ws, ws_bytes, st, kind);
   });
 }
 

@@ -508,37 +508,25 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
 }
 
 template <int BM, int BN, bool KW3 = false, bool MX = false>
-static void launch_fp8(GatherArgs& a, hipStream_t st) {
+static void launch_fp8(GatherArgs& a, ConvBuild b, hipStream_t st) {
   constexpr int smem = Fp8Smem<BM, BN, KW3, MX>::kBytes;
-  a.ntn = cdiv(a.Nout, BN);
-  int mx = 0;
-  for (int i = 0; i < a.nphase; ++i) { a.ph[i].ntm = cdiv(a.ph[i].M, BM); if (a.ph[i].ntm > mx) mx = a.ph[i].ntm; }
-  a.ntiles = a.nphase * mx * a.ntn;
-  a.stat_slices = 0;
-  if (a.stat_partial) {
-    bool even = !a.residual && !a.accumulate;
-    for (int i = 0; i < a.nphase; ++i) even = even && a.ph[i].ntm == mx;
-    if (even && (size_t)a.nphase * mx * a.Nout * 3 * sizeof(float) <= a.stat_bytes) a.stat_slices = a.nphase * mx;
-    else a.stat_partial = nullptr;
-  }
+  plan_gather_launch(a, b, conv_knobs());
 #define MI_L(BF8, EPI) do { auto kern = gather_fp8_kernel<BM, BN, BF8, EPI, KW3, MX>; static bool set_ = false; \
     if (!set_) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); set_ = true; } \
-    if (prof_on()) prof_amend_label("[%s g%dx%d%s%s%s]", MX ? "mx" : "f8", BM, BN, KW3 ? " kw3" : "", BF8 ? " bf8" : "", EPI ? " epi1" : ""); \
+    if (prof_on()) { char text[64]; conv_build_text(b, text, sizeof(text)); prof_amend_label("[%s]", text); } \
     hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(256), smem, st, a); } while (0)
-  if constexpr (MX) { if (a.stat_partial) MI_L(false, 1); else MI_L(false, 0); }
-  else if (a.a_fmt) { if (a.stat_partial) MI_L(true, 1); else MI_L(true, 0); }
-  else { if (a.stat_partial) MI_L(false, 1); else MI_L(false, 0); }
+  if constexpr (MX) { if (b.epi) MI_L(false, 1); else MI_L(false, 0); }
+  else if (b.bf8) { if (b.epi) MI_L(true, 1); else MI_L(true, 0); }
+  else { if (b.epi) MI_L(false, 1); else MI_L(false, 0); }
 #undef MI_L
 }
 
-static long g_fp8_kw3_min = -1;      // run-time switch (mi355_set_fp8_kw3); -1: the environment decides (MI355_FP8_KW3, default 1024)
-extern "C" long mi355_set_fp8_kw3(long min_tiles) { const long prev = g_fp8_kw3_min; g_fp8_kw3_min = min_tiles < 0 ? -1 : min_tiles; return prev; }
-
-static int ilog2x(int v) { int s = 0; while ((1 << s) < v) ++s; return ((1 << s) == v) ? s : -1; }
+// Run-time switch over MI355_FP8_KW3 (ConvKnobs::fp8_kw3): a negative count hands the choice back to the environment.
+extern "C" long mi355_set_fp8_kw3(long min_tiles) { const long prev = conv_knobs().fp8_kw3_set; conv_knobs().fp8_kw3_set = min_tiles < 0 ? -1 : min_tiles; return prev; }
 
 int dispatch_gather_fp8(GatherArgs& a, hipStream_t st) {
   if (a.Ci % 128) MI_FAIL(MI355_EINVAL, "fp8 gather: the contraction channels (%d) must be a multiple of 128", a.Ci);
-  a.cshift = ilog2x(a.Ci / 16);
+  a.cshift = ilog2_exact(a.Ci / 16);
   if (a.cshift < 3) MI_FAIL(MI355_EINVAL, "fp8 gather: Ci/16 must be a power of two >= 8 (Ci=%d)", a.Ci);
   if (a.Nout % 8) MI_FAIL(MI355_EINVAL, "fp8 gather: Nout=%d not a multiple of 8", a.Nout);
   if (a.nphase < 1 || a.nphase > 4) MI_FAIL(MI355_EINVAL, "fp8 gather: nphase=%d", a.nphase);
@@ -557,32 +545,14 @@ int dispatch_gather_fp8(GatherArgs& a, hipStream_t st) {
   if (mx && (!a.mx_sb || a.a_fmt || a.scale2 || a.scale3)) MI_FAIL(MI355_EINVAL, "fp8 gather: MX takes two scale arrays, e4m3 operands, no per-tensor descales");
   if (mx) { a.mx_sa_bytes = a.a_bytes / 32; a.mx_sb_bytes = a.b_bytes / 32; }
   ProfScope ps(st, flops, ((double)abytes + (double)bbytes * ntaps_tot / (a.ldb / a.Ci)) * (mx ? 33.0 / 32.0 : 1.0) + (double)Mtot * a.Nout * 2);
-  static const int force = getenv("MI355_FP8_TILE") ? atoi(getenv("MI355_FP8_TILE")) : -1;
-  const long t128 = cdiv(Mtot, 128L) * cdiv(a.Nout, 128);
-  // 3x3 / unit stride / same-size maps of a power-of-two width <= 128: the A-tile-sharing variant (KW3 above; conditions as in
-  // dispatch_gather of igemm.hip) from 1024 128x128 tiles on (MI355_FP8_KW3 / mi355_set_fp8_kw3: 0 off, n = smallest tile count).
-  // B=64: 3x3 256->256 @64x64 183 -> 168 us, @32x32 53.5 -> 48.4; below 1024 tiles neutral to slower (@16x16 18.9 -> 21.0).
-  // Iteration: ResNet-101 512x512 76.45 / 76.60 -> 76.24 / 76.05 ms, ResNet-50 32.11 / 32.06 -> 31.92 / 32.04.
-  static const long kw3_env = getenv("MI355_FP8_KW3") ? atol(getenv("MI355_FP8_KW3")) : 1024;
-  const long kw3_min = g_fp8_kw3_min >= 0 ? g_fp8_kw3_min : kw3_env;
-  bool kw3 = kw3_min > 0 && t128 >= kw3_min && a.nphase == 1 && a.ph[0].ntaps == 9 && a.in_sx == 1 && a.in_sy == 1 && a.out_sx == 1 &&
-             a.out_sy == 1 && a.ph[0].OWp == a.Wi && a.ph[0].OHp == a.Hi && a.Wo == a.Wi && a.Ho == a.Hi && a.Wi >= 8 && a.Wi <= 128 &&
-             ilog2x(a.Wi) >= 0 && a.Nout > 64;
-  for (int g = 0; g < 3 && kw3; ++g) {
-    const Tap* tp = a.taps + a.ph[0].tap0 + 3 * g;
-    int seen = 0;
-    for (int k = 0; k < 3; ++k) { if (tp[k].dy != tp[0].dy || tp[k].dx < -1 || tp[k].dx > 1) kw3 = false; else seen |= 1 << (tp[k].dx + 1); }
-    if (seen != 7 || tp[0].dy < -1 || tp[0].dy > 1) kw3 = false;
-  }
-  if (mx) {      // (the KW3 row-sharing variant has no MX build)
-    if (force == 0 || (force < 0 && t128 >= 512 && a.Nout > 64)) launch_fp8<128, 128, false, true>(a, st);
-    else if (force == 1 || (force < 0 && a.Nout > 64 && cdiv(Mtot, 64L) * cdiv(a.Nout, 128) >= 256)) launch_fp8<64, 128, false, true>(a, st);
-    else launch_fp8<64, 64, false, true>(a, st);
-  }
-  else if (kw3) { a.lw = ilog2x(a.Wi); launch_fp8<128, 128, true>(a, st); }
-  else if (force == 0 || (force < 0 && t128 >= 512 && a.Nout > 64)) launch_fp8<128, 128>(a, st);
-  else if (force == 1 || (force < 0 && a.Nout > 64 && cdiv(Mtot, 64L) * cdiv(a.Nout, 128) >= 256)) launch_fp8<64, 128>(a, st);
-  else launch_fp8<64, 64>(a, st);
+  const ConvBuild b = choose_fp8(a, conv_knobs());
+  // every build of the kernel: BM, BN, shared A tile, MX
+#define FP8_BUILDS(X) X(128, 128, true, false) X(128, 128, false, false) X(64, 128, false, false) X(64, 64, false, false) \
+                      X(128, 128, false, true) X(64, 128, false, true) X(64, 64, false, true)
+#define X(BM, BN, KW3, MX) if (b.bm == BM && b.bn == BN && b.kw3 == KW3 && (b.family == CONV_MX) == MX) launch_fp8<BM, BN, KW3, MX>(a, b, st);
+  FP8_BUILDS(X)
+#undef X
+#undef FP8_BUILDS
   MI_CHECK_LAUNCH("gather_fp8");
   return MI355_OK;
 }

@@ -547,8 +547,9 @@ __global__ __launch_bounds__(256) void pgemm_kernel(const GatherArgs p) {
 }
 
 // ------------------------------------------------------------------------------------ host
+// (the choice of a build -- pgemm_eligible, choose_pgemm -- and the tile grid are conv_plan.h)
 template <int BM, int BN, int NS, int EPI, bool ADD>
-static void launch_pgemm_epi(GatherArgs& a, int ncu, int ntm, int smem, hipStream_t st) {
+static void launch_pgemm_epi(GatherArgs& a, const ConvBuild& b, int ncu, int smem, hipStream_t st) {
   auto kern = pgemm_kernel<BM, BN, NS, EPI, ADD>;
   static int attr = 0;       // dynamic-LDS cap raised so far for this instantiation
   if (smem > attr) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr = smem; }
@@ -562,80 +563,36 @@ static void launch_pgemm_epi(GatherArgs& a, int ncu, int ntm, int smem, hipStrea
     per_cu = nb;
     for (int i = 0; i < 4; ++i) if (!occ_smem[i]) { occ_smem[i] = smem; occ_n[i] = nb; break; }
   }
-  static const int cap = getenv("MI355_PG_PER_CU") ? atoi(getenv("MI355_PG_PER_CU")) : 2;
+  const int cap = conv_knobs().pg_per_cu;
   if (per_cu > cap) per_cu = cap;
   // every block owns one column tile: the grid is a whole number of (row group, column tile) pairs, at most one per row tile
+  const int ntm = a.ph[0].ntm;
   int groups = ncu * per_cu / a.ntn; if (groups < 1) groups = 1;
   if (groups > ntm) groups = ntm;
-  if (prof_on()) prof_amend_label("[pgemm bm%d bn%d ns%d%s%s]", BM, BN, NS, EPI == 1 ? " epi1" : "", ADD ? " add" : "");
-  if (EPI == 1) a.stat_slices = groups;      // one statistics record per block and channel (slice = row group; groups <= ntm fits, checked by the caller)
+  if (prof_on()) { char text[64]; conv_build_text(b, text, sizeof(text)); prof_amend_label("[%s]", text); }
+  if (EPI == 1) a.stat_slices = groups;      // one statistics record per block and channel (slice = row group; groups <= ntm fits, checked by pgemm_plan_grid)
   hipLaunchKernelGGL(kern, dim3(groups * a.ntn), dim3(256), smem, st, a);
 }
 template <int BM, int BN, int NS>
-static bool launch_pgemm(GatherArgs& a, int ncu, hipStream_t st) {
-  const int nk = a.Ci >> 6;
-  const bool add = a.residual || a.accumulate;
-  a.pg_nadd = add ? (NS - 1) / nk + 2 : 0;                    // addend-ring slots (kernel comment): tile + mask bytes each
-  const int smem = PgSmem<BM, BN, NS>::bytes(nk) + a.pg_nadd * (PgSmem<BM, BN, NS>::kOut + BM * BN / 8);
-  if (smem > 160 * 1024) return false;
-  const int ntm = cdiv(a.ph[0].M, BM);
-  a.ntn = cdiv(a.Nout, BN);
-  a.ph[0].ntm = ntm;
-  a.ntiles = ntm * a.ntn;
-  a.stat_slices = 0;
-  if (a.stat_partial && (a.residual || a.accumulate || (size_t)ntm * a.Nout * 3 * sizeof(float) > a.stat_bytes)) a.stat_partial = nullptr;
-  if (a.stat_partial) launch_pgemm_epi<BM, BN, NS, 1, false>(a, ncu, ntm, smem, st);
-  else if (a.residual || a.accumulate) launch_pgemm_epi<BM, BN, NS, 0, true>(a, ncu, ntm, smem, st);
-  else launch_pgemm_epi<BM, BN, NS, 0, false>(a, ncu, ntm, smem, st);
-  return true;
+static void launch_pgemm(GatherArgs& a, const ConvBuild& b, int ncu, int smem, hipStream_t st) {
+  if (b.epi == 1) launch_pgemm_epi<BM, BN, NS, 1, false>(a, b, ncu, smem, st);
+  else if (b.add) launch_pgemm_epi<BM, BN, NS, 0, true>(a, b, ncu, smem, st);
+  else launch_pgemm_epi<BM, BN, NS, 0, false>(a, b, ncu, smem, st);
 }
 
-// Does the launch described by `a` (filled as for dispatch_gather) fit this kernel?  1x1, unit stride both ways (GEMM rows =
-// NHWC pixels in order), bf16, whole 64-channel K steps, a weight slice of one column tile that fits LDS beside the ring, no
-// BatchNorm-backward epilogue, no heat-map output, no concatenated second operand.
-static int g_pgemm_mode = -1;        // run-time switch (mi355_set_pgemm); -1: the environment decides (MI355_PGEMM, default 1)
-// 0: never; 1: where it measured faster than the gather kernel (below); 2: wherever the launch fits the kernel (tests, A/B runs).
+// Run-time switch over MI355_PGEMM (ConvKnobs::pgemm): a negative mode hands the choice back to the environment.
 // Returns the previous setting.
 extern "C" int mi355_set_pgemm(int mode) {
-  const int prev = g_pgemm_mode;
-  g_pgemm_mode = mode < 0 ? -1 : (mode > 2 ? 2 : mode);
+  const int prev = conv_knobs().pgemm_set;
+  conv_knobs().pgemm_set = mode < 0 ? -1 : (mode > 2 ? 2 : mode);
   return prev;
 }
-static int pg_bn(const GatherArgs& a) {       // column tile: the widest whose weight slice [BN][K] stays within 64 KB
-  if (a.Nout > 64 && (long)a.Ci * 128 * 2 <= 64 * 1024) return 128;
-  if ((long)a.Ci * 64 * 2 <= 64 * 1024) return 64;
-  return 0;
-}
-bool pgemm_eligible(const GatherArgs& a, int elem_size) {
-  static const int env_mode = getenv("MI355_PGEMM") ? atoi(getenv("MI355_PGEMM")) : 1;
-  const int mode = g_pgemm_mode >= 0 ? g_pgemm_mode : env_mode;
-  if (!mode || elem_size != 2) return false;
-  if (a.nphase != 1 || a.ph[0].ntaps != 1 || a.A2) return false;
-  const Tap& tp = a.taps[a.ph[0].tap0];
-  if (tp.dy != 0 || tp.dx != 0 || tp.widx != 0) return false;
-  if (a.in_sx != 1 || a.in_sy != 1 || a.out_sx != 1 || a.out_sy != 1) return false;
-  if (a.ph[0].OHp != a.Hi || a.ph[0].OWp != a.Wi || a.Ho != a.Hi || a.Wo != a.Wi || a.ph[0].out_oy || a.ph[0].out_ox) return false;
-  if (a.Ci % 64 || a.ldb != a.Ci || a.ldd != a.Nout || a.Nout % 8) return false;
-  if (a.bnb_partial || a.hw) return false;
-  const long Mrows = a.ph[0].M;
-  if (Mrows * a.Ci * 2 >= (1L << 31) || Mrows * a.Nout * 2 >= (1L << 31)) return false;
-  if (Mrows < 256 || !pg_bn(a)) return false;
-  if (a.residual && a.accumulate) return false;               // (one addend tensor per tile in the addend ring)
-  if (a.acc_mask && (a.Nout % 32 || !a.accumulate)) return false;      // mask bytes travel as dwords
-  if (mode >= 2) return true;
-  // residual / accumulate epilogues (addend ring): one block per CU carries ring, addend slots and a heavier epilogue -- measured
-  // 87 -> 74 us on 64 -> 256 @64x64 + residual (eval), 44 -> 46 us on 128 -> 512 @32x32 + residual: worth it for one K step per tile only
-  static const int add_maxk = getenv("MI355_PG_ADD") ? atoi(getenv("MI355_PG_ADD")) * 64 : 64;      // A/B switch: largest K taken (0 = none)
-  if ((a.residual || a.accumulate) && a.Ci > add_maxk) return false;
-  // Where it wins against the gather kernel (profiles/r04_pgemm_layers.txt: per layer, operands from HBM): the large maps
-  // (>= 32 K rows), with a short K (<= 128: wide outputs stream at 5 TB/s) or a narrow output (K = 256 -> 64 / 128 columns).
-  // K = 256 -> 256 columns needs two column tiles, i.e. the activations twice (no gain), K = 512 leaves room for 64-wide
-  // column tiles only (slower).
-  static const long min_rows = getenv("MI355_PG_MIN_ROWS") ? atol(getenv("MI355_PG_MIN_ROWS")) : 32768;
-  return Mrows >= min_rows && (a.Ci <= 128 || (a.Ci <= 256 && a.Nout <= 128));
-}
 
-int dispatch_pgemm(GatherArgs& a, hipStream_t st) {
+// every build of the kernel: BM, BN, ring depth
+#define PGEMM_BUILDS(X) \
+  X(128, 128, 4) X(64, 128, 8) X(64, 128, 6) X(64, 128, 5) X(64, 128, 4) \
+  X(128,  64, 4) X(64,  64, 8) X(64,  64, 6) X(64,  64, 5) X(64,  64, 4)
+int launch_pgemm_build(GatherArgs& a, ConvBuild b, hipStream_t st) {
   static int ncu = 0;
   if (!ncu) {
     int dev = 0, v = 0;
@@ -643,34 +600,11 @@ int dispatch_pgemm(GatherArgs& a, hipStream_t st) {
       MI_FAIL(MI355_ELAUNCH, "pgemm: cannot read the CU count");
     ncu = v;
   }
-  static const int ring_env = getenv("MI355_PG_RING") ? atoi(getenv("MI355_PG_RING")) : 0;        // experiment switches
-  static const int bm = getenv("MI355_PG_BM") ? atoi(getenv("MI355_PG_BM")) : 64;
-  const int bn = pg_bn(a);
-  const int nk = a.Ci >> 6;
-  // ring depth: the deepest ring with which TWO blocks still share a CU (each hides the other's epilogue), else the deepest that fits
-  int ring = ring_env;
-  if (!ring) {
-    const bool add = a.residual || a.accumulate;
-    auto bytes = [&](int ns) { return nk * bn * 128 + ns * 64 * 128 + 64 * bn * 2 + (add ? ((ns - 1) / nk + 2) * (64 * bn * 2 + 64 * bn / 8) : 0); };
-    if (!add) for (int ns : {8, 6, 5, 4}) if (!ring && bytes(ns) <= 80 * 1024) ring = ns;      // two blocks per CU
-    for (int ns : {8, 6, 5, 4}) if (!ring && bytes(ns) <= 160 * 1024) ring = ns;
-    if (!ring) ring = 4;
-  }
-  bool ok = false;
-  if (bn == 128) {
-    if (bm == 128) ok = launch_pgemm<128, 128, 4>(a, ncu, st);
-    else if (ring == 8) ok = launch_pgemm<64, 128, 8>(a, ncu, st);
-    else if (ring == 6) ok = launch_pgemm<64, 128, 6>(a, ncu, st);
-    else if (ring == 5) ok = launch_pgemm<64, 128, 5>(a, ncu, st);
-    else ok = launch_pgemm<64, 128, 4>(a, ncu, st);
-  } else {
-    if (bm == 128) ok = launch_pgemm<128, 64, 4>(a, ncu, st);
-    else if (ring == 8) ok = launch_pgemm<64, 64, 8>(a, ncu, st);
-    else if (ring == 6) ok = launch_pgemm<64, 64, 6>(a, ncu, st);
-    else if (ring == 5) ok = launch_pgemm<64, 64, 5>(a, ncu, st);
-    else ok = launch_pgemm<64, 64, 4>(a, ncu, st);
-  }
-  if (!ok) MI_FAIL(MI355_EINVAL, "pgemm: the weight slice of K = %d channels does not fit LDS (bn %d)", a.Ci, bn);
+  const int smem = pgemm_plan_grid(a, b);
+  if (!smem) MI_FAIL(MI355_EINVAL, "pgemm: the weight slice of K = %d channels does not fit LDS (bn %d)", a.Ci, b.bn);
+#define X(BM, BN, NS) if (b.bm == BM && b.bn == BN && b.ns == NS) launch_pgemm<BM, BN, NS>(a, b, ncu, smem, st);
+  PGEMM_BUILDS(X)
+#undef X
   MI_CHECK_LAUNCH("pgemm");
   return MI355_OK;
 }

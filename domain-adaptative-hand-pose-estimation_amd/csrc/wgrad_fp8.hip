@@ -326,17 +326,15 @@ __global__ __launch_bounds__(256, KW == 4 ? 2 : 3) void wgrad_kw28_kernel(const 
 }
 
 // ------------------------------------------------------------------------------------ host side
-static int ilog2e(int v) { int s = 0; while ((1 << s) < v) ++s; return ((1 << s) == v) ? s : -1; }
 struct Wg8Plan { int S, rows_per_split, nto, nti, ldw, mt, s2; };
-static const int g_wg8_blocks = getenv("MI355_WG_BLOCKS") ? atoi(getenv("MI355_WG_BLOCKS")) : 768;
 
 static int wg8_check(const mi355_conv_desc* d) {
   if (!d) MI_FAIL(MI355_EINVAL, "null conv desc");
   if (d->dtype != MI355_FP8) MI_FAIL(MI355_EINVAL, "wgrad_fp8: the descriptor must be an fp8 one");
   const bool s1 = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->Ho == d->Hi && d->Wo == d->Wi &&
-                  d->Wi >= 8 && ilog2e(d->Wi) >= 0;
+                  d->Wi >= 8 && ilog2_exact(d->Wi) >= 0;
   const bool s2 = d->kh == d->kw && (d->kh == 3 || d->kh == 4) && d->stride == 2 && d->pad == 1 && d->Hi % 2 == 0 && d->Wi % 2 == 0 &&
-                  d->Ho == d->Hi / 2 && d->Wo == d->Wi / 2 && d->Wo >= 8 && d->Wo <= 64 && ilog2e(d->Wo) >= 0;
+                  d->Ho == d->Hi / 2 && d->Wo == d->Wi / 2 && d->Wo >= 8 && d->Wo <= 64 && ilog2_exact(d->Wo) >= 0;
   if (!s1 && !s2)
     MI_FAIL(MI355_EINVAL, "wgrad_fp8: 3x3 / stride 1 / pad 1 with a power-of-two width >= 8, or 3x3 / 4x4 / stride 2 / pad 1 with even "
             "extents and a power-of-two output width in [8, 64] (k%dx%d s%d p%d, %dx%d -> %dx%d)", d->kh, d->kw, d->stride, d->pad,
@@ -346,19 +344,11 @@ static int wg8_check(const mi355_conv_desc* d) {
     MI_FAIL(MI355_EINVAL, "wgrad_fp8: tensor too large for 32-bit byte offsets: split the batch");
   return MI355_OK;
 }
-static Wg8Plan wg8_plan(const mi355_conv_desc* d) {      // the split rule of plan_wgrad (igemm.hip) for the kw-shared tilings
+static Wg8Plan wg8_plan(const mi355_conv_desc* d) {      // the kw-shared tilings, split like a bf16 launch on its own (wgrad_split_alone)
   Wg8Plan w; w.ldw = d->kh * d->kw * d->Ci; w.mt = d->Co <= 64 ? 1 : 2; w.s2 = d->stride == 2;
   w.nto = cdiv(d->Co, 64 * w.mt); w.nti = cdiv(d->Ci, 64);
-  const long tiles = (long)w.nto * d->kh * w.nti, M = (long)d->N * d->Ho * d->Wo, ksteps = (M + 63) / 64;
-  long S = (g_wg8_blocks + tiles - 1) / tiles;
-  const long S16 = ksteps / 16, S256 = (256 + tiles - 1) / tiles, lo = S16 > S256 ? S16 : S256;
-  if (S > lo) S = lo;
-  if (tiles >= 384) S = 1;
-  if (S > ksteps) S = ksteps;
-  if (S < 1) S = 1;
-  long rps = (M + S - 1) / S; rps = ((rps + 63) / 64) * 64;
-  S = (M + rps - 1) / rps;
-  w.S = (int)S; w.rows_per_split = (int)rps;
+  const WgradSplit s = wgrad_split_alone((long)d->N * d->Ho * d->Wo, 64, (long)w.nto * d->kh * w.nti, conv_knobs());
+  w.S = s.S; w.rows_per_split = s.rows;
   return w;
 }
 
@@ -400,7 +390,7 @@ extern "C" int mi355_conv_wgrad_fp8(const mi355_conv_desc* d, const void* x8, in
     k.X = x8; k.DY = dy8; k.out = direct ? dw : reinterpret_cast<float*>(ws);
     k.descale_x = descale_x; k.descale_dy = descale_dy;
     k.H = d->Hi; k.W = d->Wi; k.Ho = d->Ho; k.Ci = d->Ci; k.Co = d->Co;
-    k.lwo = ilog2e(d->Wo); k.lw = k.lwo > 6 ? 6 : k.lwo;
+    k.lwo = ilog2_exact(d->Wo); k.lw = k.lwo > 6 ? 6 : k.lwo;
     k.M = (int)M; k.rows_per_split = w.rows_per_split; k.ldw = w.ldw; k.slab_stride = slab; k.nto = w.nto; k.nci = w.nti;
     k.x_bytes = xb; k.dy_bytes = yb; k.dHo = make_fastdiv(d->Ho);
     if (d->kh == 3) { if (w.mt == 1) launch_kw28<1, 3>(grid, st, k, x_fmt, dy_fmt); else launch_kw28<2, 3>(grid, st, k, x_fmt, dy_fmt); }
@@ -411,7 +401,7 @@ extern "C" int mi355_conv_wgrad_fp8(const mi355_conv_desc* d, const void* x8, in
     k.X = x8; k.DY = dy8; k.out = direct ? dw : reinterpret_cast<float*>(ws);
     k.descale_x = descale_x; k.descale_dy = descale_dy;
     k.H = d->Hi; k.W = d->Wi; k.Ci = d->Ci; k.Co = d->Co;
-    k.lwf = ilog2e(d->Wi); k.lw = k.lwf > 6 ? 6 : k.lwf; k.halo = d->Wi > 64;
+    k.lwf = ilog2_exact(d->Wi); k.lw = k.lwf > 6 ? 6 : k.lwf; k.halo = d->Wi > 64;
     k.M = (int)M; k.rows_per_split = w.rows_per_split; k.ldw = w.ldw; k.slab_stride = slab; k.nto = w.nto; k.nci = w.nti;
     k.x_bytes = xb; k.dy_bytes = yb; k.dH = make_fastdiv(d->Hi);
     if (w.mt == 1) launch_kw8<1>(grid, st, k, x_fmt, dy_fmt); else launch_kw8<2>(grid, st, k, x_fmt, dy_fmt);

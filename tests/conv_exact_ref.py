@@ -431,6 +431,100 @@ PGEMM_CASES = {
 }
 
 
+# ---------------------------------------------------------------------------------------------- expected builds
+# The kernel build every case must run, as the launch-log label names it in brackets ("[g128x128 dma kg2 epi1]", csrc/common.h):
+# read from choose_conv / choose_pgemm / choose_fp8 / plan_wgrad (csrc/conv_plan.h).  test_gpu_conv_exact.py asserts them on
+# the launches, test_conv_dispatch_cpu.py on the choosers themselves.
+# group: the switches its cases run under (read once per process)
+GROUPS = {
+    'dma_kw3':   {'MI355_DMA': '2', 'MI355_KW3': '2', 'MI355_PHASES': '0'},
+    't256d':     {'MI355_T256D_MIN': '1', 'MI355_T256D_KMIN': '1'},
+    'fp8_tile0': {'MI355_FP8_TILE': '0'},
+    'fp8_tile1': {'MI355_FP8_TILE': '1'},
+}
+
+# name: (bf16, f32) x (forward, input gradient, accumulating input gradient, input gradient + BatchNorm-backward epilogue,
+# weight gradient with its slab count).  'build *4': four launches (one per phase, MI355_PHASES=0).
+EXPECT = {
+    'small7':         (('g128x64 small', 'g64x64', 'g64x64', 'g64x64', 'wgrad S9'), ('g128x64 f32 small', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S17')),
+    'small7_co72':    (('g128x64 small', None, None, None, 'wgrad S9'), ('g128x64 f32 small', None, None, None, 'wgrad S17')),
+    'stem4_crop':     (('g128x64 small', None, None, None, 'wgrad S9'), ('g128x64 f32 small', None, None, None, 'wgrad S17')),
+    'small_dgrad':    (('g64x64', 'g128x64 small', 'g128x64 small', 'g128x64 small', 'wgrad S6'), ('g64x64 f32', 'g128x64 f32 small', 'g128x64 f32 small', 'g128x64 f32 small', 'wgrad S11')),
+    't64_co72':       (('g64x64', None, None, None, 'wgrad S2'), ('g64x64 f32', None, None, None, 'wgrad S4')),
+    't64_s2':         (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S6')),
+    't64x128':        (('g64x128', 'g64x64', 'g64x64', 'g64x64', 'wgrad S94'), ('g64x128 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S113')),
+    't64x128_co136':  (('g64x128', None, None, None, 'wgrad S94'), ('g64x128 f32', None, None, None, 'wgrad S113')),
+    't64x128_dgrad':  (('g64x64', 'g64x128', 'g64x128', 'g64x128', 'wgrad S94'), ('g64x64 f32', 'g64x128 f32', 'g64x128 f32', 'g64x128 f32', 'wgrad S113')),
+    't128x64':        (('g128x64', 'g128x64', 'g128x64', 'g128x64', 'wgrad S61'), ('g128x64 f32', 'g128x64 f32', 'g128x64 f32', 'g128x64 f32', 'wgrad S121')),
+    't128x128':       (('g128x128', None, None, None, 'wgrad S31'), ('g128x128 f32 dma', None, None, None, 'wgrad S62')),
+    't128x128_dgrad': (('g128x64', 'g128x128', 'g128x128', 'g128x128', 'wgrad S61'), ('g128x64 f32', 'g128x128 f32 dma', 'g128x128 f32 dma', 'g128x128 f32 dma', 'wgrad S86')),
+    't128x128_f32_dgrad': (('g128x64', 'g128x64 small', 'g128x64 small', 'g128x64 small', 'wgrad S61'), ('g128x64 f32', 'g128x128 f32', 'g128x128 f32', 'g128x128 f32', 'wgrad S86')),
+    'kg2_64_co136':   (('g64x128 dma kg2', None, None, None, 'wgrad_kw S22'), ('g64x128 f32 dma kg2', None, None, None, 'wgrad S15')),
+    'kg2_128_co136':  (('g128x128 dma kg2', None, None, None, 'wgrad_kw S21'), ('g128x128 f32 dma kg2', None, None, None, 'wgrad S25')),
+    'kg2_64':         (('g64x128 dma kg2', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S22'), ('g64x128 f32 dma kg2', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S15')),
+    'kg2_128':        (('g128x128 dma kg2', 'g64x128 dma kg2', 'g64x128 dma kg2', 'g64x64', 'wgrad_kw S21'), ('g128x128 f32 dma kg2', 'g64x128 f32 dma kg2', 'g64x128 f32 dma kg2', 'g64x64 f32', 'wgrad S25')),
+    't256d':          (('g256x256 dma', 'g128x128 dma kg2', 'g128x128 dma kg2', 'g64x64', 'wgrad S15'), ('g128x128 f32', 'g128x128 f32 dma kg2', 'g128x128 f32 dma kg2', 'g64x64 f32', 'wgrad S23')),
+    's2_3x3_odd':     (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S5')),
+    's2_4x4_odd':     (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S4')),
+    'wkw_w8':         (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S6')),
+    'wkw_w16':        (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S5')),
+    'wkw_w32':        (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S3'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S6')),
+    'wkw_w64':        (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S5'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S10')),
+    'wkw_w128':       (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S6'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S12')),
+    'wkw_direct':     (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw S1'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S2')),
+    'wkw2_wo8':       (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S3')),
+    'wkw2_wo16':      (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S3')),
+    'wkw2_wo32':      (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S3')),
+    'wkw2_wo64':      (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S4')),
+    'wkw2_direct':    (('g64x64', 'g64x64', 'g64x64', 'g64x64', 'wgrad_kw2 S1'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S2')),
+    'wgen_direct':    (('g64x64', None, None, None, 'wgrad S1'), ('g64x64 f32', None, None, None, 'wgrad S2')),
+    'kw3_256x128':    (('g256x128 kw3', 'g128x64 kw3', 'g128x64 kw3', 'g128x64', 'wgrad_kw S128'), ('g128x128 f32 dma', 'g128x64 f32', 'g128x64 f32', 'g128x64 f32', 'wgrad S77')),
+    'dma_co136':      (('g128x128 dma', None, None, None, 'wgrad S4'), ('g128x128 f32 dma', None, None, None, 'wgrad S8')),
+    'dma_s2':         (('g128x128 dma', 'g128x128 dma *4', 'g128x128 dma *4', 'g128x128 dma *4', 'wgrad S2'), ('g128x128 f32 dma', 'g128x128 f32 dma *4', 'g128x128 f32 dma *4', 'g128x128 f32 dma *4', 'wgrad S4')),
+    'dma_s2_4x4':     (('g128x128 dma', 'g128x128 dma *4', 'g128x128 dma *4', 'g128x128 dma *4', 'wgrad S2'), ('g128x128 f32 dma', 'g128x128 f32 dma *4', 'g128x128 f32 dma *4', 'g128x128 f32 dma *4', 'wgrad S4')),
+    'kw3_w8':         (('g128x128 kw3', 'g128x64 kw3', 'g128x64 kw3', 'g64x64', 'wgrad_kw S2'), ('g128x128 f32 dma', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S4')),
+    'kw3_w16_co136':  (('g128x128 kw3', None, None, None, 'wgrad_kw S2'), ('g128x128 f32 dma', None, None, None, 'wgrad S3')),
+    'kw3_w32':        (('g128x64 kw3', 'g128x64 kw3', 'g128x64 kw3', 'g64x64', 'wgrad_kw S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S3')),
+    'kw3_w64':        (('g128x128 kw3', 'g128x64 kw3', 'g128x64 kw3', 'g64x64', 'wgrad_kw S3'), ('g128x128 f32 dma', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S6')),
+    'kw3_w128':       (('g128x64 kw3', 'g128x128 kw3', 'g128x128 kw3', 'g128x128 dma', 'wgrad_kw S6'), ('g64x64 f32', 'g128x128 f32 dma', 'g128x128 f32 dma', 'g128x128 f32 dma', 'wgrad S12')),
+    'phase_s2_odd':   (('g64x64', 'g64x64 *4', 'g64x64 *4', 'g64x64 *4', 'wgrad S3'), ('g64x64 f32', 'g64x64 f32 *4', 'g64x64 f32 *4', 'g64x64 f32 *4', 'wgrad S5')),
+    't256d_m300':     (('g256x256 dma', 'g64x64', 'g64x64', 'g64x64', 'wgrad S5'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S10')),
+    't256d_co512':    (('g256x256 dma', 'g64x64', 'g64x64', 'g64x64', 'wgrad S5'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S10')),
+    't256d_s2':       (('g64x64', 'g256x256 dma', 'g64x64', 'g64x64', 'wgrad S2'), ('g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'g64x64 f32', 'wgrad S4')),
+}
+CAT_EXPECT = {      # name: (bf16, f32)
+    'cat_64x64':    ('cat g64x64', 'cat g64x64 f32'),
+    'cat_64x64_s2': ('cat g64x64', 'cat g64x64 f32'),
+    'cat_64x128':   ('cat g64x128', 'cat g64x128 f32'),
+    'cat_128x128':  ('cat g128x128', 'cat g128x128 f32 dma'),
+    'cat_dma':      ('cat g128x128 dma', 'cat g128x128 f32 dma'),
+    'cat_256x256':  ('cat g256x256 dma', 'cat g64x64 f32'),
+}
+FP8_EXPECT = {      # name: (forward / input-gradient tile, the same with mi355_set_fp8_kw3(1) or None where the shape has no such build)
+    'f8_3x3_w8':   ('g64x64', 'g128x128 kw3'),
+    'f8_3x3_w16':  ('g64x64', 'g128x128 kw3'),
+    'f8_s2_3x3':   ('g64x64', None),
+    'f8_s2_4x4':   ('g64x64', None),
+    'f8_64x128':   (('g64x128', 'g64x64'), 'g128x128 kw3'),      # (forward, input gradient: 128 output columns are one column tile)
+    'f8_t128_w8':  ('g128x128', 'g128x128 kw3'),
+    'f8_t128_s2':  ('g128x128', None),
+    'f8_t64x128_w8': ('g64x128', 'g128x128 kw3'),
+    'f8_t64x128_s2': ('g64x128', None),
+}
+ROUNDING_EXPECT = {     # the builds of R.ROUNDING_CASES, in order
+    'default': ['g64x64', 'g64x128', 'g128x64', 'pgemm bm64 bn64 ns8', 'pgemm bm64 bn128 ns6'],
+    'dma_kw3': ['g128x128 dma'],
+    't256d': ['g256x256 dma'],
+}
+PGEMM_EXPECT = {       # name: (forward builds (plain, addend ring), input-gradient builds (plain, addend ring)) of R.PGEMM_CASES
+    'pg_k64':   (('pgemm bm64 bn128 ns6', 'pgemm bm64 bn128 ns4 add'), ('pgemm bm64 bn64 ns5', 'pgemm bm64 bn64 ns8 add')),
+    'pg_k128':  (('pgemm bm64 bn64 ns6', 'pgemm bm64 bn64 ns8 add'), ('pgemm bm64 bn128 ns6', 'pgemm bm64 bn128 ns4 add')),
+    'pg_k256':  (('pgemm bm64 bn128 ns8', 'pgemm bm64 bn128 ns4 add'), ('pgemm bm64 bn128 ns4', 'pgemm bm64 bn128 ns5 add')),
+    'pg_k512':  (('pgemm bm64 bn64 ns8', 'pgemm bm64 bn64 ns8 add'), ('pgemm bm64 bn128 ns4', 'pgemm bm64 bn128 ns5 add')),
+    'pg_co72':  (('pgemm bm64 bn128 ns6', 'pgemm bm64 bn128 ns4 add'), None),
+}
+
+
 def build_pgemm_case(name):
     if name in _cache:
         return _cache[name]
