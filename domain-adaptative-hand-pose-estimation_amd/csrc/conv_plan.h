@@ -59,6 +59,11 @@ struct GatherArgs {
   union { unsigned a2_bytes; unsigned mx_sa_bytes; };
   union { unsigned b2_bytes; unsigned mx_sb_bytes; };
   int pg_nadd;                 // (pgemm.hip, ADD build) slots of the addend ring
+  // MX build, inference epilogue (EPI 3 of gather_fp8_kernel): D = act(acc + bias + residual) with `relu` as above, no statistics,
+  // no accumulate, no scale.  mx_y8 / mx_sy (both or neither; Nout % 32 == 0): the MX copy of the bf16 values stored to D -- e4m3
+  // laid out like D, one E8M0 byte per 32 output channels of a pixel at (element offset in D) / 32.
+  int mx_act;
+  void* mx_y8; void* mx_sy;
 };
 
 // ------------------------------------------------------------------------------------ knobs
@@ -172,7 +177,7 @@ struct ConvBuild {
   int kg = 1;                // K groups per workgroup (1 or 2)
   int ns = 0; bool add = false;      // persistent GEMM: ring depth, addend ring
   bool bf8 = false;          // fp8: e5m2 gathered operand
-  int epi = 0;               // 0 plain, 1 statistics, 2 BatchNorm-backward: known once the launcher has admitted the slices
+  int epi = 0;               // 0 plain, 1 statistics, 2 BatchNorm-backward: known once the launcher has admitted the slices; 3 MX inference (mx_act)
 };
 // What the launch log shows in brackets (common.h, "profiling"): printed from the value the launch table is indexed with.
 static inline void conv_build_text(const ConvBuild& b, char* out, size_t n) {
@@ -426,7 +431,7 @@ static inline int gather_epilogue(GatherArgs& a, const ConvBuild& b, const ConvK
 // What the gather and the fp8 launcher do before they start the kernel of build `b`: tile grid, epilogue (b.epi), KW3 width.
 static inline void plan_gather_launch(GatherArgs& a, ConvBuild& b, const ConvKnobs& k) {
   plan_tile_grid(a, b.bm, b.bn, b.hm);
-  b.epi = b.family == CONV_GATHER ? gather_epilogue(a, b, k) : (a.stat_partial ? 1 : 0);
+  b.epi = b.family == CONV_GATHER ? gather_epilogue(a, b, k) : (b.family == CONV_MX && a.mx_act) ? 3 : (a.stat_partial ? 1 : 0);
   if (b.kw3) a.lw = ilog2_exact(a.Wi);
 }
 

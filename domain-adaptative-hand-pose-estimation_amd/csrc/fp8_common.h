@@ -48,3 +48,21 @@ __device__ __forceinline__ uint2 pack8_fp8(const float (&v)[8], float scale) {
   o.y = pack4_fp8<BF8>(v[4] * scale, v[5] * scale, v[6] * scale, v[7] * scale);
   return o;
 }
+
+// ---- MX (block-scaled e4m3, one E8M0 byte per 32 elements): the scale rule, stated in mx_fp8.hip.  The ONE copy: mx_quantize_kernel,
+// the weight packs and the fused copy of the gather kernel's act epilogue (igemm_fp8.hip) all call these.
+// exponent e of the rule for a finite amax >= 0 (bit arithmetic: exact for every float, subnormals included)
+__device__ __forceinline__ int mx_exp(float amax) {
+  const unsigned b = __float_as_uint(amax);
+  const int e = (int)(b >> 23) - 127 - 8 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);     // (m > 1.75: fraction bits > 0.75)
+  return e < -127 ? -127 : (e > 127 ? 127 : e);
+}
+// 2^-e as a float (e <= 120 for every finite amax, so the exponent field 127 - e stays in [7, 254])
+__device__ __forceinline__ float mx_inv_scale(int e) { return __uint_as_float((unsigned)(127 - e) << 23); }
+// |v| when finite, else 0 (and the non-finite flag set)
+__device__ __forceinline__ float mx_finite_abs(float v, bool& bad) {
+  const float a = fabsf(v);
+  const bool fin = a <= 3.40282347e38f;      // false for NaN and Inf
+  bad = bad || !fin;
+  return fin ? a : 0.f;
+}

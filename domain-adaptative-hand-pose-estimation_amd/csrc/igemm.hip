@@ -1510,10 +1510,13 @@ static int check_bnb(const mi355_bn_bwd_src* bn, const float* partial, const int
 }
 // fp8 operand launches: device scalars undoing the operand scales, and the format of the gathered operand
 // (MX: block scales sa / sb instead of the descales, e4m3 operands; mx_fp8.hip)
-struct Fp8Extra { const float* descale_a; const float* descale_b; int a_fmt; const void* sa = nullptr; const void* sb = nullptr; };
+// act: the MX inference epilogue (bias, residual, ReLU; no statistics), y8 / sy its optional MX copy of the output
+struct Fp8Extra { const float* descale_a; const float* descale_b; int a_fmt; const void* sa = nullptr; const void* sb = nullptr;
+                  bool act = false; void* y8 = nullptr; void* sy = nullptr; };
 struct CatExtra { const void* x2; const void* w2; const float* bias2; int c2; };
 static int dispatch_conv(GatherArgs& a, const mi355_conv_desc* d, const Fp8Extra* f8, hipStream_t st) {
-  if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; a.mx_sa = f8->sa; a.mx_sb = f8->sb; return dispatch_gather_fp8(a, st); }
+  if (f8) { a.scale2 = f8->descale_a; a.scale3 = f8->descale_b; a.a_fmt = f8->a_fmt; a.mx_sa = f8->sa; a.mx_sb = f8->sb;
+            a.mx_act = f8->act ? 1 : 0; a.mx_y8 = f8->y8; a.mx_sy = f8->sy; return dispatch_gather_fp8(a, st); }
   return d->dtype == MI355_BF16 ? dispatch_gather<bf16_t>(a, st) : dispatch_gather<float>(a, st);
 }
 static int conv_fwd_impl(const mi355_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
@@ -1521,9 +1524,9 @@ static int conv_fwd_impl(const mi355_conv_desc* d, const void* x, const void* w,
                          const Fp8Extra* f8 = nullptr, int relu = 0, const CatExtra* cat = nullptr) {
   if (int e = check_desc(d, true)) return e;
   if ((d->dtype == MI355_FP8) != (f8 != nullptr)) MI_FAIL(MI355_EINVAL, "fp8 descriptors go through the *_fp8 entry points (and only they)");
-  if (relu && (bn || f8 || partial)) MI_FAIL(MI355_EINVAL, "conv_fwd: the fused ReLU is an inference epilogue (no statistics / BatchNorm-backward / fp8 variant)");
+  if (relu && (bn || (f8 && !f8->act) || partial)) MI_FAIL(MI355_EINVAL, "conv_fwd: the fused ReLU is an inference epilogue (no statistics / BatchNorm-backward / fp8 variant)");
   GatherArgs a; memset(&a, 0, sizeof(a));
-  if (prof_on()) prof_set_tag("fwd%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? "mx" : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
+  if (prof_on()) prof_set_tag("fwd%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? (f8->y8 ? "mx+q" : "mx") : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
                               residual ? " +res" : "", cat ? " +cat" : "");
   a.relu = relu ? 1 : 0;
   a.A = x; a.B = w; a.D = y; a.bias = bias; a.residual = residual; a.scale = nullptr; a.accumulate = 0;
@@ -1559,6 +1562,25 @@ extern "C" int mi355_conv_fwd_mx(const mi355_conv_desc* d, const void* x8, const
   if ((partial == nullptr) != (nslices == nullptr)) MI_FAIL(MI355_EINVAL, "conv_fwd_mx: partial and nslices go together");
   Fp8Extra f8{nullptr, nullptr, 0, sx, sw};
   return conv_fwd_impl(d, x8, w8, bias, residual, y, partial, partial_bytes, nslices, stream, nullptr, &f8);
+}
+// the MX copy an act launch writes beside its bf16 output of `C` channels: both pointers or neither, whole 32-channel blocks
+static int check_mx_copy(const char* who, const void* y8, const void* sy, int C) {
+  if ((y8 == nullptr) != (sy == nullptr)) MI_FAIL(MI355_EINVAL, "%s: the MX copy of the output takes both its elements and its scales", who);
+  if (y8 && C % 32) MI_FAIL(MI355_EINVAL, "%s: an MX copy of the output needs a multiple of 32 output channels (%d)", who, C);
+  if (y8 && (uintptr_t)y8 % 8) MI_FAIL(MI355_EINVAL, "%s: the element buffer of the MX copy must be 8-byte aligned", who);
+  return MI355_OK;
+}
+// inference on MX operands: y = act(conv(x8, w8) + bias + residual) with the BatchNorm that follows folded into w8 / bias by the
+// caller (as mi355_conv_fwd_act), and optionally the MX copy (y8, sy) of that y for the next MX layer
+extern "C" int mi355_conv_fwd_mx_act(const mi355_conv_desc* d, const void* x8, const void* sx, const void* w8, const void* sw,
+                                     const float* bias, const void* residual, int relu, void* y, void* y8, void* sy, void* stream) {
+  if (!d || !x8 || !sx || !w8 || !sw || !y) MI_FAIL(MI355_EINVAL, "conv_fwd_mx_act: null descriptor, operand, scale or output");
+  if (d->dtype != MI355_FP8) MI_FAIL(MI355_EINVAL, "conv_fwd_mx_act: the descriptor's dtype must be MI355_FP8");
+  if (d->Ci < 128 || d->Ci % 128 || (d->Ci & (d->Ci - 1))) MI_FAIL(MI355_EINVAL, "conv_fwd_mx_act: Ci=%d (contracted) must be a power-of-two multiple of 128", d->Ci);
+  if (d->Co < 8 || d->Co % 8) MI_FAIL(MI355_EINVAL, "conv_fwd_mx_act: Co=%d must be a multiple of 8", d->Co);
+  if (int e = check_mx_copy("conv_fwd_mx_act", y8, sy, d->Co)) return e;
+  Fp8Extra f8{nullptr, nullptr, 0, sx, sw, true, y8, sy};
+  return conv_fwd_impl(d, x8, w8, bias, residual, y, nullptr, 0, nullptr, stream, nullptr, &f8, relu);
 }
 extern "C" int mi355_conv_fwd(const mi355_conv_desc* d, const void* x, const void* w, const float* bias,
                               const void* residual, void* y, void* stream) {
@@ -1655,6 +1677,23 @@ extern "C" int mi355_conv_dgrad_mx(const mi355_conv_desc* d, const void* dy8, co
   Fp8Extra f8{nullptr, nullptr, 0, sdy, swT};
   return conv_dgrad_impl(d, dy8, wT8, nullptr, scale_dev, accumulate, dx, partial, partial_bytes, nslices, stream, nullptr, &f8);
 }
+// inference ConvTranspose2d forward on MX operands: dx = act(dgrad(dy8) + bias), optionally with the MX copy (dx8, sdx) of dx
+extern "C" int mi355_conv_dgrad_mx_act(const mi355_conv_desc* d, const void* dy8, const void* sdy, const void* wT8, const void* swT,
+                                       const float* bias, int relu, void* dx, void* dx8, void* sdx, void* stream) {
+  if (!d || !dy8 || !sdy || !wT8 || !swT || !dx) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx_act: null descriptor, operand, scale or output");
+  if (d->dtype != MI355_FP8) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx_act: the descriptor's dtype must be MI355_FP8");
+  if (d->Co < 128 || d->Co % 128 || (d->Co & (d->Co - 1))) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx_act: Co=%d (contracted) must be a power-of-two multiple of 128", d->Co);
+  if (d->Ci < 8 || d->Ci % 8) MI_FAIL(MI355_EINVAL, "conv_dgrad_mx_act: Ci=%d must be a multiple of 8", d->Ci);
+  if (int e = check_mx_copy("conv_dgrad_mx_act", dx8, sdx, d->Ci)) return e;
+  if (int e = check_desc(d)) return e;
+  {   // every output pixel must come out of the launch: a zero-filled parity would carry neither the bias nor a copy
+    GatherArgs probe; memset(&probe, 0, sizeof(probe));
+    if (describe_dgrad(probe, d) || probe.nphase != d->stride * d->stride)
+      MI_FAIL(MI355_EINVAL, "conv_dgrad_mx_act: k%d s%d p%d leaves output pixels without a tap", d->kh, d->stride, d->pad);
+  }
+  Fp8Extra f8{nullptr, nullptr, 0, sdy, swT, true, dx8, sdx};
+  return conv_dgrad_impl(d, dy8, wT8, bias, nullptr, 0, dx, nullptr, 0, nullptr, stream, nullptr, &f8, nullptr, relu);
+}
 // conv input gradient that is the dy of a BatchNorm: that BatchNorm's backward reduction in the epilogue
 extern "C" int mi355_conv_dgrad_bnbwd(const mi355_conv_desc* d, const void* dy, const void* wT, const float* scale_dev, int accumulate,
                                       void* dx, const mi355_bn_bwd_src* bn, float* partial, size_t partial_bytes, int* nslices,
@@ -1688,7 +1727,7 @@ static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void*
                            int accumulate, void* dx, float* partial, size_t partial_bytes, int* nslices, void* stream,
                            const mi355_bn_bwd_src* bn, const Fp8Extra* f8, const void* acc_mask, int relu) {
   if (nslices) *nslices = 0;
-  if (relu && (bn || f8 || partial || accumulate)) MI_FAIL(MI355_EINVAL, "conv_dgrad: the fused ReLU is an inference epilogue of the transposed conv");
+  if (relu && (bn || (f8 && !f8->act) || partial || accumulate)) MI_FAIL(MI355_EINVAL, "conv_dgrad: the fused ReLU is an inference epilogue of the transposed conv");
   if (acc_mask && (!accumulate || bn || f8)) MI_FAIL(MI355_EINVAL, "conv_dgrad: acc_mask goes with accumulate = 1 on the plain bf16 / fp32 path only");
   if (int e = check_desc(d)) return e;
   if ((d->dtype == MI355_FP8) != (f8 != nullptr)) MI_FAIL(MI355_EINVAL, "fp8 descriptors go through the *_fp8 entry points (and only they)");
@@ -1705,7 +1744,7 @@ static int conv_dgrad_impl(const mi355_conv_desc* d, const void* dy, const void*
     MI_CHECK_LAUNCH("zero_fill");
   }
   auto tag = [&]() {      // (a launch consumes the pending tag: the per-phase launches below set it once each)
-    if (prof_on()) prof_set_tag("dgrad%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? "mx" : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
+    if (prof_on()) prof_set_tag("dgrad%s k%ds%d %d>%d @%dx%d n%d%s%s%s", f8 ? (f8->sa ? (f8->y8 ? "mx+q" : "mx") : "8") : "", d->kh, d->stride, d->Ci, d->Co, d->Hi, d->Wi, d->N, partial ? " +stats" : "",
                                 accumulate ? (acc_mask ? " +macc" : " +acc") : "", bn ? " +bnb" : "");
   };
   tag();

@@ -178,6 +178,8 @@ struct Fp8Smem {
 // 4 waves (2 x 2), each a (BM/2) x (BN/2) sub-tile of 32x32 MFMA blocks.  K-tile = 128 channels of one tap
 // (8 chunks of 16 bytes); register-staged pipeline over one LDS stage, like the bf16 kernel's default path.
 // A_BF8: the gathered operand is e5m2 (gradients), the weights are always e4m3.  EPI 1: BatchNorm statistics of the output.
+// EPI 3 (MX builds): the inference epilogue, act(acc + bias + residual), which can also write the MX copy of its own output for
+// the next MX layer (GatherArgs::mx_act; see the store loop).
 // KW3: 3x3 / unit-stride layers (forward and input gradient): the three taps of a kernel row read the same pixels shifted by
 // -1 / 0 / +1, so one staged A tile per (kernel row, 128-channel chunk) serves three K sub-steps -- the construction of the bf16
 // kernel's KW3 path (igemm.hip), whose 128-byte rows carry 64 bf16 channels where these carry 128 fp8 channels: same LDS image,
@@ -418,7 +420,7 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
 
   // ---- epilogue: (acc * descale [* lambda] + bias) -> bf16 -> LDS tile -> coalesced 16-byte rows (+residual / +dx)
   char* outs = smem;
-  const float scale = (p.scale ? *p.scale : 1.0f) * (p.scale2 ? *p.scale2 : 1.0f) * (p.scale3 ? *p.scale3 : 1.0f);
+  [[maybe_unused]] const float scale = (p.scale ? *p.scale : 1.0f) * (p.scale2 ? *p.scale2 : 1.0f) * (p.scale3 ? *p.scale3 : 1.0f);
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -431,7 +433,8 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float b = (p.bias && (n0 + nl + e) < p.Nout) ? p.bias[n0 + nl + e] : 0.f;
-          u.h[e] = (bf16_t)(acc[i][j][4 * g + e] * scale + b);
+          if constexpr (EPI == 3) u.h[e] = (bf16_t)(acc[i][j][4 * g + e] + b);      // (block scales only: no per-tensor descale)
+          else u.h[e] = (bf16_t)(acc[i][j][4 * g + e] * scale + b);
         }
         *reinterpret_cast<uint2*>(outs + ml * SM::kOutStride + nl * 2) = u.q;
       }
@@ -442,6 +445,50 @@ __global__ __launch_bounds__(256) void gather_fp8_kernel(const GatherArgs p) {
   float sn = 0.f, smean[CHO], sm2[CHO];
 #pragma unroll
   for (int e = 0; e < CHO; ++e) { smean[e] = 0.f; sm2[e] = 0.f; }
+  if constexpr (EPI == 3) {
+    // One thread owns one row and one 8-channel chunk, so the four lanes 4q .. 4q + 3 hold one 32-channel MX block of a pixel
+    // (CPR % 4 == 0, n0 % 32 == 0); with Nout % 32 == 0 the four are in or out together (`live`), and the skip is a predicate, not
+    // a `continue`: every lane reaches both exchanges.  The copy is taken from the bf16 values just stored.
+    static_assert(MX && CPR % 4 == 0 && (BM * CPR) % NTHR == 0 && BN % 32 == 0, "act epilogue: whole MX blocks per lane group, whole passes");
+    unsigned char* __restrict__ Y8 = reinterpret_cast<unsigned char*>(p.mx_y8);
+    unsigned char* __restrict__ SY = reinterpret_cast<unsigned char*>(p.mx_sy);
+    for (int id = t; id < BM * CPR; id += NTHR) {
+      const int r = id / CPR, c = id % CPR;
+      const int off = row_off[r];
+      const int n = n0 + c * CHO;
+      const bool live = off >= 0 && n < p.Nout;
+      const size_t g = live ? (size_t)off + n : 0;
+      float v[CHO];
+#pragma unroll
+      for (int e = 0; e < CHO; ++e) v[e] = 0.f;
+      if (live) {
+        Chunk<bf16_t>::load(reinterpret_cast<const bf16_t*>(outs + r * SM::kOutStride + c * 16), v);
+        if (R) { float w[CHO]; Chunk<bf16_t>::load(R + g, w);
+#pragma unroll
+          for (int e = 0; e < CHO; ++e) v[e] += w[e]; }
+        if (p.relu) {
+#pragma unroll
+          for (int e = 0; e < CHO; ++e) v[e] = v[e] < 0.f ? 0.f : v[e]; }      // (keeps NaN, like the bf16 kernel)
+#pragma unroll
+        for (int e = 0; e < CHO; ++e) v[e] = (float)(bf16_t)v[e];
+        Chunk<bf16_t>::store(D + g, v);
+      }
+      if (Y8) {
+        float amax = 0.f; bool bad = false;
+#pragma unroll
+        for (int e = 0; e < CHO; ++e) amax = fmaxf(amax, mx_finite_abs(v[e], bad));
+        int b = bad ? 1 : 0;
+#pragma unroll
+        for (int o = 1; o < 4; o <<= 1) { amax = fmaxf(amax, __shfl_xor(amax, o, 64)); b |= __shfl_xor(b, o, 64); }
+        const int ex = mx_exp(amax);
+        if (live) {
+          *reinterpret_cast<uint2*>(Y8 + g) = pack8_fp8<false>(v, mx_inv_scale(ex));
+          if (!(c & 3)) SY[g >> 5] = b ? (unsigned char)0xFF : (unsigned char)(ex + 127);
+        }
+      }
+    }
+    return;
+  }
   for (int id = t; id < BM * CPR; id += NTHR) {
     const int r = id / CPR, c = id % CPR;
     const int off = row_off[r];
@@ -515,7 +562,7 @@ static void launch_fp8(GatherArgs& a, ConvBuild b, hipStream_t st) {
     if (!set_) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); set_ = true; } \
     if (prof_on()) { char text[64]; conv_build_text(b, text, sizeof(text)); prof_amend_label("[%s]", text); } \
     hipLaunchKernelGGL(kern, dim3(a.ntiles), dim3(256), smem, st, a); } while (0)
-  if constexpr (MX) { if (b.epi) MI_L(false, 1); else MI_L(false, 0); }
+  if constexpr (MX) { if (b.epi == 3) MI_L(false, 3); else if (b.epi) MI_L(false, 1); else MI_L(false, 0); }
   else if (b.bf8) { if (b.epi) MI_L(true, 1); else MI_L(true, 0); }
   else { if (b.epi) MI_L(false, 1); else MI_L(false, 0); }
 #undef MI_L
@@ -544,6 +591,11 @@ int dispatch_gather_fp8(GatherArgs& a, hipStream_t st) {
   const bool mx = a.mx_sa != nullptr;
   if (mx && (!a.mx_sb || a.a_fmt || a.scale2 || a.scale3)) MI_FAIL(MI355_EINVAL, "fp8 gather: MX takes two scale arrays, e4m3 operands, no per-tensor descales");
   if (mx) { a.mx_sa_bytes = a.a_bytes / 32; a.mx_sb_bytes = a.b_bytes / 32; }
+  if (a.mx_act) {
+    if (!mx || a.stat_partial || a.accumulate || a.scale) MI_FAIL(MI355_EINVAL, "fp8 gather: the act epilogue is an MX one without statistics, accumulate or scale");
+    if ((a.mx_y8 == nullptr) != (a.mx_sy == nullptr) || (a.mx_y8 && (a.Nout % 32 || a.ldd % 32)))
+      MI_FAIL(MI355_EINVAL, "fp8 gather: the MX copy of the output takes both y8 and sy and Nout=%d a multiple of 32", a.Nout);
+  } else if (a.mx_y8 || a.mx_sy) MI_FAIL(MI355_EINVAL, "fp8 gather: an MX copy of the output is written by the act epilogue only");
   ProfScope ps(st, flops, ((double)abytes + (double)bbytes * ntaps_tot / (a.ldb / a.Ci)) * (mx ? 33.0 / 32.0 : 1.0) + (double)Mtot * a.Nout * 2);
   const ConvBuild b = choose_fp8(a, conv_knobs());
   // every build of the kernel: BM, BN, shared A tile, MX

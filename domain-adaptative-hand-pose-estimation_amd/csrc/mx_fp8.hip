@@ -21,21 +21,8 @@
 #include "igemm_common.h"
 #include "fp8_common.h"
 
-// exponent e of the rule above for a finite amax >= 0 (bit arithmetic: exact for every float, subnormals included)
-__device__ __forceinline__ int mx_exp(float amax) {
-  const unsigned b = __float_as_uint(amax);
-  const int e = (int)(b >> 23) - 127 - 8 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);     // (m > 1.75: fraction bits > 0.75)
-  return e < -127 ? -127 : (e > 127 ? 127 : e);
-}
-// 2^-e as a float (e <= 120 for every finite amax, so the exponent field 127 - e stays in [7, 254])
-__device__ __forceinline__ float mx_inv_scale(int e) { return __uint_as_float((unsigned)(127 - e) << 23); }
-// |v| when finite, else 0 (and the non-finite flag set)
-__device__ __forceinline__ float mx_finite_abs(float v, bool& bad) {
-  const float a = fabsf(v);
-  const bool fin = a <= 3.40282347e38f;      // false for NaN and Inf
-  bad = bad || !fin;
-  return fin ? a : 0.f;
-}
+// (mx_exp / mx_inv_scale / mx_finite_abs, the one copy of the rule above: fp8_common.h -- the fused copy of the act epilogue in
+// igemm_fp8.hip uses them too)
 
 // ------------------------------------------------------------------------------------ activations / gradients
 // 16 elements per thread-iteration; the two lanes of a pair (2k, 2k + 1) hold one 32-element block and exchange their partial

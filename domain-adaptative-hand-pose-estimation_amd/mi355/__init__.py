@@ -65,6 +65,8 @@ SIGNATURES = {
     'mi355_pack_weights_mx_batched': (_I, [_P, _I, _I, _P]),
     'mi355_conv_fwd_mx': (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P]),
     'mi355_conv_dgrad_mx': (_I, [_D, _P, _P, _P, _P, _P, _I, _P, _P, _Z, _P, _P]),
+    'mi355_conv_fwd_mx_act': (_I, [_D, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    'mi355_conv_dgrad_mx_act': (_I, [_D, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     'mi355_conv_wgrad_workspace': (_Z, [_D]),
     'mi355_conv_wgrad_fp8_workspace': (_Z, [_D]),
     'mi355_conv_wgrad_fp8': (_I, [_D, _P, _I, _P, _I, _P, _P, _P, _I, _P, _Z, _P]),
@@ -197,7 +199,8 @@ def set_compute_dtype(dt):
 
     'mxfp8': the same convolutions -- the 4x4 transposed convs of the neck included -- on MX operands instead: e4m3 for every
     operand, gradients included, with one E8M0 scale per 32 contracted elements (mx_fp8.hip), no scaling state; weight
-    gradients stay bf16, eval-mode modules take the BatchNorm-folded bf16 path, the MI355_FP8_* switches do not apply."""
+    gradients stay bf16, eval-mode modules take the BatchNorm-folded bf16 path (or, with set_mx_eval(True), the folded MX path --
+    that switch is independent of this one), the MI355_FP8_* switches do not apply."""
     global _compute_dtype, _fp8_convs, _mx_convs
     if dt in ('bf16', torch.bfloat16):
         _compute_dtype, _fp8_convs, _mx_convs = torch.bfloat16, False, False
@@ -239,6 +242,24 @@ def fp8_convs():
 def mx_convs():
     """True in 'mxfp8' mode: the K-heavy convs run their forward and input gradient on MX (block-scaled e4m3) operands."""
     return _mx_convs
+
+
+# Opt-in MX inference (MI355_MX_EVAL, read once; default off): eval-mode 3x3 / 4x4 convs and transposed convs whose BatchNorm is
+# folded run on MX operands with bias, residual and ReLU in the kernel (mi355_conv_fwd_mx_act / mi355_conv_dgrad_mx_act).
+# Independent of the compute dtype: it applies wherever activations are bf16 and per-tensor 'fp8' mode is not active.
+_mx_eval = os.environ.get('MI355_MX_EVAL', '0') == '1'
+
+
+def set_mx_eval(on):
+    """Switch the MX inference path on or off; returns the previous setting.  mi355.infer.GraphedForward drops its graphs when
+    the setting changes."""
+    global _mx_eval
+    prev, _mx_eval = _mx_eval, bool(on)
+    return prev
+
+
+def mx_eval():
+    return _mx_eval
 
 
 # ---------------------------------------------------------------- fp8 scaling states (delayed scaling)

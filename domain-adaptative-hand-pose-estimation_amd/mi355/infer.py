@@ -3,15 +3,16 @@ from a HIP graph.  Eager, one forward of the pose network is ~120 launches that 
 needs to run; replayed it is one graph launch."""
 import torch
 
-from . import compute_dtype, fp8_convs, graph_capture_mode, nn as _nn
+from . import compute_dtype, fp8_convs, graph_capture_mode, mx_eval, nn as _nn
 
 
 class GraphedForward:
     """``y = GraphedForward(model)(x)``: eval-mode, no-grad forwards are captured per input shape after ``warmup`` eager calls
     (they allocate the workspaces and fold the BatchNorms into the convs) and replayed from then on; anything else (training
     mode, gradients enabled) goes to ``model(x)``.  The graphs are dropped when a parameter, a buffer or a running statistic
-    changes (training resumed, ``load_state_dict``) or the compute dtype does (``mi355.set_compute_dtype``: the graphs hold the
-    packed weights and kernels of the dtype they were captured in).  The returned tensor is a copy: it stays valid across calls."""
+    changes (training resumed, ``load_state_dict``) or the compute dtype or the MX inference switch does
+    (``mi355.set_compute_dtype``, ``mi355.set_mx_eval``: the graphs hold the packed weights and kernels of the setting they were
+    captured under).  The returned tensor is a copy: it stays valid across calls."""
 
     def __init__(self, model, warmup=2):
         self.model, self.warmup = model, warmup
@@ -23,7 +24,7 @@ class GraphedForward:
             v = v * 1000003 + t._version + getattr(t, '_mi_epoch', 0)
         for t in self.model.buffers():
             v = v * 1000003 + t._version
-        return v & ((1 << 62) - 1), compute_dtype(), fp8_convs()
+        return v & ((1 << 62) - 1), compute_dtype(), fp8_convs(), mx_eval()
 
     def __call__(self, x):
         if self.model.training or torch.is_grad_enabled() or not x.is_cuda:

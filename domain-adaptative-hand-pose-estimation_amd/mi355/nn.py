@@ -80,6 +80,22 @@ class _LazyConv:
         return self.conv(self.x, _lazy=False)
 
 
+def _fold_key(conv, bn):
+    """What a folded copy of (conv, bn) depends on: parameter versions, running statistics, the BatchNorm itself."""
+    ver = lambda t: None if t is None else _param_version(t)
+    return (ver(conv.weight), ver(conv.bias), ver(bn.weight), ver(bn.bias), bn.running_mean._version, bn.running_var._version,
+            _BN_GEN[0], id(bn), float(bn.eps))
+
+
+def _fold_scale_shift(conv, bn):
+    """eval-mode bn(conv(x)) = conv(x) * scale + shift per output channel (fp32; the conv's own bias goes into shift)"""
+    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
+    shift = bn.bias.detach().float() - bn.running_mean.float() * scale
+    if conv.bias is not None:
+        shift = shift + conv.bias.detach().float() * scale
+    return scale, shift
+
+
 class _FoldedBn:
     """Weights and bias of one conv with the eval-mode BatchNorm behind it folded in."""
 
@@ -87,15 +103,10 @@ class _FoldedBn:
         self.key, self.w, self.bias = None, None, None
 
     def get(self, conv, bn, dtype, deconv, s2d=False):
-        ver = lambda t: None if t is None else _param_version(t)
-        key = (ver(conv.weight), ver(conv.bias), ver(bn.weight), ver(bn.bias), bn.running_mean._version, bn.running_var._version,
-               _BN_GEN[0], dtype, id(bn), float(bn.eps), s2d)
+        key = _fold_key(conv, bn) + (dtype, s2d)
         if key != self.key:
             with torch.no_grad():
-                scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
-                shift = bn.bias.detach().float() - bn.running_mean.float() * scale
-                if conv.bias is not None:
-                    shift = shift + conv.bias.detach().float() * scale
+                scale, shift = _fold_scale_shift(conv, bn)
                 wm = conv.weight.detach().permute(0, 2, 3, 1)            # memory order [O][kh][kw][I], contiguous view
                 if getattr(conv, 'groups', 1) > 1:
                     wm = _dense_from_grouped(conv.weight, conv.groups)   # dense block-diagonal [O][kh][kw][in_channels]
@@ -111,6 +122,34 @@ class _FoldedBn:
                 self.bias = shift.contiguous()
             self.key = key
         return self.w, self.bias
+
+
+class _FoldedMx:
+    """The same fold for the MX inference path (mi355.set_mx_eval): the fp32 master times the BatchNorm scale goes to
+    ops.pack_weights_mx, so the E8M0 block scales are those of the FOLDED weight.  Keyed and refreshed as _FoldedBn.
+    get() -> (e4m3 pack, its scales, bias): the forward pack [O][T][I] for a conv, the input-gradient pack [I][T][O] of the
+    conv-form (blocks along the deconv's input channels, which its forward contracts) for a transposed conv."""
+
+    def __init__(self):
+        self.key, self.bias = None, None
+        self.packs = (None, None, None, None)
+
+    def get(self, conv, bn, deconv):
+        key = _fold_key(conv, bn) + (conv.weight.device,)
+        if key != self.key:
+            with torch.no_grad():
+                scale, shift = _fold_scale_shift(conv, bn)
+                wm = conv.weight.detach().float().permute(0, 2, 3, 1)    # [O][kh][kw][I]
+                k2 = conv.kernel_size[0] * conv.kernel_size[1]
+                if deconv:       # conv-form (O = in_channels, I = out_channels): the scale goes on the I axis
+                    wm, O, I = (wm * scale.view(1, 1, 1, -1)).contiguous(), conv.in_channels, conv.out_channels
+                else:
+                    wm, O, I = (wm * scale.view(-1, 1, 1, 1)).contiguous(), conv.out_channels, conv.in_channels
+                self.packs = ops.pack_weights_mx(wm, O, k2, I, *self.packs)
+                self.bias = shift.contiguous()
+            self.key = key
+        wf, sf, wt, st = self.packs
+        return (wt, st, self.bias) if deconv else (wf, sf, self.bias)
 
 
 def _lazy_ok(mod, residual=None):
@@ -336,6 +375,21 @@ def _mx_copy(t):
 def _mx_eligible(cin, cout):
     """channel counts the MX GEMMs take as contracted axes: power-of-two multiples of the 128-channel K tile"""
     return all(c >= 128 and c % 128 == 0 and (c & (c - 1)) == 0 for c in (cin, cout))
+
+
+def _mx_eval_on():
+    """The opt-in MX inference path (mi355.set_mx_eval / MI355_MX_EVAL) applies: bf16 activations, per-tensor 'fp8' mode not active."""
+    return _rt.mx_eval() and compute_dtype() == torch.bfloat16 and not _rt.fp8_convs()
+
+
+def _mx_wants_copy(producer):
+    """Should `producer` (a conv / transposed conv on the folded MX path) also write the MX copy of its output?  Yes when the layer
+    recorded as its consumer (link_conv_bn, link_mx_consumer) will itself take that path: the consumer's _mx_copy then finds the
+    copy on the tensor and launches nothing.  Only a hint: a consumer that ends up elsewhere ignores the copy, a missing link
+    costs the consumer one mx_quantize launch."""
+    nxt = getattr(producer, '_mx_next', None)
+    return (nxt is not None and producer.out_channels % ops.MX_BLOCK == 0 and not nxt.training and nxt.bn_follows and _EVAL_FOLD and
+            nxt._mx_layer_ok())
 
 
 _PACK_BATCHED = __import__('os').environ.get('MI355_PACK_BATCHED', '1') == '1'
@@ -1104,7 +1158,7 @@ class Conv2d(_FastSlots, nn.Module):
         self._packedmx = _PackedMx()
         self._cast = _CastCopy()
         self._cast_t = _CastCopy(transposed=True)
-        self._folded = _FoldedBn()
+        self._folded, self._folded_mx = _FoldedBn(), _FoldedMx()
         self._stem_tmp = None
         self._last_partial = None
         self._in_bn_src = None
@@ -1181,6 +1235,16 @@ class Conv2d(_FastSlots, nn.Module):
         groups 1 and channel counts the 128-channel K tile divides (eligibility as _fp8_ok; no 1x1 side-output route)."""
         return (_rt.mx_convs() and self.training and self.mode == 'mfma' and self.groups == 1 and x.dtype == torch.bfloat16 and
                 self.kernel_size[0] in (3, 4) and not self._s2d_ok(x) and _mx_eligible(self.in_channels, self.out_channels))
+
+    def _mx_layer_ok(self):
+        """what _mx_ok asks of the layer itself (not of the mode or the input)"""
+        return (self.mode == 'mfma' and self.groups == 1 and self.kernel_size[0] in (3, 4) and not self._s2d and
+                _mx_eligible(self.in_channels, self.out_channels))
+
+    def _mx_eval_ok(self, x):
+        """MX operands for the folded inference launch?  The rule of _mx_ok without its mode and training terms, behind the
+        opt-in switch (mi355.set_mx_eval)."""
+        return _mx_eval_on() and x.dtype == torch.bfloat16 and not self._s2d_ok(x) and self._mx_layer_ok()
 
     def _plan_mx(self, x):
         N, C, H, W = x.shape
@@ -1292,6 +1356,17 @@ class Conv2d(_FastSlots, nn.Module):
         x = self._input_feature(x, dtype)
         N, C, H, W = x.shape
         k = self.kernel_size[0]
+        if self._mx_eval_ok(x):          # opt-in: the same launch on MX operands, the MX copy of y for an MX consumer on the side
+            desc8 = ops.make_desc_fp8(N, H, W, C, self.out_channels, k, k, self.stride[0], self.padding[0])
+            wf, sf, bias = self._folded_mx.get(self, bn, False)
+            if residual is not None:
+                residual = _as_feature(residual, dtype)
+            x8, sx = _mx_copy(x)
+            if not _mx_wants_copy(self):
+                return ops.conv_fwd_mx_act(desc8, x8, sx, wf, sf, bias, residual, relu=bool(relu))
+            y, y8, sy = ops.conv_fwd_mx_act(desc8, x8, sx, wf, sf, bias, residual, relu=bool(relu), want_copy=True)
+            y._mi_mx = (y8, sy, y._version)
+            return y
         s2d = self._s2d and C == 16
         if s2d:
             desc = ops.make_desc(N, H, W, 16, self.out_channels, 4, 4, 1, 2, x.dtype, out_hw=(H, W))
@@ -1355,7 +1430,7 @@ class ConvTranspose2d(_FastSlots, nn.Module):
         self.weight = _convform_param(in_channels, out_channels, kernel_size, kernel_size)
         self.bias = None
         self._packed = _PackedWeights()
-        self._folded = _FoldedBn()
+        self._folded, self._folded_mx = _FoldedBn(), _FoldedMx()
         self._packed8, self._q_in, self._q_dy = _PackedFp8(), _Fp8Stream(ops.E4M3), _Fp8Stream(_GRAD_FMT)
         self._packedmx = _PackedMx()
         self._last_partial = None
@@ -1372,6 +1447,13 @@ class ConvTranspose2d(_FastSlots, nn.Module):
         128-channel K tile divides (unlike 'fp8' mode, no opt-in: block scales keep the neck's precision)."""
         return (_rt.mx_convs() and self.training and x.dtype == torch.bfloat16 and self.kernel_size[0] in (3, 4) and
                 _mx_eligible(self.in_channels, self.out_channels))
+
+    def _mx_layer_ok(self):
+        return self.kernel_size[0] in (3, 4) and _mx_eligible(self.in_channels, self.out_channels)
+
+    def _mx_eval_ok(self, x):
+        """the rule of _mx_ok without its mode and training terms, behind the opt-in switch (mi355.set_mx_eval)"""
+        return _mx_eval_on() and x.dtype == torch.bfloat16 and self._mx_layer_ok()
 
     def _plan_mx(self, x):
         N, C, H, W = x.shape          # conv-form output side
@@ -1423,6 +1505,20 @@ class ConvTranspose2d(_FastSlots, nn.Module):
         x = _as_feature(x, dtype)
         if residual is not None:            # (not a shape of the model: plain deconv, then the BatchNorm's own kernel)
             return ops.bn_eval_fwd(self(x, _lazy=False), _as_feature(residual, dtype), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu)
+        if self._mx_eval_ok(x):
+            N, C, H, W = x.shape      # conv-form output side
+            k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+            if C != self.in_channels:
+                raise Mi355Error('deconv expects %d input channels, got %d' % (self.in_channels, C))
+            _chk_convform(self.weight)
+            desc8 = ops.make_desc_fp8(N, (H - 1) * s - 2 * p + k, (W - 1) * s - 2 * p + k, self.out_channels, self.in_channels, k, k, s, p)
+            wt, st, bias = self._folded_mx.get(self, bn, True)
+            x8, sx = _mx_copy(x)
+            if not _mx_wants_copy(self):
+                return ops.conv_dgrad_mx_act(desc8, x8, sx, wt, st, bias, relu=bool(relu))
+            y, y8, sy = ops.conv_dgrad_mx_act(desc8, x8, sx, wt, st, bias, relu=bool(relu), want_copy=True)
+            y._mi_mx = (y8, sy, y._version)
+            return y
         desc, _, _ = self._plan(x)
         wt, bias = self._folded.get(self, bn, dtype, True)
         return ops.deconv_fwd_act(desc, x, wt, bias, relu=bool(relu))
@@ -1526,6 +1622,34 @@ def link_conv_bn(module):
             a.bn_follows = getattr(a, 'mode', 'mfma') == 'mfma'
 
 
+def link_mx_consumer(producer, consumer):
+    """Record `consumer` as the layer that reads `producer`'s (BatchNorm-folded) output, for the MX inference path: a producer on
+    that path whose consumer will take it too writes the MX copy of its output in its own epilogue (_mx_wants_copy).  Either
+    argument may be a FusedSequential: its last conv / transposed conv (followed by BatchNorm [+ ReLU] only) resp. its first
+    child.  Only a hint, like bn_follows; not a child module (no state_dict entry)."""
+    if isinstance(producer, nn.Sequential):
+        kids = list(producer)
+        while kids and isinstance(kids[-1], (BatchNorm2d, ReLU)):
+            kids.pop()
+        producer = kids[-1] if kids else None
+    if isinstance(consumer, nn.Sequential):
+        consumer = consumer[0] if len(consumer) else None
+    if isinstance(producer, (Conv2d, ConvTranspose2d)) and isinstance(consumer, (Conv2d, ConvTranspose2d)):
+        object.__setattr__(producer, '_mx_next', consumer)
+
+
+def _link_mx_runs(seq):
+    """conv -> BatchNorm [-> ReLU] -> conv runs of a FusedSequential (children run in registration order)"""
+    kids = list(seq)
+    for i, a in enumerate(kids):
+        if isinstance(a, (Conv2d, ConvTranspose2d)) and i + 1 < len(kids) and isinstance(kids[i + 1], BatchNorm2d):
+            j = i + 2
+            if j < len(kids) and isinstance(kids[j], ReLU):
+                j += 1
+            if j < len(kids) and isinstance(kids[j], (Conv2d, ConvTranspose2d)):
+                link_mx_consumer(a, kids[j])
+
+
 class FusedSequential(nn.Sequential):
     """nn.Sequential with the same child indices (state_dict keys) that runs [BatchNorm2d, ReLU] pairs as one
     fused kernel."""
@@ -1533,6 +1657,7 @@ class FusedSequential(nn.Sequential):
     def __init__(self, *args):
         super().__init__(*args)
         link_conv_bn(self)
+        _link_mx_runs(self)
 
     def forward(self, x):
         mods = list(self)

@@ -480,6 +480,53 @@ def conv_dgrad_mx(desc, dy8, sdy, wT8, swT, scale_dev=None, out=None, accumulate
     return dx
 
 
+def conv_fwd_mx_act(desc, x8, sx, w8, sw, bias=None, residual=None, relu=False, want_copy=False, out=None, out8=None, out_scales=None):
+    """Inference: y (bf16, channels_last) = act(conv(x8 * 2^sx, w8 * 2^sw) + bias (+ residual)) on MX operands (desc from
+    make_desc_fp8), the BatchNorm behind the conv folded into w8 / bias by the caller.  want_copy: the launch also writes the MX
+    copy of y -- (y8 e4m3 shaped and strided like y, sy [pixels][Co/32]) = what mx_quantize(y) returns -- and the result is
+    (y, y8, sy)."""
+    _chk_dev(x8, sx, w8, sw)
+    nx, nw, ny = desc.N * desc.Hi * desc.Wi * desc.Ci, desc.Co * desc.kh * desc.kw * desc.Ci, desc.N * desc.Ho * desc.Wo * desc.Co
+    want_copy = bool(want_copy) or out8 is not None or out_scales is not None
+    for what, t, need in (('x8', x8, nx), ('sx', sx, nx // MX_BLOCK), ('w8', w8, nw), ('sw', sw, nw // MX_BLOCK),
+                          ('residual', residual, ny), ('bias', bias, desc.Co), ('out', out, ny), ('out8', out8, ny),
+                          ('out_scales', out_scales, ny // MX_BLOCK)):
+        _chk_room('conv_fwd_mx_act ' + what, t, need)
+    y = out if out is not None else nhwc_empty(desc.N, desc.Co, desc.Ho, desc.Wo, torch.bfloat16, x8.device)
+    y8 = sy = None
+    if want_copy:
+        if desc.Co % MX_BLOCK:
+            raise Mi355Error('conv_fwd_mx_act: an MX copy of the output needs a multiple of %d output channels (%d)' % (MX_BLOCK, desc.Co))
+        y8 = out8 if out8 is not None else torch.empty_strided(y.shape, y.stride(), dtype=torch.uint8, device=y.device)
+        sy = out_scales if out_scales is not None else torch.empty(ny // MX_BLOCK, dtype=torch.uint8, device=y.device)
+        _chk_dev(y8, sy)
+    call('mi355_conv_fwd_mx_act', ctypes.byref(desc), ptr(x8), ptr(sx), ptr(w8), ptr(sw), ptr(bias), ptr(residual), int(bool(relu)),
+         ptr(y), ptr(y8), ptr(sy), stream_ptr())
+    return (y, y8, sy) if want_copy else y
+
+
+def conv_dgrad_mx_act(desc, dy8, sdy, wT8, swT, bias=None, relu=False, want_copy=False, out=None, out8=None, out_scales=None):
+    """Inference ConvTranspose2d forward on MX operands: dx (bf16) = act(dgrad(dy8 * 2^sdy, wT8 * 2^swT) + bias); want_copy as in
+    conv_fwd_mx_act: (dx, dx8, sdx) with the MX copy of dx written by the same launch."""
+    _chk_dev(dy8, sdy, wT8, swT)
+    ndy, nw, nx = desc.N * desc.Ho * desc.Wo * desc.Co, desc.Co * desc.kh * desc.kw * desc.Ci, desc.N * desc.Ci * desc.Hi * desc.Wi
+    want_copy = bool(want_copy) or out8 is not None or out_scales is not None
+    for what, t, need in (('dy8', dy8, ndy), ('sdy', sdy, ndy // MX_BLOCK), ('wT8', wT8, nw), ('swT', swT, nw // MX_BLOCK),
+                          ('bias', bias, desc.Ci), ('out', out, nx), ('out8', out8, nx), ('out_scales', out_scales, nx // MX_BLOCK)):
+        _chk_room('conv_dgrad_mx_act ' + what, t, need)
+    dx = out if out is not None else nhwc_empty(desc.N, desc.Ci, desc.Hi, desc.Wi, torch.bfloat16, dy8.device)
+    dx8 = sdx = None
+    if want_copy:
+        if desc.Ci % MX_BLOCK:
+            raise Mi355Error('conv_dgrad_mx_act: an MX copy of the output needs a multiple of %d output channels (%d)' % (MX_BLOCK, desc.Ci))
+        dx8 = out8 if out8 is not None else torch.empty_strided(dx.shape, dx.stride(), dtype=torch.uint8, device=dx.device)
+        sdx = out_scales if out_scales is not None else torch.empty(nx // MX_BLOCK, dtype=torch.uint8, device=dx.device)
+        _chk_dev(dx8, sdx)
+    call('mi355_conv_dgrad_mx_act', ctypes.byref(desc), ptr(dy8), ptr(sdy), ptr(wT8), ptr(swT), ptr(bias), int(bool(relu)),
+         ptr(dx), ptr(dx8), ptr(sdx), stream_ptr())
+    return (dx, dx8, sdx) if want_copy else dx
+
+
 # ---------------------------------------------------------------- batch norm
 def bn_relu_mask(x):
     """uint8 buffer for the ReLU bit mask of a BatchNorm over x: one byte per 16-byte chunk of every row."""

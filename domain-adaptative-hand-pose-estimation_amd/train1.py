@@ -2,7 +2,7 @@
 """Domain-adaptive hand-pose training on the MI355X kernels — same command line, log / checkpoint layout and
 training schedule as the reference's ``train1.py`` (main :37-275, pretrain :278-325, train :328-492,
 validate :495-536, CLI :591-675).  Additive flags: ``--synthetic`` (seeded synthetic data instead of the
-out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--no-graph``, ``--device-augment`` (the training
+out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--mx-eval``, ``--no-graph``, ``--device-augment`` (the training
 augmentation chain, the validation resize and the labels of both on the GPU).
 
     python train1.py data/H3D -t Hand3DStudio --synthetic -a resnet50 -b 64
@@ -369,6 +369,8 @@ def validate(val_loader, model, criterion, args):
     acc = AverageMeterDict(dataset.keypoints_group.keys(), ":3.2f")
     progress = ProgressMeter(len(val_loader), [batch_time, losses, acc['all']], prefix='Test: ')
     model.eval()
+    if getattr(args, 'mx_eval', False):
+        mi355.set_mx_eval(True)              # (eval-mode modules only: training forwards are not affected)
     from mi355.infer import GraphedForward
     forward = GraphedForward(model)          # full batches replay one HIP graph; the ragged last batch runs eagerly
     batches = val_loader
@@ -456,6 +458,8 @@ _OPTIONS = [
     # additive
     (('--synthetic',), dict(action='store_true', help='seeded synthetic batches instead of the CPU dataset layer')),
     (('--dtype',), dict(default='bf16', choices=['bf16', 'f32', 'fp8', 'mxfp8'], help="compute dtype of activations / packed weights ('fp8': bf16 storage, fp8 operands in the K-heavy conv GEMMs; 'mxfp8': the same convs and the neck's transposed convs on block-scaled MX e4m3 operands)")),
+    (('--mx-eval',), dict(action='store_true', help='validation / test forwards: the BatchNorm-folded 3x3 / 4x4 convs and transposed convs '
+                          'on block-scaled MX e4m3 operands (opt-in, any --dtype with bf16 activations; also MI355_MX_EVAL=1)')),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--device-augment',), dict(action='store_true', help='run the training augmentation chain (rotate, resized crop, colour '
                                   'jitter, blur, normalisation), the validation resize + normalisation and the heat-map labels '

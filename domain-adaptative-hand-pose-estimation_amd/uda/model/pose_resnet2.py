@@ -3,7 +3,7 @@
 (state_dict keys ``{0,3,6}.weight`` deconvs, ``{1,4,7}.*`` BatchNorms) and initialisation."""
 import torch.nn as nn
 
-from mi355.nn import Conv2d, ConvTranspose2d, BatchNorm2d, ReLU, FusedSequential
+from mi355.nn import Conv2d, ConvTranspose2d, BatchNorm2d, ReLU, FusedSequential, link_mx_consumer
 
 
 class Upsampling(FusedSequential):
@@ -37,6 +37,7 @@ class PoseResNet(nn.Module):
         self.backbone = backbone
         self.upsampling = upsampling
         self.head = Conv2d(feature_dim, num_keypoints, 1, 1, 0)
+        link_mx_consumer(upsampling, self.head)      # (a 1x1 head never takes the MX path: the neck then writes no MX copy)
         self.finetune = finetune
         nn.init.normal_(self.head.weight, std=0.001)
         nn.init.constant_(self.head.bias, 0)

@@ -8,7 +8,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from mi355.nn import Conv2d, BatchNorm2d, ReLU, FusedSequential, GradFanIn
+from mi355.nn import Conv2d, BatchNorm2d, ReLU, FusedSequential, GradFanIn, link_mx_consumer
 from utils.gl import WarmStartGradientLayer
 from uda.model.regda_4 import _GaussianLabels, PseudoLabelGenerator
 
@@ -93,6 +93,7 @@ class PoseResNetx9(nn.Module):
         self.backbone = backbone
         self.upsampling = upsampling
         self.head = _simple_head(num_head_layers, feature_dim, num_keypoints)
+        link_mx_consumer(upsampling, self.head)      # eval: the neck's last transposed conv feeds the main head's first 3x3 conv
         self.head_adv = _simple_head(num_head_layers, feature_dim, num_keypoints)
         self.head_adv2 = make_head(num_head_layers, feature_dim, num_keypoints)
         self.head_adv3 = make_head2(num_head_layers, feature_dim, num_keypoints)

@@ -188,6 +188,22 @@ int mi355_conv_fwd_mx(const mi355_conv_desc* d, const void* x8, const void* sx, 
 int mi355_conv_dgrad_mx(const mi355_conv_desc* d, const void* dy8, const void* sdy, const void* wT8, const void* swT,
                         const float* scale_dev, int accumulate, void* dx, float* partial, size_t partial_bytes, int* nslices,
                         void* stream);
+/* Inference on MX operands (opt-in, mi355.set_mx_eval / MI355_MX_EVAL): the eval-mode forms of the same reference layers --
+ * Bottleneck conv2 + bn2 + relu (resnet.py:92-107), the transposed convs + BatchNorm + ReLU of the upsampling neck
+ * (pose_resnet2.py:33-41) and the 3x3 conv + BatchNorm + ReLU runs of the heads (regda_7.py:4906-4929) -- with the BatchNorm
+ * folded into the packed weights and the bias by the caller, as for mi355_conv_fwd_act / mi355_conv_dgrad_act:
+ *   y  (bf16) = act(conv(x8 * 2^sx, w8 * 2^sw) + bias [+ residual])      act = max(., 0) when relu, else the identity
+ *   dx (bf16) = act(dgrad(dy8 * 2^sdy, wT8 * 2^swT) + bias)              (the transposed conv's forward, every stride-2 phase)
+ * Operand constraints as mi355_conv_fwd_mx / mi355_conv_dgrad_mx; bias and residual nullable; y / dx required.  No statistics, no
+ * accumulate, no scale_dev.  y8 + sy (dx8 + sdx): nullable, together only, output channel count a multiple of 32, y8 8-byte
+ * aligned -- the MX copy of the bf16 values just stored, by the rule of mi355_mx_quantize: e4m3 laid out like y and one E8M0 byte
+ * per 32 channels of a pixel ([pixels][C/32] in y's pixel order), i.e. what mi355_mx_quantize(y) would write, without the launch.
+ * The dgrad form refuses geometries that leave output pixels without a tap (kernel smaller than the stride).  Every violation
+ * fails with MI355_EINVAL before any launch. */
+int mi355_conv_fwd_mx_act(const mi355_conv_desc* d, const void* x8, const void* sx, const void* w8, const void* sw, const float* bias,
+                          const void* residual, int relu, void* y, void* y8, void* sy, void* stream);
+int mi355_conv_dgrad_mx_act(const mi355_conv_desc* d, const void* dy8, const void* sdy, const void* wT8, const void* swT,
+                            const float* bias, int relu, void* dx, void* dx8, void* sdx, void* stream);
 /* The 3x3 / unit-stride fp8 launches (forward and input gradient) use the variant that stages one operand tile per kernel ROW
  * and reads it shifted for the three taps (a third fewer bytes per MFMA) from `min_tiles` 128x128 output tiles on: 0 never,
  * 1 wherever the shape allows (tests), -1 back to the environment's choice (MI355_FP8_KW3, default 1024).  Returns the previous

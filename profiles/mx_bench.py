@@ -2,6 +2,7 @@
 
     python profiles/mx_bench.py layers      > profiles/mx_layers.txt        # (a) per-layer GEMM times + the MX quantiser
     python profiles/mx_bench.py converge    > profiles/mx_convergence.txt   # (b) convergence table + (c) ms per replayed iteration
+    python profiles/mx_bench.py eval        >> profiles/mx_eval.txt         # (d) the inference launches of the MX-eval switch
 
 (a) Operands from HBM, 20 warm-up + 50 timed launches per layer between two events (ResNet-50 256x256, B=64 shapes).  Kernel-only
     durations: run the same command under `rocprofv3 --kernel-trace --stats -d DIR -o run -- python profiles/mx_bench.py layers`.
@@ -10,6 +11,10 @@
     fp8 + MI355_FP8_DECONV=1 and mxfp8, each mode in a fresh child process (the fp8 switches are read at import).  The bf16 row is
     first checked against `bench.py --dtype bf16 --steps 600 --warmup 5`'s losses_last_step, bit for bit.
 (c) ms per replayed iteration: the mean over the last 200 iterations of each run of (b).
+(d) The eval-mode (BatchNorm-folded, bias + ReLU in the epilogue) launch of the five neck / head layers and of one backbone 3x3
+    conv per stage (ResNet-50 256x256, B=64), timed as (a) times its layers, in three forms: the bf16 folded launch; MX with a
+    stand-alone quantise of the input (mx_quantize + mi355_conv_*_mx_act); MX fed by a fused copy (the launch alone, writing the
+    MX copy of its own output where its consumer is an MX layer -- which is what a layer behind an MX producer costs).
 """
 import json
 import os
@@ -93,6 +98,50 @@ def layers():
     print('fp8_quantize (per-tensor, delayed) same tensor: %.1f us, %.2f TB/s' % (t8, n * 3 / t8 / 1e6))
 
 
+def eval_layers():
+    import torch
+    import mi355
+    from mi355 import ops
+    mi355.load()
+    dev = torch.device('cuda:0')
+    g = torch.Generator(device=dev).manual_seed(0)
+    print('%-46s %10s %12s %12s %10s %10s' % ('layer (B=64, eval: + bias + ReLU)', 'bf16 us', 'mx+quant us', 'mx fused us', 'quant us', 'fused/bf16'))
+    rows = [  # name, N, conv-form H, W, Ci, Co, k, s, p, kind, writes the copy for its consumer
+        ('4x4 s2 transposed 2048->256 @8x8->16x16', 64, 16, 16, 256, 2048, 4, 2, 1, 'deconv', True),
+        ('4x4 s2 transposed 256->256 @16x16->32x32', 64, 32, 32, 256, 256, 4, 2, 1, 'deconv', True),
+        ('4x4 s2 transposed 256->256 @32x32->64x64', 64, 64, 64, 256, 256, 4, 2, 1, 'deconv', True),
+        ('3x3 256->256 @64x64 (head, first)', 64, 64, 64, 256, 256, 3, 1, 1, 'conv', True),
+        ('3x3 256->256 @64x64 (head, last 3x3)', 64, 64, 64, 256, 256, 3, 1, 1, 'conv', False),
+        ('3x3 128->128 @32x32 (layer2 conv2)', 64, 32, 32, 128, 128, 3, 1, 1, 'conv', False),
+        ('3x3 256->256 @16x16 (layer3 conv2)', 64, 16, 16, 256, 256, 3, 1, 1, 'conv', False),
+        ('3x3 512->512 @8x8 (layer4 conv2)', 64, 8, 8, 512, 512, 3, 1, 1, 'conv', False)]
+    for name, N, H, W, Ci, Co, k, s, p, kind, copy in rows:
+        d16 = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, torch.bfloat16)
+        d8 = ops.make_desc_fp8(N, H, W, Ci, Co, k, k, s, p)
+        w = (torch.randn(Co, k * k, Ci, device=dev, generator=g) / (Ci * k * k) ** 0.5).contiguous()
+        wf, wt = ops.pack_weights(w, Co, k * k, Ci, Ci, torch.bfloat16)
+        wfm, sfm, wtm, stm = ops.pack_weights_mx(w, Co, k * k, Ci)
+        if kind == 'conv':
+            x = torch.randn(N, H, W, Ci, device=dev, generator=g).to(torch.bfloat16).permute(0, 3, 1, 2)
+            bias = torch.randn(Co, device=dev, generator=g)
+            y = ops.nhwc_empty(N, Co, d16.Ho, d16.Wo, torch.bfloat16, dev)
+            f16 = lambda: ops.conv_fwd(d16, x, wf, bias, None, relu=True)
+            fmx = lambda: ops.conv_fwd_mx_act(d8, xm, sxm, wfm, sfm, bias, relu=True, out=y, out8=y8, out_scales=sy)
+        else:       # the deconv input is the conv-form's output side
+            x = torch.randn(N, d16.Ho, d16.Wo, Co, device=dev, generator=g).to(torch.bfloat16).permute(0, 3, 1, 2)
+            bias = torch.randn(Ci, device=dev, generator=g)
+            y = ops.nhwc_empty(N, Ci, H, W, torch.bfloat16, dev)
+            f16 = lambda: ops.deconv_fwd_act(d16, x, wt, bias, relu=True)
+            fmx = lambda: ops.conv_dgrad_mx_act(d8, xm, sxm, wtm, stm, bias, relu=True, out=y, out8=y8, out_scales=sy)
+        xm, sxm = ops.mx_quantize(x)
+        y8 = torch.empty_strided(y.shape, y.stride(), dtype=torch.uint8, device=dev) if copy else None
+        sy = torch.empty(y.numel() // 32, dtype=torch.uint8, device=dev) if copy else None
+        tq = _timeit(lambda: ops.mx_quantize(x, xm, sxm))
+        t16, tmx = _timeit(f16), _timeit(fmx)
+        tboth = _timeit(lambda: (ops.mx_quantize(x, xm, sxm), fmx()))
+        print('%-46s %10.1f %12.1f %12.1f %10.1f %10.3f' % (name + (' +copy' if copy else ''), t16, tboth, tmx, tq, tmx / t16))
+
+
 def converge_child(mode, iters_list):
     """one mode, bench.py's construction; prints a JSON line"""
     import torch
@@ -159,6 +208,8 @@ if __name__ == '__main__':
     what = sys.argv[1] if len(sys.argv) > 1 else 'layers'
     if what == 'layers':
         layers()
+    elif what == 'eval':
+        eval_layers()
     elif what == 'converge':
         converge()
     elif what == 'converge-child':
