@@ -31,6 +31,7 @@ static long bwd_slices() { static const long v = getenv("MI355_BN_BWD_SLICES") ?
 extern "C" size_t mi355_bn_workspace(long rows, int C) {
   int ns = 0;
   for (int ch = 4; ch <= 8; ch += 4) {     // fp32 / bf16 chunking, forward / backward plan: the largest
+    if (C < ch || C % ch) continue;        // no such launch (C = 4 is fp32 only: cpr = 0 would divide by zero in bn_plan)
     BnPlan p = bn_plan(rows, C, ch), q = bn_plan(rows, C, ch, bwd_slices());
     if (p.nslices > ns) ns = p.nslices;
     if (q.nslices > ns) ns = q.nslices;

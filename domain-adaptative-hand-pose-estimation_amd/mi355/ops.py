@@ -624,6 +624,12 @@ def bn_resident_reset():
     call('mi355_bn_resident_reset')
 
 
+def bn_set_resident(on):
+    """Switch the one-launch BatchNorm backward on (1), off (0: always reduce + finalize + apply) or back to the environment's
+    choice (-1); returns the previous setting, to be handed back to this function."""
+    return int(load().mi355_bn_set_resident(int(on)))
+
+
 def bn_resident_set_spin_limit(limit):
     """Test hook: poll iterations before a block of the one-launch BatchNorm backward gives up (0 = default)."""
     call('mi355_bn_resident_set_spin_limit', int(limit))

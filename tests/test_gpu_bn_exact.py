@@ -1,0 +1,347 @@
+"""The BatchNorm kernels (csrc/bn.hip) bit for bit on exact integer operands (tests/bn_exact_ref.py).
+
+Every comparison here is one of three kinds, named next to it:
+  [equal]  torch.equal with the float64 reference (rounded to nearest even into the activation type where that is bf16);
+  [bound]  the derived bound B of the roundings that remain (ragged row counts, the forward's apply pass);
+  [stats]  the project's own tightest statistics tolerances (test_conv_fwd_concat_k): rtol 1e-5 / atol 1e-6 on means,
+           rtol 2e-5 / atol 1e-6 on invstd and variances.
+Operands go to the device with plain torch; the float64 references are the functions test_bn_exact_cpu.py holds against
+torch on the CPU, evaluated with torch's float64 on the device so that the 16 M-element cases stay within seconds.  The form
+of the backward that ran (reduce + finalize + apply, or the one-launch LDS-resident kernel) is read from the launch log, so a
+silent fallback cannot make two runs of one path pass as two paths.  Nothing here provokes a give-up of the resident kernel."""
+import pytest
+import torch
+
+import bn_exact_ref as R
+
+pytestmark = pytest.mark.gpu
+
+MEAN_TOL = dict(rtol=1e-5, atol=1e-6)
+VAR_TOL = dict(rtol=2e-5, atol=1e-6)
+
+
+def _ops():
+    import mi355
+    from mi355 import ops
+    mi355.load()
+    return ops
+
+
+@pytest.fixture(scope='module', autouse=True)
+def launch_log(gpu):
+    ops = _ops()
+    assert ops.bn_resident_timeouts() == 0
+    ops.prof_enable(2)          # level 2: every logged family (BatchNorm launches are family 1)
+    yield
+    ops.prof_enable(0)
+    _HOLD.clear()
+    assert ops.bn_resident_timeouts() == 0
+
+
+_HOLD = {}       # the operands and references of the (rows, C) in hand: consecutive cases of one shape share them
+
+
+def _case(gpu, rows, C, mirror=False):
+    key = (rows, C, mirror)
+    if key not in _HOLD:
+        _HOLD.clear()
+        c = R.make_case(rows, C, device=gpu, mirror=mirror)
+        c['dev'], c['ref'] = {}, {}
+        _HOLD[key] = c
+    return _HOLD[key]
+
+
+def _put(mat, dt):
+    return R.nchw(mat).to(R.TDT[dt]).contiguous(memory_format=torch.channels_last)
+
+
+def _dev(c, dt, residual=True):
+    """The case's operands in the activation type (plain torch casts of exact values) and its fp32 per-channel vectors."""
+    key = (dt, residual)
+    if key not in c['dev']:
+        y = R.fwd_y(c, residual, True)
+        d = dict(x=_put(c['x'], dt), dy=_put(c['dy'], dt), res=_put(c['res'], dt), y=_put(y, dt), mask=R.pack_mask(y > 0, R.PER[dt]))
+        for k in ('gamma', 'beta', 'mean', 'invstd'):
+            d[k] = c[k].float()
+        for k in ('x', 'dy', 'res', 'y'):
+            assert torch.equal(R.rows_of(d[k]).double(), c[k] if k != 'y' else y)          # the casts lost nothing
+        c['dev'][key] = d
+    return c['dev'][key]
+
+
+def _ref(c, source, residual=True):
+    key = (source if source != 3 else 1, residual)
+    if key not in c['ref']:
+        mask = None if source == 0 else (c['ypre'] > 0 if source == 2 else R.fwd_y(c, residual, True) > 0)
+        c['ref'][key] = R.bn_bwd(c, mask)
+    return c['ref'][key]
+
+
+def _labels(ops, fn):
+    ops.prof_reset()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, [l['label'] for l in ops.prof_launches()]
+
+
+def _backward(ops, c, dt, form, relu, dres, acc, partial=None, q8=None, residual=True):
+    """One mi355_bn_bwd in the forced form: (dx, dres, dgamma, dbeta, launch labels).  dgamma / dbeta start from integer priors
+    (accumulate) or from a sentinel the kernel must overwrite."""
+    d = _dev(c, dt, residual)
+    C, gpu = c['C'], c['x'].device
+    dg = R.int_prior(C, 'dg', gpu).float() if acc else torch.full((C,), 777.0, device=gpu)
+    db = R.int_prior(C, 'db', gpu).float() if acc else torch.full((C,), -777.0, device=gpu)
+    prev = ops.bn_set_resident(1 if form == 'resident' else 0)
+    try:
+        (dx, dr), labels = _labels(ops, lambda: ops.bn_bwd(d['dy'], d['x'], d['y'] if relu == 1 else None, d['gamma'], d['mean'], d['invstd'],
+                                                          dg, db, acc, relu != 0, dres, beta=d['beta'], partial=partial,
+                                                          relu_mask=d['mask'] if relu == 3 else None, q8=q8))
+    finally:
+        ops.bn_set_resident(prev)
+    return dx, dr, dg, db, labels
+
+
+def _assert_form(labels, form):
+    if form == 'resident':
+        assert labels and all(l.startswith('bn_bwd_res ') for l in labels), labels
+    else:
+        assert [l.split(' ')[0] for l in labels] == ['bn_bwd_reduce', 'bn_bwd_finalize', 'bn_bwd_apply'], labels
+
+
+def _assert_sums(c, r, dr, dg, db, dres, acc, dt):
+    gpu = c['x'].device
+    pg = R.int_prior(c['C'], 'dg', gpu) if acc else 0
+    pb = R.int_prior(c['C'], 'db', gpu) if acc else 0
+    assert torch.equal(dg.double(), r['s2'] + pg), 'dgamma'           # [equal]
+    assert torch.equal(db.double(), r['s1'] + pb), 'dbeta'            # [equal]
+    if dres:
+        assert torch.equal(R.rows_of(dr).double(), r['dres']), 'dres'      # [equal]
+    else:
+        assert dr is None
+
+
+# ---------------------------------------------------------------- a. backward, bit for bit
+@pytest.mark.parametrize('case', R.bwd_cases(R.BWD_SHAPES, R.BWD_MODES), ids=R.case_id)
+def test_backward_bit_for_bit(gpu, case):
+    rows, C, dt, form, relu, dres, acc = case
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    r = _ref(c, relu)
+    dx, dr, dg, db, labels = _backward(ops, c, dt, form, relu, dres, acc)
+    _assert_form(labels, form)
+    _assert_sums(c, r, dr, dg, db, dres, acc, dt)
+    assert torch.equal(R.rows_of(dx).double(), R.rne(r['dx'], dt)), 'dx'       # [equal]
+    assert ops.bn_resident_timeouts() == 0
+
+
+# ---------------------------------------------------------------- b. backward, ragged row counts
+@pytest.mark.parametrize('case', R.bwd_cases(R.RAGGED_SHAPES, R.RAGGED_MODES), ids=R.case_id)
+def test_backward_ragged_rows(gpu, case):
+    rows, C, dt, form, relu, dres, acc = case
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    r = _ref(c, relu)
+    dx, dr, dg, db, labels = _backward(ops, c, dt, form, relu, dres, acc)
+    _assert_form(labels, form)
+    _assert_sums(c, r, dr, dg, db, dres, acc, dt)
+    # [bound] 1.0f / rows is rounded, so dx = k0 * (g - k1 - xhat * k2) is no longer exact.  k0, g and xhat are; the roundings
+    # left are at most six: 1 / rows, s1 * inv, s2 * inv, xhat * k2 (or its FMA), g - k1, ... - xhat * k2.  Each is one unit of
+    # roundoff 2^-24 relative to a value no larger than |g| + |k1| + |xhat * k2|; the factor 8 covers the six.
+    B = R.dx_bound(r)
+    got = R.rows_of(dx).double()
+    if dt == 'f32':
+        assert bool(((got - r['dx']).abs() <= B).all()), float(((got - r['dx']).abs() - B).max())
+    else:
+        assert bool((R.rne(r['dx'] - B, dt) <= got).all()) and bool((got <= R.rne(r['dx'] + B, dt)).all())
+    assert ops.bn_resident_timeouts() == 0
+
+
+# ---------------------------------------------------------------- c. mi355_bn_bwd_partials and the finalize loop edges
+@pytest.mark.parametrize('case', R.BWD_PARTIAL_CASES, ids=R.case_id)
+def test_backward_from_crafted_partials(gpu, case):
+    ns, rows, C, dt, relu, dres, acc = case
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    r = _ref(c, relu)
+    p = R.bwd_partials(r['s1'], r['s2'], ns, relu).float().contiguous()
+    dx, dr, dg, db, labels = _backward(ops, c, dt, 'three', relu, dres, acc, partial=(p, ns))
+    _assert_sums(c, r, dr, dg, db, dres, acc, dt)
+    assert torch.equal(R.rows_of(dx).double(), R.rne(r['dx'], dt)), 'dx'       # [equal]
+
+
+# ---------------------------------------------------------------- d. forward statistics that notice one row
+def _running_start(C, gpu):
+    return R.int_prior(C, 'rm', gpu), R.int_prior(C, 'rv', gpu).abs() + 1
+
+
+@pytest.mark.parametrize('updates', R.STAT_UPDATES)
+@pytest.mark.parametrize('shape', R.STATS_SHAPES, ids=R.case_id)
+def test_forward_statistics(gpu, shape, updates):
+    rows, C, dt = shape
+    ops = _ops()
+    s = R.stats_case(rows, C, device=gpu)
+    rm0, rv0 = _running_start(C, gpu)
+    f = R.train_fwd(s['x'], s['gamma'], s['beta'], rm0=rm0, rv0=rv0, repeats=updates)
+    rm, rv, nbt = rm0.float(), rv0.float(), torch.full((), 5, dtype=torch.int64, device=gpu)
+    y, mean, invstd = ops.bn_train_fwd(_put(s['x'], dt), None, s['gamma'].float(), s['beta'].float(), rm, rv, nbt, R.EPS, R.MOMENTUM, False,
+                                       stat_updates=updates)
+    assert torch.allclose(mean.double(), f['mean'], **MEAN_TOL), float((mean.double() - f['mean']).abs().max())          # [stats]
+    assert torch.allclose(invstd.double(), f['invstd'], **VAR_TOL), float((invstd.double() / f['invstd'] - 1).abs().max())   # [stats]
+    assert int(nbt) == 5 + updates
+    if updates == 0:
+        assert torch.equal(rm, rm0.float()) and torch.equal(rv, rv0.float())          # [equal] the sentinels are untouched
+    else:
+        assert torch.allclose(rm.double(), f['rm'], **MEAN_TOL)       # [stats]
+        assert torch.allclose(rv.double(), f['rv'], **VAR_TOL)        # [stats]
+
+
+# ---------------------------------------------------------------- e. forward apply, eval forward and the mask bits
+@pytest.mark.parametrize('res,relu', R.APPLY_MODES)
+@pytest.mark.parametrize('shape', R.APPLY_SHAPES, ids=R.case_id)
+def test_forward_apply_eval_and_mask_bits(gpu, shape, res, relu):
+    """apply_grid gives bn_apply_kernel rows / (4 TY) blocks per column group (below its cap of 2048), each striding by
+    gridDim.y * TY rows: four trips of the grid-stride loop at (32768, 64) in either type (256 x 32 rows per trip in bf16,
+    512 x 16 in fp32), five at (315, 64) in bf16 (2 x 32 rows per trip)."""
+    rows, C, dt = shape
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    d = _dev(c, dt)
+    rd = d['res'] if res else None
+    rm0, rv0 = _running_start(C, gpu)
+    nbt = torch.zeros((), dtype=torch.int64, device=gpu)
+    mask = ops.bn_relu_mask(d['x'])
+    y, mean_k, invstd_k = ops.bn_train_fwd(d['x'], rd, d['gamma'], d['beta'], rm0.float(), rv0.float(), nbt, R.EPS, R.MOMENTUM, relu, relu_mask=mask)
+    y2, mean2, invstd2 = ops.bn_train_fwd(d['x'], rd, d['gamma'], d['beta'], rm0.float(), rv0.float(), nbt, R.EPS, R.MOMENTUM, relu)
+    assert torch.equal(y, y2) and torch.equal(mean_k, mean2) and torch.equal(invstd_k, invstd2)        # [equal]
+    # the statistics the kernel saved (held to float64 by test_forward_statistics) define the reference of the apply pass
+    # [bound] sc = g * invstd and sh = b - mean * sc are rounded, then x * sc + sh (+ res): at most five roundings touch each
+    # of the terms below; the factor 8 covers them
+    sc = c['gamma'] * invstd_k.double()
+    pre = (c['x'] - mean_k.double()) * sc + c['beta'] + (c['res'] if res else 0)
+    B = 8 * R.U32 * ((c['x'] * sc).abs() + (mean_k.double() * sc).abs() + c['beta'].abs() + (c['res'].abs() if res else 0))
+    lo, hi = (torch.clamp(pre - B, min=0.0), torch.clamp(pre + B, min=0.0)) if relu else (pre - B, pre + B)
+    got = R.rows_of(y).double()
+    if dt == 'f32':
+        assert bool((lo <= got).all()) and bool((got <= hi).all())                           # [bound]
+    else:
+        assert bool((R.rne(lo, dt) <= got).all()) and bool((got <= R.rne(hi, dt)).all())      # [bound]
+    bits = R.unpack_mask(mask, rows, C, R.PER[dt])
+    sure = pre.abs() > B
+    assert float(sure.double().mean()) > 0.8
+    assert torch.equal(bits[sure], (pre > 0)[sure])               # [bound] the bit is y > 0 wherever the bound leaves no doubt
+    # eval forward: running_mean integers, running_var powers of four
+    rmean, rvar = c['mean'], 1.0 / (c['invstd'] * c['invstd'])
+    ye = ops.bn_eval_fwd(d['x'], rd, d['gamma'], d['beta'], rmean.float(), rvar.float(), R.EPS, relu)
+    sce = c['gamma'] / torch.sqrt(rvar + R.EPS)
+    pree = (c['x'] - rmean) * sce + c['beta'] + (c['res'] if res else 0)
+    Be = 8 * R.U32 * ((c['x'] * sce).abs() + (rmean * sce).abs() + c['beta'].abs() + (c['res'].abs() if res else 0))
+    lo, hi = (torch.clamp(pree - Be, min=0.0), torch.clamp(pree + Be, min=0.0)) if relu else (pree - Be, pree + Be)
+    got = R.rows_of(ye).double()
+    if dt == 'f32':
+        assert bool((lo <= got).all()) and bool((got <= hi).all())                           # [bound]
+    else:
+        assert bool((R.rne(lo, dt) <= got).all()) and bool((got <= R.rne(hi, dt)).all())      # [bound]
+
+
+# ---------------------------------------------------------------- f. mi355_bn_train_fwd_partials at its finalize edges
+@pytest.mark.parametrize('case', R.FWD_PARTIAL_CASES, ids=R.case_id)
+def test_forward_from_crafted_partials(gpu, case):
+    """512 slices switch to bn_finalize_wide_kernel; 1024 and 2048 are the loop strides of the two finalize kernels."""
+    ns, C, dt = case
+    ops = _ops()
+    p = R.sliced_stats_partials(ns, C, device=gpu)
+    n, mean, m2 = R.combine_fwd_partials(p)
+    x = _put(R.stats_case(16, C, device=gpu)['x'], dt)              # tiny: only the statistics are under test
+    gamma, beta = torch.ones(C, device=gpu), torch.zeros(C, device=gpu)
+    rm0, rv0 = _running_start(C, gpu)
+    for updates in (1, 3):
+        rm, rv, nbt = rm0.float(), rv0.float(), torch.full((), 7, dtype=torch.int64, device=gpu)
+        y, mean_k, invstd_k = ops.bn_train_fwd(x, None, gamma, beta, rm, rv, nbt, R.EPS, R.MOMENTUM, False, stat_updates=updates,
+                                               partial=(p.float().contiguous(), ns))
+        rmr, rvr = R.running(mean, m2, float(n[0]), rm0, rv0, R.MOMENTUM, updates)
+        assert torch.allclose(mean_k.double(), mean, **MEAN_TOL), float((mean_k.double() - mean).abs().max())        # [stats]
+        assert torch.allclose(invstd_k.double(), 1.0 / torch.sqrt(m2 / n + R.EPS), **VAR_TOL)                          # [stats]
+        assert torch.allclose(rm.double(), rmr, **MEAN_TOL) and torch.allclose(rv.double(), rvr, **VAR_TOL)          # [stats]
+        assert int(nbt) == 7 + updates
+
+
+# ---------------------------------------------------------------- g. mi355_colsum and mi355_apply_relu_mask
+@pytest.mark.parametrize('shape', R.COLSUM_SHAPES, ids=R.case_id)
+def test_colsum_bit_for_bit(gpu, shape):
+    rows, C, dt = shape
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    d = _dev(c, dt)
+    out = torch.full((C,), 777.0, device=gpu)
+    ops.colsum(d['dy'], out, False)
+    assert torch.equal(out.double(), R.colsum(c['dy']))                 # [equal]
+    prior = R.int_prior(C, 'colsum', gpu)
+    out = prior.float()
+    ops.colsum(d['dy'], out, True)
+    assert torch.equal(out.double(), R.colsum(c['dy'], prior))          # [equal]
+
+
+@pytest.mark.parametrize('shape', R.MASK_APPLY_SHAPES, ids=R.case_id)
+def test_apply_relu_mask_bit_for_bit(gpu, shape):
+    """(16400, 512) in bf16 holds 1 049 600 chunks: more than the 4096 blocks x 256 threads of the launch, so the grid-stride
+    loop runs past its first trip."""
+    rows, C, dt = shape
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    per = R.PER[dt]
+    b = R.mask_bytes(rows * C // per, 'apply').to(gpu)
+    g = _put(c['dy'], dt)
+    out = ops.apply_relu_mask(g, b)
+    assert torch.equal(R.rows_of(out).double(), R.apply_relu_mask(c['dy'], b, per))          # [equal]
+
+
+# ---------------------------------------------------------------- h. fp8 side outputs (bf16 only)
+def _q8(d, gpu):
+    N, C, H, W = d['x'].shape
+    q = torch.zeros((N, H, W, C), dtype=torch.uint8, device=gpu).permute(0, 3, 1, 2)
+    st = torch.tensor([1.0, 1.0, 0.0, 0.0], device=gpu)           # {scale, descale, amax bits, pad}: scale 1, y * scale is exact
+    return q, st
+
+
+def _amax_of(st):
+    return float(st[2:3].view(torch.int32).view(torch.float32))
+
+
+@pytest.mark.parametrize('rows,C', R.FP8_SHAPES)
+def test_fp8_side_output_of_the_forward(gpu, rows, C):
+    """The e4m3 copy is the cast of the values AS STORED.  y itself cannot be made exact in e4m3 (invstd = 1 / sqrt(var + eps)
+    is never a power of two), so both sides round the same bf16 values; |y| stays far below 448, nothing saturates."""
+    ops = _ops()
+    c = _case(gpu, rows, C, mirror=True)
+    d = _dev(c, 'bf16', residual=False)
+    rm0, rv0 = _running_start(C, gpu)
+    nbt = torch.zeros((), dtype=torch.int64, device=gpu)
+    for relu in (False, True):
+        q, st = _q8(d, gpu)
+        y, _, _ = ops.bn_train_fwd(d['x'], None, d['gamma'], d['beta'], rm0.float(), rv0.float(), nbt, R.EPS, R.MOMENTUM, relu, q8=(q, st))
+        y0, _, _ = ops.bn_train_fwd(d['x'], None, d['gamma'], d['beta'], rm0.float(), rv0.float(), nbt, R.EPS, R.MOMENTUM, relu)
+        assert torch.equal(y, y0)                                      # [equal]
+        assert float(y.float().abs().max()) < 448
+        assert torch.equal(q.view(torch.uint8), y.float().to(torch.float8_e4m3fn).view(torch.uint8))      # [equal]
+        assert _amax_of(st) == float(y.float().abs().max())           # [equal]
+
+
+@pytest.mark.parametrize('relu,dres', [(0, False), (1, True), (2, False), (3, True)])
+@pytest.mark.parametrize('rows,C', R.FP8_SHAPES)
+def test_fp8_side_output_of_the_backward(gpu, rows, C, relu, dres):
+    """Mirrored rows (the second half repeats the first with dy negated): both sums vanish, dx = k0 * g is 1, 2 or 3 times a
+    power of two, exact in e5m2.  The side output is written by the three-launch form only: asked for with the one-launch form
+    switched ON, the launch log must still show reduce + finalize + apply."""
+    ops = _ops()
+    c = _case(gpu, rows, C, mirror=True)
+    d = _dev(c, 'bf16', residual=False)
+    r = _ref(c, relu, residual=False)
+    q, st = _q8(d, gpu)
+    dx, dr, dg, db, labels = _backward(ops, c, 'bf16', 'resident', relu, dres, False, q8=(q, st), residual=False)
+    _assert_form(labels, 'three')
+    _assert_sums(c, r, dr, dg, db, dres, False, 'bf16')
+    assert float(r['s1'].abs().max()) == 0 and float(r['s2'].abs().max()) == 0
+    assert torch.equal(R.rows_of(dx).double(), r['dx'])               # [equal] (exact in bf16 without rounding)
+    assert torch.equal(q.view(torch.uint8), dx.float().to(torch.float8_e5m2).view(torch.uint8))          # [equal]
+    assert _amax_of(st) == float(dx.float().abs().max()) and _amax_of(st) > 0          # [equal]
+    assert ops.bn_resident_timeouts() == 0
