@@ -59,3 +59,69 @@ extern "C" int mi355_cast_f32(const float* in, void* out, long n, int dtype, voi
   MI_CHECK_LAUNCH("cast");
   return MI355_OK;
 }
+
+// EMA ("mean teacher") update of uda/model/loss.py:252-261 (update_ema_variables5; train1.py:461):
+//   v_ema = v_ema * m + (1. - m) * v_main        -- three fp32 roundings: a = fl(e*k), b = fl(p*c), e' = fl(a + b)
+// k = float32(m) and c = float32(1.0 - m) are read from coef_dev[0..1] (a replayed graph sees the warm-up schedule).  An FMA
+// form differs from torch in about a quarter of the elements, so the multiplies and the add never contract, whatever the
+// build's flags say.
+__device__ __forceinline__ float ema1(float e, float p, float k, float c) {
+#pragma clang fp contract(off)
+  const float a = e * k;
+  const float b = p * c;
+  return a + b;
+}
+
+// Flat range (the mirror of one FusedSGD group): pure stream, float4 per lane, grid-stride, scalar tail.  p is only read.
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ e, const float* __restrict__ p, long n,
+                                                   const float* __restrict__ coef_dev) {
+  const float k = coef_dev[0], c = coef_dev[1];
+  const long n4 = n >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const float4 ev = reinterpret_cast<float4*>(e)[i];
+    const float4 pv = reinterpret_cast<const float4*>(p)[i];
+    reinterpret_cast<float4*>(e)[i] = make_float4(ema1(ev.x, pv.x, k, c), ema1(ev.y, pv.y, k, c), ema1(ev.z, pv.z, k, c),
+                                                  ema1(ev.w, pv.w, k, c));
+  }
+  for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) e[i] = ema1(e[i], p[i], k, c);
+}
+
+extern "C" int mi355_ema_update(float* e, const float* p, long n, const float* coef_dev, void* stream) {
+  if (!e || !p || !coef_dev || n < 1) MI_FAIL(MI355_EINVAL, "ema_update: bad args");
+  if (((uintptr_t)e | (uintptr_t)p) & 15) MI_FAIL(MI355_EINVAL, "ema_update: pointers must be 16-byte aligned");
+  int grid = (int)((n / 4 + 255) / 256); if (grid < 1) grid = 1; if (grid > 4096) grid = 4096;
+  hipLaunchKernelGGL(ema_kernel, dim3(grid), dim3(256), 0, as_stream(stream), e, p, n, coef_dev);
+  MI_CHECK_LAUNCH("ema_update");
+  return MI355_OK;
+}
+
+// Everything that is not in flat storage (BatchNorm running statistics, parameters FusedSGD never laid out, the
+// num_batches_tracked counters) in ONE launch: records live in device memory, block b finds its record by binary search over
+// the records' first-block prefix (as mi355_pack_weights_batched) and handles MI355_EMA_CHUNK of its elements.
+__global__ __launch_bounds__(256) void ema_batched_kernel(const mi355_ema_item* __restrict__ items, int nitems,
+                                                           const float* __restrict__ coef_dev) {
+  int lo = 0, hi = nitems - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (items[mid].blk0 <= b) lo = mid; else hi = mid - 1; }
+  const mi355_ema_item it = items[lo];
+  const long i0 = (long)(b - it.blk0) * MI355_EMA_CHUNK;
+  const long i1 = i0 + MI355_EMA_CHUNK < it.n ? i0 + MI355_EMA_CHUNK : it.n;
+  if (it.kind == MI355_EMA_COPY64) {
+    const long long* __restrict__ s = reinterpret_cast<const long long*>(it.src);
+    long long* __restrict__ d = reinterpret_cast<long long*>(it.dst);
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) d[i] = s[i];
+  } else {
+    const float k = coef_dev[0], c = coef_dev[1];
+    const float* __restrict__ s = reinterpret_cast<const float*>(it.src);
+    float* __restrict__ d = reinterpret_cast<float*>(it.dst);
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) d[i] = ema1(d[i], s[i], k, c);
+  }
+}
+
+extern "C" int mi355_ema_update_batched(const mi355_ema_item* items_dev, int count, int total_blocks, const float* coef_dev,
+                                        void* stream) {
+  if (!items_dev || !coef_dev || count < 1 || total_blocks < 1) MI_FAIL(MI355_EINVAL, "ema_update_batched: bad args");
+  hipLaunchKernelGGL(ema_batched_kernel, dim3(total_blocks), dim3(256), 0, as_stream(stream), items_dev, count, coef_dev);
+  MI_CHECK_LAUNCH("ema_update_batched");
+  return MI355_OK;
+}

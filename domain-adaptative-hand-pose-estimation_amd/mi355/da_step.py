@@ -126,8 +126,9 @@ class DAStep:
     """Holds the static batch buffers and runs A/B/C.  ``optimizers`` = dict with keys f, h, h_adv, h_adv2,
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
-    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True):
+    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
+        self.ema = ema               # optional mi355.optim.EMATeacher: updated behind step C's optimizer (train1.py:461)
         self.trade_off, self.skip, self.track_acc = trade_off, skip_discarded, track_accuracy
         self.graphs = None
         self.out = {}
@@ -275,6 +276,8 @@ class DAStep:
 
     def _update_C(self):
         self.opt['f'].step()
+        if self.ema is not None:
+            self.ema.update()
 
     def _accuracy(self, b):
         """Device side of the four accuracy() calls of train1.py:464-475: arg-max coordinates + PCK distances."""
@@ -327,6 +330,8 @@ class DAStep:
         self._begin_reduce(('f',))
         self._fwdbwd_C(batch)
         self._end_reduce(('f',))
+        if self.ema is not None:
+            self.ema.sync()
         self._update_C()
         self._accuracy(batch)
         self.model.step()
@@ -336,7 +341,8 @@ class DAStep:
     def capture(self, batch, warmup=3):
         """Capture the iteration as six HIP graphs (fwd+bwd and update of A, B, C) over static copies of
         `batch`; the gradient all-reduces run eagerly between them.  Everything that changes per iteration
-        (inputs, learning rates, GL lambda) is read from device memory."""
+        (inputs, learning rates, GL lambda, the EMA coefficients) is read from device memory.  With an EMA teacher attached its
+        update is captured into the last update graph, behind optimizer_f's step, where the eager iteration has it."""
         self.model.train()
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
         side = torch.cuda.Stream()
@@ -412,6 +418,8 @@ class DAStep:
         gl = getattr(self.model, 'gl_layer', None)
         if gl is not None:
             gl.sync()
+        if self.ema is not None:
+            self.ema.sync()
 
     def replay(self, batch=None):
         if batch is not None and batch is not self.static:
@@ -433,6 +441,8 @@ class DAStep:
             g[4].replay()
             _allreduce_mean(self._grads(('f',)))
             g[5].replay()
+        if self.ema is not None:
+            self.ema.mark_updated()          # the launches sit in the last graph (_update_C)
         self.model.step()
         return self.out
 

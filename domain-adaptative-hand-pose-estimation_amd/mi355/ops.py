@@ -836,6 +836,44 @@ def cast_f32(src, dst):
     call('mi355_cast_f32', ptr(src), ptr(dst), src.numel(), dtype_code(dst.dtype), stream_ptr())
 
 
+EMA_CHUNK, EMA_F32, EMA_COPY64 = 2048, 0, 1        # MI355_EMA_CHUNK and the record kinds of mi355_ema_item
+EMA_ITEM_BYTES = 32
+
+
+def ema_update(e, p, coef_dev):
+    """e = e * k + c * p over the flat fp32 range e (k, c = coef_dev[0], coef_dev[1]); p is only read."""
+    _chk_dev(e, p, coef_dev)
+    _chk_room('ema_update p', p, e.numel())
+    _chk_room('ema_update coef_dev', coef_dev, 2)
+    call('mi355_ema_update', ptr(e), ptr(p), e.numel(), ptr(coef_dev), stream_ptr())
+
+
+def ema_table(records, device):
+    """records: (src tensor, dst tensor, kind) -> (uint8 device tensor of mi355_ema_item records, their number, total blocks).
+    Each pair must share one dense memory layout: the kernel walks the two storages element by element."""
+    import numpy as np
+    rec = np.zeros(len(records), dtype=[('src', '<u8'), ('dst', '<u8'), ('n', '<i8'), ('kind', '<i4'), ('blk0', '<i4')])
+    blk = 0
+    for i, (src, dst, kind) in enumerate(records):
+        _chk_dev(src, dst)
+        want = torch.int64 if kind == EMA_COPY64 else torch.float32
+        n = dst.numel()
+        if src.dtype != want or dst.dtype != want or src.shape != dst.shape or src.stride() != dst.stride() or n < 1 or \
+                1 + sum((s - 1) * st for s, st in zip(dst.shape, dst.stride())) != n:
+            raise Mi355Error('ema_table: record %d needs two dense %s tensors of one layout' % (i, want))
+        rec[i] = (src.data_ptr(), dst.data_ptr(), n, kind, blk)
+        blk += (n + EMA_CHUNK - 1) // EMA_CHUNK
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(device), len(records), blk
+
+
+def ema_update_batched(table, count, total_blocks, coef_dev):
+    """table: uint8 device tensor holding `count` mi355_ema_item records (ema_table)."""
+    _chk_dev(table, coef_dev)
+    _chk_room('ema_update_batched table', table, count * EMA_ITEM_BYTES)
+    _chk_room('ema_update_batched coef_dev', coef_dev, 2)
+    call('mi355_ema_update_batched', ptr(table), int(count), int(total_blocks), ptr(coef_dev), stream_ptr())
+
+
 # ---------------------------------------------------------------- kernel timer (bench.py roofline)
 def spin_us(us):
     call('mi355_spin_us', int(us), stream_ptr())

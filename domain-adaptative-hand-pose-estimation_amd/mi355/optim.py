@@ -224,3 +224,122 @@ class FusedSGD(Optimizer):
                 st['momentum_buffer'] = mv
                 off += (n + 3) // 4 * 4
         self.sync_lr(force=True)
+
+
+class EMATeacher:
+    """The reference's "mean teacher" (uda/model/loss.py:252-261, the call at train1.py:461): after every training iteration
+
+        v_ema = v_ema * m + (1. - m) * v_main     for every floating-point tensor of the two ``state_dict()``s
+        v_ema = v_main                            for ``num_batches_tracked``
+
+    in at most one launch per flat FusedSGD group plus one batched launch for everything else.  Once the optimizers are
+    flat the teacher's parameters move onto flat fp32 buffers that mirror each group's parameter buffer (same offsets, same
+    16-byte slots; parameter objects keep their identity), so ``mi355_ema_update`` streams group against mirror.  BatchNorm
+    running statistics, parameters no optimizer laid out (the unused ``backbone.fc``) and the ``num_batches_tracked`` counters
+    go through one ``mi355_ema_update_batched`` launch.  The coefficients are read from a two-float device buffer
+    (``sync()``, outside capture), so ``update()`` can be captured into a HIP graph; ``mark_updated()`` is the host half of an
+    update (step count, cache invalidation) for the caller that replays such a graph.
+
+    ``warmup=True`` is ``update_ema_variables2``: m = min(1 - 1/(step + 1), decay), step counted from 0."""
+
+    def __init__(self, model, model_ema, optimizers, decay, warmup=False):
+        self.model, self.model_ema = model, model_ema
+        self.optimizers = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)
+        self.decay, self.warmup, self.step = float(decay), bool(warmup), 0
+        objs = lambda m: dict(list(m.named_parameters(remove_duplicate=False)) + list(m.named_buffers(remove_duplicate=False)))
+        main, ema = objs(model), objs(model_ema)
+        self.pairs = []                      # (key, main tensor object, teacher tensor object, is num_batches_tracked)
+        for (k_main, v_main), (k_ema, v_ema) in zip(model.state_dict().items(), model_ema.state_dict().items()):
+            assert k_main == k_ema, "state_dict names are different!"
+            assert v_main.shape == v_ema.shape, "state_dict shapes are different!"
+            counter = 'num_batches_tracked' in k_ema
+            if not counter and v_ema.dtype != torch.float32:
+                raise TypeError('EMATeacher: %s is %s, only fp32 tensors and num_batches_tracked are handled' % (k_ema, v_ema.dtype))
+            self.pairs.append((k_ema, main[k_main], ema[k_ema], counter))
+        assert len(self.pairs) == len(model.state_dict()) == len(model_ema.state_dict()), "state_dict lengths are different!"
+        self._ema_of = {id(a): b for _, a, b, _ in self.pairs}
+        self._params_ema = [b for _, _, b, _ in self.pairs if isinstance(b, torch.nn.Parameter)]
+        dev = self.pairs[0][2].device
+        self.coef = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._coef_m = None
+        self._layout_sig, self._flat, self._owned, self._table, self._table_sig = None, [], set(), None, None
+
+    # ------------------------------------------------------------ coefficients
+    def momentum(self):
+        return min(1 - 1 / (self.step + 1), self.decay) if self.warmup else self.decay
+
+    def sync(self):
+        """Write (float32(m), float32(1.0 - m)) of the coming update to the device pair (call outside graph capture)."""
+        m = self.momentum()
+        if m != self._coef_m:
+            self.coef[0].fill_(m)
+            self.coef[1].fill_(1.0 - m)
+            self._coef_m = m
+
+    # ------------------------------------------------------------ storage
+    def _groups(self):
+        return [f for o in self.optimizers if getattr(o, '_flat', None) is not None for f in o._flat if f is not None]
+
+    def _ensure_layout(self):
+        """Mirror the optimizers' flat parameter buffers (again after FusedSGD laid its own out again) and rebuild the
+        record table of everything else when any of those tensors moved."""
+        groups = self._groups()
+        sig = tuple((f['P'].data_ptr(), f['P'].numel()) for f in groups)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if sig != self._layout_sig:
+            if capturing:
+                raise RuntimeError('EMATeacher: the optimizers changed their flat layout during graph capture; run one eager '
+                                   'iteration with the teacher attached before capturing')
+            flat, owned = [], set()
+            with torch.no_grad():
+                for f in groups:
+                    E = torch.zeros_like(f['P'])
+                    for p in f['params']:
+                        pe = self._ema_of.get(id(p))
+                        if pe is None:
+                            raise RuntimeError('EMATeacher: an optimizer parameter is not part of model.state_dict()')
+                        o, n = f['offs'][id(p)][0], p.numel()
+                        ev = E[o:o + n].as_strided(p.shape, p.stride())
+                        ev.copy_(pe.data)
+                        pe.data = ev
+                        pe._mi_epoch = getattr(pe, '_mi_epoch', 0) + 1        # packed copies must be rebuilt (storage moved)
+                        owned.add(id(pe))
+                    flat.append((E, f['P']))
+            self._flat, self._owned, self._layout_sig, self._table_sig = flat, owned, sig, None
+        rest = [(a, b, c) for _, a, b, c in self.pairs if id(b) not in self._owned]
+        tsig = tuple((a.data_ptr(), b.data_ptr()) for a, b, _ in rest)
+        if tsig != self._table_sig:
+            if capturing:
+                raise RuntimeError('EMATeacher: a tensor outside flat storage moved during graph capture')
+            self._table = ops.ema_table([(a.detach(), b.detach(), ops.EMA_COPY64 if c else ops.EMA_F32) for a, b, c in rest],
+                                        self.coef.device) if rest else None
+            self._table_sig = tsig
+
+    # ------------------------------------------------------------ the update
+    @torch.no_grad()
+    def update(self):
+        """Enqueue the update on the current stream (safe during graph capture once one eager update has run).  Outside
+        capture this also does the host half, mark_updated()."""
+        self._ensure_layout()
+        for E, P in self._flat:
+            ops.ema_update(E, P, self.coef)
+        if self._table is not None:
+            ops.ema_update_batched(*self._table, self.coef)
+        if not torch.cuda.is_current_stream_capturing():
+            self.mark_updated()
+
+    def mark_updated(self):
+        """Host half of one update: count it, and make the teacher's packed weights, folded BatchNorms and captured eval graphs
+        stale -- the kernels wrote behind autograd's back (as FusedSGD.step and the training BatchNorm forward do)."""
+        from . import nn as _nn
+        self.step += 1
+        for p in self._params_ema:
+            p._mi_epoch = getattr(p, '_mi_epoch', 0) + 1
+        _nn._BN_GEN[0] += 1
+
+    # ------------------------------------------------------------ state
+    def state_dict(self):
+        return {'step': self.step, 'decay': self.decay, 'warmup': self.warmup}
+
+    def load_state_dict(self, state):
+        self.step = int(state['step'])

@@ -2,7 +2,7 @@
 """Evaluation entry point, mirror of the reference's ``test.py`` (= its train1.py with ``--checkpoint`` instead of
 ``--resume`` and one ``validate()`` on the source and target test splits, test.py:157,192-226,584).
 
-    python test.py data/H3D -t Hand3DStudio --checkpoint models/H3D_best_754.pth [--synthetic]
+    python test.py data/H3D -t Hand3DStudio --checkpoint models/H3D_best_754.pth [--synthetic] [--ema_model .../model_ema.pth]
 """
 import os
 import sys
@@ -49,6 +49,11 @@ def main(args):
     print("Source: {:4.3f} Target: {:4.3f}".format(s_acc['all'], t_acc['all']))
     for name, acc in t_acc.items():
         print("{}: {:4.3f}".format(name, acc))
+    if args.ema_model:
+        # the EMA teacher of a --ema-update run (its model_ema.pth): same network, the file's `model_ema` weights
+        model.load_state_dict(torch.load(args.ema_model, map_location='cpu', weights_only=False)['model_ema'])
+        e_acc = T.validate(val_target_loader, model, criterion, args)
+        print("ema: {:4.3f}".format(e_acc['all']))
     logger.close()
 
 

@@ -3,7 +3,8 @@
 training schedule as the reference's ``train1.py`` (main :37-275, pretrain :278-325, train :328-492,
 validate :495-536, CLI :591-675).  Additive flags: ``--synthetic`` (seeded synthetic data instead of the
 out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--mx-eval``, ``--no-graph``, ``--device-augment`` (the training
-augmentation chain, the validation resize and the labels of both on the GPU).
+augmentation chain, the validation resize and the labels of both on the GPU), ``--ema-update {off,const,warmup}`` (keep the
+EMA teacher ``model_ema`` up to date: the reference's commented-out call at train1.py:461).
 
     python train1.py data/H3D -t Hand3DStudio --synthetic -a resnet50 -b 64
 
@@ -41,10 +42,10 @@ import mi355
 import uda.model as models
 from mi355 import ops as _ops
 from mi355.da_step import build_training, broadcast_module, _allreduce_mean
-from mi355.optim import FusedSGD
+from mi355.optim import EMATeacher, FusedSGD
 from uda.model.loss import JointsKLLoss
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
-from uda.model.regda_7 import PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
+from uda.model.regda_7 import MainOutput, PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
 from utils.data import ForeverDataIterator, DevicePrefetcher, DeviceAugmentIterator, ragged_collate
 from utils.keypoint_detection import accuracy, accuracy_from_preds, get_max_preds_device
 from utils.logger import CompleteLogger
@@ -163,7 +164,7 @@ def main(args):
         # host -> HBM copies of the next batch overlap the current step (pinned, double-buffered, side stream)
         train_source_iter, train_target_iter = DevicePrefetcher(train_source_iter, device), DevicePrefetcher(train_target_iter, device)
 
-    # model (+ the frozen EMA copy the reference builds and checkpoints, train1.py:102-128)
+    # model (+ the EMA copy the reference builds and checkpoints, train1.py:102-128; frozen unless --ema-update is on)
     backbone = models.__dict__[args.arch](pretrained=True)
     upsampling = Upsampling(backbone.out_features)
     num_keypoints = train_s.num_keypoints
@@ -185,6 +186,10 @@ def main(args):
         for c in step.crit.values():
             if hasattr(c, 'guard_empty_maps'):
                 c.guard_empty_maps = True
+    ema = None
+    if args.ema_update != 'off':
+        # the teacher follows the model after every iteration (uda/model/loss.py:252-261 at train1.py:461), on the device
+        ema = step.ema = EMATeacher(model, model_ema, opts, args.ema_decay, warmup=args.ema_update == 'warmup')
     start_epoch = 0
     if args.resume is None:
         if args.pretrain is None or (args.synthetic and not os.path.exists(args.pretrain)):
@@ -221,6 +226,14 @@ def main(args):
                 opts[k].load_state_dict(ck['optimizer_' + k]); scheds[k].load_state_dict(ck['lr_scheduler_' + k])
         model.gl_layer.iter_num = ck.get('gl_iter_num', 0)
         start_epoch = ck['epoch'] + 1
+        if ema is not None:
+            # the teacher: --ema_model, else the model_ema.pth written next to the resumed checkpoint, else the model (above)
+            beside = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'model_ema.pth')
+            ema_path = args.ema_model or (beside if os.path.exists(beside) else None)
+            if ema_path is not None:
+                model_ema.load_state_dict(torch.load(ema_path, map_location='cpu', weights_only=False)['model_ema'])
+            if 'ema_state' in ck:
+                ema.load_state_dict(ck['ema_state'])
     broadcast_module(model)                              # replicas start bit-identical whatever each rank loaded
     broadcast_module(model_ema)
 
@@ -241,6 +254,7 @@ def main(args):
         train(train_source_iter, train_target_iter, step, scheds, epoch, args)
         s_acc = validate(val_source_loader, model, criterion, args)
         t_acc = validate(val_target_loader, model, criterion, args)
+        e_acc = validate(val_target_loader, MainOutput(model_ema), criterion, args) if ema is not None else None   # (validate2, :243)
         # a one-launch BatchNorm backward whose blocks could not all get onto the chip has written NaN gradients: raise
         # instead of training on (the poll synchronises, validation just has)
         step.check_health('epoch %d' % epoch)
@@ -251,7 +265,8 @@ def main(args):
                 dist.barrier()
             best_acc = max(best_acc, t_acc['all'])
             continue
-        torch.save({'model': model.state_dict(),
+        ck_extra = {'ema_state': ema.state_dict()} if ema is not None else {}
+        torch.save({'model': model.state_dict(), **ck_extra,
                     'optimizer_f': opts['f'].state_dict(), 'optimizer_h': opts['h'].state_dict(),
                     'optimizer_h_adv': opts['h_adv'].state_dict(),
                     'lr_scheduler_f': scheds['f'].state_dict(), 'lr_scheduler_h': scheds['h'].state_dict(),
@@ -267,6 +282,8 @@ def main(args):
         if WORLD > 1:
             dist.barrier()                               # checkpoints of this epoch are complete
         print("Source: {:4.3f} Target: {:4.3f} Target(best): {:4.3f}".format(s_acc['all'], t_acc['all'], best_acc))
+        if e_acc is not None:
+            print("ema: {:4.3f}".format(e_acc['all']))
         for name, acc in t_acc.items():
             print("{}: {:4.3f}".format(name, acc))
     logger.close()
@@ -431,7 +448,8 @@ _OPTIONS = [
     (('--heatmap-size',), dict(type=int, default=64, help='heat-map side of the main head')),
     (('-a2', '--arch2'), dict(metavar='ARCH', default='net_hg', help='unused (reference CLI parity)')),
     (('--pretrain',), dict(type=str, default='models/pretrain_rhd.pth', help='source-only pre-training checkpoint')),
-    (('--ema_model',), dict(type=str, default=None, help='unused (reference CLI parity)')),
+    (('--ema_model',), dict(type=str, default=None, help='checkpoint whose `model_ema` key holds the EMA teacher: read on '
+                          '--resume when --ema-update is on (train1.py), evaluated in addition to --checkpoint (test.py)')),
     (('--resume',), dict(type=str, default=None, help='checkpoint to continue from')),
     (('--resume2',), dict(type=str, default=None, help='unused (reference CLI parity)')),
     (('--num-head-layers',), dict(type=int, default=2)),
@@ -454,12 +472,15 @@ _OPTIONS = [
     (('--log',), dict(type=str, default='logs/mt', help='run directory (logs, checkpoints, images)')),
     (('--phase',), dict(type=str, default='train', choices=['train', 'test'])),
     (('--debug',), dict(action='store_true', help='accepted for CLI parity (visualisation is out of scope)')),
-    (('--ema-decay',), dict(default=0.999, type=float, metavar='ALPHA', help='unused (reference CLI parity)')),
+    (('--ema-decay',), dict(default=0.999, type=float, metavar='ALPHA', help='decay m of the EMA teacher (--ema-update): v_ema = v_ema * m + (1 - m) * v')),
     # additive
     (('--synthetic',), dict(action='store_true', help='seeded synthetic batches instead of the CPU dataset layer')),
     (('--dtype',), dict(default='bf16', choices=['bf16', 'f32', 'fp8', 'mxfp8'], help="compute dtype of activations / packed weights ('fp8': bf16 storage, fp8 operands in the K-heavy conv GEMMs; 'mxfp8': the same convs and the neck's transposed convs on block-scaled MX e4m3 operands)")),
     (('--mx-eval',), dict(action='store_true', help='validation / test forwards: the BatchNorm-folded 3x3 / 4x4 convs and transposed convs '
                           'on block-scaled MX e4m3 operands (opt-in, any --dtype with bf16 activations; also MI355_MX_EVAL=1)')),
+    (('--ema-update',), dict(default='off', choices=['off', 'const', 'warmup'], help="update the EMA teacher after every iteration on the "
+                            "GPU, validate it on the target set ('ema:' line) and checkpoint it (model_ema.pth, ema_state): 'const' uses "
+                            "--ema-decay, 'warmup' min(1 - 1/(step + 1), --ema-decay); 'off': the teacher stays at its initial weights")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--device-augment',), dict(action='store_true', help='run the training augmentation chain (rotate, resized crop, colour '
                                   'jitter, blur, normalisation), the validation resize + normalisation and the heat-map labels '

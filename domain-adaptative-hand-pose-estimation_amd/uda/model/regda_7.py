@@ -146,6 +146,18 @@ class PoseResNetx10(PoseResNetx9):
     _always_tuple = True
 
 
+class MainOutput(nn.Module):
+    """``model(x)[0]`` of a PoseResNetx10 as a module of its own: what the reference's validate2 scores (train1.py:539-580,
+    ``y, y_adv, y_adv2, y_adv3, f = model(x)``).  The adversarial heads, whose outputs validate2 drops, are not run."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+
+    def forward(self, x):
+        return self.model.head(self.model.features(x))
+
+
 class PseudoLabelGenerator01(_GaussianLabels):
     """16x16 labels: centre = trunc(arg-max / 4), 7x7 Gaussian patch (tmp_size = 1.5*sigma)."""
 

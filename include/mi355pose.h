@@ -429,6 +429,20 @@ int mi355_pck_dists(const float* pred_xy, const float* tgt_xy, float* dists, int
 int mi355_sgd_nesterov(float* p, const float* g, float* buf, long n, const float* lr_dev, float momentum,
                        float wd, int nesterov, void* p_lowp, void* stream);
 int mi355_cast_f32(const float* in, void* out, long n, int dtype, void* stream);
+/* EMA ("mean teacher") update of uda/model/loss.py:252-261 (update_ema_variables5, the call at train1.py:461) over a flat
+ * fp32 range:   e = fl(fl(e * k) + fl(p * c)),   k = coef_dev[0] = float32(m), c = coef_dev[1] = float32(1.0 - m)
+ * -- torch's `v_ema * m + (1. - m) * v_main` bit for bit: two multiplies and one add, never contracted.  p is only read.
+ * e and p 16-byte aligned (the mirror of a FusedSGD group and the group's parameter buffer). */
+int mi355_ema_update(float* e, const float* p, long n, const float* coef_dev, void* stream);
+/* The same for many tensors in one launch (BatchNorm running statistics, parameters outside flat storage, the
+ * num_batches_tracked counters).  items: DEVICE array; kind MI355_EMA_F32: dst = EMA of n floats, MI355_EMA_COPY64: dst = src for
+ * n 64-bit words (`v_ema.copy_(v_main)`); pointers need their element's natural alignment only.  blk0 = first block of the
+ * item = sum over earlier items of ceil(n / MI355_EMA_CHUNK); total_blocks = that sum over all. */
+#define MI355_EMA_CHUNK 2048
+#define MI355_EMA_F32 0
+#define MI355_EMA_COPY64 1
+typedef struct mi355_ema_item { const void* src; void* dst; long n; int kind; int blk0; } mi355_ema_item;
+int mi355_ema_update_batched(const mi355_ema_item* items_dev, int count, int total_blocks, const float* coef_dev, void* stream);
 
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
