@@ -121,6 +121,8 @@ SIGNATURES = {
     'mi355_cast_f32': (_I, [_P, _P, _L, _I, _P]),
     'mi355_ema_update': (_I, [_P, _P, _L, _P, _P]),
     'mi355_ema_update_batched': (_I, [_P, _I, _I, _P, _P]),
+    'mi355_bn_fold_batched': (_I, [_P, _P, _I, _I, _P]),
+    'mi355_mse_heatmap': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'mi355_augment_workspace': (_Z, [_I, _I]),
     'mi355_augment': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'mi355_resize_normalize': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P]),

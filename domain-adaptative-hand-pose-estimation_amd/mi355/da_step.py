@@ -126,9 +126,14 @@ class DAStep:
     """Holds the static batch buffers and runs A/B/C.  ``optimizers`` = dict with keys f, h, h_adv, h_adv2,
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
-    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None):
+    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         self.ema = ema               # optional mi355.optim.EMATeacher: updated behind step C's optimizer (train1.py:461)
+        # optional mi355.teacher.MeanTeacher: step C's loss gains m * mt_loss(y_t, model_ema(x_t_ema)) (train1.py:351-364,
+        # uda/model/loss.py:265-297); the teacher's folded operands are refreshed behind the EMA update
+        self.mt = mt
+        if mt is not None and self.ema is None:
+            self.ema = mt.ema
         self.trade_off, self.skip, self.track_acc = trade_off, skip_discarded, track_accuracy
         self.graphs = None
         self.out = {}
@@ -227,8 +232,11 @@ class DAStep:
         if self.skip:
             with _rt.bn_updates(2):               # this forward also stands for step C's (identical) one
                 f_t = m.features(b['x_t'])
-                y_t = m.head(f_t).detach()        # only ever used detached (pseudo-labels) in B and C
-            self._shared = (f_t, y_t)
+                y_t_grad = m.head(f_t)
+                y_t = y_t_grad.detach()           # only ever used detached (pseudo-labels) in B and C ...
+                if self.mt is None:
+                    y_t_grad = None               # ... but for the consistency term of step C: else the head's graph is freed here
+            self._shared = (f_t, y_t, y_t_grad)
             y_t_adv, y_t_adv2, y_t_adv3 = m.adv_heads(f_t.detach())
         else:
             y_t, y_t_adv, y_t_adv2, y_t_adv3, _ = m(b['x_t'])
@@ -257,27 +265,39 @@ class DAStep:
                 p.requires_grad_(False)
         try:
             if self.skip:
-                f_t, y_t = self._shared
+                f_t, y_t, y_t_grad = self._shared
                 self._shared = None
                 y_t_adv, y_t_adv2, y_t_adv3 = m.adv_heads(f_t)
             else:
                 y_t, y_t_adv, y_t_adv2, y_t_adv3, _ = m(b['x_t'])
+                y_t_grad = y_t
             loss1 = c['rd2'](y_t, y_t_adv2, None, b['w_t'], mode='min', scale=0.3 * to)
             loss2 = c['rd'](y_t, y_t_adv, None, b['w_t'], mode='min', scale=to)
             loss_gt = loss1 + loss2                     # = 0.3 to rd2 + to rd   (train1.py:443-448)
+            loss_mt = None
+            if self.mt is not None:
+                # the main head's weight gradients of this backward are discarded by the next step A's zero_grad, like the
+                # adversarial heads'; only optimizer_f steps in C
+                x_ema = b['x_t_ema'] if b.get('x_t_ema') is not None else b['x_t']
+                loss_mt = self.mt.term(y_t_grad, x_ema)
+            total = loss_gt if loss_mt is None else loss_gt + loss_mt
             with _rt.grouped_wgrads():
-                loss_gt.backward(_rt.unit_grad(loss_gt))
+                total.backward(_rt.unit_grad(total))
             _rt.join_side()
         finally:
             if self.skip:
                 for p in self._adv_params:
                     p.requires_grad_(True)
         self.out.update(loss_gt=loss_gt.detach(), y_t=y_t.detach(), y_t_adv=y_t_adv.detach())
+        if loss_mt is not None:
+            self.out.update(loss_mt=loss_mt.detach())
 
     def _update_C(self):
         self.opt['f'].step()
         if self.ema is not None:
             self.ema.update()
+            if self.mt is not None:
+                self.mt.teacher.refresh()        # the teacher's folded operands follow its weights, in place
 
     def _accuracy(self, b):
         """Device side of the four accuracy() calls of train1.py:464-475: arg-max coordinates + PCK distances."""
@@ -314,7 +334,8 @@ class DAStep:
 
     # ------------------------------------------------------------------ eager iteration
     def run(self, batch):
-        """batch: dict x_s, label_s, w_s, x_t, w_t (+ optional label_t for the PCK bookkeeping)."""
+        """batch: dict x_s, label_s, w_s, x_t, w_t (+ optional label_t for the PCK bookkeeping; with `mt`: x_t_ema, the teacher's
+        view of the target batch -- x_t itself when the key is absent)."""
         if self.graphs is not None:
             return self.replay(batch)
         from uda.model.regda_4 import _CENTRES
@@ -420,6 +441,8 @@ class DAStep:
             gl.sync()
         if self.ema is not None:
             self.ema.sync()
+        if self.mt is not None:
+            self.mt.sync()
 
     def replay(self, batch=None):
         if batch is not None and batch is not self.static:

@@ -70,6 +70,9 @@ _FP8_EVAL = _os.environ.get('MI355_FP8_EVAL', '0') == '1'
 _BN_GEN = [0]        # bumped by every training-mode BatchNorm forward: its kernels update running statistics in place
 
 
+_FOLD_TRACE = None   # a list while mi355.teacher records which (conv, BatchNorm) pairs an eval forward folds
+
+
 class _LazyConv:
     __slots__ = ('conv', 'x')
 
@@ -101,8 +104,14 @@ class _FoldedBn:
 
     def __init__(self):
         self.key, self.w, self.bias = None, None, None
+        self.pin = None           # ((id(bn), dtype, deconv, s2d), packed operand, bias): storage refreshed on the device (mi355.teacher)
 
     def get(self, conv, bn, dtype, deconv, s2d=False):
+        pin = self.pin
+        if pin is not None and pin[0] == (id(bn), dtype, bool(deconv), bool(s2d)):
+            return pin[1], pin[2]       # no key comparison: whoever pinned the entry keeps it current (InIterationTeacher.refresh)
+        if _FOLD_TRACE is not None:
+            _FOLD_TRACE.append((self, conv, bn, dtype, bool(deconv), bool(s2d)))
         key = _fold_key(conv, bn) + (dtype, s2d)
         if key != self.key:
             with torch.no_grad():
@@ -395,6 +404,13 @@ def _mx_wants_copy(producer):
 _PACK_BATCHED = __import__('os').environ.get('MI355_PACK_BATCHED', '1') == '1'
 
 
+def pack_item_dtype():
+    """numpy layout of mi355_pack_item (include/mi355pose.h)"""
+    import numpy as np
+    return np.dtype([('w', '<u8'), ('wf', '<u8'), ('wt', '<u8'), ('O', '<i4'), ('T', '<i4'), ('I', '<i4'), ('Ipad', '<i4'),
+                     ('blk0', '<i4'), ('pad', '<i4')])
+
+
 def repack_params(params, cache):
     """Refresh the packed compute-dtype copies of every conv weight in `params` with ONE kernel (called by FusedSGD right
     after its step, instead of one pack launch per conv at the next forward).  `cache`: a dict owned by the caller."""
@@ -408,8 +424,7 @@ def repack_params(params, cache):
         if torch.cuda.is_current_stream_capturing():
             return                                     # table not built yet: the convs repack lazily, as before
         import numpy as np
-        rec = np.zeros(len(ents), dtype=[('w', '<u8'), ('wf', '<u8'), ('wt', '<u8'), ('O', '<i4'), ('T', '<i4'), ('I', '<i4'),
-                                         ('Ipad', '<i4'), ('blk0', '<i4'), ('pad', '<i4')])
+        rec = np.zeros(len(ents), dtype=pack_item_dtype())
         blk = 0
         for i, (p, (pk, O, T, I, Ipad)) in enumerate(ents):
             rec[i] = (p.data_ptr(), pk.wf.data_ptr(), pk.wt.data_ptr(), O, T, I, Ipad, blk, 0)

@@ -874,6 +874,85 @@ def ema_update_batched(table, count, total_blocks, coef_dev):
     call('mi355_ema_update_batched', ptr(table), int(count), int(total_blocks), ptr(coef_dev), stream_ptr())
 
 
+# ---------------------------------------------------------------- mean-teacher consistency (csrc/teacher.hip)
+FOLD_CHUNK = 2048                                   # MI355_FOLD_CHUNK
+FOLD_ITEM_BYTES = 88
+
+
+def _fold_dtype():
+    import numpy as np
+    return np.dtype([(n, '<u8') for n in ('w', 'gamma', 'beta', 'mean', 'var', 'conv_bias', 'out_w', 'out_bias')] +
+                    [('eps', '<f4'), ('O', '<i4'), ('T', '<i4'), ('I', '<i4'), ('axis', '<i4'), ('blk0', '<i4')])
+
+
+def fold_table(records, device):
+    """records: (w, gamma, beta, mean, var, conv_bias or None, out_w, out_bias, eps, O, T, I, axis) with fp32 device tensors ->
+    (host record array, uint8 device copy of it, number of records, total blocks): the arguments of bn_fold_batched.  w and
+    out_w are dense in memory order [O][T][I] (any view whose storage walks that order)."""
+    import numpy as np
+    rec = np.zeros(len(records), dtype=_fold_dtype())
+    assert rec.dtype.itemsize == FOLD_ITEM_BYTES
+    blk = 0
+    for i, (w, gamma, beta, mean, var, cbias, out_w, out_bias, eps, O, T, I, axis) in enumerate(records):
+        ts = (w, gamma, beta, mean, var, cbias, out_w, out_bias)
+        _chk_dev(*ts)
+        if any(t is not None and t.dtype != torch.float32 for t in ts):
+            raise Mi355Error('fold_table: record %d needs fp32 tensors' % i)
+        if axis not in (0, 1) or min(O, T, I) < 1:
+            raise Mi355Error('fold_table: record %d: O=%r T=%r I=%r axis=%r' % (i, O, T, I, axis))
+        n, C = O * T * I, (O if axis == 0 else I)
+        _chk_room('fold_table w', w, n)
+        _chk_room('fold_table out_w', out_w, n)
+        for what, t in (('gamma', gamma), ('beta', beta), ('mean', mean), ('var', var), ('conv_bias', cbias), ('out_bias', out_bias)):
+            _chk_room('fold_table ' + what, t, C)
+        rec[i] = tuple(ptr(t) for t in ts) + (float(eps), O, T, I, axis, blk)
+        blk += (n + FOLD_CHUNK - 1) // FOLD_CHUNK
+    return rec, torch.from_numpy(rec.view(np.uint8).copy()).to(device), len(records), blk
+
+
+def bn_fold_batched(rec_host, table, count, total_blocks):
+    """One launch: fold every record's eval-mode BatchNorm into out_w / out_bias (fold_table).  Capturable; allocates nothing."""
+    _chk_dev(table)
+    _chk_room('bn_fold_batched table', table, count * FOLD_ITEM_BYTES)
+    if rec_host.dtype.itemsize != FOLD_ITEM_BYTES or rec_host.size < count or not rec_host.flags['C_CONTIGUOUS']:
+        raise Mi355Error('bn_fold_batched: the host table does not hold %d records' % count)
+    call('mi355_bn_fold_batched', rec_host.ctypes.data, ptr(table), int(count), int(total_blocks), stream_ptr())
+
+
+def mse_record(joint_mask, grad_scale, device=None, out=None):
+    """The device record {int32 joint_mask, float grad_scale} of mse_heatmap as a 2-element int32 tensor (new, or `out` rewritten)."""
+    import numpy as np
+    host = np.zeros(1, dtype=[('mask', '<u4'), ('gs', '<f4')])
+    host[0] = (int(joint_mask) & 0xffffffff, np.float32(grad_scale))
+    t = torch.from_numpy(host.view(np.int32).copy())
+    if out is None:
+        return t.to(device)
+    _chk_room('mse_record out', out, 2)
+    out.copy_(t)
+    return out
+
+
+def mse_heatmap(pred, target, rec, want_grad, rows=None, grad=None):
+    """Returns (rows [B,K] = per-map sums of squared differences, unit_grad [B,K,H,W] or None); maps whose joint is outside the
+    record's mask give exact zeros.  rec: mse_record()."""
+    pred, target = _hm(pred), _hm(target)
+    B, K, H, W = pred.shape
+    if tuple(target.shape) != (B, K, H, W):
+        raise Mi355Error('mse_heatmap: pred %s vs target %s' % (tuple(pred.shape), tuple(target.shape)))
+    _chk_dev(rec)
+    if rec.dtype != torch.int32:
+        raise Mi355Error('mse_heatmap: rec must be the int32 pair of mse_record')
+    _chk_room('mse_heatmap rec', rec, 2)
+    if rows is None:
+        rows = torch.empty((B, K), dtype=torch.float32, device=pred.device)
+    if want_grad and grad is None:
+        grad = torch.empty_like(pred)
+    _chk_room('mse_heatmap rows', rows, B * K)
+    _chk_room('mse_heatmap unit_grad', grad, B * K * H * W)
+    call('mi355_mse_heatmap', ptr(pred), ptr(target), ptr(rec), ptr(rows), ptr(grad) if want_grad else 0, B, K, H * W, stream_ptr())
+    return rows, (grad if want_grad else None)
+
+
 # ---------------------------------------------------------------- kernel timer (bench.py roofline)
 def spin_us(us):
     call('mi355_spin_us', int(us), stream_ptr())

@@ -4,7 +4,9 @@ training schedule as the reference's ``train1.py`` (main :37-275, pretrain :278-
 validate :495-536, CLI :591-675).  Additive flags: ``--synthetic`` (seeded synthetic data instead of the
 out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--mx-eval``, ``--no-graph``, ``--device-augment`` (the training
 augmentation chain, the validation resize and the labels of both on the GPU), ``--ema-update {off,const,warmup}`` (keep the
-EMA teacher ``model_ema`` up to date: the reference's commented-out call at train1.py:461).
+EMA teacher ``model_ema`` up to date: the reference's commented-out call at train1.py:461), ``--mt-loss {off,on}`` with
+``--mt-weight`` / ``--mt-k`` (the mean-teacher consistency term on the target batch: the reference's unused ``x_t_ema``, ``m`` and
+``mt_loss``, train1.py:351-364 and uda/model/loss.py:265-297).
 
     python train1.py data/H3D -t Hand3DStudio --synthetic -a resnet50 -b 64
 
@@ -158,11 +160,15 @@ def main(args):
     train_source_iter, train_target_iter = ForeverDataIterator(train_source_loader), ForeverDataIterator(train_target_loader)
     if args.device_augment and not args.synthetic:
         # packed sources -> HBM, augmentation and heat-map labels on the GPU (mi355.augment, utils.labels)
-        dev_aug = lambda it: DeviceAugmentIterator(it, device, args.image_size, args.heatmap_size)
-        train_source_iter, train_target_iter = dev_aug(train_source_iter), dev_aug(train_target_iter)
+        dev_aug = lambda it, ema=False: DeviceAugmentIterator(it, device, args.image_size, args.heatmap_size, want_ema=ema)
+        # (--mt-loss: the target batches also carry meta['image_ema'], the geometry-only image the teacher sees)
+        train_source_iter, train_target_iter = dev_aug(train_source_iter), dev_aug(train_target_iter, args.mt_loss == 'on')
     else:
         # host -> HBM copies of the next batch overlap the current step (pinned, double-buffered, side stream)
-        train_source_iter, train_target_iter = DevicePrefetcher(train_source_iter, device), DevicePrefetcher(train_target_iter, device)
+        # (--mt-loss: meta['image_ema'] of the target batches travels with them instead of as a blocking copy inside the iteration)
+        ema_keys = ('image_ema',) if args.mt_loss == 'on' and not args.synthetic else ()
+        train_source_iter = DevicePrefetcher(train_source_iter, device)
+        train_target_iter = DevicePrefetcher(train_target_iter, device, meta_keys=ema_keys)
 
     # model (+ the EMA copy the reference builds and checkpoints, train1.py:102-128; frozen unless --ema-update is on)
     backbone = models.__dict__[args.arch](pretrained=True)
@@ -190,6 +196,10 @@ def main(args):
     if args.ema_update != 'off':
         # the teacher follows the model after every iteration (uda/model/loss.py:252-261 at train1.py:461), on the device
         ema = step.ema = EMATeacher(model, model_ema, opts, args.ema_decay, warmup=args.ema_update == 'warmup')
+    if args.mt_loss == 'on':
+        # step C gains m * mt_loss(y_t, model_ema(x_t_ema)) (train1.py:351-364); the teacher runs inside the iteration
+        from mi355.teacher import MeanTeacher
+        step.mt = MeanTeacher(ema, weight=args.mt_weight, k=args.mt_k)
     start_epoch = 0
     if args.resume is None:
         if args.pretrain is None or (args.synthetic and not os.path.exists(args.pretrain)):
@@ -326,14 +336,20 @@ def _pck(dists, thr=0.5):
 def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     names = ['Time', 'Data', 'Loss (s)', 'Loss (t, false)', 'Loss (t, truth)', 'Acc (s)', 'Acc (t)', 'Acc (s, adv)', 'Acc (t, adv)']
     fmts = [':4.2f', ':3.1f', ':.2e', ':.2e', ':.2e', ':3.2f', ':3.2f', ':3.2f', ':3.2f']
+    mt = getattr(step, 'mt', None)
+    if mt is not None:
+        mt.set_epoch(epoch)                              # m and k are functions of the epoch (train1.py:351-353)
+        names, fmts = names + ['Loss (mt)'], fmts + [':.2e']
     meters = [AverageMeter(n, f) for n, f in zip(names, fmts)]
     progress = ProgressMeter(args.iters_per_epoch, meters, prefix="Epoch: [{}]".format(epoch))
     end = time.time()
     for i in range(args.iters_per_epoch):
         x_s, label_s, weight_s, _ = next(train_source_iter)
-        x_t, label_t, weight_t, _ = next(train_target_iter)
+        x_t, label_t, weight_t, meta_t = next(train_target_iter)
         to = lambda t: t.to(device, non_blocking=True)
         batch = dict(x_s=to(x_s), label_s=to(label_s), w_s=to(weight_s), x_t=to(x_t), w_t=to(weight_t), label_t=to(label_t))
+        if mt is not None:                               # x_t_ema = meta_t['image_ema'] (train1.py:364); synthetic images have no augmentation
+            batch['x_t_ema'] = batch['x_t'] if args.synthetic else to(meta_t['image_ema'])
         meters[1].update(time.time() - end)
         # HIP-graph replay once this process has run three eager iterations (whatever epoch it resumed at).  With several
         # ranks the eager path overlaps the gradient exchange with the backward, which only pays while the host can enqueue an
@@ -365,8 +381,10 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
         if i % args.print_freq == 0:
             for m, k in zip(meters[2:5], ('loss_s', 'loss_gf', 'loss_gt')):
                 m.update(float(out[k]), args.batch_size)
-            for m, k in zip(meters[5:], ('pck_s', 'pck_t', 'pck_s_adv', 'pck_t_adv')):
+            for m, k in zip(meters[5:9], ('pck_s', 'pck_t', 'pck_s_adv', 'pck_t_adv')):
                 a, c = _pck(out[k]); m.update(a, c)
+            if mt is not None:
+                meters[9].update(float(out['loss_mt']), args.batch_size)
             meters[0].update(time.time() - end)
             progress.display(i)
         end = time.time()
@@ -437,6 +455,10 @@ def validate(val_loader, model, criterion, args):
 
 # (flags, kwargs) for every option of the reference's command line (train1.py:602-674: same names, types and
 # defaults), followed by the additive ones of this implementation
+def _mt_weight(text):
+    return 'ref' if text == 'ref' else float(text)
+
+
 _OPTIONS = [
     (('--source_root',), dict(default='data/RHD', help='source dataset directory')),
     (('target_root',), dict(help='target dataset directory')),
@@ -481,6 +503,13 @@ _OPTIONS = [
     (('--ema-update',), dict(default='off', choices=['off', 'const', 'warmup'], help="update the EMA teacher after every iteration on the "
                             "GPU, validate it on the target set ('ema:' line) and checkpoint it (model_ema.pth, ema_state): 'const' uses "
                             "--ema-decay, 'warmup' min(1 - 1/(step + 1), --ema-decay); 'off': the teacher stays at its initial weights")),
+    (('--mt-loss',), dict(default='off', choices=['off', 'on'], help="mean-teacher consistency on the target batch: step C's loss gains "
+                         "m * mt_loss(y_t, model_ema(x_t_ema), weight_t, k), the teacher running in eval mode inside the iteration; needs "
+                         "--ema-update const|warmup")),
+    (('--mt-weight',), dict(default='ref', type=_mt_weight, metavar='ref|FLOAT', help="weight m of the consistency term: 'ref' is the "
+                           "reference schedule (0.01 * epoch, 0.3 once epoch > 30), a number a constant")),
+    (('--mt-k',), dict(default='all', choices=['all', 'epoch'], help="joints the consistency term compares: 'all' (k = 400) or the "
+                      "reference's curriculum with k = epoch (the wrist below 100, one more joint per finger every 100 epochs)")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--device-augment',), dict(action='store_true', help='run the training augmentation chain (rotate, resized crop, colour '
                                   'jitter, blur, normalisation), the validation resize + normalisation and the heat-map labels '
@@ -489,9 +518,19 @@ _OPTIONS = [
 ]
 
 
+class _Parser(argparse.ArgumentParser):
+    """Checks between flags that argparse cannot express."""
+
+    def parse_args(self, *a, **kw):
+        args = super().parse_args(*a, **kw)
+        if getattr(args, 'mt_loss', 'off') == 'on' and getattr(args, 'ema_update', 'off') == 'off':
+            self.error('--mt-loss on needs a moving teacher: add --ema-update const (or warmup)')
+        return args
+
+
 def build_parser(description='Domain-adaptive hand-pose training on MI355X'):
     archs = sorted(n for n in models.__dict__ if n.islower() and not n.startswith('__') and callable(models.__dict__[n]))
-    parser = argparse.ArgumentParser(description=description)
+    parser = _Parser(description=description)
     parser.add_argument('-a', '--arch', metavar='ARCH', default='resnet101', choices=archs, help=' | '.join(archs))
     for flags, kw in _OPTIONS:
         parser.add_argument(*flags, **kw)

@@ -1,5 +1,6 @@
 """``JointsKLLoss`` (reference ``uda/model/loss.py:115-158``) as one fused row kernel: log-softmax,
-target normalisation, KL sum, weighting and the gradient w.r.t. the prediction in a single pass."""
+target normalisation, KL sum, weighting and the gradient w.r.t. the prediction in a single pass; ``mt_loss`` (reference
+``uda/model/loss.py:265-297``), the mean-teacher consistency term, as one masked squared-difference row kernel."""
 import torch
 import torch.nn as nn
 
@@ -45,3 +46,86 @@ class JointsKLLoss(nn.Module):
             return loss
         elif self.reduction == 'none':
             return rows.detach().mean(dim=-1) * float(scale)     # forward-only, as no caller differentiates it
+
+
+# ---------------------------------------------------------------- mean-teacher consistency (reference uda/model/loss.py:265-297)
+# the joint curriculum of mt_loss: k < 100 the wrist, then one more joint per finger every 100, all joints from 400 on
+MT_SUBSETS = ((100, (0,)),
+              (200, (0, 1, 5, 9, 13, 17)),
+              (300, (0, 1, 2, 5, 6, 9, 10, 13, 14, 17, 18)),
+              (400, (0, 1, 2, 3, 5, 6, 7, 9, 10, 11, 13, 14, 15, 17, 18, 19)))
+
+
+def mt_subset(k, num_joints):
+    """The joints mt_loss(k) compares, as a tuple of channel indices."""
+    for bound, joints in MT_SUBSETS:
+        if k < bound:
+            if joints[-1] >= num_joints:
+                raise IndexError('mt_loss: joint %d of the k = %d subset, heat-maps have %d channels' % (joints[-1], k, num_joints))
+            return joints
+    return tuple(range(num_joints))
+
+
+class _MSEFn(torch.autograd.Function):
+    """loss = (*scale_dev) * sum(rows).  As _KLFn: the kernel writes d loss / d pred in the forward (its factor rides in the
+    device record), the backward hands it on when the incoming gradient is the unit scalar."""
+
+    @staticmethod
+    def forward(ctx, pred, target, rec, scale_dev):
+        rows, g = ops.mse_heatmap(pred, target, rec, ctx.needs_input_grad[0])
+        ctx.save_for_backward(g)
+        return ops.scale_by_dev(ops.reduce_sum(rows.view(-1)), scale_dev)
+
+    @staticmethod
+    def backward(ctx, gout):
+        g, = ctx.saved_tensors
+        if g is None or gout is None:
+            return None, None, None, None
+        if _rt.is_unit_grad(gout):
+            return g, None, None, None
+        return ops.scale_by_dev(g, gout.contiguous().float()), None, None, None
+
+
+class MeanTeacherLoss:
+    """``m * mt_loss(pre, label, weight, k)`` with everything that changes per epoch -- the joint mask, m / n and 2 m / n, n = B *
+    |subset| * H * W -- in device memory: ``set()`` rewrites it (outside graph capture), a captured graph that contains the
+    loss replays with the new values.  Both quotients are computed in double and rounded once to fp32."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.rec = torch.zeros(2, dtype=torch.int32, device=self.device)         # {int32 joint_mask, float grad_scale}
+        self.scale = torch.zeros((), dtype=torch.float32, device=self.device)    # m / n
+        self.state = None
+
+    def set(self, m, k, shape):
+        B, K, H, W = shape
+        if K > 32:
+            raise ValueError('mt_loss: at most 32 joints, got %d' % K)
+        joints = mt_subset(k, K)
+        mask = sum(1 << j for j in joints)
+        n = B * len(joints) * H * W
+        state = (float(m), mask, n)
+        if state != self.state:
+            ops.mse_record(mask, 2.0 * float(m) / n, out=self.rec)
+            self.scale.copy_(torch.tensor(float(m) / n, dtype=torch.float64).to(torch.float32))
+            self.state = state
+        return self
+
+    def __call__(self, pre, label):
+        if self.state is None:
+            raise RuntimeError('MeanTeacherLoss: set(m, k, shape) first')
+        return _MSEFn.apply(pre, label.detach(), self.rec, self.scale)
+
+
+_mt_cache = {}
+
+
+def mt_loss(pre, label, weight, k):
+    """The reference's ``mt_loss(pre, label, weight, k)``: ``MSELoss()`` (mean over every element) of the joints k selects;
+    ``weight`` is accepted and ignored, as there.  Differentiable w.r.t. ``pre``."""
+    B, K, H, W = pre.shape
+    key = (pre.device, K, mt_subset(k, K), B * H * W)
+    crit = _mt_cache.get(key)
+    if crit is None:
+        crit = _mt_cache[key] = MeanTeacherLoss(pre.device).set(1.0, k, (B, K, H, W))
+    return crit(pre, label)

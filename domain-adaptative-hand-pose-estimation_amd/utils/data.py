@@ -47,12 +47,15 @@ class DevicePrefetcher:
     """Host -> HBM staging off the critical path (replaces the blocking ``.to(device)`` calls of the
     reference's loop, train1.py:359-366): while the training step consumes batch i, batch i+1 is copied on a side stream
     from pinned host memory.  Tensors the loader did not pin go through persistent pinned staging buffers (two slots,
-    double-buffered), so no pinned allocation happens per batch.  Non-tensor items (the ``meta`` dicts) pass through.
+    double-buffered), so no pinned allocation happens per batch.  Non-tensor items (the ``meta`` dicts) pass through, except
+    for the tensors under ``meta_keys`` (``('image_ema',)`` for the mean-teacher's view of the target batch), which are staged
+    like the batch's own tensors.
 
     ``next()`` returns the batch with every tensor on ``device``; the consumer's stream waits on the copy event and the
     tensors are recorded on it, so the caching allocator does not recycle them early."""
 
-    def __init__(self, iterator, device, slots=2):
+    def __init__(self, iterator, device, slots=2, meta_keys=()):
+        self.meta_keys = tuple(meta_keys)
         self.it = iter(iterator)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
@@ -74,6 +77,15 @@ class DevicePrefetcher:
             t = buf
         return t.to(self.device, non_blocking=True)
 
+    def _stage_meta(self, slot, idx, x):
+        if not self.meta_keys or not isinstance(x, dict):
+            return x
+        x = dict(x)
+        for k in self.meta_keys:
+            if torch.is_tensor(x.get(k)):
+                x[k] = self._to_device(slot, (idx, k), x[k])
+        return x
+
     def _preload(self):
         try:
             host = next(self.it)
@@ -87,7 +99,7 @@ class DevicePrefetcher:
         seq = isinstance(host, (tuple, list))
         items = list(host) if seq else [host]
         with torch.cuda.stream(self.stream):
-            out = [self._to_device(slot, i, x) if torch.is_tensor(x) else x for i, x in enumerate(items)]
+            out = [self._to_device(slot, i, x) if torch.is_tensor(x) else self._stage_meta(slot, i, x) for i, x in enumerate(items)]
             ev = torch.cuda.Event()
             ev.record(self.stream)
         self._slot_free[slot] = ev
@@ -105,6 +117,10 @@ class DevicePrefetcher:
         for x in (batch if isinstance(batch, (tuple, list)) else [batch]):
             if torch.is_tensor(x):
                 x.record_stream(cur)
+            elif self.meta_keys and isinstance(x, dict):
+                for k in self.meta_keys:
+                    if torch.is_tensor(x.get(k)) and x[k].is_cuda:
+                        x[k].record_stream(cur)
         self._preload()
         return batch
 

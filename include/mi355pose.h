@@ -444,6 +444,37 @@ int mi355_ema_update(float* e, const float* p, long n, const float* coef_dev, vo
 typedef struct mi355_ema_item { const void* src; void* dst; long n; int kind; int blk0; } mi355_ema_item;
 int mi355_ema_update_batched(const mi355_ema_item* items_dev, int count, int total_blocks, const float* coef_dev, void* stream);
 
+/* ---------------------------------------------------------------- mean-teacher consistency (csrc/teacher.hip)
+ * Eval-mode BatchNorm folded into the conv in front of it, for many (conv, bn) pairs in ONE launch and into caller-owned
+ * storage: the device form of mi355/nn.py's _fold_scale_shift + multiply, which the teacher of train1.py:364 / :461 needs
+ * once per iteration (its weights move with every EMA update).  Per item, with c the channel of an element:
+ *   scale[c]    = gamma[c] / sqrtf(var[c] + eps)                       (correctly rounded divide and square root)
+ *   out_bias[c] = fl(beta[c] - fl(mean[c] * scale[c]))                 (+ fl(conv_bias[c] * scale[c]) when conv_bias is given)
+ *   out_w[e]    = fl(w[e] * scale[c(e)])                               w, out_w: fp32 in memory order [O][T][I]
+ * axis 0: c(e) = e / (T * I), C = O (a conv);  axis 1: c(e) = e % I, C = I (the conv-form of a transposed conv).  Nothing is
+ * contracted into an FMA.  blk0 = first block of the item = sum over earlier items of ceil(O*T*I / MI355_FOLD_CHUNK);
+ * total_blocks = that sum over all.  As with mi355_augment the records are passed twice: `items_host` (host memory) is what the
+ * argument checks read before anything is enqueued, `items_dev` (an identical copy in device memory) is what the kernel reads.
+ * Pointers need 4-byte alignment only (16-byte accesses are used where w and out_w allow).  Never allocates; capturable. */
+#define MI355_FOLD_CHUNK 2048
+typedef struct mi355_fold_item {
+  const float* w; const float* gamma; const float* beta; const float* mean; const float* var;
+  const float* conv_bias;      /* nullable */
+  float* out_w; float* out_bias;
+  float eps; int O, T, I, axis, blk0;
+} mi355_fold_item;
+int mi355_bn_fold_batched(const mi355_fold_item* items_host, const mi355_fold_item* items_dev, int count, int total_blocks,
+                          void* stream);
+/* mt_loss of uda/model/loss.py:265-297 (MSELoss over the joint subset its curriculum selects; the weight `m` of
+ * train1.py:351-353 rides in grad_scale) on fp32 NCHW heat-maps pred, target [B][K][HW], K <= 32, HW >= 1.  rec: DEVICE record
+ * (refreshed per epoch without recapturing a graph).  Row r = b * K + k:
+ *   rows[r]         = sum_j fl(fl(p_j - t_j)^2) in a fixed order          (exactly 0 when bit k of joint_mask is clear)
+ *   unit_grad[r][j] = fl(fl(p_j - t_j) * grad_scale)   (nullable)         (exactly 0 when bit k of joint_mask is clear)
+ * The scalar loss is mi355_reduce_sum(rows) times a device-resident m / n (mi355_scale_by_dev). */
+typedef struct mi355_mse_rec { int32_t joint_mask; float grad_scale; } mi355_mse_rec;
+int mi355_mse_heatmap(const float* pred, const float* target, const mi355_mse_rec* rec_dev, float* rows, float* unit_grad,
+                      int B, int K, int HW, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
