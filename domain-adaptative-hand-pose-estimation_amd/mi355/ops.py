@@ -823,6 +823,63 @@ def pck_dists(pred_xy, tgt_xy, norm_x, norm_y):
     return d
 
 
+# ---------------------------------------------------------------- evaluation at image resolution
+def _size2(size):
+    H, W = (size, size) if isinstance(size, int) else size
+    return int(H), int(W)
+
+
+def upsample_argmax(hm, size, out=None):
+    """Arg-max of nn.Upsample(size, mode='bilinear')(hm) without the up-sampled maps: (idx int32 [B,K], xy fp32 [B,K,2],
+    maxval fp32 [B,K,1]), argmax2d's rules on the size[0] x size[1] grid.  `out`: an (idx, xy, maxval) triple to write into."""
+    hm = _hm(hm)
+    if hm.dim() != 4:
+        raise Mi355Error('upsample_argmax: heat-maps must be (B, K, h, w), got %s' % (tuple(hm.shape),))
+    B, K, h, w = hm.shape
+    H, W = _size2(size)
+    if min(B * K, h, w, H, W) < 1 or H * W >= 2 ** 31 - 1:
+        raise Mi355Error('upsample_argmax: %s -> %d x %d' % (tuple(hm.shape), H, W))
+    if out is None:
+        out = (torch.empty((B, K), dtype=torch.int32, device=hm.device), torch.empty((B, K, 2), dtype=torch.float32, device=hm.device),
+               torch.empty((B, K, 1), dtype=torch.float32, device=hm.device))
+    idx, xy, mv = out
+    _chk_dev(idx, xy, mv)
+    for what, t, need, dt in (('idx', idx, B * K, torch.int32), ('xy', xy, 2 * B * K, torch.float32), ('maxval', mv, B * K, torch.float32)):
+        _chk_room('upsample_argmax ' + what, t, need)
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise Mi355Error('upsample_argmax %s: needs a contiguous %s tensor' % (what, dt))
+    call('mi355_upsample_argmax', ptr(hm), ptr(idx), ptr(xy), ptr(mv), B * K, h, w, H, W, stream_ptr())
+    return idx, xy, mv
+
+
+def pose_metrics_state(K, T, device):
+    """Zeroed accumulators of pose_metrics: (sum_err float64 [K], count int32 [K], hits int32 [K,T])."""
+    return (torch.zeros(K, dtype=torch.float64, device=device), torch.zeros(K, dtype=torch.int32, device=device),
+            torch.zeros((K, T), dtype=torch.int32, device=device))
+
+
+def pose_metrics(pred, gt, vis, thr, state):
+    """Add one batch to `state` = (sum_err [K] float64, count [K] int32, hits [K,T] int32): per visible joint the float64
+    end-point error of pred against gt (B,K,2) and a hit per threshold of `thr` (T,) it stays strictly below."""
+    if pred.dim() != 3 or pred.shape[2] != 2 or tuple(gt.shape) != tuple(pred.shape):
+        raise Mi355Error('pose_metrics: pred %s vs gt %s, both must be (B, K, 2)' % (tuple(pred.shape), tuple(gt.shape)))
+    B, K, _ = pred.shape
+    if vis.numel() != B * K:
+        raise Mi355Error('pose_metrics: vis has %d elements for %d x %d joints' % (vis.numel(), B, K))
+    f = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+    pred, gt, vis, thr = f(pred), f(gt), f(vis), f(thr)
+    sum_err, count, hits = state
+    _chk_dev(pred, gt, vis, thr, sum_err, count, hits)
+    T = thr.numel()
+    if B < 1 or K < 1 or T < 1:
+        raise Mi355Error('pose_metrics: B=%d K=%d T=%d' % (B, K, T))
+    for what, t, need, dt in (('sum_err', sum_err, K, torch.float64), ('count', count, K, torch.int32), ('hits', hits, K * T, torch.int32)):
+        _chk_room('pose_metrics ' + what, t, need)
+        if t.dtype != dt or not t.is_contiguous():
+            raise Mi355Error('pose_metrics %s: needs a contiguous %s tensor' % (what, dt))
+    call('mi355_pose_metrics', ptr(pred), ptr(gt), ptr(vis), ptr(thr), T, B, K, ptr(sum_err), ptr(count), ptr(hits), stream_ptr())
+
+
 # ---------------------------------------------------------------- optimiser
 def sgd_nesterov(p, g, buf, lr_dev, momentum, wd, nesterov, p_lowp=None):
     for what, t in (('g', g), ('buf', buf), ('p_lowp', p_lowp)):

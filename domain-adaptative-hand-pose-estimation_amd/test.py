@@ -3,6 +3,11 @@
 ``--resume`` and one ``validate()`` on the source and target test splits, test.py:157,192-226,584).
 
     python test.py data/H3D -t Hand3DStudio --checkpoint models/H3D_best_754.pth [--synthetic] [--ema_model .../model_ema.pth]
+
+``--dump-preds PATH`` (implies ``--metrics full``) writes the predictions of every evaluated split for tools outside this
+script: ``PATH.source.npz``, ``PATH.target.npz`` and, with ``--ema_model``, ``PATH.ema.npz``, each with ``pred`` (N,K,2) and
+``gt`` (N,K,2) in image pixels, ``visible`` (N,K), ``maxval`` (N,K), ``image_size``, ``decode``, ``thresholds`` and the reported
+``epe``, ``auc`` and ``pck_curve``, in data-set order.
 """
 import os
 import sys
@@ -44,15 +49,26 @@ def main(args):
         model.load_state_dict(ck['model'])
         print('loaded checkpoint (epoch %s)' % ck.get('epoch'))
     criterion = JointsKLLoss()
-    s_acc = T.validate(val_source_loader, model, criterion, args)
-    t_acc = T.validate(val_target_loader, model, criterion, args)
+
+    def evaluate(loader, split):
+        if not args.dump_preds:
+            return T.validate(loader, model, criterion, args)
+        dump = {}
+        acc = T.validate(loader, model, criterion, args, dump=dump)
+        if T.RANK == 0:                                   # (gathered in validate: data-set order, one copy per split)
+            import numpy as np
+            np.savez('%s.%s.npz' % (args.dump_preds, split), **dump)
+        return acc
+
+    s_acc = evaluate(val_source_loader, 'source')
+    t_acc = evaluate(val_target_loader, 'target')
     print("Source: {:4.3f} Target: {:4.3f}".format(s_acc['all'], t_acc['all']))
     for name, acc in t_acc.items():
         print("{}: {:4.3f}".format(name, acc))
     if args.ema_model:
         # the EMA teacher of a --ema-update run (its model_ema.pth): same network, the file's `model_ema` weights
         model.load_state_dict(torch.load(args.ema_model, map_location='cpu', weights_only=False)['model_ema'])
-        e_acc = T.validate(val_target_loader, model, criterion, args)
+        e_acc = evaluate(val_target_loader, 'ema')
         print("ema: {:4.3f}".format(e_acc['all']))
     logger.close()
 
@@ -60,4 +76,6 @@ def main(args):
 if __name__ == '__main__':
     p = T.build_parser('Evaluation for Keypoint Detection Domain Adaptation')
     p.add_argument('--checkpoint', type=str, default=None, help='where restore model parameters from.')
+    p.add_argument('--dump-preds', type=str, default=None, metavar='PATH', help='write PATH.<split>.npz (pred, gt, visible, maxval in '
+                   'image pixels, thresholds, epe, auc, pck_curve) per evaluated split; implies --metrics full')
     main(p.parse_args())

@@ -6,7 +6,9 @@ out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--mx-eval``
 augmentation chain, the validation resize and the labels of both on the GPU), ``--ema-update {off,const,warmup}`` (keep the
 EMA teacher ``model_ema`` up to date: the reference's commented-out call at train1.py:461), ``--mt-loss {off,on}`` with
 ``--mt-weight`` / ``--mt-k`` (the mean-teacher consistency term on the target batch: the reference's unused ``x_t_ema``, ``m`` and
-``mt_loss``, train1.py:351-364 and uda/model/loss.py:265-297).
+``mt_loss``, train1.py:351-364 and uda/model/loss.py:265-297), ``--metrics {pck,full}`` with ``--decode {argmax,upsample}`` and
+``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
+unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205).
 
     python train1.py data/H3D -t Hand3DStudio --synthetic -a resnet50 -b 64
 
@@ -49,7 +51,7 @@ from uda.model.loss import JointsKLLoss
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
 from uda.model.regda_7 import MainOutput, PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
 from utils.data import ForeverDataIterator, DevicePrefetcher, DeviceAugmentIterator, ragged_collate
-from utils.keypoint_detection import accuracy, accuracy_from_preds, get_max_preds_device
+from utils.keypoint_detection import accuracy, accuracy_from_preds, get_max_preds_device, decode_keypoints, PoseMetrics
 from utils.logger import CompleteLogger
 from utils.meter import AverageMeter, ProgressMeter, AverageMeterDict
 
@@ -396,9 +398,20 @@ def validate_batch_metrics(y, label, weight, criterion):
     return criterion(y, label, weight).detach(), get_max_preds_device(y)[0], get_max_preds_device(label)[0]
 
 
-def validate(val_loader, model, criterion, args):
+def _allreduce_sum(t):
+    if WORLD > 1:
+        dist.all_reduce(t)
+
+
+def validate(val_loader, model, criterion, args, dump=None):
     """The host reads the metrics only when a progress line is due and at the end, so the printed Time field is the mean over
-    the batches since the last read (time since then / batches metered), not the time of the single last batch."""
+    the batches since the last read (time since then / batches metered), not the time of the single last batch.
+
+    ``--metrics full``: every batch is also decoded to image pixels (``--decode``) and added to a PoseMetrics against
+    ``meta['keypoint2d']`` with ``weight`` as visibility -- launches only, nothing is read per batch; one more line (EPE, AUC)
+    and the per-group EPEs are printed at the end.  ``dump`` (a dict, test.py --dump-preds): filled with the predictions of the
+    whole data set in data-set order (rank 0; None elsewhere) and the reported numbers."""
+    full = getattr(args, 'metrics', 'pck') == 'full'
     batch_time, losses = AverageMeter('Time', ':6.3f'), AverageMeter('Loss', ':.2e')
     dataset = val_loader.dataset
     acc = AverageMeterDict(dataset.keypoints_group.keys(), ":3.2f")
@@ -414,6 +427,8 @@ def validate(val_loader, model, criterion, args):
         batches = DeviceAugmentIterator(val_loader, device, dataset.image_size[0], dataset.heatmap_size[0], dataset.sigma,
                                         geometry_only=True)
     pending = []                             # (loss, pred, label pred, batch size, heat-map h, w) of the batches not yet metered
+    pose = PoseMetrics(dataset.num_keypoints, args.auc_max_px, device=device) if full else None
+    kept = []                                # --dump-preds: (pred, gt, visible, maxval) of every batch, on the device
 
     def meter(since):
         # one stack and one copy per kind, then the meters replayed batch by batch (reference arithmetic, train1.py:505-524)
@@ -436,6 +451,13 @@ def validate(val_loader, model, criterion, args):
             x, label, weight = x.to(device, non_blocking=True), label.to(device, non_blocking=True), weight.to(device, non_blocking=True)
             y = forward(x)
             pending.append(validate_batch_metrics(y, label, weight, criterion) + (x.size(0), y.shape[2], y.shape[3]))
+            if full:
+                kp, mv = decode_keypoints(y, x.shape[3], args.decode, with_maxval=True)
+                gt = torch.as_tensor(meta['keypoint2d']).float().to(device, non_blocking=True)
+                vis = weight.reshape(gt.shape[0], -1)
+                pose.update(kp, gt, vis)
+                if dump is not None:
+                    kept.append((kp, gt, vis, mv.reshape(vis.shape)))
             if i % args.print_freq == 0:     # the host reads only when something is printed, and once at the end
                 meter(end)
                 end = time.time()
@@ -450,7 +472,40 @@ def validate(val_loader, model, criterion, args):
         for j, k in enumerate(keys):
             acc[k].sum, acc[k].count = t[2 * j], t[2 * j + 1]
             acc[k].avg = acc[k].sum / max(acc[k].count, 1)
+    if full:
+        res = pose.result(dataset.keypoints_group, reduce=_allreduce_sum)
+        print('EPE: {:.3f} px  AUC(0-{:g}px): {:.4f}'.format(res['epe'], args.auc_max_px, res['auc']))
+        for name in dataset.keypoints_group:
+            print('EPE {}: {:.3f} px'.format(name, res['epe_' + name]))
+        if dump is not None:
+            dump.update(_gather_preds(kept, len(dataset), dataset.num_keypoints), image_size=x.shape[3], decode=args.decode,
+                        thresholds=res['thresholds'], epe=res['epe'], auc=res['auc'], pck_curve=res['pck_curve'])
     return acc.average()
+
+
+def _gather_preds(kept, n_total, K):
+    """The per-batch (pred, gt, visible, maxval) device tensors of this rank's shard (rank::WORLD, make_loader) -> numpy arrays
+    of the whole data set in data-set order on rank 0 (None elsewhere): one concatenation and one copy per split."""
+    names = ('pred', 'gt', 'visible', 'maxval')
+    if kept:
+        flat = torch.cat([torch.cat([t.reshape(t.shape[0], -1).float() for t in row], 1) for row in kept])      # (n, 6K)
+    else:
+        flat = torch.zeros((0, 6 * K), dtype=torch.float32, device=device)
+    if WORLD > 1:
+        per = (n_total + WORLD - 1) // WORLD                 # the longest shard; shorter ones are padded for the gather
+        pad = torch.zeros((per, 6 * K), dtype=torch.float32, device=device)
+        pad[:flat.shape[0]] = flat
+        every = [torch.zeros_like(pad) for _ in range(WORLD)]
+        dist.all_gather(every, pad)
+        if RANK != 0:
+            return {k: None for k in names}
+        full = torch.zeros((n_total, 6 * K), dtype=torch.float32, device=device)
+        for r, part in enumerate(every):
+            full[r::WORLD] = part[:len(range(r, n_total, WORLD))]
+        flat = full
+    a = flat.cpu().numpy()
+    return {'pred': a[:, :2 * K].reshape(-1, K, 2), 'gt': a[:, 2 * K:4 * K].reshape(-1, K, 2), 'visible': a[:, 4 * K:5 * K],
+            'maxval': a[:, 5 * K:]}
 
 
 # (flags, kwargs) for every option of the reference's command line (train1.py:602-674: same names, types and
@@ -511,6 +566,13 @@ _OPTIONS = [
     (('--mt-k',), dict(default='all', choices=['all', 'epoch'], help="joints the consistency term compares: 'all' (k = 400) or the "
                       "reference's curriculum with k = epoch (the wrist below 100, one more joint per finger every 100 epochs)")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
+    (('--metrics',), dict(default='pck', choices=['pck', 'full'], help="'full': validation also decodes key points in image pixels "
+                         "and reports the mean end-point error, the PCK curve's AUC and per-group EPEs (on the device, one read at "
+                         "the end); 'pck': the reference's heat-map PCK alone")),
+    (('--decode',), dict(default='argmax', choices=['argmax', 'upsample'], help="key points of --metrics full: 'argmax' = heat-map "
+                        "arg-max times image / heat-map size; 'upsample' = arg-max of the heat-maps up-sampled bilinearly to the "
+                        "image size (compute_uv_from_heatmaps2), in one kernel")),
+    (('--auc-max-px',), dict(default=30.0, type=float, metavar='FLOAT', help='upper end of the PCK thresholds of --metrics full (0 .. this, 31 steps)')),
     (('--device-augment',), dict(action='store_true', help='run the training augmentation chain (rotate, resized crop, colour '
                                   'jitter, blur, normalisation), the validation resize + normalisation and the heat-map labels '
                                   'of both on the GPU, bit-exact with the CPU chains; the loader workers (validation included) '
@@ -525,6 +587,10 @@ class _Parser(argparse.ArgumentParser):
         args = super().parse_args(*a, **kw)
         if getattr(args, 'mt_loss', 'off') == 'on' and getattr(args, 'ema_update', 'off') == 'off':
             self.error('--mt-loss on needs a moving teacher: add --ema-update const (or warmup)')
+        if getattr(args, 'dump_preds', None):
+            args.metrics = 'full'                        # (test.py: predictions are what --metrics full decodes)
+        if getattr(args, 'decode', 'argmax') == 'upsample' and getattr(args, 'metrics', 'pck') != 'full':
+            self.error('--decode upsample decodes the key points of --metrics full: add --metrics full')
         return args
 
 

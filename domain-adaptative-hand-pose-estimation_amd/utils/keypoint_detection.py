@@ -77,3 +77,81 @@ def accuracy(output, target, hm_type='gaussian', thr=0.5):
 def compute_uv_from_heatmaps3(heatmap: torch.Tensor) -> torch.Tensor:
     """Soft-arg-max: softmax(100*hm) expectation of (column, row), times 4 (reference :209-239)."""
     return ops.softargmax(heatmap.detach(), beta=100.0, out_scale=4.0)
+
+
+# ---------------------------------------------------------------- evaluation at image resolution
+def compute_uv_from_heatmaps2(hm, resize_dim):
+    """Arg-max of the heat-maps up-sampled bilinearly to ``resize_dim`` (reference :172-205): (B,K,2) fp32 [x,y] in pixels of
+    that size on the device, zero where the maximum is not positive.  One launch, no up-sampled maps in memory, no
+    synchronisation."""
+    return ops.upsample_argmax(_to_dev(hm), resize_dim)[1]
+
+
+def decode_keypoints(y, image_size, mode='argmax', with_maxval=False):
+    """Key points in image pixels from heat-maps y (B,K,h,w), on the device.  ``argmax``: the heat-map arg-max times
+    image_size / heatmap_size (the scaling the reference's ``visualize`` uses); ``upsample``: compute_uv_from_heatmaps2 at
+    size = image_size."""
+    y = _to_dev(y)
+    if mode == 'argmax':
+        _, xy, mv = ops.argmax2d(y)
+        xy = xy * (float(image_size) / float(y.shape[3]))
+    elif mode == 'upsample':
+        _, xy, mv = ops.upsample_argmax(y, image_size)
+    else:
+        raise ValueError("decode mode must be 'argmax' or 'upsample', got %r" % (mode,))
+    return (xy, mv) if with_maxval else xy
+
+
+def _trapz(y, x):
+    """np.trapz's arithmetic (numpy 2 renamed the function)."""
+    y, x = np.asarray(y, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    return float((np.diff(x) * (y[1:] + y[:-1]) / 2.0).sum())
+
+
+class PoseMetrics:
+    """End-point error in pixels and the PCK curve with its AUC over ``linspace(0, max_px, steps)`` (the RHD / STB 2-D
+    protocol: 0 - 30 px), accumulated on the device: mean joint distance as the reference's ``accuracy_2d`` (:128-136) over the
+    visible joints, thresholded curve and trapezoid AUC as its ``accuracy_3d`` (:95-126).  ``update`` launches one kernel and
+    does not synchronise; ``result`` reads the device once."""
+
+    def __init__(self, num_keypoints, max_px=30.0, steps=31, device='cuda'):
+        self.K, self.max_px = int(num_keypoints), float(max_px)
+        self.thresholds = np.linspace(0.0, self.max_px, int(steps)).astype(np.float32)
+        self.device = torch.device(device)
+        self._state = None
+        if self.device.type == 'cuda':
+            self.thr_dev = torch.from_numpy(self.thresholds).to(self.device)
+            self._state = ops.pose_metrics_state(self.K, len(self.thresholds), self.device)
+
+    def update(self, pred, gt, vis):
+        """pred, gt (B,K,2) in pixels, vis (B,K) or (B,K,1): a joint counts where vis > 0."""
+        ops.pose_metrics(pred, gt, vis, self.thr_dev, self._state)
+
+    def state(self, reduce=None):
+        """(sum_err float64 [K], count int64 [K], hits int64 [K,T]) as numpy: one device read.  ``reduce``: called with the three
+        device accumulators packed into one float64 tensor before the read (the all-reduce over ranks; every value is an integer
+        or a float64 sum, so the packing is exact)."""
+        s, c, h = self._state
+        flat = torch.cat([s, c.double(), h.double().reshape(-1)])
+        if reduce is not None:
+            reduce(flat)
+        flat = flat.cpu().numpy()
+        K, T = self.K, len(self.thresholds)
+        return flat[:K].copy(), flat[K:2 * K].astype(np.int64), flat[2 * K:].astype(np.int64).reshape(K, T)
+
+    def result(self, groups=None, reduce=None, state=None):
+        """{'epe', 'epe_<group>' per entry of ``groups`` (name -> joint indices), 'pck_curve', 'auc', 'thresholds'}.  A data set
+        with no visible joint gives nan.  ``state``: accumulators to evaluate instead of the device's."""
+        sum_err, count, hits = self.state(reduce) if state is None else state
+        sum_err, count, hits = np.asarray(sum_err, np.float64), np.asarray(count, np.int64), np.asarray(hits, np.int64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            n = np.float64(count.sum())
+            out = {'epe': float(sum_err.sum() / n)}
+            for name, ks in (groups or {}).items():
+                ks = list(ks)
+                out['epe_' + name] = float(sum_err[ks].sum() / np.float64(count[ks].sum()))
+            out['pck_curve'] = hits.sum(0) / n
+        thr = self.thresholds.astype(np.float64)
+        out['auc'] = _trapz(out['pck_curve'], thr) / self.max_px
+        out['thresholds'] = self.thresholds
+        return out

@@ -421,6 +421,23 @@ int mi355_bilinear_up(const float* in, float* out, int rows, int h, int w, int H
 int mi355_pck_dists(const float* pred_xy, const float* tgt_xy, float* dists, int rows, float norm_x,
                     float norm_y, void* stream);
 
+/* ---------------------------------------------------------------- evaluation at image resolution (csrc/eval.hip)
+ * upsample_argmax: utils/keypoint_detection.py:172-205 (compute_uv_from_heatmaps2) in one launch.  The arg-max of the VIRTUAL
+ *   map nn.Upsample(size=(H,W), mode='bilinear') (align_corners=False; index / weight rule and expression order of
+ *   mi355_bilinear_up) of hm[rows][h][w], reduced by mi355_argmax2d's rules: first maximum in row-major order of the H x W grid,
+ *   NaN counts as maximum, x = idx % W, y = idx / W, both zeroed when the maximum is <= 0, maxval = the value at idx.  Nothing of
+ *   rows*H*W elements is allocated or written.  Any h, w, H, W >= 1 (H*W < 2^31); H == h and W == w is mi355_argmax2d itself.
+ *   idx / xy / maxval nullable; pointers need 4-byte alignment only (16-byte loads where hm and h*w allow). */
+int mi355_upsample_argmax(const float* hm, int32_t* idx, float* xy, float* maxval, int rows, int h, int w, int H, int W,
+                          void* stream);
+/* pose_metrics: the accumulation behind EPE (accuracy_2d, :128-136) and the PCK curve / AUC (the threshold loop of accuracy_3d,
+ *   :95-126) on pred_xy, gt_xy [B][K][2] and vis [B][K].  sum_err[K], count[K], hits[K][T] are persistent DEVICE accumulators the
+ *   caller zeroes; every call adds to them.  Per joint k, for b = 0 .. B-1 in that order, where vis[b][k] > 0:
+ *     e = sqrt(dx^2 + dy^2) in float64 from the fp32 inputs;  sum_err[k] += e;  count[k] += 1;  hits[k][t] += (e < (double)thr[t])
+ *   (strict).  The float64 sum is sequential in b: the same bits whether a data set arrives in one batch or in many. */
+int mi355_pose_metrics(const float* pred_xy, const float* gt_xy, const float* vis, const float* thr, int T, int B, int K,
+                       double* sum_err, int32_t* count, int32_t* hits, void* stream);
+
 /* ---------------------------------------------------------------- optimiser
  * torch.optim.SGD(momentum, weight_decay, nesterov=True) of train1.py:141-148 over a flat fp32 range:
  *   g' = g + wd*p ; buf = momentum*buf + g' ; p -= lr * (nesterov ? g' + momentum*buf : buf)
