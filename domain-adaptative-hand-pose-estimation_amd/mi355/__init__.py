@@ -119,6 +119,8 @@ SIGNATURES = {
     'mi355_pck_dists': (_I, [_P, _P, _P, _I, _F, _F, _P]),
     'mi355_upsample_argmax': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mi355_pose_metrics': (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'mi355_mirror_batch': (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    'mi355_flip_decode': (_I, [_P, _P, _I, _P, _I, _P, _I, _F, _F, _P, _P, _P, _I, _I, _I, _P]),
     'mi355_sgd_nesterov': (_I, [_P, _P, _P, _L, _P, _F, _F, _I, _P, _P]),
     'mi355_cast_f32': (_I, [_P, _P, _L, _I, _P]),
     'mi355_ema_update': (_I, [_P, _P, _L, _P, _P]),

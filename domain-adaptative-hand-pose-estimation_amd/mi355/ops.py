@@ -852,6 +852,79 @@ def upsample_argmax(hm, size, out=None):
     return idx, xy, mv
 
 
+def mirror_batch(x):
+    """(2B,C,H,W): the batch x (B,C,H,W) fp32 followed by its images mirrored along W -- the input of one flip-test forward."""
+    if x.dim() != 4:
+        raise Mi355Error('mirror_batch: the input must be (B, C, H, W), got %s' % (tuple(x.shape),))
+    x = _hm(x)
+    B, C, H, W = x.shape
+    if min(B, C, H, W) < 1:
+        raise Mi355Error('mirror_batch: empty input %s' % (tuple(x.shape),))
+    out = torch.empty((2 * B, C, H, W), dtype=torch.float32, device=x.device)
+    call('mi355_mirror_batch', ptr(x), ptr(out), B, C, H, W, stream_ptr())
+    return out
+
+
+DECODE_MODES = {'argmax': 0, 'quarter': 1, 'taylor': 2}
+_TAPS = {}
+
+
+def gaussian_taps(sigma):
+    """(fp32 numpy taps [2 r + 1], r) of the smoothing in front of the taylor decode: r = ceil(2.5 sigma),
+    exp(-i^2 / (2 sigma^2)) in float64, normalised to sum 1, rounded to fp32 (11 taps at sigma 2: DARK's kernel)."""
+    import math
+    import numpy as np
+    sigma = float(sigma)
+    if not (sigma > 0 and math.isfinite(sigma)):
+        raise Mi355Error('flip_decode: sigma must be a positive number, got %r' % (sigma,))
+    r = int(math.ceil(2.5 * sigma))
+    if not 1 <= r <= 16:
+        raise Mi355Error('flip_decode: sigma %g gives a smoothing radius of %d, outside 1..16' % (sigma, r))
+    i = np.arange(-r, r + 1, dtype=np.float64)
+    g = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    return (g / g.sum()).astype(np.float32), r
+
+
+def _taps_on(sigma, device):
+    key = (float(sigma), torch.device(device))
+    ent = _TAPS.get(key)
+    if ent is None:
+        g, r = gaussian_taps(sigma)
+        ent = _TAPS[key] = (torch.from_numpy(g).to(device), r)
+    return ent
+
+
+def flip_decode(hm, hm_flip=None, shift=1, mode='argmax', sigma=2.0, scale=(1., 1.), want_avg=False):
+    """Flip-test average and key-point decode in one launch: (idx int32 [B,K], xy fp32 [B,K,2], maxval fp32 [B,K,1], avg or
+    None).  The working map is hm, or 0.5 * (hm + hm_flip mirrored back) where hm_flip holds the heat-maps of the mirrored
+    images (`shift` = 1 moves them one column to the right first, Simple Baselines' SHIFT_HEATMAP); `want_avg` returns it.
+    mode 'argmax' | 'quarter' (a quarter pixel towards the higher neighbour) | 'taylor' (DARK's second-order step on the log of
+    the map smoothed by a Gaussian of `sigma`); xy = (x * scale[0], y * scale[1]) in heat-map pixels times the scales, zero where
+    the maximum is not positive."""
+    hm = _hm(hm)
+    if hm.dim() != 4:
+        raise Mi355Error('flip_decode: heat-maps must be (B, K, h, w), got %s' % (tuple(hm.shape),))
+    B, K, h, w = hm.shape
+    if min(B * K, h, w) < 1 or h * w > 2 ** 31 - 1:
+        raise Mi355Error('flip_decode: %s' % (tuple(hm.shape),))
+    if mode not in DECODE_MODES:
+        raise Mi355Error("flip_decode: mode must be one of %s, got %r" % (sorted(DECODE_MODES), mode))
+    if shift not in (0, 1):
+        raise Mi355Error('flip_decode: shift must be 0 or 1, got %r' % (shift,))
+    if hm_flip is not None:
+        hm_flip = _hm(hm_flip)
+        if tuple(hm_flip.shape) != tuple(hm.shape) or hm_flip.device != hm.device:
+            raise Mi355Error('flip_decode: hm %s on %s vs hm_flip %s on %s' % (tuple(hm.shape), hm.device, tuple(hm_flip.shape), hm_flip.device))
+    taps, radius = _taps_on(sigma, hm.device) if mode == 'taylor' else (None, 0)
+    idx = torch.empty((B, K), dtype=torch.int32, device=hm.device)
+    xy = torch.empty((B, K, 2), dtype=torch.float32, device=hm.device)
+    mv = torch.empty((B, K, 1), dtype=torch.float32, device=hm.device)
+    avg = torch.empty_like(hm) if want_avg else None
+    call('mi355_flip_decode', ptr(hm), ptr(hm_flip), int(shift), ptr(avg), DECODE_MODES[mode], ptr(taps), radius, float(scale[0]),
+         float(scale[1]), ptr(idx), ptr(xy), ptr(mv), B * K, h, w, stream_ptr())
+    return idx, xy, mv, avg
+
+
 def pose_metrics_state(K, T, device):
     """Zeroed accumulators of pose_metrics: (sum_err float64 [K], count int32 [K], hits int32 [K,T])."""
     return (torch.zeros(K, dtype=torch.float64, device=device), torch.zeros(K, dtype=torch.int32, device=device),

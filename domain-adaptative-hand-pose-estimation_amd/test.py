@@ -6,8 +6,11 @@
 
 ``--dump-preds PATH`` (implies ``--metrics full``) writes the predictions of every evaluated split for tools outside this
 script: ``PATH.source.npz``, ``PATH.target.npz`` and, with ``--ema_model``, ``PATH.ema.npz``, each with ``pred`` (N,K,2) and
-``gt`` (N,K,2) in image pixels, ``visible`` (N,K), ``maxval`` (N,K), ``image_size``, ``decode``, ``thresholds`` and the reported
-``epe``, ``auc`` and ``pck_curve``, in data-set order.
+``gt`` (N,K,2) in image pixels, ``visible`` (N,K), ``maxval`` (N,K), ``image_size``, ``decode``, ``flip_test``, ``flip_shift``,
+``thresholds`` and the reported ``epe``, ``auc`` and ``pck_curve``, in data-set order.
+
+``--flip-test`` (with ``--flip-shift {0,1}``) evaluates the average of the heat-maps of every image and its mirror image;
+``--decode quarter|taylor`` decode the key points of ``--metrics full`` to sub-pixel positions.
 """
 import os
 import sys

@@ -6,9 +6,11 @@ out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--mx-eval``
 augmentation chain, the validation resize and the labels of both on the GPU), ``--ema-update {off,const,warmup}`` (keep the
 EMA teacher ``model_ema`` up to date: the reference's commented-out call at train1.py:461), ``--mt-loss {off,on}`` with
 ``--mt-weight`` / ``--mt-k`` (the mean-teacher consistency term on the target batch: the reference's unused ``x_t_ema``, ``m`` and
-``mt_loss``, train1.py:351-364 and uda/model/loss.py:265-297), ``--metrics {pck,full}`` with ``--decode {argmax,upsample}`` and
+``mt_loss``, train1.py:351-364 and uda/model/loss.py:265-297), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
-unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205).
+unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
+sub-pixel decodes ``quarter`` and ``taylor`` are not in the reference), ``--flip-test`` with ``--flip-shift`` (validation averages
+the heat-maps of every image and its mirror image, as Simple Baselines / HRNet evaluate; not in the reference either).
 
     python train1.py data/H3D -t Hand3DStudio --synthetic -a resnet50 -b 64
 
@@ -410,8 +412,14 @@ def validate(val_loader, model, criterion, args, dump=None):
     ``--metrics full``: every batch is also decoded to image pixels (``--decode``) and added to a PoseMetrics against
     ``meta['keypoint2d']`` with ``weight`` as visibility -- launches only, nothing is read per batch; one more line (EPE, AUC)
     and the per-group EPEs are printed at the end.  ``dump`` (a dict, test.py --dump-preds): filled with the predictions of the
-    whole data set in data-set order (rank 0; None elsewhere) and the reported numbers."""
+    whole data set in data-set order (rank 0; None elsewhere) and the reported numbers.
+
+    ``--flip-test``: every batch goes through the network together with its mirror image (FlipForward: one forward of twice the
+    batch) and the two sets of heat-maps are averaged (``--flip-shift``); the loss, the heat-map PCK and the ``--metrics full``
+    decode all use the average.  With ``--metrics full`` the average comes out of the decode's own launch."""
     full = getattr(args, 'metrics', 'pck') == 'full'
+    flip, shift = bool(getattr(args, 'flip_test', False)), int(getattr(args, 'flip_shift', 1))
+    mode = getattr(args, 'decode', 'argmax')
     batch_time, losses = AverageMeter('Time', ':6.3f'), AverageMeter('Loss', ':.2e')
     dataset = val_loader.dataset
     acc = AverageMeterDict(dataset.keypoints_group.keys(), ":3.2f")
@@ -419,8 +427,11 @@ def validate(val_loader, model, criterion, args, dump=None):
     model.eval()
     if getattr(args, 'mx_eval', False):
         mi355.set_mx_eval(True)              # (eval-mode modules only: training forwards are not affected)
-    from mi355.infer import GraphedForward
-    forward = GraphedForward(model)          # full batches replay one HIP graph; the ragged last batch runs eagerly
+    from mi355.infer import FlipForward, GraphedForward
+    forward = (FlipForward if flip else GraphedForward)(model)   # full batches replay one HIP graph; the ragged last batch runs eagerly
+    sigma = getattr(args, 'decode_sigma', None)
+    if sigma is None:
+        sigma = getattr(dataset, 'sigma', 2.0)
     batches = val_loader
     if getattr(getattr(dataset, 'transforms', None), 'labels_on_device', False):
         # DeviceResize data set: packed sources -> HBM, resize + normalisation and the heat-map labels on the GPU
@@ -449,10 +460,19 @@ def validate(val_loader, model, criterion, args, dump=None):
         end = time.time()
         for i, (x, label, weight, meta) in enumerate(batches):
             x, label, weight = x.to(device, non_blocking=True), label.to(device, non_blocking=True), weight.to(device, non_blocking=True)
-            y = forward(x)
+            if flip:
+                y, y_flip = forward(x)
+                if full:
+                    kp, mv, y = decode_keypoints(y, x.shape[3], mode, with_maxval=True, y_flip=y_flip, flip_shift=shift, sigma=sigma,
+                                                 return_avg=True)
+                else:
+                    y = _ops.flip_decode(y, y_flip, shift, want_avg=True)[3]
+            else:
+                y = forward(x)
             pending.append(validate_batch_metrics(y, label, weight, criterion) + (x.size(0), y.shape[2], y.shape[3]))
             if full:
-                kp, mv = decode_keypoints(y, x.shape[3], args.decode, with_maxval=True)
+                if not flip:
+                    kp, mv = decode_keypoints(y, x.shape[3], mode, with_maxval=True, sigma=sigma)
                 gt = torch.as_tensor(meta['keypoint2d']).float().to(device, non_blocking=True)
                 vis = weight.reshape(gt.shape[0], -1)
                 pose.update(kp, gt, vis)
@@ -478,7 +498,7 @@ def validate(val_loader, model, criterion, args, dump=None):
         for name in dataset.keypoints_group:
             print('EPE {}: {:.3f} px'.format(name, res['epe_' + name]))
         if dump is not None:
-            dump.update(_gather_preds(kept, len(dataset), dataset.num_keypoints), image_size=x.shape[3], decode=args.decode,
+            dump.update(_gather_preds(kept, len(dataset), dataset.num_keypoints), image_size=x.shape[3], decode=mode, flip_test=flip, flip_shift=shift,
                         thresholds=res['thresholds'], epe=res['epe'], auc=res['auc'], pck_curve=res['pck_curve'])
     return acc.average()
 
@@ -569,9 +589,17 @@ _OPTIONS = [
     (('--metrics',), dict(default='pck', choices=['pck', 'full'], help="'full': validation also decodes key points in image pixels "
                          "and reports the mean end-point error, the PCK curve's AUC and per-group EPEs (on the device, one read at "
                          "the end); 'pck': the reference's heat-map PCK alone")),
-    (('--decode',), dict(default='argmax', choices=['argmax', 'upsample'], help="key points of --metrics full: 'argmax' = heat-map "
-                        "arg-max times image / heat-map size; 'upsample' = arg-max of the heat-maps up-sampled bilinearly to the "
-                        "image size (compute_uv_from_heatmaps2), in one kernel")),
+    (('--decode',), dict(default='argmax', choices=['argmax', 'upsample', 'quarter', 'taylor'], help="key points of --metrics full: "
+                        "'argmax' = heat-map arg-max times image / heat-map size; 'upsample' = arg-max of the heat-maps up-sampled "
+                        "bilinearly to the image size (compute_uv_from_heatmaps2), in one kernel; 'quarter' = the arg-max moved a "
+                        "quarter heat-map pixel towards its higher neighbour; 'taylor' = the second-order (DARK) step on the log of "
+                        "the smoothed heat-map, exact for Gaussian labels")),
+    (('--decode-sigma',), dict(default=None, type=float, metavar='FLOAT', help="Gaussian of the smoothing in front of --decode taylor "
+                              "(default: the sigma of the data set's labels)")),
+    (('--flip-test',), dict(action='store_true', help='validation / test: average the heat-maps of every image with those of its mirror '
+                           'image (one forward of twice the batch); the loss, the heat-map PCK and the --metrics full decode use the average')),
+    (('--flip-shift',), dict(default=1, type=int, choices=[0, 1], help="columns the mirrored heat-maps move to the right before they "
+                            "are averaged (1: Simple Baselines' SHIFT_HEATMAP, the alignment of a 4x down-sampled map; 0: plain mirror)")),
     (('--auc-max-px',), dict(default=30.0, type=float, metavar='FLOAT', help='upper end of the PCK thresholds of --metrics full (0 .. this, 31 steps)')),
     (('--device-augment',), dict(action='store_true', help='run the training augmentation chain (rotate, resized crop, colour '
                                   'jitter, blur, normalisation), the validation resize + normalisation and the heat-map labels '
@@ -589,8 +617,8 @@ class _Parser(argparse.ArgumentParser):
             self.error('--mt-loss on needs a moving teacher: add --ema-update const (or warmup)')
         if getattr(args, 'dump_preds', None):
             args.metrics = 'full'                        # (test.py: predictions are what --metrics full decodes)
-        if getattr(args, 'decode', 'argmax') == 'upsample' and getattr(args, 'metrics', 'pck') != 'full':
-            self.error('--decode upsample decodes the key points of --metrics full: add --metrics full')
+        if getattr(args, 'decode', 'argmax') != 'argmax' and getattr(args, 'metrics', 'pck') != 'full':
+            self.error('--decode %s decodes the key points of --metrics full: add --metrics full' % args.decode)
         return args
 
 

@@ -87,19 +87,40 @@ def compute_uv_from_heatmaps2(hm, resize_dim):
     return ops.upsample_argmax(_to_dev(hm), resize_dim)[1]
 
 
-def decode_keypoints(y, image_size, mode='argmax', with_maxval=False):
+def decode_keypoints(y, image_size, mode='argmax', with_maxval=False, y_flip=None, flip_shift=1, sigma=2.0, return_avg=False):
     """Key points in image pixels from heat-maps y (B,K,h,w), on the device.  ``argmax``: the heat-map arg-max times
     image_size / heatmap_size (the scaling the reference's ``visualize`` uses); ``upsample``: compute_uv_from_heatmaps2 at
-    size = image_size."""
+    size = image_size; ``quarter``: the arg-max moved a quarter heat-map pixel towards its higher neighbour (Simple Baselines /
+    HRNet ``get_final_preds``); ``taylor``: DARK's second-order step on the log of the map smoothed by a Gaussian of ``sigma``
+    (exact for the Gaussian labels the network is trained on), both times the same scaling.
+
+    ``y_flip``: the heat-maps of the mirrored images (flip test).  They are mirrored back, moved ``flip_shift`` columns to the
+    right (1: Simple Baselines' SHIFT_HEATMAP, which puts the two peaks a quarter heat-map pixel either side of the truth
+    instead of three quarters to one side) and averaged with ``y`` in the decode's own launch; ``upsample`` averages first and
+    decodes the average.  No joint pairs are swapped: a single hand has no left / right pairs.  ``return_avg`` appends the
+    map that was decoded (``y`` itself without ``y_flip``).  Without ``y_flip``, ``argmax`` and ``upsample`` launch what they
+    always did."""
     y = _to_dev(y)
-    if mode == 'argmax':
+    if mode not in ('argmax', 'upsample', 'quarter', 'taylor'):
+        raise ValueError("decode mode must be 'argmax', 'upsample', 'quarter' or 'taylor', got %r" % (mode,))
+    if y_flip is not None:
+        y_flip = _to_dev(y_flip)
+    scale = (float(image_size) / float(y.shape[3]), float(image_size) / float(y.shape[2]))
+    avg = y
+    if mode == 'upsample':
+        if y_flip is not None:
+            avg = ops.flip_decode(y, y_flip, flip_shift, 'argmax', want_avg=True)[3]
+        _, xy, mv = ops.upsample_argmax(avg, image_size)
+    elif mode == 'argmax' and y_flip is None:
         _, xy, mv = ops.argmax2d(y)
         xy = xy * (float(image_size) / float(y.shape[3]))
-    elif mode == 'upsample':
-        _, xy, mv = ops.upsample_argmax(y, image_size)
     else:
-        raise ValueError("decode mode must be 'argmax' or 'upsample', got %r" % (mode,))
-    return (xy, mv) if with_maxval else xy
+        _, xy, mv, a = ops.flip_decode(y, y_flip, flip_shift, mode, sigma, scale, want_avg=return_avg and y_flip is not None)
+        avg = a if a is not None else y
+    out = (xy, mv) if with_maxval else (xy,)
+    if return_avg:
+        out = out + (avg,)
+    return out if len(out) > 1 else out[0]
 
 
 def _trapz(y, x):

@@ -437,6 +437,36 @@ int mi355_upsample_argmax(const float* hm, int32_t* idx, float* xy, float* maxva
  *   (strict).  The float64 sum is sequential in b: the same bits whether a data set arrives in one batch or in many. */
 int mi355_pose_metrics(const float* pred_xy, const float* gt_xy, const float* vis, const float* thr, int T, int B, int K,
                        double* sum_err, int32_t* count, int32_t* hits, void* stream);
+/* mirror_batch: the input half of the flip test of Simple Baselines / HRNet (lib/core/function.py validate(), TEST.FLIP_TEST:
+ *   `input_flipped = np.flip(input, 3)`), for ONE forward of 2B images.  x [B][C][H][W] fp32 contiguous; out has room for 2B
+ *   images: out[b] = x[b], out[B+b][c][y][X] = x[b][c][y][W-1-X].  One launch, 16-byte accesses when W % 4 == 0 and both
+ *   pointers are 16-byte aligned, any W >= 1 otherwise.  x and out must not overlap. */
+int mi355_mirror_batch(const float* x, float* out, int B, int C, int H, int W, void* stream);
+/* flip_decode: the output half of that flip test and the sub-pixel decodes of the same code bases, one workgroup per map
+ *   hm[rows][h][w].  The working map m is hm, or with hm_flip (the heat-maps of the mirrored image)
+ *     m[y][x] = 0.5f * (hm[y][x] + f[y][x]),  f[y][x] = hm_flip[y][w-1-x]                      (shift 0)
+ *                                             f[y][x] = hm_flip[y][w-x], f[y][0] = hm_flip[y][w-1]   (shift 1)
+ *   (function.py `(output + output_flipped) * 0.5` after flip_back; shift 1 is its TEST.SHIFT_HEATMAP
+ *   `output_flipped[:, :, :, 1:] = output_flipped.clone()[:, :, :, 0:-1]`), sum and product rounded separately.  avg_out
+ *   (nullable) receives m.  The arg-max of m follows mi355_argmax2d (first maximum, NaN counts as maximum; idx, maxval as there,
+ *   nullable); at the arg-max (px, py), in heat-map pixels:
+ *     mode 0  no offset;
+ *     mode 1  get_final_preds (lib/core/inference.py): 0.25 * sign(m[py][px+1] - m[py][px-1]) where 1 <= px <= w-2, likewise in
+ *             y; sign(0) = 0, a NaN difference gives 0;
+ *     mode 2  the second-order Taylor step of DARK (Zhang et al., CVPR 2020, "Distribution-Aware Coordinate Representation for
+ *             Human Pose Estimation", eq. 8-10; mmpose post_dark_udp / its taylor()) where 2 <= px <= w-3 and 2 <= py <= h-3:
+ *             S = m smoothed by the separable taps[0 .. 2*radius] (zero padding; fp32, for dy ascending: row = sum over dx
+ *             ascending of taps[dx+radius] * m, tot += taps[dy+radius] * row, every product and sum rounded on its own) at the
+ *             13 points (0,0), (+-1,0), (+-2,0), (0,+-1), (0,+-2), (+-1,+-1); then in float64 L = log(max(S, 1e-10)),
+ *             gx = (L(1,0) - L(-1,0)) / 2, dxx = (L(2,0) - 2 L(0,0) + L(-2,0)) / 4 (gy, dyy likewise),
+ *             dxy = (L(1,1) - L(-1,1) - L(1,-1) + L(-1,-1)) / 4, det = dxx dyy - dxy^2, and where det != 0 and both are finite
+ *             ox = -(dyy gx - dxy gy) / det, oy = -(dxx gy - dxy gx) / det.  DARK's renormalisation of S to the maximum of m
+ *             adds one constant to every L and cancels; it is left out.  radius 1..16; taps is not read in modes 0, 1.
+ *   xy = ((float)(px + ox) * scale_x, (float)(py + oy) * scale_y), (0, 0) unless maxval > 0.  hm_flip == NULL, mode 0, scales 1:
+ *   mi355_argmax2d's bits.  The map is staged in LDS up to 64 KB and read through the caches above; no workgroup waits on
+ *   another.  Pointers need 4-byte alignment only. */
+int mi355_flip_decode(const float* hm, const float* hm_flip, int shift, float* avg_out, int mode, const float* taps, int radius,
+                      float scale_x, float scale_y, int32_t* idx, float* xy, float* maxval, int rows, int h, int w, void* stream);
 
 /* ---------------------------------------------------------------- optimiser
  * torch.optim.SGD(momentum, weight_decay, nesterov=True) of train1.py:141-148 over a flat fp32 range:
