@@ -22,15 +22,33 @@ def is_nhwc(x):
 
 def _chk_room(what, t, need):
     """Raise before any launch when the caller-provided buffer `t` holds fewer than `need` elements: the kernels index it
-    from the problem size alone and would write past its end."""
+    from the problem size alone and would read or write past its end."""
     if t is not None and t.numel() < need:
-        raise Mi355Error('%s: buffer of %d elements, the launch writes %d' % (what, t.numel(), need))
+        raise Mi355Error('%s: buffer of %d elements, the launch indexes %d' % (what, t.numel(), need))
 
 
 def _chk_dev(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise Mi355Error('mi355 ops need CUDA/HIP tensors (got a %s tensor); there is no CPU fallback' % t.device)
+
+
+def _chk_feature(what, t, shape=None):
+    """`t` must be a channels_last (NHWC memory) bf16 / fp32 feature tensor, of logical shape `shape` when given: the kernels
+    index it from the problem size alone."""
+    if t is None:
+        return
+    if not is_nhwc(t):
+        raise Mi355Error('%s: needs a channels_last (NHWC memory) tensor, got shape %s strides %s' % (what, tuple(t.shape), t.stride()))
+    if t.dtype not in (torch.bfloat16, torch.float32):
+        raise Mi355Error('%s: needs a bf16 or fp32 tensor, got %s' % (what, t.dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise Mi355Error('%s: shape %s, the launch indexes %s' % (what, tuple(t.shape), tuple(shape)))
+
+
+def _chk_heatmap(what, t):
+    if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise Mi355Error('%s: needs a contiguous fp32 (N, K, H, W) heat-map, got %s %s strides %s' % (what, t.dtype, tuple(t.shape), t.stride()))
 
 
 def to_nhwc(x, dtype=None, cpad=None):
@@ -650,6 +668,8 @@ def bn_resident_check(where=''):
 
 
 def maxpool_fwd(x):
+    _chk_dev(x)
+    _chk_feature('maxpool_fwd x', x)
     N, C, H, W = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = nhwc_empty(N, C, Ho, Wo, x.dtype, x.device)
@@ -660,6 +680,12 @@ def maxpool_fwd(x):
 
 def maxpool_bwd(dy, arg, in_shape):
     N, C, H, W = in_shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    _chk_dev(dy, arg)
+    _chk_feature('maxpool_bwd dy', dy, (N, C, Ho, Wo))
+    if arg.dtype != torch.uint8 or not arg.is_contiguous():
+        raise Mi355Error('maxpool_bwd arg: needs the contiguous uint8 window codes of maxpool_fwd, got %s strides %s' % (arg.dtype, arg.stride()))
+    _chk_room('maxpool_bwd arg', arg, N * Ho * Wo * C)
     dx = nhwc_empty(N, C, H, W, dy.dtype, dy.device)
     call('mi355_maxpool_bwd', ptr(dy), ptr(arg), ptr(dx), N, H, W, C, dtype_code(dy.dtype), stream_ptr())
     return dx
@@ -676,15 +702,31 @@ def conv1x1_heatmap(x, w_packed, bias, K):
 
 def pw_c2k(x, w, bias, K, w_transposed=False):
     """x channels_last [N,C,H,W] -> heat-map [N,K,H,W] fp32 contiguous."""
+    _chk_dev(x, w, bias)
+    _chk_feature('pw_c2k x', x)
     N, C, H, W = x.shape
+    _chk_room('pw_c2k w', w, K * C)
+    _chk_room('pw_c2k bias', bias, K)
     y = torch.empty((N, K, H, W), dtype=torch.float32, device=x.device)
     call('mi355_pw_c2k', ptr(x), ptr(w), ptr(bias), ptr(y), N, H * W, C, K, int(w_transposed), dtype_code(x.dtype),
          stream_ptr())
     return y
 
 
+def _chk_k2c(what, y, w, bias, C, dtype, residual, scale_dev):
+    _chk_dev(y, w, bias, residual, scale_dev)
+    _chk_heatmap(what + ' y', y)
+    N, K, H, W = y.shape
+    _chk_room(what + ' w', w, K * C)
+    _chk_room(what + ' bias', bias, C)
+    _chk_feature(what + ' residual', residual, (N, C, H, W))
+    if residual is not None and residual.dtype != dtype:
+        raise Mi355Error('%s residual: %s, the output is %s' % (what, residual.dtype, dtype))
+
+
 def pw_k2c(y, w, bias, C, dtype, residual=None, scale_dev=None, w_transposed=False):
     """heat-map [N,K,H,W] fp32 -> channels_last [N,C,H,W] `dtype`."""
+    _chk_k2c('pw_k2c', y, w, bias, C, dtype, residual, scale_dev)
     N, K, H, W = y.shape
     out = nhwc_empty(N, C, H, W, dtype, y.device)
     call('mi355_pw_k2c', ptr(y), ptr(w), ptr(bias), ptr(residual), ptr(scale_dev), ptr(out), N, H * W, C, K,
@@ -694,6 +736,7 @@ def pw_k2c(y, w, bias, C, dtype, residual=None, scale_dev=None, w_transposed=Fal
 
 def pw_k2c_stats(y, w, bias, C, dtype, residual=None):
     """pw_k2c + BatchNorm statistics partials of its output.  Returns (out, (partial, nslices))."""
+    _chk_k2c('pw_k2c_stats', y, w, bias, C, dtype, residual, None)
     N, K, H, W = y.shape
     out = nhwc_empty(N, C, H, W, dtype, y.device)
     ns_max = N * ((H * W + 63) // 64)
@@ -705,8 +748,13 @@ def pw_k2c_stats(y, w, bias, C, dtype, residual=None):
 
 
 def pw_wgrad(x, y, dw, kc_layout, accumulate):
+    _chk_dev(x, y, dw)
+    _chk_feature('pw_wgrad x', x)
+    _chk_heatmap('pw_wgrad y', y)
     N, C, H, W = x.shape
     K = y.shape[1]
+    if (y.shape[0], y.shape[2], y.shape[3]) != (N, H, W):
+        raise Mi355Error('pw_wgrad y: shape %s does not match the features %s' % (tuple(y.shape), tuple(x.shape)))
     _chk_room('pw_wgrad dw', dw, C * K)
     ws = workspace(load().mi355_pw_wgrad_workspace(N, H * W, C, K), x.device)
     call('mi355_pw_wgrad', ptr(x), ptr(y), ptr(dw), int(kc_layout), int(accumulate), N, H * W, C, K,
@@ -955,6 +1003,7 @@ def pose_metrics(pred, gt, vis, thr, state):
 
 # ---------------------------------------------------------------- optimiser
 def sgd_nesterov(p, g, buf, lr_dev, momentum, wd, nesterov, p_lowp=None):
+    _chk_dev(p, g, buf, lr_dev, p_lowp)
     for what, t in (('g', g), ('buf', buf), ('p_lowp', p_lowp)):
         _chk_room('sgd_nesterov ' + what, t, p.numel())
     call('mi355_sgd_nesterov', ptr(p), ptr(g), ptr(buf), p.numel(), ptr(lr_dev), float(momentum), float(wd),
@@ -962,6 +1011,7 @@ def sgd_nesterov(p, g, buf, lr_dev, momentum, wd, nesterov, p_lowp=None):
 
 
 def cast_f32(src, dst):
+    _chk_dev(src, dst)
     _chk_room('cast_f32 dst', dst, src.numel())
     call('mi355_cast_f32', ptr(src), ptr(dst), src.numel(), dtype_code(dst.dtype), stream_ptr())
 
