@@ -127,6 +127,8 @@ SIGNATURES = {
     'mi355_ema_update_batched': (_I, [_P, _I, _I, _P, _P]),
     'mi355_bn_fold_batched': (_I, [_P, _P, _I, _I, _P]),
     'mi355_mse_heatmap': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'mi355_mmd_workspace': (_Z, [_I, _I]),
+    'mi355_mmd_heatmap': (_I, [_P, _P, _P, _Z, _P, _P, _P, _I, _I, _I, _F, _I, _F, _F, _P]),
     'mi355_augment_workspace': (_Z, [_I, _I]),
     'mi355_augment': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'mi355_resize_normalize': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P]),
@@ -236,6 +238,25 @@ def graph_capture_mode():
         time.sleep(0.2)
         return 'thread_local'
     return 'global'
+
+
+class no_gc_in_capture:
+    """Around every graph capture of this package.  A DAStep that is dropped -- with its model, its captured graphs and their
+    memory pool -- is a reference cycle (the stage hooks on the model point back at it) and dies only when Python's cyclic
+    collector runs.  torch.cuda.graph no longer collects on entry, so an automatic collection can land in the middle of a
+    capture, and a finalizer that destroys another graph or releases its pool there aborts the process (seen in the test
+    suite, where earlier modules leave such steps behind).  Collect before the capture, keep the collector off during it."""
+
+    def __enter__(self):
+        import gc
+        gc.collect()
+        self.was_enabled = gc.isenabled()
+        gc.disable()
+
+    def __exit__(self, *exc):
+        if self.was_enabled:
+            import gc
+            gc.enable()
 
 
 def compute_dtype():

@@ -122,11 +122,27 @@ def broadcast_module(module, src=0):
         dist.broadcast(d, src)
 
 
+class MMDAlign:
+    """What ``DAStep(mmd=...)`` takes: step C's loss gains ``weight * MMD_loss3(y_s.detach(), y_t)`` (reference
+    uda/model/loss.py:1061-1104), the per-joint multi-kernel MMD between the source heat-maps of step A and the target heat-maps
+    of the main head.  The weight rides inside the kernels (``scale=``); only the target side gets a gradient."""
+
+    def __init__(self, weight=0.1, kernel_mul=2.0, kernel_num=5):
+        from uda.model.loss import MMD_loss3
+        if not weight > 0:
+            raise ValueError('MMDAlign: the weight must be positive, got %r' % (weight,))
+        self.weight = float(weight)
+        self.crit = MMD_loss3(kernel_mul=kernel_mul, kernel_num=kernel_num)
+
+    def term(self, y_s, y_t):
+        return self.crit(y_s.detach(), y_t, scale=self.weight)
+
+
 class DAStep:
     """Holds the static batch buffers and runs A/B/C.  ``optimizers`` = dict with keys f, h, h_adv, h_adv2,
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
-    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None):
+    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         self.ema = ema               # optional mi355.optim.EMATeacher: updated behind step C's optimizer (train1.py:461)
         # optional mi355.teacher.MeanTeacher: step C's loss gains m * mt_loss(y_t, model_ema(x_t_ema)) (train1.py:351-364,
@@ -134,6 +150,9 @@ class DAStep:
         self.mt = mt
         if mt is not None and self.ema is None:
             self.ema = mt.ema
+        # optional MMDAlign: step C's loss gains w * MMD_loss3(y_s.detach(), y_t) (uda/model/loss.py:1061-1104), y_s = the
+        # heat-maps step A left in self.out['y_s']
+        self.mmd = mmd
         self.trade_off, self.skip, self.track_acc = trade_off, skip_discarded, track_accuracy
         self.graphs = None
         self.out = {}
@@ -234,8 +253,8 @@ class DAStep:
                 f_t = m.features(b['x_t'])
                 y_t_grad = m.head(f_t)
                 y_t = y_t_grad.detach()           # only ever used detached (pseudo-labels) in B and C ...
-                if self.mt is None:
-                    y_t_grad = None               # ... but for the consistency term of step C: else the head's graph is freed here
+                if self.mt is None and self.mmd is None:
+                    y_t_grad = None               # ... but for the consistency / MMD term of step C: else the head's graph is freed here
             self._shared = (f_t, y_t, y_t_grad)
             y_t_adv, y_t_adv2, y_t_adv3 = m.adv_heads(f_t.detach())
         else:
@@ -281,6 +300,12 @@ class DAStep:
                 x_ema = b['x_t_ema'] if b.get('x_t_ema') is not None else b['x_t']
                 loss_mt = self.mt.term(y_t_grad, x_ema)
             total = loss_gt if loss_mt is None else loss_gt + loss_mt
+            loss_mmd = None
+            if self.mmd is not None:
+                # as with the mean teacher: only optimizer_f steps in C, the main head's weight gradients are discarded.  y_s lives
+                # in self.out since step A (under capture: produced in the first graph, its storage held by that reference)
+                loss_mmd = self.mmd.term(self.out['y_s'], y_t_grad)
+                total = total + loss_mmd
             with _rt.grouped_wgrads():
                 total.backward(_rt.unit_grad(total))
             _rt.join_side()
@@ -291,6 +316,8 @@ class DAStep:
         self.out.update(loss_gt=loss_gt.detach(), y_t=y_t.detach(), y_t_adv=y_t_adv.detach())
         if loss_mt is not None:
             self.out.update(loss_mt=loss_mt.detach())
+        if loss_mmd is not None:
+            self.out.update(loss_mmd=loss_mmd.detach())
 
     def _update_C(self):
         self.opt['f'].step()
@@ -395,11 +422,12 @@ class DAStep:
         segs = [seg_a, self._update_A, seg_b, self._update_B, seg_c, lambda: (self._update_C(), self._accuracy(self.static))]
         mode = _rt.graph_capture_mode()        # 'thread_local' beside an RCCL process group (its watchdog thread polls events)
         graphs = []
-        for fn in segs:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=mode):
-                fn()
-            graphs.append(g)
+        with _rt.no_gc_in_capture():
+            for fn in segs:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=pool, capture_error_mode=mode):
+                    fn()
+                graphs.append(g)
         self.graphs = graphs          # capturing executes nothing: model / optimizer state is unchanged
         return self
 

@@ -4,7 +4,7 @@ needs to run; replayed it is one graph launch.  ``FlipForward`` is the flip test
 graph) and ``PosePredictor`` the one-call interface on top: normalised images in, key points in image pixels out."""
 import torch
 
-from . import compute_dtype, fp8_convs, graph_capture_mode, mx_eval, nn as _nn
+from . import compute_dtype, fp8_convs, graph_capture_mode, mx_eval, nn as _nn, no_gc_in_capture
 
 
 class GraphedForward:
@@ -42,7 +42,7 @@ class GraphedForward:
             sx = x.clone()
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
-            with torch.cuda.graph(g, capture_error_mode=graph_capture_mode()):
+            with no_gc_in_capture(), torch.cuda.graph(g, capture_error_mode=graph_capture_mode()):
                 sy = self.model(sx)
             ent = self._graphs[key] = (g, sx, sy)
         g, sx, sy = ent

@@ -1133,6 +1133,61 @@ def mse_heatmap(pred, target, rec, want_grad, rows=None, grad=None):
     return rows, (grad if want_grad else None)
 
 
+# ---------------------------------------------------------------- MMD alignment (csrc/mmd.hip)
+MMD_MAX_ROWS, MMD_MAX_KERNELS = 256, 8
+_mmd_ws = {}
+
+
+def _mmd_workspace(device, B, K):
+    """The (K, n, n) fp32 distance / coefficient matrices of mmd_heatmap, one buffer per shape: a captured graph that contains the
+    launches keeps seeing the address it was captured with.  Allocated outside graph capture only (warm up before capturing)."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), B, K)
+    buf = _mmd_ws.get(key)
+    if buf is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise Mi355Error('mmd_heatmap: the workspace for B=%d K=%d would be allocated during graph capture: warm up first' % (B, K))
+        nbytes = load().mi355_mmd_workspace(B, K)
+        if nbytes == 0:
+            raise Mi355Error('mmd_heatmap: B=%d K=%d refused (1 <= B, n = 2 B <= %d rows, 1 <= K)' % (B, K, MMD_MAX_ROWS))
+        buf = _mmd_ws[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    return buf
+
+
+def mmd_heatmap(source, target, want_source_grad, want_target_grad, kernel_mul=2.0, kernel_num=5, fix_sigma=None, scale=1.0,
+                rows=None, grad_source=None, grad_target=None):
+    """Per-joint multi-kernel MMD of source, target (B, K, H, W) or (B, K, HW), fp32 with every row (b, k) contiguous.  Returns
+    (rows [K] = loss_k, grad_source or None, grad_target or None); the scalar loss is reduce_sum(rows, scale / K) and the gradients
+    are d(that scalar) / d source and / d target.  A side whose gradient is not wanted is neither allocated nor written."""
+    _chk_dev(source, target)
+    for what, t in (('source', source), ('target', target)):
+        if t.dim() not in (3, 4) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise Mi355Error('mmd_heatmap: %s must be a contiguous fp32 (B, K, HW) or (B, K, H, W) tensor, got %s %s strides %s'
+                             % (what, t.dtype, tuple(t.shape), t.stride()))
+    if tuple(source.shape) != tuple(target.shape):
+        raise Mi355Error('mmd_heatmap: source %s vs target %s: the kernel matrix is sliced by one batch size' % (tuple(source.shape), tuple(target.shape)))
+    B, K = source.shape[:2]
+    HW = source[0, 0].numel() if B and K else 0
+    work = _mmd_workspace(source.device, B, K)
+    n = 2 * B
+    if rows is None:
+        rows = torch.empty((K,), dtype=torch.float32, device=source.device)
+    if want_source_grad and grad_source is None:
+        grad_source = torch.empty_like(source)
+    if want_target_grad and grad_target is None:
+        grad_target = torch.empty_like(target)
+    _chk_dev(rows, grad_source, grad_target)
+    _chk_room('mmd_heatmap source', source, B * K * HW)
+    _chk_room('mmd_heatmap target', target, B * K * HW)
+    _chk_room('mmd_heatmap work', work, K * n * n)
+    _chk_room('mmd_heatmap rows', rows, K)
+    _chk_room('mmd_heatmap grad_source', grad_source if want_source_grad else None, B * K * HW)
+    _chk_room('mmd_heatmap grad_target', grad_target if want_target_grad else None, B * K * HW)
+    call('mi355_mmd_heatmap', ptr(source), ptr(target), ptr(work), work.numel() * 4, ptr(rows),
+         ptr(grad_source) if want_source_grad else 0, ptr(grad_target) if want_target_grad else 0, int(B), int(K), int(HW),
+         float(kernel_mul), int(kernel_num), float(fix_sigma) if fix_sigma else 0.0, float(scale), stream_ptr())
+    return rows, (grad_source if want_source_grad else None), (grad_target if want_target_grad else None)
+
+
 # ---------------------------------------------------------------- kernel timer (bench.py roofline)
 def spin_us(us):
     call('mi355_spin_us', int(us), stream_ptr())

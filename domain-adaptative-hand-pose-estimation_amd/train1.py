@@ -6,7 +6,9 @@ out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--mx-eval``
 augmentation chain, the validation resize and the labels of both on the GPU), ``--ema-update {off,const,warmup}`` (keep the
 EMA teacher ``model_ema`` up to date: the reference's commented-out call at train1.py:461), ``--mt-loss {off,on}`` with
 ``--mt-weight`` / ``--mt-k`` (the mean-teacher consistency term on the target batch: the reference's unused ``x_t_ema``, ``m`` and
-``mt_loss``, train1.py:351-364 and uda/model/loss.py:265-297), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
+``mt_loss``, train1.py:351-364 and uda/model/loss.py:265-297), ``--mmd-loss {off,on}`` with ``--mmd-weight`` / ``--mmd-kernels`` /
+``--mmd-mul`` (MMD alignment of the target heat-maps with the source heat-maps in step C: the reference's unused ``MMD_loss3``,
+uda/model/loss.py:1061-1104), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
 sub-pixel decodes ``quarter`` and ``taylor`` are not in the reference), ``--flip-test`` with ``--flip-shift`` (validation averages
@@ -204,6 +206,10 @@ def main(args):
         # step C gains m * mt_loss(y_t, model_ema(x_t_ema)) (train1.py:351-364); the teacher runs inside the iteration
         from mi355.teacher import MeanTeacher
         step.mt = MeanTeacher(ema, weight=args.mt_weight, k=args.mt_k)
+    if args.mmd_loss == 'on':
+        # step C gains w * MMD_loss3(y_s.detach(), y_t) (uda/model/loss.py:1061-1104): a non-adversarial alignment term
+        from mi355.da_step import MMDAlign
+        step.mmd = MMDAlign(weight=args.mmd_weight, kernel_mul=args.mmd_mul, kernel_num=args.mmd_kernels)
     start_epoch = 0
     if args.resume is None:
         if args.pretrain is None or (args.synthetic and not os.path.exists(args.pretrain)):
@@ -344,6 +350,9 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     if mt is not None:
         mt.set_epoch(epoch)                              # m and k are functions of the epoch (train1.py:351-353)
         names, fmts = names + ['Loss (mt)'], fmts + [':.2e']
+    mmd = getattr(step, 'mmd', None)
+    if mmd is not None:
+        names, fmts = names + ['Loss (mmd)'], fmts + [':.2e']
     meters = [AverageMeter(n, f) for n, f in zip(names, fmts)]
     progress = ProgressMeter(args.iters_per_epoch, meters, prefix="Epoch: [{}]".format(epoch))
     end = time.time()
@@ -389,6 +398,8 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
                 a, c = _pck(out[k]); m.update(a, c)
             if mt is not None:
                 meters[9].update(float(out['loss_mt']), args.batch_size)
+            if mmd is not None:
+                meters[-1].update(float(out['loss_mmd']), args.batch_size)
             meters[0].update(time.time() - end)
             progress.display(i)
         end = time.time()
@@ -585,6 +596,12 @@ _OPTIONS = [
                            "reference schedule (0.01 * epoch, 0.3 once epoch > 30), a number a constant")),
     (('--mt-k',), dict(default='all', choices=['all', 'epoch'], help="joints the consistency term compares: 'all' (k = 400) or the "
                       "reference's curriculum with k = epoch (the wrist below 100, one more joint per finger every 100 epochs)")),
+    (('--mmd-loss',), dict(default='off', choices=['off', 'on'], help="MMD alignment of the target heat-maps with the source heat-maps: "
+                          "step C's loss gains w * MMD_loss3(y_s.detach(), y_t), the per-joint multi-Gaussian-kernel MMD of "
+                          "uda/model/loss.py:1061-1104, computed by the mmd_ kernels; 'off': nothing is launched")),
+    (('--mmd-weight',), dict(default=0.1, type=float, metavar='FLOAT', help='weight w of the MMD term (constant, positive)')),
+    (('--mmd-kernels',), dict(default=5, type=int, metavar='N', help='Gaussian kernels of the MMD term (1 .. 8)')),
+    (('--mmd-mul',), dict(default=2.0, type=float, metavar='FLOAT', help='ratio of successive kernel bandwidths of the MMD term')),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--metrics',), dict(default='pck', choices=['pck', 'full'], help="'full': validation also decodes key points in image pixels "
                          "and reports the mean end-point error, the PCK curve's AUC and per-group EPEs (on the device, one read at "
@@ -615,6 +632,15 @@ class _Parser(argparse.ArgumentParser):
         args = super().parse_args(*a, **kw)
         if getattr(args, 'mt_loss', 'off') == 'on' and getattr(args, 'ema_update', 'off') == 'off':
             self.error('--mt-loss on needs a moving teacher: add --ema-update const (or warmup)')
+        if getattr(args, 'mmd_loss', 'off') == 'on':
+            if not args.mmd_weight > 0:
+                self.error('--mmd-weight must be positive, got %r' % (args.mmd_weight,))
+            if not 1 <= args.mmd_kernels <= 8:
+                self.error('--mmd-kernels must be 1 .. 8, got %d' % args.mmd_kernels)
+            if not args.mmd_mul > 0:
+                self.error('--mmd-mul must be positive, got %r' % (args.mmd_mul,))
+            if args.batch_size > 128:
+                self.error('--mmd-loss on takes at most 128 images per domain and GPU (the kernels hold n = 2 B <= 256 rows), got -b %d' % args.batch_size)
         if getattr(args, 'dump_preds', None):
             args.metrics = 'full'                        # (test.py: predictions are what --metrics full decodes)
         if getattr(args, 'decode', 'argmax') != 'argmax' and getattr(args, 'metrics', 'pck') != 'full':

@@ -1,6 +1,8 @@
 """``JointsKLLoss`` (reference ``uda/model/loss.py:115-158``) as one fused row kernel: log-softmax,
 target normalisation, KL sum, weighting and the gradient w.r.t. the prediction in a single pass; ``mt_loss`` (reference
-``uda/model/loss.py:265-297``), the mean-teacher consistency term, as one masked squared-difference row kernel."""
+``uda/model/loss.py:265-297``), the mean-teacher consistency term, as one masked squared-difference row kernel; ``MMD_loss3``,
+``MMD_loss`` and ``mmd_rbf`` (reference ``uda/model/loss.py:1061-1196``), the multi-kernel MMD between a source and a target
+batch, as three launches that never form the reference's n x n x HW temporaries."""
 import torch
 import torch.nn as nn
 
@@ -129,3 +131,79 @@ def mt_loss(pre, label, weight, k):
     if crit is None:
         crit = _mt_cache[key] = MeanTeacherLoss(pre.device).set(1.0, k, (B, K, H, W))
     return crit(pre, label)
+
+
+# ---------------------------------------------------------------- MMD alignment (reference uda/model/loss.py:1061-1196)
+class _MMDFn(torch.autograd.Function):
+    """loss = scale * mean over joints of the multi-kernel MMD between source and target (B, K, HW).  As _KLFn: the kernels
+    write d loss / d source and / d target in the forward, for whichever of the two needs a gradient (the other side is
+    neither allocated nor written); the backward hands them on when the incoming gradient is the unit scalar.  The bandwidth
+    is a constant for the gradient, as the reference's ``.data`` makes it."""
+
+    @staticmethod
+    def forward(ctx, source, target, kernel_mul, kernel_num, fix_sigma, scale):
+        rows, gs, gt = ops.mmd_heatmap(source, target, ctx.needs_input_grad[0], ctx.needs_input_grad[1], kernel_mul, kernel_num,
+                                       fix_sigma, scale)
+        ctx.save_for_backward(gs, gt)
+        return ops.reduce_sum(rows, float(scale) / rows.numel())
+
+    @staticmethod
+    def backward(ctx, gout):
+        gs, gt = ctx.saved_tensors
+        if gout is None or (gs is None and gt is None):
+            return None, None, None, None, None, None
+        if not _rt.is_unit_grad(gout):
+            gout = gout.contiguous().float()
+            gs, gt = (None if g is None else ops.scale_by_dev(g, gout) for g in (gs, gt))
+        return gs, gt, None, None, None, None
+
+
+def _mmd_operand(t):
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def _mmd(source, target, kernel_mul, kernel_num, fix_sigma, scale):
+    if tuple(source.shape) != tuple(target.shape):
+        raise ValueError('MMD: source %s and target %s must have the same shape (the kernel matrix is sliced by one batch size)'
+                         % (tuple(source.shape), tuple(target.shape)))
+    return _MMDFn.apply(_mmd_operand(source), _mmd_operand(target), float(kernel_mul), int(kernel_num), fix_sigma, float(scale))
+
+
+class MMD_loss3(nn.Module):
+    """Per joint, the multi-Gaussian-kernel MMD between the batch of source heat-maps and the batch of target heat-maps
+    (B, K, H, W), averaged over the joints (reference ``uda/model/loss.py:1061-1104``).
+
+    ``scale`` (extension, default 1 = reference): coefficient of this term in the total loss, folded into the kernels.
+    Extension: a joint whose 2 B maps are all identical has bandwidth 0, for which the reference returns NaN (0 / 0); here it
+    contributes loss 0 and zero gradients -- the rule ``guard_empty_maps`` (regda_7.py) applies to empty pseudo-label maps."""
+
+    def __init__(self, kernel_mul=2.0, kernel_num=5):
+        super().__init__()
+        self.kernel_num = kernel_num
+        self.kernel_mul = kernel_mul
+        self.fix_sigma = None
+
+    def forward(self, source, target, scale=1.0):
+        if source.dim() != 4:
+            raise ValueError('MMD_loss3: (B, K, H, W) heat-maps, got %s' % (tuple(source.shape),))
+        return _mmd(source, target, self.kernel_mul, self.kernel_num, self.fix_sigma, scale)
+
+
+def mmd_rbf(source, target, kernel_mul=2.0, kernel_num=5, fix_sigma=None, scale=1.0):
+    """The reference's ``mmd_rbf`` (``uda/model/loss.py:1140-1161``) on (n, D) features: the same kernels with K = 1."""
+    if source.dim() != 2:
+        raise ValueError('mmd_rbf: (n, D) features, got %s' % (tuple(source.shape),))
+    return _mmd(source.unsqueeze(1), target.unsqueeze(1), kernel_mul, kernel_num, fix_sigma, scale)
+
+
+class MMD_loss(nn.Module):
+    """Multi-kernel MMD between (n, D) source and target features (reference ``uda/model/loss.py:1164-1196``)."""
+
+    def __init__(self, kernel_mul=2.0, kernel_num=5):
+        super().__init__()
+        self.kernel_num = kernel_num
+        self.kernel_mul = kernel_mul
+        self.fix_sigma = None
+
+    def forward(self, source, target, scale=1.0):
+        return mmd_rbf(source, target, self.kernel_mul, self.kernel_num, self.fix_sigma, scale)

@@ -182,6 +182,8 @@ class _Disparity(nn.Module):
     kind = 1          # ground-false rule of the builder kernel
     normalise = True  # per-map division by its maximum
     guard_empty_maps = False   # extension (off = reference): leave an all-zero ground-false map at zero instead of 0/0 = NaN
+    # (the same rule, always on, in uda.model.loss.MMD_loss3: a joint whose 2 B maps are identical has bandwidth 0, for which the
+    #  reference returns 0/0 = NaN; it contributes loss 0 and zero gradients instead)
 
     def __init__(self, pseudo_label_generator, criterion: nn.Module):
         super().__init__()

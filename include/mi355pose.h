@@ -522,6 +522,34 @@ typedef struct mi355_mse_rec { int32_t joint_mask; float grad_scale; } mi355_mse
 int mi355_mse_heatmap(const float* pred, const float* target, const mi355_mse_rec* rec_dev, float* rows, float* unit_grad,
                       int B, int K, int HW, void* stream);
 
+/* ---------------------------------------------------------------- MMD alignment (csrc/mmd.hip)
+ * MMD_loss3 of uda/model/loss.py:1061-1104 (per joint, the multi-Gaussian-kernel MMD between a batch of source and a batch of
+ * target heat-maps; with K = 1 the MMD_loss / mmd_rbf of uda/model/loss.py:1107-1196 on (n, D) features) and its gradient, on
+ * fp32 source, target [B][K][HW] (row (b, k) contiguous; the same B on both sides), without the n x n x HW temporaries of the
+ * reference's expression.  n = 2 B <= MI355_MMD_MAX_ROWS; rows x_0 .. x_{n-1} of joint k are source[0..B)[k], then
+ * target[0..B)[k].  Three launches (two when both gradient pointers are null):
+ *   mmd_dist  D[k][i][j] = sum_p (x_i[p] - x_j[p])^2, the difference form; every unordered pair once, written to both places
+ *             (D symmetric bit for bit), D[k][i][i] = 0; into `work`
+ *   mmd_coef  bw = sum_ij D_ij / (n^2 - n), or fix_sigma when fix_sigma > 0;  bw /= kernel_mul^(kernel_num / 2);
+ *             bw_m = bw * kernel_mul^m, m < kernel_num;  Kmat_ij = sum_m exp(-D_ij / bw_m);
+ *             loss_rows[k] = (1 / B^2) sum_{a,b<B} ((Kmat[a][b] + Kmat[B+a][B+b]) - Kmat[a][B+b]) - Kmat[B+a][b];
+ *             `work` is overwritten with c_ij = s_ij * scale / (B^2 K) * sum_m (-1 / bw_m) exp(-D_ij / bw_m), s_ij = +1 inside a
+ *             domain, -1 across
+ *   mmd_grad  grad[i][p] = 4 sum_j c_ij (x_i[p] - x_j[p])  = d (scale * mean_k loss_rows[k]) / d x_i[p], the bandwidth taken as
+ *             a constant (`.data` in the reference); grad_source [B][K][HW] and grad_target [B][K][HW] are each nullable: a null
+ *             pointer means that side is detached and nothing is written for it
+ * The scalar loss is mi355_reduce_sum(loss_rows, scale / K).  A joint whose distances are ALL zero has bw = 0 and the reference
+ * returns NaN (0 / 0); here it contributes loss_rows[k] = 0 and zero gradient rows (as `guard_empty_maps` does for empty maps).
+ * work: mi355_mmd_workspace(B, K) bytes (K n^2 floats; 0 when the shape is refused).  Pointers need 4-byte alignment; 16-byte
+ * accesses are used when HW % 4 == 0 and the bases allow.  1 <= kernel_num <= MI355_MMD_MAX_KERNELS, kernel_mul > 0, K <= 65535,
+ * HW <= 2^30.  Deterministic: no atomics, fixed summation orders.  Never allocates; capturable. */
+#define MI355_MMD_MAX_ROWS 256
+#define MI355_MMD_MAX_KERNELS 8
+size_t mi355_mmd_workspace(int B, int K);
+int mi355_mmd_heatmap(const float* source, const float* target, float* work, size_t work_bytes, float* loss_rows,
+                      float* grad_source, float* grad_target, int B, int K, int HW, float kernel_mul, int kernel_num,
+                      float fix_sigma, float scale, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
