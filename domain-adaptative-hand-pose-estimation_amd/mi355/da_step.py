@@ -138,11 +138,40 @@ class MMDAlign:
         return self.crit(y_s.detach(), y_t, scale=self.weight)
 
 
+class JointFeatureAlign:
+    """What ``DAStep(jfa=...)`` takes: step C's loss gains ``weight * loss3(f_t, <desc_s>, xy_t, .)`` (reference
+    uda/model/loss.py:331-378), the KL divergence between the channel distributions of the neck output pooled around the
+    predicted key points of the target batch and of the source batch.  Step A keeps only the source descriptors (B, K, C) fp32;
+    the key points are the device arg-max of the detached heat-maps; only the target features get a gradient.  The weight rides
+    inside the kernels (``scale=``)."""
+
+    def __init__(self, weight=1.0, radius=6, axes='xy'):
+        if not weight > 0:
+            raise ValueError('JointFeatureAlign: the weight must be positive, got %r' % (weight,))
+        if not 1 <= int(radius) <= 16 or int(radius) != radius:
+            raise ValueError('JointFeatureAlign: the radius must be 1 .. 16, got %r' % (radius,))
+        if axes not in ops.JFA_AXES:
+            raise ValueError("JointFeatureAlign: axes must be 'xy' or 'ref', got %r" % (axes,))
+        self.weight, self.radius, self.axes = float(weight), int(radius), axes
+
+    def source(self, f_s, y_s):
+        """Step A: the descriptors of the source batch, detached."""
+        from uda.model.regda_4 import cached_centres
+        return ops.joint_pool(f_s.detach(), cached_centres(y_s), self.radius, self.axes)
+
+    def term(self, f_t, desc_s, y_t):
+        """Step C: (the term, the target descriptors it was computed from)."""
+        from uda.model.loss import loss1, joint_kl_loss
+        from uda.model.regda_4 import cached_centres
+        desc_t = loss1(f_t, cached_centres(y_t), self.radius, self.axes)
+        return joint_kl_loss(desc_t, desc_s, self.weight), desc_t.detach()
+
+
 class DAStep:
     """Holds the static batch buffers and runs A/B/C.  ``optimizers`` = dict with keys f, h, h_adv, h_adv2,
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
-    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None):
+    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         self.ema = ema               # optional mi355.optim.EMATeacher: updated behind step C's optimizer (train1.py:461)
         # optional mi355.teacher.MeanTeacher: step C's loss gains m * mt_loss(y_t, model_ema(x_t_ema)) (train1.py:351-364,
@@ -153,6 +182,9 @@ class DAStep:
         # optional MMDAlign: step C's loss gains w * MMD_loss3(y_s.detach(), y_t) (uda/model/loss.py:1061-1104), y_s = the
         # heat-maps step A left in self.out['y_s']
         self.mmd = mmd
+        # optional JointFeatureAlign: step C's loss gains w * loss3(f_t, <desc_s>, xy_t, .) (uda/model/loss.py:331-378), desc_s = the
+        # source descriptors step A left in self.out['jfa_desc_s']
+        self.jfa = jfa
         self.trade_off, self.skip, self.track_acc = trade_off, skip_discarded, track_accuracy
         self.graphs = None
         self.out = {}
@@ -230,7 +262,10 @@ class DAStep:
         for o in self.opt.values():
             o.zero_grad()
         with _rt.grouped_wgrads():
-            y_s, y_s_adv, y_s_adv2, y_s_adv3, _ = m(b['x_s'])
+            y_s, y_s_adv, y_s_adv2, y_s_adv3, f_s = m(b['x_s'])
+            if self.jfa is not None:
+                # only the (B, K, C) descriptors outlive this step: the source feature map goes with its backward
+                self.out.update(jfa_desc_s=self.jfa.source(f_s, y_s))
             # the coefficients of train1.py:384-387 ride inside the loss kernels (scale=), the total's gradient is the unit scalar
             loss_s = c['kl'](y_s, b['label_s'], b['w_s'], scale=2) + \
                 c['rd2'](y_s, y_s_adv2, None, b['w_s'], mode='min', scale=4) + \
@@ -288,7 +323,7 @@ class DAStep:
                 self._shared = None
                 y_t_adv, y_t_adv2, y_t_adv3 = m.adv_heads(f_t)
             else:
-                y_t, y_t_adv, y_t_adv2, y_t_adv3, _ = m(b['x_t'])
+                y_t, y_t_adv, y_t_adv2, y_t_adv3, f_t = m(b['x_t'])
                 y_t_grad = y_t
             loss1 = c['rd2'](y_t, y_t_adv2, None, b['w_t'], mode='min', scale=0.3 * to)
             loss2 = c['rd'](y_t, y_t_adv, None, b['w_t'], mode='min', scale=to)
@@ -306,6 +341,11 @@ class DAStep:
                 # in self.out since step A (under capture: produced in the first graph, its storage held by that reference)
                 loss_mmd = self.mmd.term(self.out['y_s'], y_t_grad)
                 total = total + loss_mmd
+            loss_jfa = None
+            if self.jfa is not None:
+                # only f_t gets a gradient, through its GradFanIn beside the heads' input gradients; only optimizer_f steps in C
+                loss_jfa, desc_t = self.jfa.term(f_t, self.out['jfa_desc_s'], y_t)
+                total = total + loss_jfa
             with _rt.grouped_wgrads():
                 total.backward(_rt.unit_grad(total))
             _rt.join_side()
@@ -318,6 +358,8 @@ class DAStep:
             self.out.update(loss_mt=loss_mt.detach())
         if loss_mmd is not None:
             self.out.update(loss_mmd=loss_mmd.detach())
+        if loss_jfa is not None:
+            self.out.update(loss_jfa=loss_jfa.detach(), jfa_desc_t=desc_t)
 
     def _update_C(self):
         self.opt['f'].step()

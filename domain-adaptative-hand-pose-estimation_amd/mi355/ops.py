@@ -1188,6 +1188,111 @@ def mmd_heatmap(source, target, want_source_grad, want_target_grad, kernel_mul=2
     return rows, (grad_source if want_source_grad else None), (grad_target if want_target_grad else None)
 
 
+# ---------------------------------------------------------------- joint feature alignment (csrc/jfa.hip)
+JFA_MAX_JOINTS = 32
+JFA_AXES = {'ref': 1, 'xy': 0}        # 'ref': x selects the rows (the reference's indexing), 'xy': y selects the rows
+
+
+def joint_divisor(radius, scale=1.0):
+    """(2 radius + 1)^2 / scale as the fp32 the kernels divide by; with scale = 1 the reference's 13 * 13."""
+    if not scale > 0:
+        raise Mi355Error('joint_pool: scale must be positive, got %r' % (scale,))
+    return float(torch.tensor((2 * int(radius) + 1) ** 2 / float(scale), dtype=torch.float64).to(torch.float32))
+
+
+def _chk_joints(who, xy, B):
+    if xy.dim() != 3 or xy.shape[0] != B or xy.shape[2] != 2 or xy.dtype != torch.float32 or not xy.is_contiguous():
+        raise Mi355Error('%s: key points must be a contiguous fp32 (%d, K, 2) tensor, got %s %s strides %s'
+                         % (who, B, xy.dtype, tuple(xy.shape), xy.stride()))
+    if not 1 <= xy.shape[1] <= JFA_MAX_JOINTS:
+        raise Mi355Error('%s: K=%d joints (1 .. %d)' % (who, xy.shape[1], JFA_MAX_JOINTS))
+    return xy.shape[1]
+
+
+def _chk_jfa(who, C, H, W, radius, axes):
+    if axes not in JFA_AXES:
+        raise Mi355Error("%s: axes must be 'ref' or 'xy', got %r" % (who, axes))
+    if C < 8 or C % 8:
+        raise Mi355Error('%s: C=%d channels (a multiple of 8, at least 8)' % (who, C))
+    if H < 1 or W < 1 or int(radius) < 1 or int(radius) != radius:
+        raise Mi355Error('%s: H=%d W=%d radius=%r (each at least 1)' % (who, H, W, radius))
+
+
+def _chk_desc(who, what, t, shape=None):
+    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise Mi355Error('%s: %s must be a contiguous, 16-byte aligned fp32 (B, K, C) tensor%s, got %s %s strides %s offset %d'
+                         % (who, what, '' if shape is None else ' of shape %s' % (tuple(shape),), t.dtype, tuple(t.shape), t.stride(), t.data_ptr() % 16))
+
+
+def joint_pool(f, xy, radius=6, axes='ref', divisor=None, out=None):
+    """desc (B, K, C) fp32: the box sum of the window of the channels_last feature map f (B, C, H, W; bf16 / fp32) around each key
+    point xy (B, K, 2) = (x, y), divided by `divisor` ((2 radius + 1)^2 when None): the reference's loss1
+    (uda/model/loss.py:331-365)."""
+    _chk_dev(f, xy, out)
+    _chk_feature('joint_pool feature', f)
+    B, C, H, W = f.shape
+    K = _chk_joints('joint_pool', xy, B)
+    _chk_jfa('joint_pool', C, H, W, radius, axes)
+    if f.data_ptr() % 16:
+        raise Mi355Error('joint_pool: the feature map must start on a 16-byte boundary (offset %d)' % (f.data_ptr() % 16))
+    if out is None:
+        out = torch.empty((B, K, C), dtype=torch.float32, device=f.device)
+    _chk_desc('joint_pool', 'out', out, (B, K, C))
+    _chk_room('joint_pool feature', f, B * C * H * W)
+    _chk_room('joint_pool xy', xy, B * K * 2)
+    _chk_room('joint_pool out', out, B * K * C)
+    call('mi355_jfa_pool', ptr(f), ptr(xy), ptr(out), B, K, C, H, W, int(radius), joint_divisor(radius) if divisor is None else float(divisor),
+         JFA_AXES[axes], dtype_code(f.dtype), stream_ptr())
+    return out
+
+
+def joint_kl(a, b, want_a, want_b, scale=1.0, rows=None, grad_a=None, grad_b=None):
+    """KL between the channel distributions of two sets of descriptors a, b (B, K, C) fp32 (the reference's loss3 behind its two
+    loss1 calls, uda/model/loss.py:368-378): a goes through log_softmax, b is normalised to sum 1 after adding 1e-6.  Returns
+    (rows (B, K), grad_a or None, grad_b or None); the scalar loss is reduce_sum(rows, scale / (B K)) and the gradients are
+    d(that scalar) / d a and / d b.  A side whose gradient is not wanted is neither allocated nor written."""
+    _chk_dev(a, b, rows, grad_a, grad_b)
+    _chk_desc('joint_kl', 'a', a)
+    _chk_desc('joint_kl', 'b', b, a.shape)
+    B, K, C = a.shape
+    if B < 1 or K < 1 or C < 8 or C % 8:
+        raise Mi355Error('joint_kl: B=%d K=%d C=%d (C a multiple of 8, at least 8)' % (B, K, C))
+    if rows is None:
+        rows = torch.empty((B, K), dtype=torch.float32, device=a.device)
+    if want_a and grad_a is None:
+        grad_a = torch.empty_like(a)
+    if want_b and grad_b is None:
+        grad_b = torch.empty_like(b)
+    if rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise Mi355Error('joint_kl: rows must be a contiguous fp32 tensor')
+    for what, g, want in (('grad_a', grad_a, want_a), ('grad_b', grad_b, want_b)):
+        if want:
+            _chk_desc('joint_kl', what, g, a.shape)
+    _chk_room('joint_kl rows', rows, B * K)
+    call('mi355_jfa_kl', ptr(a), ptr(b), ptr(rows), ptr(grad_a) if want_a else 0, ptr(grad_b) if want_b else 0, B * K, C,
+         float(scale) / (B * K), stream_ptr())
+    return rows, (grad_a if want_a else None), (grad_b if want_b else None)
+
+
+def joint_scatter(gd, xy, out, accumulate, radius=6, axes='ref', divisor=None):
+    """The backward of joint_pool: `out` (B, C, H, W channels_last, bf16 / fp32) receives, at every pixel, the sum of gd[b, j, :] /
+    divisor over the joints whose window holds the pixel (ascending j, fp32).  accumulate=False writes it (zeros outside every
+    window); accumulate=True adds it onto what `out` holds, one rounding, and leaves uncovered pixels alone."""
+    _chk_dev(gd, xy, out)
+    _chk_feature('joint_scatter out', out)
+    B, C, H, W = out.shape
+    K = _chk_joints('joint_scatter', xy, B)
+    _chk_jfa('joint_scatter', C, H, W, radius, axes)
+    _chk_desc('joint_scatter', 'gd', gd, (B, K, C))
+    if out.data_ptr() % 16:
+        raise Mi355Error('joint_scatter: the feature gradient must start on a 16-byte boundary (offset %d)' % (out.data_ptr() % 16))
+    _chk_room('joint_scatter gd', gd, B * K * C)
+    _chk_room('joint_scatter out', out, B * C * H * W)
+    call('mi355_jfa_scatter', ptr(gd), ptr(xy), ptr(out), int(bool(accumulate)), B, K, C, H, W, int(radius),
+         joint_divisor(radius) if divisor is None else float(divisor), JFA_AXES[axes], dtype_code(out.dtype), stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------- kernel timer (bench.py roofline)
 def spin_us(us):
     call('mi355_spin_us', int(us), stream_ptr())

@@ -8,7 +8,9 @@ EMA teacher ``model_ema`` up to date: the reference's commented-out call at trai
 ``--mt-weight`` / ``--mt-k`` (the mean-teacher consistency term on the target batch: the reference's unused ``x_t_ema``, ``m`` and
 ``mt_loss``, train1.py:351-364 and uda/model/loss.py:265-297), ``--mmd-loss {off,on}`` with ``--mmd-weight`` / ``--mmd-kernels`` /
 ``--mmd-mul`` (MMD alignment of the target heat-maps with the source heat-maps in step C: the reference's unused ``MMD_loss3``,
-uda/model/loss.py:1061-1104), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
+uda/model/loss.py:1061-1104), ``--jfa-loss {off,on}`` with ``--jfa-weight`` / ``--jfa-radius`` / ``--jfa-axes`` (alignment of the
+neck features pooled around the predicted key points of the target batch with those of the source batch in step C: the
+reference's unused ``loss3``, train1.py:25 and uda/model/loss.py:331-378), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
 sub-pixel decodes ``quarter`` and ``taylor`` are not in the reference), ``--flip-test`` with ``--flip-shift`` (validation averages
@@ -210,6 +212,10 @@ def main(args):
         # step C gains w * MMD_loss3(y_s.detach(), y_t) (uda/model/loss.py:1061-1104): a non-adversarial alignment term
         from mi355.da_step import MMDAlign
         step.mmd = MMDAlign(weight=args.mmd_weight, kernel_mul=args.mmd_mul, kernel_num=args.mmd_kernels)
+    if args.jfa_loss == 'on':
+        # step C gains w * loss3(f_t, <source descriptors>, xy_t, .) (uda/model/loss.py:331-378): alignment on the neck features
+        from mi355.da_step import JointFeatureAlign
+        step.jfa = JointFeatureAlign(weight=args.jfa_weight, radius=args.jfa_radius, axes=args.jfa_axes)
     start_epoch = 0
     if args.resume is None:
         if args.pretrain is None or (args.synthetic and not os.path.exists(args.pretrain)):
@@ -353,6 +359,9 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     mmd = getattr(step, 'mmd', None)
     if mmd is not None:
         names, fmts = names + ['Loss (mmd)'], fmts + [':.2e']
+    jfa = getattr(step, 'jfa', None)
+    if jfa is not None:
+        names, fmts = names + ['Loss (jfa)'], fmts + [':.2e']
     meters = [AverageMeter(n, f) for n, f in zip(names, fmts)]
     progress = ProgressMeter(args.iters_per_epoch, meters, prefix="Epoch: [{}]".format(epoch))
     end = time.time()
@@ -399,7 +408,9 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
             if mt is not None:
                 meters[9].update(float(out['loss_mt']), args.batch_size)
             if mmd is not None:
-                meters[-1].update(float(out['loss_mmd']), args.batch_size)
+                meters[names.index('Loss (mmd)')].update(float(out['loss_mmd']), args.batch_size)
+            if jfa is not None:
+                meters[names.index('Loss (jfa)')].update(float(out['loss_jfa']), args.batch_size)
             meters[0].update(time.time() - end)
             progress.display(i)
         end = time.time()
@@ -602,6 +613,15 @@ _OPTIONS = [
     (('--mmd-weight',), dict(default=0.1, type=float, metavar='FLOAT', help='weight w of the MMD term (constant, positive)')),
     (('--mmd-kernels',), dict(default=5, type=int, metavar='N', help='Gaussian kernels of the MMD term (1 .. 8)')),
     (('--mmd-mul',), dict(default=2.0, type=float, metavar='FLOAT', help='ratio of successive kernel bandwidths of the MMD term')),
+    (('--jfa-loss',), dict(default='off', choices=['off', 'on'], help="joint feature alignment: step C's loss gains "
+                          "w * loss3(f_t, <source descriptors>, xy_t, .), the KL divergence between the channel distributions of the neck "
+                          "features pooled around the predicted key points of the target and of the source batch "
+                          "(uda/model/loss.py:331-378), computed by the jfa_ kernels; 'off': nothing is launched")),
+    (('--jfa-weight',), dict(default=1.0, type=float, metavar='FLOAT', help='weight w of the joint feature alignment term (constant, '
+                            'positive; the default is a placeholder: its effect on convergence has not been measured)')),
+    (('--jfa-radius',), dict(default=6, type=int, metavar='N', help='half side of the pooling window in heat-map pixels (1 .. 16)')),
+    (('--jfa-axes',), dict(default='xy', choices=['xy', 'ref'], help="'xy': y selects the rows of the feature map; 'ref': the "
+                          "reference's indexing, x selects the rows (uda/model/loss.py:353)")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--metrics',), dict(default='pck', choices=['pck', 'full'], help="'full': validation also decodes key points in image pixels "
                          "and reports the mean end-point error, the PCK curve's AUC and per-group EPEs (on the device, one read at "
@@ -641,6 +661,11 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--mmd-mul must be positive, got %r' % (args.mmd_mul,))
             if args.batch_size > 128:
                 self.error('--mmd-loss on takes at most 128 images per domain and GPU (the kernels hold n = 2 B <= 256 rows), got -b %d' % args.batch_size)
+        if getattr(args, 'jfa_loss', 'off') == 'on':
+            if not args.jfa_weight > 0:
+                self.error('--jfa-weight must be positive, got %r' % (args.jfa_weight,))
+            if not 1 <= args.jfa_radius <= 16:
+                self.error('--jfa-radius must be 1 .. 16, got %d' % args.jfa_radius)
         if getattr(args, 'dump_preds', None):
             args.metrics = 'full'                        # (test.py: predictions are what --metrics full decodes)
         if getattr(args, 'decode', 'argmax') != 'argmax' and getattr(args, 'metrics', 'pck') != 'full':

@@ -550,6 +550,35 @@ int mi355_mmd_heatmap(const float* source, const float* target, float* work, siz
                       float* grad_source, float* grad_target, int B, int K, int HW, float kernel_mul, int kernel_num,
                       float fix_sigma, float scale, void* stream);
 
+/* ---------------------------------------------------------------- joint feature alignment (csrc/jfa.hip)
+ * loss1 / loss3 of uda/model/loss.py:331-378, the per-joint feature alignment term the reference imports (train1.py:25) and
+ * never connects, without its Python loop over B x 21 windows and the two host reads of each.  Features are NHWC [B][H][W][C]
+ * (dtype MI355_F32 / MI355_BF16), key points xy [B][K][2] = (x, y) fp32 in pixels of the map, on the device.
+ * The window of joint (b, j), with (cr, cc) = (x, y) when rows_by_x (the reference's indexing, :353) and (y, x) otherwise:
+ *   r0 = int(max(cr - radius, 0)), r1 = int(min(cr + radius, H - 1)), q0 = int(max(cc - radius, 0)), q1 = int(min(cc + radius, W - 1))
+ * in fp32, truncated towards zero (.int(), :349-352), rows [r0, r1) x columns [q0, q1); the reference's constant 63 is H - 1 =
+ * W - 1 of its 64 x 64 map.  r1 <= r0 or q1 <= q0 is an empty window (a coordinate outside the map: the reference falls into
+ * negative-index slicing there); a NaN coordinate gives an empty window too.
+ *   mi355_jfa_pool     desc[b][j][c] = (sum of feature[b][r][q][c] over the window) / divisor, fp32, one IEEE division (:353-357;
+ *                      divisor = (2 radius + 1)^2 = 169 there); an empty window gives zeros
+ *   mi355_jfa_kl       on a, b [nrows][C] fp32 (loss3, :368-378): lp = log_softmax(a), q = (b + 1e-6) / S, S = sum_c (b_c + 1e-6),
+ *                      rows[i] = sum_c q_c (log q_c - lp_c); grad_a = coef (softmax(a) - q) and grad_b = coef ((log q - lp) -
+ *                      rows[i]) / S, each nullable (nothing is written for a null one).  The scalar loss is
+ *                      mi355_reduce_sum(rows, scale / nrows) and coef = scale / nrows.  b + 1e-6 must be positive.  The arithmetic
+ *                      behind the fp32 operands and results is fp64 (the row is a small difference of large logarithms).
+ *   mi355_jfa_scatter  the backward of mi355_jfa_pool as a gather: gd[b][j][c] = grad_desc[b][j][c] / divisor, and for every pixel
+ *                      s = sum of gd[b][j][:] over the joints whose window holds it, j ascending, in fp32.  accumulate = 0:
+ *                      grad_feature = s rounded to dtype (+0 where no window covers); accumulate = 1: a covered pixel becomes
+ *                      round(grad_feature + s), one rounding, an uncovered one is not touched.
+ * C a multiple of 8, 1 <= K <= MI355_JFA_MAX_JOINTS, H, W >= 1, radius >= 1, divisor > 0; feature, desc, a, b and the gradients
+ * 16-byte aligned.  Deterministic: no atomics, fixed summation orders.  Never allocates; capturable. */
+#define MI355_JFA_MAX_JOINTS 32
+int mi355_jfa_pool(const void* feature, const float* xy, float* desc, int B, int K, int C, int H, int W, int radius, float divisor,
+                   int rows_by_x, int dtype, void* stream);
+int mi355_jfa_kl(const float* a, const float* b, float* rows, float* grad_a, float* grad_b, int nrows, int C, float coef, void* stream);
+int mi355_jfa_scatter(const float* grad_desc, const float* xy, void* grad_feature, int accumulate, int B, int K, int C, int H, int W,
+                      int radius, float divisor, int rows_by_x, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
