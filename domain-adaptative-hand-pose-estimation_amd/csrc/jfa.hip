@@ -5,31 +5,11 @@
 // runs in a fixed order, so two runs give the same bits.
 #include <math.h>
 #include "common.h"
+#include "jfa_common.h"
 
 #define JFA_T 256                     // threads of a block
 #define JFA_CT 256                    // channels of a block's channel tile: at most 32 bf16 / 64 fp32 chunks of 16 bytes
 #define JFA_STRIP 256                 // jfa_scatter: pixels of a block's strip
-
-struct jfa_win { int r0, r1, q0, q1; };          // rows [r0, r1) x columns [q0, q1); empty when r1 <= r0 or q1 <= q0
-
-// The reference's window (loss1): r0 = int(max(cr - radius, 0)), r1 = int(min(cr + radius, H - 1)) and the same for the columns
-// with W - 1 -- fp32 arithmetic, truncation towards zero as .int() does, the half-open slice r0:r1.  `rows_by_x`: the reference
-// slices the row axis by x and the column axis by y; 0 is the geometric indexing.  A coordinate outside the map leaves r1 <= r0
-// (the reference falls into negative-index slicing there): an empty window.  A NaN coordinate gives an empty window as well.
-// The bounds are brought into [0, H] and [-1, H - 1] as floats before the conversion, so that an infinity or a value past 2^31
-// never reaches the cast; for every other value this changes nothing (a lower bound above H and an upper bound below 0 are
-// empty windows either way).
-__device__ __forceinline__ jfa_win jfa_window(const float* __restrict__ xy, int radius, int rows_by_x, int H, int W) {
-  const float x = xy[0], y = xy[1], rad = (float)radius;
-  const float cr = rows_by_x ? x : y, cc = rows_by_x ? y : x;
-  jfa_win w;
-  if (cr != cr || cc != cc) { w.r0 = 0; w.r1 = 0; w.q0 = 0; w.q1 = 0; return w; }
-  w.r0 = (int)fminf(fmaxf(cr - rad, 0.f), (float)H);
-  w.r1 = (int)fmaxf(fminf(cr + rad, (float)(H - 1)), -1.f);
-  w.q0 = (int)fminf(fmaxf(cc - rad, 0.f), (float)W);
-  w.q1 = (int)fmaxf(fminf(cc + rad, (float)(W - 1)), -1.f);
-  return w;
-}
 
 // ---------------------------------------------------------------- pooling
 // One block per (b, j) and channel tile.  Thread t owns chunk t % CW of the tile and pixel group g = t / CW: it adds the window's
@@ -193,26 +173,12 @@ __global__ __launch_bounds__(JFA_T) void jfa_scatter_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- host
-static const char* jfa_geometry(const char* who, int B, int K, int C, int H, int W, int radius, float divisor, int dtype) {
-  static thread_local char msg[160];
-  msg[0] = 0;
-  if (dtype != MI355_F32 && dtype != MI355_BF16) snprintf(msg, sizeof(msg), "%s: dtype=%d (fp32 or bf16 features)", who, dtype);
-  else if (B < 1 || B > 65535) snprintf(msg, sizeof(msg), "%s: B=%d (1 .. 65535)", who, B);
-  else if (K < 1 || K > MI355_JFA_MAX_JOINTS) snprintf(msg, sizeof(msg), "%s: K=%d (1 .. %d joints)", who, K, MI355_JFA_MAX_JOINTS);
-  else if (C < 8 || C % 8) snprintf(msg, sizeof(msg), "%s: C=%d (a multiple of 8, at least 8)", who, C);
-  else if (H < 1 || W < 1 || (long)H * W > (1L << 24)) snprintf(msg, sizeof(msg), "%s: H=%d W=%d (at least 1, H W <= 2^24)", who, H, W);
-  else if (radius < 1 || radius > (1 << 20)) snprintf(msg, sizeof(msg), "%s: radius=%d (at least 1)", who, radius);
-  else if (!(divisor > 0.f) || !isfinite(divisor)) snprintf(msg, sizeof(msg), "%s: divisor=%g must be positive", who, (double)divisor);
-  else if (cdiv(C, JFA_CT) > 65535) snprintf(msg, sizeof(msg), "%s: C=%d too large (at most 65535 channel tiles of %d)", who, C, JFA_CT);
-  return msg[0] ? msg : nullptr;
-}
-
 extern "C" int mi355_jfa_pool(const void* feature, const float* xy, float* desc, int B, int K, int C, int H, int W, int radius,
                               float divisor, int rows_by_x, int dtype, void* stream) {
   if (!feature || !xy || !desc) MI_FAIL(MI355_EINVAL, "jfa_pool: null pointer");
   if (((uintptr_t)feature | (uintptr_t)desc) & 15) MI_FAIL(MI355_EINVAL, "jfa_pool: feature and desc must be 16-byte aligned");
   if ((uintptr_t)xy & 3) MI_FAIL(MI355_EINVAL, "jfa_pool: xy must be 4-byte aligned");
-  if (const char* m = jfa_geometry("jfa_pool", B, K, C, H, W, radius, divisor, dtype)) MI_FAIL(MI355_EINVAL, "%s", m);
+  if (const char* m = jfa_geometry("jfa_pool", B, K, C, H, W, radius, divisor, dtype, JFA_CT)) MI_FAIL(MI355_EINVAL, "%s", m);
   hipStream_t s = as_stream(stream);
   const int esz = dtype == MI355_BF16 ? 2 : 4;
   const int side = 2 * radius < (H > W ? H : W) ? 2 * radius : (H > W ? H : W);
@@ -248,7 +214,7 @@ extern "C" int mi355_jfa_scatter(const float* grad_desc, const float* xy, void* 
   if (!grad_desc || !xy || !grad_feature) MI_FAIL(MI355_EINVAL, "jfa_scatter: null pointer");
   if (((uintptr_t)grad_desc | (uintptr_t)grad_feature) & 15) MI_FAIL(MI355_EINVAL, "jfa_scatter: grad_desc and grad_feature must be 16-byte aligned");
   if ((uintptr_t)xy & 3) MI_FAIL(MI355_EINVAL, "jfa_scatter: xy must be 4-byte aligned");
-  if (const char* m = jfa_geometry("jfa_scatter", B, K, C, H, W, radius, divisor, dtype)) MI_FAIL(MI355_EINVAL, "%s", m);
+  if (const char* m = jfa_geometry("jfa_scatter", B, K, C, H, W, radius, divisor, dtype, JFA_CT)) MI_FAIL(MI355_EINVAL, "%s", m);
   hipStream_t s = as_stream(stream);
   const int esz = dtype == MI355_BF16 ? 2 : 4;
   char lab[96];

@@ -167,11 +167,85 @@ class JointFeatureAlign:
         return joint_kl_loss(desc_t, desc_s, self.weight), desc_t.detach()
 
 
+class PrototypeAlign:
+    """What ``DAStep(proto=...)`` takes: step C's loss gains ``weight * lossx`` (``criterion='kl'``, reference
+    uda/model/loss.py:381-466) or ``weight * lossx3`` (``'softkl'``, :560-652) between the per-joint class prototypes of the target
+    and of the source batch: the neck output pooled around the predicted key points (each window divided by its own s1 * s2),
+    averaged over the batch and blended with a running memory per domain, ``P = m * mean + (1 - m) * memory``, ``memory <- P``.
+    Step A updates the source memory and keeps the source prototypes (K, C); step C updates the target memory.  The key points
+    are the device arg-max of the detached heat-maps; only the target features get a gradient.  The weight rides inside the
+    kernels; m sits in device memory (``set_m``), and the memories live at fixed addresses, so captured graphs carry the state
+    from replay to replay.  With several ranks each rank keeps its own memories, as BatchNorm statistics are per GPU here."""
+
+    def __init__(self, weight=1.0, radius=6, axes='xy', m=0.999, criterion='kl'):
+        from uda.model.loss import PrototypeMemory
+        if not weight > 0:
+            raise ValueError('PrototypeAlign: the weight must be positive, got %r' % (weight,))
+        if not 1 <= int(radius) <= 16 or int(radius) != radius:
+            raise ValueError('PrototypeAlign: the radius must be 1 .. 16, got %r' % (radius,))
+        if axes not in ops.JFA_AXES:
+            raise ValueError("PrototypeAlign: axes must be 'xy' or 'ref', got %r" % (axes,))
+        if not 0.0 < float(m) <= 1.0:
+            raise ValueError('PrototypeAlign: m must be in (0, 1], got %r' % (m,))
+        if criterion not in ops.PROTO_MODES:
+            raise ValueError("PrototypeAlign: the criterion must be 'kl' or 'softkl', got %r" % (criterion,))
+        self.weight, self.radius, self.axes, self.m, self.criterion = float(weight), int(radius), axes, float(m), criterion
+        self.mem_s, self.mem_t, self.blend = PrototypeMemory(), PrototypeMemory(), None
+
+    def _blend(self, device):
+        if self.blend is None:
+            self.blend = ops.proto_blend(self.m, device=device)
+        return self.blend
+
+    def set_m(self, m):
+        """Change m (outside graph capture): the device record is rewritten in place and captured graphs follow."""
+        if not 0.0 < float(m) <= 1.0:
+            raise ValueError('PrototypeAlign: m must be in (0, 1], got %r' % (m,))
+        self.m = float(m)
+        if self.blend is not None:
+            ops.proto_blend(self.m, out=self.blend)
+
+    def _proto(self, f, y, mem):
+        from uda.model.loss import prototype
+        from uda.model.regda_4 import cached_centres
+        xy = cached_centres(y)
+        return prototype(f, xy, mem.tensor(xy.shape[1], f.shape[1], f.device), self._blend(f.device), self.radius, self.axes)
+
+    def source(self, f_s, y_s):
+        """Step A: the source prototypes (K, C), detached; the source memory is updated."""
+        return self._proto(f_s.detach(), y_s, self.mem_s)
+
+    def term(self, f_t, proto_s, y_t):
+        """Step C: (the term, the target prototypes it was computed from); the target memory is updated."""
+        from uda.model.loss import prototype_kl_loss
+        proto_t = self._proto(f_t, y_t, self.mem_t)
+        return prototype_kl_loss(proto_t, proto_s, self.criterion, self.weight), proto_t.detach()
+
+    def reset(self):
+        self.mem_s.reset()
+        self.mem_t.reset()
+
+    def state_dict(self):
+        """Both memories (CPU copies; None before first use) and m: what the epoch checkpoint keeps as ``proto_state``."""
+        cpu = lambda mem: mem.val.detach().cpu().clone() if torch.is_tensor(mem.val) else None
+        return {'memory_s': cpu(self.mem_s), 'memory_t': cpu(self.mem_t), 'm': self.m}
+
+    def load_state_dict(self, state, device=None):
+        for mem, key in ((self.mem_s, 'memory_s'), (self.mem_t, 'memory_t')):
+            v = state.get(key)
+            if v is None:
+                mem.reset()
+            else:
+                mem.set(v.to(device) if (device is not None and not torch.is_tensor(mem.val)) else v)
+        self.set_m(state.get('m', self.m))
+
+
 class DAStep:
     """Holds the static batch buffers and runs A/B/C.  ``optimizers`` = dict with keys f, h, h_adv, h_adv2,
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
-    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None):
+    def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None,
+                 proto=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         self.ema = ema               # optional mi355.optim.EMATeacher: updated behind step C's optimizer (train1.py:461)
         # optional mi355.teacher.MeanTeacher: step C's loss gains m * mt_loss(y_t, model_ema(x_t_ema)) (train1.py:351-364,
@@ -185,6 +259,9 @@ class DAStep:
         # optional JointFeatureAlign: step C's loss gains w * loss3(f_t, <desc_s>, xy_t, .) (uda/model/loss.py:331-378), desc_s = the
         # source descriptors step A left in self.out['jfa_desc_s']
         self.jfa = jfa
+        # optional PrototypeAlign: step C's loss gains w * lossx / lossx3 (uda/model/loss.py:381-466, 560-652) between the target
+        # prototypes and the source prototypes step A left in self.out['proto_s']; both steps update their domain's memory
+        self.proto = proto
         self.trade_off, self.skip, self.track_acc = trade_off, skip_discarded, track_accuracy
         self.graphs = None
         self.out = {}
@@ -266,6 +343,9 @@ class DAStep:
             if self.jfa is not None:
                 # only the (B, K, C) descriptors outlive this step: the source feature map goes with its backward
                 self.out.update(jfa_desc_s=self.jfa.source(f_s, y_s))
+            if self.proto is not None:
+                # only the (K, C) prototypes outlive this step; the source memory is updated here, once per iteration
+                self.out.update(proto_s=self.proto.source(f_s, y_s))
             # the coefficients of train1.py:384-387 ride inside the loss kernels (scale=), the total's gradient is the unit scalar
             loss_s = c['kl'](y_s, b['label_s'], b['w_s'], scale=2) + \
                 c['rd2'](y_s, y_s_adv2, None, b['w_s'], mode='min', scale=4) + \
@@ -346,6 +426,11 @@ class DAStep:
                 # only f_t gets a gradient, through its GradFanIn beside the heads' input gradients; only optimizer_f steps in C
                 loss_jfa, desc_t = self.jfa.term(f_t, self.out['jfa_desc_s'], y_t)
                 total = total + loss_jfa
+            loss_proto = None
+            if self.proto is not None:
+                # as the JFA term: only f_t gets a gradient, through its GradFanIn; only optimizer_f steps in C
+                loss_proto, proto_t = self.proto.term(f_t, self.out['proto_s'], y_t)
+                total = total + loss_proto
             with _rt.grouped_wgrads():
                 total.backward(_rt.unit_grad(total))
             _rt.join_side()
@@ -360,6 +445,8 @@ class DAStep:
             self.out.update(loss_mmd=loss_mmd.detach())
         if loss_jfa is not None:
             self.out.update(loss_jfa=loss_jfa.detach(), jfa_desc_t=desc_t)
+        if loss_proto is not None:
+            self.out.update(loss_proto=loss_proto.detach(), proto_t=proto_t)
 
     def _update_C(self):
         self.opt['f'].step()

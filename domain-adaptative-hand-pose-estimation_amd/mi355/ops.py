@@ -1293,6 +1293,130 @@ def joint_scatter(gd, xy, out, accumulate, radius=6, axes='ref', divisor=None):
     return out
 
 
+# ---------------------------------------------------------------- prototype alignment with running memory (csrc/proto.hip)
+PROTO_MODES = {'kl': 0, 'softkl': 1}      # lossx (uda/model/loss.py:381-466), lossx3 (:560-652)
+
+
+def proto_blend(m, device=None, out=None):
+    """The device record {m, 1 - m} of proto_update / proto_scatter as a 2-element fp32 tensor (new, or `out` rewritten): both
+    are formed in double and rounded once, as the reference's Python floats ``m`` and ``(1 - m)`` are where they meet the tensor."""
+    m = float(m)
+    if not 0.0 < m <= 1.0:
+        raise Mi355Error('proto_blend: m must be in (0, 1], got %r' % (m,))
+    host = torch.tensor([m, 1.0 - m], dtype=torch.float64).to(torch.float32)
+    if out is None:
+        return host.to(device)
+    if out.dtype != torch.float32 or out.numel() != 2 or not out.is_contiguous():
+        raise Mi355Error('proto_blend: out must be a contiguous fp32 tensor of 2 elements')
+    out.copy_(host)
+    return out
+
+
+def _chk_proto(who, what, t, shape=None):
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise Mi355Error('%s: %s must be a contiguous, 16-byte aligned fp32 (K, C) tensor%s, got %s %s strides %s offset %d'
+                         % (who, what, '' if shape is None else ' of shape %s' % (tuple(shape),), t.dtype, tuple(t.shape), t.stride(), t.data_ptr() % 16))
+    if not 1 <= t.shape[0] <= JFA_MAX_JOINTS or t.shape[1] < 8 or t.shape[1] % 8:
+        raise Mi355Error('%s: %s K=%d C=%d (1 .. %d joints, C a multiple of 8, at least 8)' % (who, what, t.shape[0], t.shape[1], JFA_MAX_JOINTS))
+
+
+def _chk_blend(who, blend):
+    if blend.dtype != torch.float32 or blend.numel() != 2 or not blend.is_contiguous():
+        raise Mi355Error('%s: blend must be the 2-element fp32 record of proto_blend, got %s %s' % (who, blend.dtype, tuple(blend.shape)))
+
+
+def proto_pool(f, xy, radius=6, axes='ref', out=None):
+    """desc (B, K, C) fp32: the box sum of the window of the channels_last feature map f (B, C, H, W; bf16 / fp32) around each key
+    point xy (B, K, 2) = (x, y), divided by the window's own s_row * s_col, s = hi - lo + 1 (the reference's lossx.loss1 up to its
+    stack, uda/model/loss.py:402-433)."""
+    _chk_dev(f, xy, out)
+    _chk_feature('proto_pool feature', f)
+    B, C, H, W = f.shape
+    K = _chk_joints('proto_pool', xy, B)
+    _chk_jfa('proto_pool', C, H, W, radius, axes)
+    if f.data_ptr() % 16:
+        raise Mi355Error('proto_pool: the feature map must start on a 16-byte boundary (offset %d)' % (f.data_ptr() % 16))
+    if out is None:
+        out = torch.empty((B, K, C), dtype=torch.float32, device=f.device)
+    _chk_desc('proto_pool', 'out', out, (B, K, C))
+    _chk_room('proto_pool feature', f, B * C * H * W)
+    _chk_room('proto_pool xy', xy, B * K * 2)
+    _chk_room('proto_pool out', out, B * K * C)
+    call('mi355_proto_pool', ptr(f), ptr(xy), ptr(out), B, K, C, H, W, int(radius), JFA_AXES[axes], dtype_code(f.dtype), stream_ptr())
+    return out
+
+
+def proto_update(desc, memory, blend, out=None):
+    """P (K, C) = m * mean_b desc[b] + (1 - m) * memory, and memory <- P in place (uda/model/loss.py:436-448, :454): desc (B, K, C)
+    fp32, memory (K, C) fp32 at its fixed address, blend = proto_blend(m).  Returns P (new, or `out`; never the memory itself)."""
+    _chk_dev(desc, memory, blend, out)
+    _chk_desc('proto_update', 'desc', desc)
+    B, K, C = desc.shape
+    if B < 1:
+        raise Mi355Error('proto_update: B=%d' % B)
+    _chk_proto('proto_update', 'memory', memory, (K, C))
+    _chk_blend('proto_update', blend)
+    if out is None:
+        out = torch.empty((K, C), dtype=torch.float32, device=desc.device)
+    _chk_proto('proto_update', 'out', out, (K, C))
+    if out.data_ptr() == memory.data_ptr():
+        raise Mi355Error('proto_update: out must not be the memory itself (the loss needs P after the memory is overwritten)')
+    _chk_room('proto_update desc', desc, B * K * C)
+    _chk_room('proto_update memory', memory, K * C)
+    _chk_room('proto_update out', out, K * C)
+    call('mi355_proto_update', ptr(desc), ptr(memory), ptr(blend), ptr(out), B, K, C, stream_ptr())
+    return out
+
+
+def proto_kl(pt, ps, want_t, want_s, mode='kl', scale=1.0, rows=None, grad_t=None, grad_s=None):
+    """KL between the channel distributions of the prototypes pt, ps (K, C) fp32: pt goes through log_softmax; mode 'kl' (lossx,
+    uda/model/loss.py:455-466) normalises ps to sum 1, mode 'softkl' (lossx3, :645) takes its softmax.  Returns (rows (K,), grad_t
+    or None, grad_s or None); the scalar loss is reduce_sum(rows, scale / K) for 'kl' and reduce_sum(rows, scale) for 'softkl',
+    and the gradients are d(that scalar) / d pt and / d ps.  A side whose gradient is not wanted is neither allocated nor written."""
+    _chk_dev(pt, ps, rows, grad_t, grad_s)
+    if mode not in PROTO_MODES:
+        raise Mi355Error("proto_kl: mode must be 'kl' or 'softkl', got %r" % (mode,))
+    _chk_proto('proto_kl', 'pt', pt)
+    _chk_proto('proto_kl', 'ps', ps, pt.shape)
+    K, C = pt.shape
+    if rows is None:
+        rows = torch.empty((K,), dtype=torch.float32, device=pt.device)
+    if want_t and grad_t is None:
+        grad_t = torch.empty_like(pt)
+    if want_s and grad_s is None:
+        grad_s = torch.empty_like(ps)
+    if rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise Mi355Error('proto_kl: rows must be a contiguous fp32 tensor')
+    for what, g, want in (('grad_t', grad_t, want_t), ('grad_s', grad_s, want_s)):
+        if want:
+            _chk_proto('proto_kl', what, g, pt.shape)
+    _chk_room('proto_kl rows', rows, K)
+    call('mi355_proto_kl', ptr(pt), ptr(ps), ptr(rows), ptr(grad_t) if want_t else 0, ptr(grad_s) if want_s else 0, K, C,
+         PROTO_MODES[mode], float(scale) / K if mode == 'kl' else float(scale), stream_ptr())
+    return rows, (grad_t if want_t else None), (grad_s if want_s else None)
+
+
+def proto_scatter(gp, xy, blend, out, accumulate, radius=6, axes='ref'):
+    """The backward of proto_pool + proto_update: `out` (B, C, H, W channels_last, bf16 / fp32) receives, at every pixel, the sum of
+    (gp[j, :] * (m / B)) / (s_row s_col)(b, j) over the joints whose window holds the pixel (ascending j, fp32); gp (K, C) is the
+    gradient w.r.t. the prototypes, the same for every image.  accumulate=False writes it (zeros outside every window);
+    accumulate=True adds it onto what `out` holds, one rounding, and leaves uncovered pixels alone."""
+    _chk_dev(gp, xy, blend, out)
+    _chk_feature('proto_scatter out', out)
+    B, C, H, W = out.shape
+    K = _chk_joints('proto_scatter', xy, B)
+    _chk_jfa('proto_scatter', C, H, W, radius, axes)
+    _chk_proto('proto_scatter', 'gp', gp, (K, C))
+    _chk_blend('proto_scatter', blend)
+    if out.data_ptr() % 16:
+        raise Mi355Error('proto_scatter: the feature gradient must start on a 16-byte boundary (offset %d)' % (out.data_ptr() % 16))
+    _chk_room('proto_scatter gp', gp, K * C)
+    _chk_room('proto_scatter out', out, B * C * H * W)
+    call('mi355_proto_scatter', ptr(gp), ptr(xy), ptr(blend), ptr(out), int(bool(accumulate)), B, K, C, H, W, int(radius),
+         JFA_AXES[axes], dtype_code(out.dtype), stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------- kernel timer (bench.py roofline)
 def spin_us(us):
     call('mi355_spin_us', int(us), stream_ptr())

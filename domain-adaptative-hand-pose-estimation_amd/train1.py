@@ -10,7 +10,9 @@ EMA teacher ``model_ema`` up to date: the reference's commented-out call at trai
 ``--mmd-mul`` (MMD alignment of the target heat-maps with the source heat-maps in step C: the reference's unused ``MMD_loss3``,
 uda/model/loss.py:1061-1104), ``--jfa-loss {off,on}`` with ``--jfa-weight`` / ``--jfa-radius`` / ``--jfa-axes`` (alignment of the
 neck features pooled around the predicted key points of the target batch with those of the source batch in step C: the
-reference's unused ``loss3``, train1.py:25 and uda/model/loss.py:331-378), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
+reference's unused ``loss3``, train1.py:25 and uda/model/loss.py:331-378), ``--proto-loss {off,kl,softkl}`` with ``--proto-weight`` /
+``--proto-radius`` / ``--proto-axes`` / ``--proto-m`` (alignment of per-joint class prototypes of those features, blended with a running
+memory per domain: the reference's unused ``lossx`` / ``lossx3``, uda/model/loss.py:381-466 and 560-652), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
 sub-pixel decodes ``quarter`` and ``taylor`` are not in the reference), ``--flip-test`` with ``--flip-shift`` (validation averages
@@ -216,6 +218,12 @@ def main(args):
         # step C gains w * loss3(f_t, <source descriptors>, xy_t, .) (uda/model/loss.py:331-378): alignment on the neck features
         from mi355.da_step import JointFeatureAlign
         step.jfa = JointFeatureAlign(weight=args.jfa_weight, radius=args.jfa_radius, axes=args.jfa_axes)
+    if args.proto_loss != 'off':
+        # step C gains w * lossx / lossx3 on the per-joint class prototypes of the neck features, blended with a running memory
+        # per domain (uda/model/loss.py:381-466, 560-652)
+        from mi355.da_step import PrototypeAlign
+        step.proto = PrototypeAlign(weight=args.proto_weight, radius=args.proto_radius, axes=args.proto_axes, m=args.proto_m,
+                                    criterion=args.proto_loss)
     start_epoch = 0
     if args.resume is None:
         if args.pretrain is None or (args.synthetic and not os.path.exists(args.pretrain)):
@@ -260,6 +268,8 @@ def main(args):
                 model_ema.load_state_dict(torch.load(ema_path, map_location='cpu', weights_only=False)['model_ema'])
             if 'ema_state' in ck:
                 ema.load_state_dict(ck['ema_state'])
+        if getattr(step, 'proto', None) is not None and 'proto_state' in ck:
+            step.proto.load_state_dict(ck['proto_state'], device)      # both prototype memories and m
     broadcast_module(model)                              # replicas start bit-identical whatever each rank loaded
     broadcast_module(model_ema)
 
@@ -292,6 +302,8 @@ def main(args):
             best_acc = max(best_acc, t_acc['all'])
             continue
         ck_extra = {'ema_state': ema.state_dict()} if ema is not None else {}
+        if getattr(step, 'proto', None) is not None:
+            ck_extra['proto_state'] = step.proto.state_dict()
         torch.save({'model': model.state_dict(), **ck_extra,
                     'optimizer_f': opts['f'].state_dict(), 'optimizer_h': opts['h'].state_dict(),
                     'optimizer_h_adv': opts['h_adv'].state_dict(),
@@ -362,6 +374,9 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     jfa = getattr(step, 'jfa', None)
     if jfa is not None:
         names, fmts = names + ['Loss (jfa)'], fmts + [':.2e']
+    proto = getattr(step, 'proto', None)
+    if proto is not None:
+        names, fmts = names + ['Loss (proto)'], fmts + [':.2e']
     meters = [AverageMeter(n, f) for n, f in zip(names, fmts)]
     progress = ProgressMeter(args.iters_per_epoch, meters, prefix="Epoch: [{}]".format(epoch))
     end = time.time()
@@ -411,6 +426,8 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
                 meters[names.index('Loss (mmd)')].update(float(out['loss_mmd']), args.batch_size)
             if jfa is not None:
                 meters[names.index('Loss (jfa)')].update(float(out['loss_jfa']), args.batch_size)
+            if proto is not None:
+                meters[names.index('Loss (proto)')].update(float(out['loss_proto']), args.batch_size)
             meters[0].update(time.time() - end)
             progress.display(i)
         end = time.time()
@@ -622,6 +639,18 @@ _OPTIONS = [
     (('--jfa-radius',), dict(default=6, type=int, metavar='N', help='half side of the pooling window in heat-map pixels (1 .. 16)')),
     (('--jfa-axes',), dict(default='xy', choices=['xy', 'ref'], help="'xy': y selects the rows of the feature map; 'ref': the "
                           "reference's indexing, x selects the rows (uda/model/loss.py:353)")),
+    (('--proto-loss',), dict(default='off', choices=['off', 'kl', 'softkl'], help="prototype alignment with running memory: step C's "
+                            "loss gains w * lossx ('kl', uda/model/loss.py:381-466) or w * lossx3 ('softkl', :560-652) between the per-joint "
+                            "class prototypes of the target and of the source batch -- the neck features pooled around the predicted "
+                            "key points, averaged over the batch and blended with a memory per domain -- computed by the proto_ "
+                            "kernels; the memories travel in the epoch checkpoint (proto_state); 'off': nothing is launched")),
+    (('--proto-weight',), dict(default=1.0, type=float, metavar='FLOAT', help='weight w of the prototype alignment term (constant, '
+                              'positive; the default is a placeholder: its effect on convergence has not been measured)')),
+    (('--proto-radius',), dict(default=6, type=int, metavar='N', help='half side of the pooling window in heat-map pixels (1 .. 16)')),
+    (('--proto-axes',), dict(default='xy', choices=['xy', 'ref'], help="'xy': y selects the rows of the feature map; 'ref': the "
+                            "reference's indexing, x selects the rows (uda/model/loss.py:421)")),
+    (('--proto-m',), dict(default=0.999, type=float, metavar='FLOAT', help="weight m of the current batch in the prototype, the memory "
+                         "gets 1 - m (0 < m <= 1; 0.999 is the reference's constant, uda/model/loss.py:400)")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--metrics',), dict(default='pck', choices=['pck', 'full'], help="'full': validation also decodes key points in image pixels "
                          "and reports the mean end-point error, the PCK curve's AUC and per-group EPEs (on the device, one read at "
@@ -666,6 +695,13 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--jfa-weight must be positive, got %r' % (args.jfa_weight,))
             if not 1 <= args.jfa_radius <= 16:
                 self.error('--jfa-radius must be 1 .. 16, got %d' % args.jfa_radius)
+        if getattr(args, 'proto_loss', 'off') != 'off':
+            if not args.proto_weight > 0:
+                self.error('--proto-weight must be positive, got %r' % (args.proto_weight,))
+            if not 1 <= args.proto_radius <= 16:
+                self.error('--proto-radius must be 1 .. 16, got %d' % args.proto_radius)
+            if not 0 < args.proto_m <= 1:
+                self.error('--proto-m must be in (0, 1], got %r' % (args.proto_m,))
         if getattr(args, 'dump_preds', None):
             args.metrics = 'full'                        # (test.py: predictions are what --metrics full decodes)
         if getattr(args, 'decode', 'argmax') != 'argmax' and getattr(args, 'metrics', 'pck') != 'full':

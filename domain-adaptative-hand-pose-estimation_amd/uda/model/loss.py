@@ -4,7 +4,9 @@ target normalisation, KL sum, weighting and the gradient w.r.t. the prediction i
 ``MMD_loss`` and ``mmd_rbf`` (reference ``uda/model/loss.py:1061-1196``), the multi-kernel MMD between a source and a target
 batch, as three launches that never form the reference's n x n x HW temporaries; ``loss1`` and ``loss3`` (reference
 ``uda/model/loss.py:331-378``), the per-joint feature alignment term, as a pooling kernel, a KL row kernel and a gather for the
-pooling's backward instead of a Python loop over B x 21 windows."""
+pooling's backward instead of a Python loop over B x 21 windows; ``lossx`` and ``lossx3`` (reference ``uda/model/loss.py:381-466``,
+``560-652``), the alignment of per-joint class prototypes blended with a running memory, as four launches whose memory lives at
+fixed device addresses."""
 import torch
 import torch.nn as nn
 
@@ -231,12 +233,28 @@ def _jfa_points(pre, B):
     return pre if (pre.dtype == torch.float32 and pre.is_contiguous()) else pre.float().contiguous()
 
 
+def _fan_in_scatter(fan, like, scatter):
+    """The gradient of a pooled feature map, through the ``mi355.nn.GradFanIn`` protocol: ``scatter(out, accumulate)`` runs the
+    gather into ``out``.  When the fan-in buffer exists, the gradient is accumulated onto it in place and None is returned (for
+    autograd); otherwise a new map is written, registered as the buffer when there is a fan-in, and returned -- the convs that
+    run later accumulate onto it.  Returning a dense tensor beside an existing buffer would make autograd add the two into a NEW
+    tensor and lose every later in-place addition."""
+    shape, dtype, device = like
+    if fan is not None and fan.buf is not None and tuple(fan.buf.shape) == shape and fan.buf.dtype == dtype and ops.is_nhwc(fan.buf):
+        scatter(fan.buf, True)
+        return None
+    B, C, H, W = shape
+    dx = scatter(ops.nhwc_empty(B, C, H, W, dtype, device), False)
+    if fan is not None:
+        fan.buf = dx
+    return dx
+
+
 class _JointPoolFn(torch.autograd.Function):
     """desc = joint_pool(feature, xy).  The backward is the gather ``jfa_scatter``.  A feature tensor that carries a
     ``mi355.nn.GradFanIn`` (the neck output, which the heads consume as well) gets its gradient through that protocol: when the
     fan-in buffer exists, this gradient is accumulated onto it in place and autograd is handed None; otherwise the buffer is
-    written here, registered, and returned -- the convs that run later accumulate onto it.  Returning a dense tensor beside an
-    existing buffer would make autograd add the two into a NEW tensor and lose every later in-place addition."""
+    written here, registered, and returned (``_fan_in_scatter``)."""
 
     @staticmethod
     def forward(ctx, feature, xy, radius, axes, divisor, fan):
@@ -248,20 +266,12 @@ class _JointPoolFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gdesc):
         xy, = ctx.saved_tensors
-        shape, dtype, device = ctx.like
         if gdesc is None or not ctx.needs_input_grad[0]:
             return None, None, None, None, None, None
         radius, axes, divisor = ctx.args
         if gdesc.dtype != torch.float32 or not gdesc.is_contiguous():
             gdesc = gdesc.float().contiguous()
-        fan = ctx.fan
-        if fan is not None and fan.buf is not None and tuple(fan.buf.shape) == shape and fan.buf.dtype == dtype and ops.is_nhwc(fan.buf):
-            ops.joint_scatter(gdesc, xy, fan.buf, True, radius, axes, divisor)
-            return None, None, None, None, None, None
-        B, C, H, W = shape
-        dx = ops.joint_scatter(gdesc, xy, ops.nhwc_empty(B, C, H, W, dtype, device), False, radius, axes, divisor)
-        if fan is not None:
-            fan.buf = dx
+        dx = _fan_in_scatter(ctx.fan, ctx.like, lambda out, acc: ops.joint_scatter(gdesc, xy, out, acc, radius, axes, divisor))
         return dx, None, None, None, None, None
 
 
@@ -325,3 +335,184 @@ def loss3(f1, f2, pre1, pre2, radius=6, axes='ref', scale=1.0):
         raise ValueError('loss3: the two sides must have one batch size, channel count and joint count, got features %s / %s, key points %s / %s'
                          % (tuple(f1.shape), tuple(f2.shape), tuple(pre1.shape), tuple(pre2.shape)))
     return joint_kl_loss(loss1(f1, pre1, radius, axes), loss1(f2, pre2, radius, axes), scale)
+
+
+# ---------------------------------------------------------------- prototype alignment (reference uda/model/loss.py:381-466, 560-652)
+class _ProtoFn(torch.autograd.Function):
+    """P = m * mean_b pool(feature, xy)[b] + (1 - m) * memory, and memory <- P in place: ``proto_pool`` and ``proto_update``.  The
+    backward is the gather ``proto_scatter``, which reads the (K, C) gradient broadcast over the batch; the feature gradient goes
+    through ``_fan_in_scatter`` as ``_JointPoolFn``'s does."""
+
+    @staticmethod
+    def forward(ctx, feature, xy, memory, blend, radius, axes, fan):
+        ctx.args, ctx.fan = (radius, axes), fan
+        ctx.like = (tuple(feature.shape), feature.dtype, feature.device)
+        ctx.save_for_backward(xy, blend)
+        return ops.proto_update(ops.proto_pool(feature, xy, radius, axes), memory, blend)
+
+    @staticmethod
+    def backward(ctx, gp):
+        xy, blend = ctx.saved_tensors
+        if gp is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None, None
+        radius, axes = ctx.args
+        if gp.dtype != torch.float32 or not gp.is_contiguous():
+            gp = gp.float().contiguous()
+        dx = _fan_in_scatter(ctx.fan, ctx.like, lambda out, acc: ops.proto_scatter(gp, xy, blend, out, acc, radius, axes))
+        return dx, None, None, None, None, None, None
+
+
+class _ProtoKLFn(torch.autograd.Function):
+    """loss = scale * mean_j rows ('kl') or scale * sum_j rows ('softkl') on prototypes pt, ps (K, C).  As _JointKLFn: the kernel
+    writes d loss / d pt and / d ps in the forward, for whichever needs a gradient; the backward hands them on when the incoming
+    gradient is the unit scalar."""
+
+    @staticmethod
+    def forward(ctx, pt, ps, mode, scale):
+        rows, gt, gs = ops.proto_kl(pt, ps, ctx.needs_input_grad[0], ctx.needs_input_grad[1], mode, scale)
+        ctx.save_for_backward(gt, gs)
+        return ops.reduce_sum(rows, float(scale) / rows.numel() if mode == 'kl' else float(scale))
+
+    @staticmethod
+    def backward(ctx, gout):
+        gt, gs = ctx.saved_tensors
+        if gout is None or (gt is None and gs is None):
+            return None, None, None, None
+        if not _rt.is_unit_grad(gout):
+            gout = gout.contiguous().float()
+            gt, gs = (None if g is None else ops.scale_by_dev(g, gout) for g in (gt, gs))
+        return gt, gs, None, None
+
+
+def prototype(feature, pre, memory, blend, radius=6, axes='ref'):
+    """The reference's ``lossx.loss1(feature, pre, fea)`` (``uda/model/loss.py:394-449``): per joint, the window mean of
+    ``feature[b]`` around ``pre[b, j] = (x, y)`` -- the sum over ``int(max(. - radius, 0)) : int(min(. + radius, side - 1))`` on
+    both axes divided by the window's own ``s1 * s2``, ``s = hi - lo + 1`` -- averaged over the batch and blended with ``memory``
+    (K, C): ``P = m * mean + (1 - m) * memory``.  Returns P (K, C) fp32 and overwrites ``memory`` with it in place (the reference's
+    ``self.val1 = fea_c1.detach()``).  ``blend = ops.proto_blend(m)`` holds m on the device.  Differentiable w.r.t. ``feature``.
+    ``axes`` and the deviations from the reference (empty windows outside the map and for NaN, the clamp ``side - 1``, any K up
+    to 32) are ``loss1``'s."""
+    f = _jfa_feature(feature)
+    fan = getattr(feature, '_mi_fan', None) if (f is feature and torch.is_grad_enabled() and feature.requires_grad) else None
+    return _ProtoFn.apply(f, _jfa_points(pre, f.shape[0]), memory, blend, int(radius), axes, fan)
+
+
+def prototype_kl_loss(proto_t, proto_s, criterion='kl', scale=1.0):
+    """The part of ``lossx`` (``criterion='kl'``, ``uda/model/loss.py:455-466``) or ``lossx3`` (``'softkl'``, ``:645``) behind the
+    two prototypes (K, C): ``proto_t`` goes through log_softmax; ``proto_s`` is normalised to sum 1 ('kl', mean over the joints)
+    or goes through softmax ('softkl', sum over the joints).  Deviation: under 'kl' a joint whose source prototype sums to 0 or
+    less contributes 0 and gets zero gradients (the reference returns NaN)."""
+    if proto_t.dim() != 2 or tuple(proto_t.shape) != tuple(proto_s.shape):
+        raise ValueError('prototype_kl_loss: prototypes (K, C) of one shape, got %s and %s' % (tuple(proto_t.shape), tuple(proto_s.shape)))
+    if criterion not in ops.PROTO_MODES:
+        raise ValueError("prototype_kl_loss: criterion must be 'kl' or 'softkl', got %r" % (criterion,))
+    pt, ps = (p if (p.dtype == torch.float32 and p.is_contiguous()) else p.float().contiguous() for p in (proto_t, proto_s))
+    return _ProtoKLFn.apply(pt, ps, criterion, float(scale))
+
+
+class PrototypeMemory:
+    """The running memory of one side, (K, C) fp32 at a fixed device address once first used, and the device record of m."""
+
+    def __init__(self):
+        self.val = 0.
+
+    def tensor(self, K, C, device):
+        """The memory as a tensor: allocated as zeros (the reference's scalar 0., bit for bit) the first time it is asked for."""
+        if not torch.is_tensor(self.val):
+            if torch.cuda.is_current_stream_capturing():
+                raise _rt.Mi355Error('prototype memory (%d, %d) would be allocated during graph capture: warm up first' % (K, C))
+            self.val = torch.full((K, C), float(self.val), dtype=torch.float32, device=device)
+        if tuple(self.val.shape) != (K, C) or self.val.device != torch.device(device):
+            raise ValueError('prototype memory is %s on %s, the prototypes are (%d, %d) on %s: reset() belongs to one shape'
+                             % (tuple(self.val.shape), self.val.device, K, C, device))
+        return self.val
+
+    def reset(self):
+        if torch.is_tensor(self.val):
+            self.val.zero_()
+        else:
+            self.val = 0.
+
+    def set(self, val):
+        if torch.is_tensor(self.val) and torch.is_tensor(val):
+            self.val.copy_(val)                 # (in place: a captured graph keeps the address)
+        elif torch.is_tensor(val):
+            self.val = val.detach().to(torch.float32).contiguous().clone()
+        elif torch.is_tensor(self.val):
+            self.val.fill_(float(val))
+        else:
+            self.val = float(val)
+
+
+class _ProtoLoss(nn.Module):
+    criterion = None
+
+    def __init__(self, reduction='mean', epsilon=0., radius=6, axes='ref', m=0.999, scale=1.0):
+        super().__init__()
+        if not 1 <= int(radius) or int(radius) != radius:
+            raise ValueError('%s: the radius must be an integer of at least 1, got %r' % (type(self).__name__, radius))
+        if axes not in ops.JFA_AXES:
+            raise ValueError("%s: axes must be 'ref' or 'xy', got %r" % (type(self).__name__, axes))
+        if not 0.0 < float(m) <= 1.0:
+            raise ValueError('%s: m must be in (0, 1], got %r' % (type(self).__name__, m))
+        self.reduction, self.epsilon = reduction, epsilon            # (kept for the signature; the reference ignores both)
+        self.radius, self.axes, self.m, self.scale = int(radius), axes, float(m), float(scale)
+        self._mem1, self._mem2, self._blend = PrototypeMemory(), PrototypeMemory(), None
+
+    val1 = property(lambda self: self._mem1.val)
+    val2 = property(lambda self: self._mem2.val)
+
+    def reset(self):
+        self._mem1.reset()
+        self._mem2.reset()
+
+    def updata(self, val1, val2):
+        self._mem1.set(val1)
+        self._mem2.set(val2)
+
+    def set_m(self, m):
+        """Change m: the device record is rewritten in place, so a captured graph that contains the loss follows."""
+        if not 0.0 < float(m) <= 1.0:
+            raise ValueError('%s: m must be in (0, 1], got %r' % (type(self).__name__, m))
+        self.m = float(m)
+        if self._blend is not None:
+            ops.proto_blend(self.m, out=self._blend)
+
+    def forward(self, f1, f2, pre1, pre2):
+        for f, pre in ((f1, pre1), (f2, pre2)):                  # (both sides are checked before anything is launched)
+            if f.dim() != 4:
+                raise ValueError('%s: (B, C, H, W) features, got %s' % (type(self).__name__, tuple(f.shape)))
+            _jfa_points(pre, f.shape[0])
+        if pre1.shape[1] != pre2.shape[1] or f1.shape[1] != f2.shape[1]:
+            raise ValueError('%s: the two sides must have one channel count and joint count, got features %s / %s, key points %s / %s'
+                             % (type(self).__name__, tuple(f1.shape), tuple(f2.shape), tuple(pre1.shape), tuple(pre2.shape)))
+        K, C = pre1.shape[1], f1.shape[1]
+        if self._blend is None or self._blend.device != f1.device:
+            self._blend = ops.proto_blend(self.m, device=f1.device)
+        p1 = prototype(f1, pre1, self._mem1.tensor(K, C, f1.device), self._blend, self.radius, self.axes)
+        p2 = prototype(f2, pre2, self._mem2.tensor(K, C, f2.device), self._blend, self.radius, self.axes)
+        return prototype_kl_loss(p1, p2, self.criterion, self.scale)
+
+
+class lossx(_ProtoLoss):
+    """The reference's ``lossx`` (``uda/model/loss.py:381-466``): ``forward(f1, f2, pre1, pre2)`` is the mean over the joints of the
+    KL divergence between the source prototype ``P2[j]`` normalised to sum 1 and ``softmax(P1[j])``, where ``P = m * (batch mean
+    of the window means) + (1 - m) * memory`` (``prototype``) and the memories ``val1`` / ``val2`` are overwritten with the
+    prototypes at every call.  ``reset()`` zeroes them, ``updata(val1, val2)`` (sic) copies into them; they are the float ``0.``
+    until first used and (K, C) fp32 device tensors at fixed addresses from then on.  Either feature argument may require a
+    gradient.  ``reduction`` and ``epsilon`` are accepted and ignored, as there.
+
+    Extensions: ``radius`` (6 there), ``axes`` ('ref': x selects the rows, as there; 'xy': y does), ``m`` (0.999 there, the weight
+    of the current batch), ``scale`` (coefficient of the term, folded into the kernels).  Deviations from the reference: a
+    coordinate outside the map, or NaN, gives an empty window and a zero descriptor; at sides other than 64 the upper clamp is
+    ``side - 1``; any K up to 32; a joint whose source prototype sums to 0 or less contributes 0 to the loss and gets zero
+    gradients (the reference returns NaN for an all-zero source); the source gradient of an element whose prototype is exactly
+    0 is 0 (the reference's autograd gives -inf there)."""
+    criterion = 'kl'
+
+
+class lossx3(_ProtoLoss):
+    """The reference's ``lossx3`` (``uda/model/loss.py:560-652``): as ``lossx`` with the softmax of both prototypes and the sum
+    over joints and channels (``F.kl_div(P1.softmax(-1).log(), P2.softmax(-1), reduction='sum')``).  Extensions and deviations
+    as ``lossx``'s, without the zero-sum rule (a softmax has no zero sum)."""
+    criterion = 'softkl'

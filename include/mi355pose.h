@@ -579,6 +579,39 @@ int mi355_jfa_kl(const float* a, const float* b, float* rows, float* grad_a, flo
 int mi355_jfa_scatter(const float* grad_desc, const float* xy, void* grad_feature, int accumulate, int B, int K, int C, int H, int W,
                       int radius, float divisor, int rows_by_x, int dtype, void* stream);
 
+/* ---------------------------------------------------------------- prototype alignment with running memory (csrc/proto.hip)
+ * lossx (uda/model/loss.py:381-466) and lossx3 (:560-652): per joint, the descriptors of a batch averaged into one class prototype,
+ * blended with a memory kept from call to call, and the KL divergence between the channel distributions of the target and the
+ * source prototypes -- without the Python loop over B x 21 windows and the host reads of each.  Layouts, key points, windows,
+ * `rows_by_x` and the empty-window rule as in the joint feature alignment section above; the reference's constants 6 and 63 are
+ * `radius` and the side - 1 (:410-417, :588-595).  blend = {m, 1 - m}, two fp32 in device memory (m = 0.999 at :400 / :578).
+ *   mi355_proto_pool     desc[b][j][c] = (sum of feature[b][r][q][c] over the window) / (s_row s_col), s = hi - lo + 1 on either axis,
+ *                        one more than the pixels summed (:418-425, :596-603); fp32 sum, one IEEE division; an empty window gives zeros
+ *   mi355_proto_update   pbar[j][c] = (sum_b desc[b][j][c]) / B, b ascending in fp32 (:433-437, :611-615); proto = m pbar + (1 - m)
+ *                        memory (:448, :626); memory <- proto in place (self.val1 = fea_c1.detach(), :454 / :460, :632 / :639)
+ *   mi355_proto_kl       on proto_t, proto_s [K][C] fp32: lp = log_softmax(proto_t); MI355_PROTO_KL (:455-466): q = proto_s / S, S =
+ *                        sum_c proto_s; MI355_PROTO_SOFTKL (:645): q = softmax(proto_s).  rows[j] = sum_c q_c (log q_c - lp_c), an
+ *                        element with q_c = 0 adding 0.  grad_t = coef (softmax(proto_t) - q); grad_s = coef ((log q - lp) - rows[j])
+ *                        / S (kl; 0 where q_c = 0) or coef q ((log q - lp) - rows[j]) (softkl); each nullable (nothing is written for a
+ *                        null one).  The scalar loss is mi355_reduce_sum(rows, scale / K) with coef = scale / K for kl (.mean(), :466),
+ *                        mi355_reduce_sum(rows, scale) with coef = scale for softkl (reduction='sum').  kl with S <= 0: rows[j] = 0 and
+ *                        zero gradients (the reference gives NaN).  fp64 arithmetic behind the fp32 operands and results.
+ *   mi355_proto_scatter  the backward of pool + update as a gather: gd[b][j][c] = (grad_proto[j][c] * (m / B)) / (s_row s_col)(b, j),
+ *                        and for every pixel s = sum of gd[b][j][:] over the joints whose window holds it, j ascending, in fp32.
+ *                        accumulate = 0: grad_feature = s rounded to dtype (+0 where no window covers); accumulate = 1: a covered
+ *                        pixel becomes round(grad_feature + s), one rounding, an uncovered one is not touched.
+ * C a multiple of 8, 1 <= K <= MI355_JFA_MAX_JOINTS, H, W >= 1, radius >= 1; feature, desc, memory, the prototypes and the gradients
+ * 16-byte aligned; proto != memory.  Deterministic: no atomics, fixed summation orders.  Never allocates; capturable. */
+#define MI355_PROTO_KL 0
+#define MI355_PROTO_SOFTKL 1
+int mi355_proto_pool(const void* feature, const float* xy, float* desc, int B, int K, int C, int H, int W, int radius, int rows_by_x,
+                     int dtype, void* stream);
+int mi355_proto_update(const float* desc, float* memory, const float* blend, float* proto, int B, int K, int C, void* stream);
+int mi355_proto_kl(const float* proto_t, const float* proto_s, float* rows, float* grad_t, float* grad_s, int K, int C, int mode,
+                   float coef, void* stream);
+int mi355_proto_scatter(const float* grad_proto, const float* xy, const float* blend, void* grad_feature, int accumulate, int B, int K,
+                        int C, int H, int W, int radius, int rows_by_x, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
