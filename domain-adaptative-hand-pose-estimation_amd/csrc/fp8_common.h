@@ -24,6 +24,28 @@ __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d
   return (unsigned)w;
 }
 
+// One step of a thread's running max of |v| over the non-NaN elements (Inf counts).  A compare and a select, not fmaxf: that
+// becomes v_max_f32 on the raw inputs, which answers a SIGNALLING NaN (any bf16 pattern 0x7f81..0x7fbf widened by a shift is
+// one) with a quiet NaN; the next element then replaces that NaN and the maximum seen so far, an Inf included, is forgotten.
+__device__ __forceinline__ float fp8_amax_step(float amax, float v) {
+  const float a = fabsf(v);
+  return a > amax ? a : amax;
+}
+// The scale exponent of the per-tensor rule: the largest k with amax * 2^margin * 2^k <= 1.75 * 2^max_exp (e4m3: 448 =
+// 1.75 * 2^8, e5m2: 57344 = 1.75 * 2^15), clamped to [-126, 126] so that 2^k and 2^-k are both normal floats.  For a finite
+// amax > 0, from its bits (exact for every float, subnormals included; as mx_exp below).
+__device__ __forceinline__ int fp8_scale_exp(float amax, int max_exp, int margin) {
+  const unsigned b = __float_as_uint(amax);
+  int ex = (int)(b >> 23);
+  unsigned frac = b & 0x7fffffu;
+  if (ex == 0) {                                   // subnormal: bring the leading one to bit 23
+    const int sh = __clz((int)frac) - 8;
+    frac = (frac << sh) & 0x7fffffu;
+    ex = 1 - sh;
+  }
+  const int k = max_exp - (ex - 127) - margin - (frac > 0x600000u ? 1 : 0);      // (mantissa > 1.75: one power less)
+  return k < -126 ? -126 : (k > 126 ? 126 : k);
+}
 
 // amax of a block into state[2]: ONE integer atomic per block (exact and order-independent).  `seen` = state[2] as loaded at the
 // START of the kernel (a plain load whose latency hides behind the main loop): blocks that cannot raise it skip the atomic, and

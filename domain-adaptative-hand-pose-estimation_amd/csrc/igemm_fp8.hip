@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void quantize_fp8_kernel(const T* __restrict__
       for (int e = 0; e < PER; ++e) v[c * PER + e] = w[e];
     }
 #pragma unroll
-    for (int e = 0; e < 16; ++e) amax = fmaxf(amax, fabsf(v[e]));      // (fmaxf ignores NaN)
+    for (int e = 0; e < 16; ++e) amax = fp8_amax_step(amax, v[e]);      // (skips NaN)
     if constexpr (WRITE) {
       uint4 o;
       o.x = pack4_fp8<BF8>(v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale);
@@ -50,17 +50,18 @@ __global__ __launch_bounds__(256) void quantize_fp8_kernel(const T* __restrict__
   fp8_record_amax(amax, state, seen);
 }
 
-// scale := fmt_max / (amax * 2^margin) (1 when nothing was seen yet), descale := 1 / scale, amax := 0.  `n` states.
-__global__ void fp8_update_scale_kernel(float* __restrict__ states, int n, int stride, float fmt_max, float margin_pow2) {
+// scale := 2^k, k = the largest integer with amax * 2^margin * 2^k <= fmt_max, clamped to [-126, 126] (1 when nothing was seen
+// yet), descale := 2^-k, amax := 0.  `n` states; fmt_max = 1.75 * 2^max_exp.  A power-of-two scale: scaling / descaling are
+// exact, only the fp8 rounding itself loses bits.  k comes from the bits of amax (fp8_scale_exp): through
+// fmt_max / (amax * 2^margin) in floats a tiny amax gave scale = Inf, descale = 0, and amax * 2^margin = Inf gave scale = 0.
+__global__ void fp8_update_scale_kernel(float* __restrict__ states, int n, int stride, int max_exp, int margin) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float* s = states + (size_t)i * stride;
   const float amax = __uint_as_float(reinterpret_cast<unsigned*>(s)[2]);
   if (amax > 0.f && amax < 3.0e38f) {
-    // power-of-two scale: scaling / descaling are exact, only the fp8 rounding itself loses bits
-    const float raw = fmt_max / (amax * margin_pow2);
-    const float sc = exp2f(floorf(log2f(raw)));
-    s[0] = sc; s[1] = 1.0f / sc;
+    const int k = fp8_scale_exp(amax, max_exp, margin);
+    s[0] = __uint_as_float((unsigned)(127 + k) << 23); s[1] = __uint_as_float((unsigned)(127 - k) << 23);
   } else if (s[0] == 0.f) { s[0] = 1.f; s[1] = 1.f; }
   reinterpret_cast<unsigned*>(s)[2] = 0u;
 }
@@ -90,7 +91,7 @@ extern "C" int mi355_fp8_update_scale(float* states, int n, int stride_floats, i
   if (!states || n < 1 || stride_floats < 3 || (fmt != 0 && fmt != 1) || margin < 0 || margin > 8)
     MI_FAIL(MI355_EINVAL, "fp8_update_scale: bad args");
   hipLaunchKernelGGL(fp8_update_scale_kernel, dim3(cdiv(n, 64)), dim3(64), 0, as_stream(stream), states, n, stride_floats,
-                     fmt ? 57344.f : 448.f, (float)(1 << margin));
+                     fmt ? 15 : 8, margin);      // 57344 = 1.75 * 2^15, 448 = 1.75 * 2^8
   MI_CHECK_LAUNCH("fp8_update_scale");
   return MI355_OK;
 }
@@ -113,7 +114,7 @@ __device__ __forceinline__ void pack_fp8_block(const float* __restrict__ w, unsi
   for (int k = 0; k < 4; ++k) {
     const int o = o0 + ty + 8 * k;
     const float v = w[((size_t)o * T + tap) * I + i0 + tx];
-    amax = fmaxf(amax, fabsf(v));
+    amax = fp8_amax_step(amax, v);
     tile[ty + 8 * k][tx] = v * scale;
   }
   amax = block_max<4>(amax, red);                     // (contains the barriers that publish `tile`)

@@ -303,7 +303,7 @@ def colsum(dy, out, accumulate):
 
 # ---------------------------------------------------------------- fp8 operand path (conv forward / input gradient)
 E4M3, E5M2 = 0, 1
-FP8_MARGIN = 0          # scale = 2^floor(log2(fmt_max / (amax * 2^margin)))
+FP8_MARGIN = 0          # scale = 2^k, k = the largest integer with amax * 2^margin * 2^k <= fmt_max, clamped to [-126, 126]
 
 
 def fp8_state(device):

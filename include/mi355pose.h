@@ -133,8 +133,9 @@ int mi355_conv_fwd_bnbwd(const mi355_conv_desc* d, const void* x, const void* w,
  *   state[2] = max(state[2], max |x|) -- with write = 0 only the amax is taken (just-in-time scaling: amax, update, quantise);
  *   write = 2: q has 16 more bytes behind its n, which receive this copy's own record {scale, descale, 0, 0} (usable wherever
  *   a state's descale is read).
- * mi355_fp8_update_scale: for each of n states (stride_floats apart): scale = 2^floor(log2(fmt_max / (amax * 2^margin)))
- *   (kept when no amax was recorded; 1 if never set), descale = 1/scale, amax = 0.
+ * mi355_fp8_update_scale: for each of n states (stride_floats apart): scale = 2^k, k = the largest integer with
+ *   amax * 2^margin * 2^k <= fmt_max, clamped to [-126, 126] (kept when no amax, or one >= 3.0e38, was recorded; 1 if never
+ *   set), descale = 2^-k, amax = 0.  max |x| skips NaN elements and counts Inf.
  * mi355_pack_weights_fp8: fp32 master [O][T][I] -> e4m3 wf [O][T][I] and wt [I][T][O] (O, I multiples of 32).  margin >= 0:
  *   just-in-time per-tensor scale from amax(|w|), left in `state`; margin < 0: the scale already in `state` (delayed
  *   scaling).  Either way amax(|w|) is recorded in state[2] for the next mi355_fp8_update_scale, and state[3] = the descale
