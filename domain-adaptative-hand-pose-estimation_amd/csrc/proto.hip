@@ -6,63 +6,42 @@
 // runs give the same bits.  Nothing here reads device memory on the host or allocates: all of it can be captured into a graph.
 #include <math.h>
 #include "common.h"
-#include "jfa_common.h"
+#include "joint_pool.h"
 
-#define PROTO_T 256                   // threads of a block
-#define PROTO_CT 256                  // channels of a block's channel tile: at most 32 bf16 / 64 fp32 chunks of 16 bytes
-#define PROTO_STRIP 256               // proto_scatter: pixels of a block's strip
 #define PROTO_UNROLL 8                // proto_update: images whose descriptors are loaded before they are added
 
 // The reference's divisor s1 * s2 (:418-419, :425): s = hi - lo + 1 on either axis, ONE MORE than the pixels the half-open slice
 // lo:hi sums.  Only asked for a window that is not empty, so both factors are at least 2.
-__device__ __forceinline__ float proto_divisor(const jfa_win& w) { return (float)((w.r1 - w.r0 + 1) * (w.q1 - w.q0 + 1)); }
-__device__ __forceinline__ bool proto_empty(const jfa_win& w) { return w.r1 <= w.r0 || w.q1 <= w.q0; }
+__device__ __forceinline__ float proto_divisor(const joint_win& w) { return (float)((w.r1 - w.r0 + 1) * (w.q1 - w.q0 + 1)); }
+__device__ __forceinline__ bool proto_empty(const joint_win& w) { return w.r1 <= w.r0 || w.q1 <= w.q0; }
 
-// ---------------------------------------------------------------- pooling
-// One block per (b, j) and channel tile, in jfa_pool's form.  Thread t owns chunk t % CW of the tile and pixel group g = t / CW:
-// it adds the window's pixels g, g + G, g + 2 G, ... (row-major inside the window) in that order, the G partial sums meet in LDS
-// and the threads of group 0 add them in ascending g, divide once by the window's own divisor and store.  An empty window stores
-// zeros (and divides by nothing).
-template <typename T>
-__global__ __launch_bounds__(PROTO_T) void proto_pool_kernel(const T* __restrict__ f, const float* __restrict__ xy, float* __restrict__ desc,
-                                                              int K, int C, int H, int W, int radius, int rows_by_x) {
-  constexpr int N = Chunk<T>::N;
-  __shared__ __attribute__((aligned(16))) float part[PROTO_T][N];
-  const int t = threadIdx.x, bj = blockIdx.x, b = bj / K;
-  const int c0 = blockIdx.y * PROTO_CT;
-  const int CW = min(C - c0, PROTO_CT) / N, G = PROTO_T / CW;
-  const int ch = t % CW, g = t / CW;
-  const jfa_win w = jfa_window(xy + 2L * bj, radius, rows_by_x, H, W);
-  const int nr = max(w.r1 - w.r0, 0), nq = max(w.q1 - w.q0, 0), np = nr * nq;
-  float acc[N];
-#pragma unroll
-  for (int e = 0; e < N; ++e) acc[e] = 0.f;
-  if (g < G) {
-    const T* __restrict__ fb = f + (long)b * H * W * C + c0 + ch * N;
-    for (int p = g; p < np; p += G) {
-      const int r = w.r0 + p / nq, q = w.q0 + p % nq;
-      float v[N];
-      Chunk<T>::load(fb + ((long)r * W + q) * C, v);
-#pragma unroll
-      for (int e = 0; e < N; ++e) acc[e] += v[e];
+// The pooling divides by the window's own divisor; an empty window stores zeros (and divides by nothing).
+struct proto_window_divisor {
+  __device__ bool zero(const joint_win& w) const { return proto_empty(w); }
+  __device__ float of(const joint_win& w) const { return proto_divisor(w); }
+};
+
+// The gather's table: gd[j][c] = (g[j][c] * (m / B)) / divisor(b, j) -- the prototype gradient [K][C], the same for every image,
+// times d P / d desc = m / B, over the window's own divisor (1 for an empty window, which covers no pixel).  m is blend[0] in
+// device memory, as in proto_update.
+struct proto_grad {
+  static constexpr const char* GRAD = "grad_proto";
+  static constexpr bool BLEND = true;
+  const float* g;                     // [K][C]
+  const float* blend;
+  int B;
+  __device__ void fill(float* gd, const joint_win* win, int, int K, int C, int c0, int CT) const {
+    __shared__ float dv[MI355_JFA_MAX_JOINTS];
+    const int t = threadIdx.x;
+    if (t < K) dv[t] = proto_empty(win[t]) ? 1.f : proto_divisor(win[t]);
+    __syncthreads();
+    const float fac = blend[0] / (float)B;
+    for (int e = t; e < K * CT; e += JOINT_T) {
+      const int j = e / CT, c = e - j * CT;
+      gd[j * JOINT_CT + c] = (g[(long)j * C + c0 + c] * fac) / dv[j];
     }
   }
-#pragma unroll
-  for (int e = 0; e < N; ++e) part[t][e] = acc[e];
-  __syncthreads();
-  if (g == 0) {
-    for (int gg = 1; gg < G; ++gg)
-#pragma unroll
-      for (int e = 0; e < N; ++e) acc[e] += part[gg * CW + ch][e];
-    float* __restrict__ d = desc + (long)bj * C + c0 + ch * N;
-    const bool empty = np == 0;
-    const float div = empty ? 1.f : proto_divisor(w);
-#pragma unroll
-    for (int e4 = 0; e4 < N; e4 += 4)
-      *reinterpret_cast<float4*>(d + e4) = empty ? make_float4(0.f, 0.f, 0.f, 0.f)
-                                                 : make_float4(acc[e4] / div, acc[e4 + 1] / div, acc[e4 + 2] / div, acc[e4 + 3] / div);
-  }
-}
+};
 
 // ---------------------------------------------------------------- batch mean, blend with the memory, memory update
 // One thread per 4 channels of one joint: pbar = (sum_b desc[b][j][c]) / B with b ascending in fp32, P = m pbar + (1 - m) M as two
@@ -101,15 +80,9 @@ __global__ __launch_bounds__(WAVE) void proto_update_kernel(const float* __restr
 // q_c = 0, where the reference's autograd gives -inf) and coef q ((log q - lp) - row) in mode 1.  Mode 0, S <= 0 or NaN: row 0
 // and zero gradients (the reference returns NaN for an all-zero source prototype).  fp64 behind the fp32 operands, as jfa_kl:
 // the row is a small difference of large logarithms.
-__device__ inline double proto_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(PROTO_T) void proto_kl_kernel(const float* __restrict__ pt, const float* __restrict__ ps, float* __restrict__ rows,
+__global__ __launch_bounds__(JOINT_T) void proto_kl_kernel(const float* __restrict__ pt, const float* __restrict__ ps, float* __restrict__ rows,
                                                             float* __restrict__ gt, float* __restrict__ gs, int K, int C, int mode, float coef) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * (PROTO_T / WAVE) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, row = blockIdx.x * (JOINT_T / WAVE) + (threadIdx.x >> 6);
   if (row >= K) return;
   const float* __restrict__ ar = pt + (long)row * C;
   const float* __restrict__ br = ps + (long)row * C;
@@ -124,13 +97,13 @@ __global__ __launch_bounds__(PROTO_T) void proto_kl_kernel(const float* __restri
   ma = wave_max(ma);
   mb = wave_max(mb);
   const double mad = (double)ma, mbd = (double)mb;
-  double S = proto_wave_sum(s), za = 0.0, zb = 0.0;
+  double S = wave_sum(s), za = 0.0, zb = 0.0;
   for (int c = 4 * lane; c < C; c += 4 * WAVE) {
     const float4 va = *reinterpret_cast<const float4*>(ar + c), vb = *reinterpret_cast<const float4*>(br + c);
     za += (exp((double)va.x - mad) + exp((double)va.y - mad)) + (exp((double)va.z - mad) + exp((double)va.w - mad));
     if (mode) zb += (exp((double)vb.x - mbd) + exp((double)vb.y - mbd)) + (exp((double)vb.z - mbd) + exp((double)vb.w - mbd));
   }
-  const double lsa = log(proto_wave_sum(za)), lsb = mode ? log(proto_wave_sum(zb)) : 0.0;
+  const double lsa = log(wave_sum(za)), lsb = mode ? log(wave_sum(zb)) : 0.0;
   const bool dead = !mode && !(S > 0.0);            // (also a NaN sum)
   double kl = 0.0;
   for (int c = 4 * lane; c < C && !dead; c += 4 * WAVE) {
@@ -146,7 +119,7 @@ __global__ __launch_bounds__(PROTO_T) void proto_kl_kernel(const float* __restri
     }
     kl += (e[0] + e[1]) + (e[2] + e[3]);
   }
-  kl = proto_wave_sum(kl);
+  kl = wave_sum(kl);
   if (lane == 0) rows[row] = (float)kl;
   if (!gt && !gs) return;
   const double cf = (double)coef;
@@ -168,86 +141,10 @@ __global__ __launch_bounds__(PROTO_T) void proto_kl_kernel(const float* __restri
   }
 }
 
-// ---------------------------------------------------------------- backward of pooling + batch mean + blend, as a gather
-// One block per strip of PROTO_STRIP pixels of one image and channel tile, in jfa_scatter's form.  The image's K windows and
-// gd[j][c] = (g[j][c] * (m / B)) / divisor(b, j) -- the prototype gradient [K][C], the same for every image, times d P / d desc =
-// m / B, over the window's own divisor; formed once per (b, j, c) -- sit in LDS.  Thread t owns chunk t % CW of every pixel gp,
-// gp + G, ... of the strip: it adds gd[j] over the joints whose window holds the pixel, j ascending, in fp32.  Write mode stores
-// the sum rounded to T (+0 where no window covers); accumulate mode leaves an uncovered pixel alone and stores RNE(old + sum) on
-// a covered one.  m is blend[0] in device memory, as in proto_update.
-template <typename T, bool ACC>
-__global__ __launch_bounds__(PROTO_T) void proto_scatter_kernel(const float* __restrict__ g, const float* __restrict__ xy, const float* __restrict__ blend,
-                                                                 T* __restrict__ out, int B, int K, int C, int H, int W, int radius, int rows_by_x) {
-  constexpr int N = Chunk<T>::N;
-  __shared__ __attribute__((aligned(16))) float gd[MI355_JFA_MAX_JOINTS * PROTO_CT];
-  __shared__ jfa_win win[MI355_JFA_MAX_JOINTS];
-  __shared__ float dv[MI355_JFA_MAX_JOINTS];
-  const int t = threadIdx.x, b = blockIdx.y;
-  const int c0 = blockIdx.z * PROTO_CT;
-  const int CT = min(C - c0, PROTO_CT), CW = CT / N, G = PROTO_T / CW;
-  if (t < K) {
-    const jfa_win w = jfa_window(xy + 2L * (b * K + t), radius, rows_by_x, H, W);
-    win[t] = w;
-    dv[t] = proto_empty(w) ? 1.f : proto_divisor(w);
-  }
-  __syncthreads();
-  const float fac = blend[0] / (float)B;
-  for (int e = t; e < K * CT; e += PROTO_T) {
-    const int j = e / CT, c = e - j * CT;
-    gd[j * PROTO_CT + c] = (g[(long)j * C + c0 + c] * fac) / dv[j];
-  }
-  __syncthreads();
-  const int ch = t % CW, gp = t / CW;
-  if (gp >= G) return;
-  const int p0 = blockIdx.x * PROTO_STRIP, p1 = min(p0 + PROTO_STRIP, H * W);
-  T* __restrict__ ob = out + (long)b * H * W * C + c0 + ch * N;
-  for (int p = p0 + gp; p < p1; p += G) {
-    const int r = p / W, q = p - r * W;
-    float acc[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) acc[e] = 0.f;
-    bool covered = false;
-    for (int j = 0; j < K; ++j) {
-      const jfa_win w = win[j];
-      if (r < w.r0 || r >= w.r1 || q < w.q0 || q >= w.q1) continue;
-      covered = true;
-      const float* __restrict__ s = gd + j * PROTO_CT + ch * N;
-#pragma unroll
-      for (int e4 = 0; e4 < N; e4 += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(s + e4);
-        acc[e4] += v.x; acc[e4 + 1] += v.y; acc[e4 + 2] += v.z; acc[e4 + 3] += v.w;
-      }
-    }
-    T* __restrict__ o = ob + (long)p * C;
-    if (ACC) {
-      if (!covered) continue;
-      float old[N];
-      Chunk<T>::load(o, old);
-#pragma unroll
-      for (int e = 0; e < N; ++e) acc[e] = old[e] + acc[e];
-    }
-    Chunk<T>::store(o, acc);
-  }
-}
-
 // ---------------------------------------------------------------- host
 extern "C" int mi355_proto_pool(const void* feature, const float* xy, float* desc, int B, int K, int C, int H, int W, int radius,
                                 int rows_by_x, int dtype, void* stream) {
-  if (!feature || !xy || !desc) MI_FAIL(MI355_EINVAL, "proto_pool: null pointer");
-  if (((uintptr_t)feature | (uintptr_t)desc) & 15) MI_FAIL(MI355_EINVAL, "proto_pool: feature and desc must be 16-byte aligned");
-  if ((uintptr_t)xy & 3) MI_FAIL(MI355_EINVAL, "proto_pool: xy must be 4-byte aligned");
-  if (const char* m = jfa_geometry("proto_pool", B, K, C, H, W, radius, 1.f, dtype, PROTO_CT)) MI_FAIL(MI355_EINVAL, "%s", m);
-  hipStream_t s = as_stream(stream);
-  const int esz = dtype == MI355_BF16 ? 2 : 4;
-  const int side = 2 * radius < (H > W ? H : W) ? 2 * radius : (H > W ? H : W);
-  char lab[96];
-  snprintf(lab, sizeof(lab), "proto_pool B%d K%d C%d %dx%d r%d %s%s", B, K, C, H, W, radius, rows_by_x ? "ref" : "xy", esz == 2 ? "" : " f32");
-  ProfScope ps(s, 0.0, (double)B * K * C * ((double)side * side * esz + 4.0), 2, lab);
-  const dim3 grid(B * K, cdiv(C, PROTO_CT));
-  if (esz == 2) hipLaunchKernelGGL(proto_pool_kernel<bf16_t>, grid, dim3(PROTO_T), 0, s, (const bf16_t*)feature, xy, desc, K, C, H, W, radius, rows_by_x ? 1 : 0);
-  else hipLaunchKernelGGL(proto_pool_kernel<float>, grid, dim3(PROTO_T), 0, s, (const float*)feature, xy, desc, K, C, H, W, radius, rows_by_x ? 1 : 0);
-  MI_CHECK_LAUNCH("proto_pool");
-  return MI355_OK;
+  return joint_pool_launch("proto_pool", feature, xy, desc, B, K, C, H, W, radius, rows_by_x, dtype, stream, proto_window_divisor{});
 }
 
 extern "C" int mi355_proto_update(const float* desc, float* memory, const float* blend, float* proto, int B, int K, int C, void* stream) {
@@ -281,28 +178,13 @@ extern "C" int mi355_proto_kl(const float* proto_t, const float* proto_s, float*
   char lab[96];
   snprintf(lab, sizeof(lab), "proto_kl K%d C%d %s grads%d%d", K, C, mode ? "softkl" : "kl", grad_t ? 1 : 0, grad_s ? 1 : 0);
   ProfScope ps(s, 0.0, 4.0 * K * C * (2.0 + (grad_t ? 1 : 0) + (grad_s ? 1 : 0)), 2, lab);
-  hipLaunchKernelGGL(proto_kl_kernel, dim3(cdiv(K, PROTO_T / WAVE)), dim3(PROTO_T), 0, s, proto_t, proto_s, rows, grad_t, grad_s, K, C, mode, coef);
+  hipLaunchKernelGGL(proto_kl_kernel, dim3(cdiv(K, JOINT_T / WAVE)), dim3(JOINT_T), 0, s, proto_t, proto_s, rows, grad_t, grad_s, K, C, mode, coef);
   MI_CHECK_LAUNCH("proto_kl");
   return MI355_OK;
 }
 
 extern "C" int mi355_proto_scatter(const float* grad_proto, const float* xy, const float* blend, void* grad_feature, int accumulate, int B, int K,
                                    int C, int H, int W, int radius, int rows_by_x, int dtype, void* stream) {
-  if (!grad_proto || !xy || !blend || !grad_feature) MI_FAIL(MI355_EINVAL, "proto_scatter: null pointer");
-  if (((uintptr_t)grad_proto | (uintptr_t)grad_feature) & 15) MI_FAIL(MI355_EINVAL, "proto_scatter: grad_proto and grad_feature must be 16-byte aligned");
-  if (((uintptr_t)xy | (uintptr_t)blend) & 3) MI_FAIL(MI355_EINVAL, "proto_scatter: xy and blend must be 4-byte aligned");
-  if (const char* m = jfa_geometry("proto_scatter", B, K, C, H, W, radius, 1.f, dtype, PROTO_CT)) MI_FAIL(MI355_EINVAL, "%s", m);
-  hipStream_t s = as_stream(stream);
-  const int esz = dtype == MI355_BF16 ? 2 : 4;
-  char lab[96];
-  snprintf(lab, sizeof(lab), "proto_scatter B%d K%d C%d %dx%d r%d %s %s%s", B, K, C, H, W, radius, rows_by_x ? "ref" : "xy", accumulate ? "acc" : "write",
-           esz == 2 ? "" : " f32");
-  ProfScope ps(s, 0.0, (double)B * H * W * C * esz * (accumulate ? 2.0 : 1.0), 2, lab);
-  const dim3 grid(cdiv((long)H * W, PROTO_STRIP), B, cdiv(C, PROTO_CT));
-#define PROTO_SCATTER(T, ACC) hipLaunchKernelGGL((proto_scatter_kernel<T, ACC>), grid, dim3(PROTO_T), 0, s, grad_proto, xy, blend, (T*)grad_feature, B, K, C, H, W, radius, rows_by_x ? 1 : 0)
-  if (esz == 2) { if (accumulate) PROTO_SCATTER(bf16_t, true); else PROTO_SCATTER(bf16_t, false); }
-  else { if (accumulate) PROTO_SCATTER(float, true); else PROTO_SCATTER(float, false); }
-#undef PROTO_SCATTER
-  MI_CHECK_LAUNCH("proto_scatter");
-  return MI355_OK;
+  return joint_gather_launch("proto_scatter", xy, grad_feature, accumulate, B, K, C, H, W, radius, rows_by_x, dtype, stream,
+                             proto_grad{grad_proto, blend, B});
 }

@@ -122,108 +122,109 @@ def broadcast_module(module, src=0):
         dist.broadcast(d, src)
 
 
-class MMDAlign:
+class _Term:
+    """An optional term of step C's loss, as ``DAStep`` sees it (``mi355.teacher.MeanTeacher`` is the fourth).  ``key`` names it:
+    the attribute of the step that holds it, ``out['loss_<key>']`` and the meter column.  ``needs_head_graph``: step C
+    differentiates the term through the main head, so step B must keep that head's autograd graph."""
+    key, needs_head_graph = None, False
+
+    def step_a(self, f_s, y_s):
+        """Step A, behind the source forward: what must outlive the step, as entries of ``step.out``."""
+        return {}
+
+    def step_c(self, step, batch, f_t, y_t, y_t_grad):
+        """Step C: (the term, further entries of ``step.out``).  ``y_t`` is detached; ``y_t_grad`` carries the head's graph when
+        some term asked for it."""
+        raise NotImplementedError
+
+
+class MMDAlign(_Term):
     """What ``DAStep(mmd=...)`` takes: step C's loss gains ``weight * MMD_loss3(y_s.detach(), y_t)`` (reference
     uda/model/loss.py:1061-1104), the per-joint multi-kernel MMD between the source heat-maps of step A and the target heat-maps
     of the main head.  The weight rides inside the kernels (``scale=``); only the target side gets a gradient."""
+    key, needs_head_graph = 'mmd', True
 
     def __init__(self, weight=0.1, kernel_mul=2.0, kernel_num=5):
-        from uda.model.loss import MMD_loss3
-        if not weight > 0:
-            raise ValueError('MMDAlign: the weight must be positive, got %r' % (weight,))
+        from uda.model.loss import MMD_loss3, check_positive, check_whole
+        check_positive('MMDAlign: the weight', weight)
+        check_positive('MMDAlign: kernel_mul', kernel_mul)
+        check_whole('MMDAlign: kernel_num', kernel_num, 8)
         self.weight = float(weight)
         self.crit = MMD_loss3(kernel_mul=kernel_mul, kernel_num=kernel_num)
 
-    def term(self, y_s, y_t):
-        return self.crit(y_s.detach(), y_t, scale=self.weight)
+    def step_c(self, step, batch, f_t, y_t, y_t_grad):
+        # y_s lives in step.out since step A (under capture: produced in the first graph, its storage held by that reference)
+        return self.crit(step.out['y_s'].detach(), y_t_grad, scale=self.weight), {}
 
 
-class JointFeatureAlign:
+class JointFeatureAlign(_Term):
     """What ``DAStep(jfa=...)`` takes: step C's loss gains ``weight * loss3(f_t, <desc_s>, xy_t, .)`` (reference
     uda/model/loss.py:331-378), the KL divergence between the channel distributions of the neck output pooled around the
-    predicted key points of the target batch and of the source batch.  Step A keeps only the source descriptors (B, K, C) fp32;
-    the key points are the device arg-max of the detached heat-maps; only the target features get a gradient.  The weight rides
-    inside the kernels (``scale=``)."""
+    predicted key points of the target batch and of the source batch.  Step A keeps only the source descriptors (B, K, C) fp32
+    (the source feature map goes with its backward); the key points are the device arg-max of the detached heat-maps; only the
+    target features get a gradient, through their GradFanIn beside the heads' input gradients.  The weight rides inside the
+    kernels (``scale=``)."""
+    key = 'jfa'
 
     def __init__(self, weight=1.0, radius=6, axes='xy'):
-        if not weight > 0:
-            raise ValueError('JointFeatureAlign: the weight must be positive, got %r' % (weight,))
-        if not 1 <= int(radius) <= 16 or int(radius) != radius:
-            raise ValueError('JointFeatureAlign: the radius must be 1 .. 16, got %r' % (radius,))
-        if axes not in ops.JFA_AXES:
-            raise ValueError("JointFeatureAlign: axes must be 'xy' or 'ref', got %r" % (axes,))
+        from uda.model.loss import check_axes, check_positive, check_whole
+        check_positive('JointFeatureAlign: the weight', weight)
+        check_whole('JointFeatureAlign: the radius', radius, 16)
+        check_axes('JointFeatureAlign: axes', axes)
         self.weight, self.radius, self.axes = float(weight), int(radius), axes
 
-    def source(self, f_s, y_s):
-        """Step A: the descriptors of the source batch, detached."""
+    def step_a(self, f_s, y_s):
         from uda.model.regda_4 import cached_centres
-        return ops.joint_pool(f_s.detach(), cached_centres(y_s), self.radius, self.axes)
+        return {'jfa_desc_s': ops.joint_pool(f_s.detach(), cached_centres(y_s), self.radius, self.axes)}
 
-    def term(self, f_t, desc_s, y_t):
-        """Step C: (the term, the target descriptors it was computed from)."""
+    def step_c(self, step, batch, f_t, y_t, y_t_grad):
         from uda.model.loss import loss1, joint_kl_loss
         from uda.model.regda_4 import cached_centres
         desc_t = loss1(f_t, cached_centres(y_t), self.radius, self.axes)
-        return joint_kl_loss(desc_t, desc_s, self.weight), desc_t.detach()
+        return joint_kl_loss(desc_t, step.out['jfa_desc_s'], self.weight), {'jfa_desc_t': desc_t.detach()}
 
 
-class PrototypeAlign:
+class PrototypeAlign(_Term):
     """What ``DAStep(proto=...)`` takes: step C's loss gains ``weight * lossx`` (``criterion='kl'``, reference
     uda/model/loss.py:381-466) or ``weight * lossx3`` (``'softkl'``, :560-652) between the per-joint class prototypes of the target
     and of the source batch: the neck output pooled around the predicted key points (each window divided by its own s1 * s2),
     averaged over the batch and blended with a running memory per domain, ``P = m * mean + (1 - m) * memory``, ``memory <- P``.
-    Step A updates the source memory and keeps the source prototypes (K, C); step C updates the target memory.  The key points
-    are the device arg-max of the detached heat-maps; only the target features get a gradient.  The weight rides inside the
-    kernels; m sits in device memory (``set_m``), and the memories live at fixed addresses, so captured graphs carry the state
-    from replay to replay.  With several ranks each rank keeps its own memories, as BatchNorm statistics are per GPU here."""
+    Step A updates the source memory, once per iteration, and keeps the source prototypes (K, C); step C updates the target
+    memory.  The key points are the device arg-max of the detached heat-maps; only the target features get a gradient, as the JFA
+    term's.  The weight rides inside the kernels; m sits in device memory (``set_m``), and the memories live at fixed addresses, so
+    captured graphs carry the state from replay to replay (``uda.model.loss.PrototypeState``).  With several ranks each rank keeps
+    its own memories, as BatchNorm statistics are per GPU here."""
+    key = 'proto'
 
     def __init__(self, weight=1.0, radius=6, axes='xy', m=0.999, criterion='kl'):
-        from uda.model.loss import PrototypeMemory
-        if not weight > 0:
-            raise ValueError('PrototypeAlign: the weight must be positive, got %r' % (weight,))
-        if not 1 <= int(radius) <= 16 or int(radius) != radius:
-            raise ValueError('PrototypeAlign: the radius must be 1 .. 16, got %r' % (radius,))
-        if axes not in ops.JFA_AXES:
-            raise ValueError("PrototypeAlign: axes must be 'xy' or 'ref', got %r" % (axes,))
-        if not 0.0 < float(m) <= 1.0:
-            raise ValueError('PrototypeAlign: m must be in (0, 1], got %r' % (m,))
+        from uda.model.loss import PrototypeState, check_positive
+        check_positive('PrototypeAlign: the weight', weight)
         if criterion not in ops.PROTO_MODES:
             raise ValueError("PrototypeAlign: the criterion must be 'kl' or 'softkl', got %r" % (criterion,))
-        self.weight, self.radius, self.axes, self.m, self.criterion = float(weight), int(radius), axes, float(m), criterion
-        self.mem_s, self.mem_t, self.blend = PrototypeMemory(), PrototypeMemory(), None
+        self.weight, self.criterion = float(weight), criterion
+        self.state = PrototypeState('PrototypeAlign', radius, axes, m, max_radius=16)
+        self.mem_s, self.mem_t = self.state.mems
+        self.set_m, self.reset = self.state.set_m, self.state.reset
 
-    def _blend(self, device):
-        if self.blend is None:
-            self.blend = ops.proto_blend(self.m, device=device)
-        return self.blend
+    m = property(lambda self: self.state.m)
 
-    def set_m(self, m):
-        """Change m (outside graph capture): the device record is rewritten in place and captured graphs follow."""
-        if not 0.0 < float(m) <= 1.0:
-            raise ValueError('PrototypeAlign: m must be in (0, 1], got %r' % (m,))
-        self.m = float(m)
-        if self.blend is not None:
-            ops.proto_blend(self.m, out=self.blend)
-
-    def _proto(self, f, y, mem):
-        from uda.model.loss import prototype
+    def _proto(self, side, f, y):
         from uda.model.regda_4 import cached_centres
-        xy = cached_centres(y)
-        return prototype(f, xy, mem.tensor(xy.shape[1], f.shape[1], f.device), self._blend(f.device), self.radius, self.axes)
+        return self.state.prototype(side, f, cached_centres(y))
 
-    def source(self, f_s, y_s):
-        """Step A: the source prototypes (K, C), detached; the source memory is updated."""
-        return self._proto(f_s.detach(), y_s, self.mem_s)
+    def step_a(self, f_s, y_s):
+        return {'proto_s': self._proto(0, f_s.detach(), y_s)}
 
     def term(self, f_t, proto_s, y_t):
-        """Step C: (the term, the target prototypes it was computed from); the target memory is updated."""
+        """(the term, the target prototypes it was computed from); the target memory is updated.  A method of its own with
+        plain operands: tests/test_gpu_proto.py wraps it to record what step C hands the term."""
         from uda.model.loss import prototype_kl_loss
-        proto_t = self._proto(f_t, y_t, self.mem_t)
+        proto_t = self._proto(1, f_t, y_t)
         return prototype_kl_loss(proto_t, proto_s, self.criterion, self.weight), proto_t.detach()
 
-    def reset(self):
-        self.mem_s.reset()
-        self.mem_t.reset()
+    def step_c(self, step, batch, f_t, y_t, y_t_grad):
+        loss, proto_t = self.term(f_t, step.out['proto_s'], y_t)
+        return loss, {'proto_t': proto_t}
 
     def state_dict(self):
         """Both memories (CPU copies; None before first use) and m: what the epoch checkpoint keeps as ``proto_state``."""
@@ -248,20 +249,12 @@ class DAStep:
                  proto=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         self.ema = ema               # optional mi355.optim.EMATeacher: updated behind step C's optimizer (train1.py:461)
-        # optional mi355.teacher.MeanTeacher: step C's loss gains m * mt_loss(y_t, model_ema(x_t_ema)) (train1.py:351-364,
-        # uda/model/loss.py:265-297); the teacher's folded operands are refreshed behind the EMA update
-        self.mt = mt
+        # the optional terms of step C's loss (`_Term`; any of them may also be assigned after construction): a
+        # mi355.teacher.MeanTeacher, whose folded operands are refreshed behind the EMA update, an MMDAlign, a JointFeatureAlign,
+        # a PrototypeAlign
+        self.mt, self.mmd, self.jfa, self.proto = mt, mmd, jfa, proto
         if mt is not None and self.ema is None:
             self.ema = mt.ema
-        # optional MMDAlign: step C's loss gains w * MMD_loss3(y_s.detach(), y_t) (uda/model/loss.py:1061-1104), y_s = the
-        # heat-maps step A left in self.out['y_s']
-        self.mmd = mmd
-        # optional JointFeatureAlign: step C's loss gains w * loss3(f_t, <desc_s>, xy_t, .) (uda/model/loss.py:331-378), desc_s = the
-        # source descriptors step A left in self.out['jfa_desc_s']
-        self.jfa = jfa
-        # optional PrototypeAlign: step C's loss gains w * lossx / lossx3 (uda/model/loss.py:381-466, 560-652) between the target
-        # prototypes and the source prototypes step A left in self.out['proto_s']; both steps update their domain's memory
-        self.proto = proto
         self.trade_off, self.skip, self.track_acc = trade_off, skip_discarded, track_accuracy
         self.graphs = None
         self.out = {}
@@ -334,18 +327,18 @@ class DAStep:
             _allreduce_mean(self._grads(keys))
 
     # ------------------------------------------------------------------ the three steps (fwd+bwd, then update)
+    def terms(self):
+        """The optional terms that are on, in the order in which step C adds them and issues their kernels."""
+        return [t for t in (self.mt, self.mmd, self.jfa, self.proto) if t is not None]
+
     def _fwdbwd_A(self, b):
         m, c = self.model, self.crit
         for o in self.opt.values():
             o.zero_grad()
         with _rt.grouped_wgrads():
             y_s, y_s_adv, y_s_adv2, y_s_adv3, f_s = m(b['x_s'])
-            if self.jfa is not None:
-                # only the (B, K, C) descriptors outlive this step: the source feature map goes with its backward
-                self.out.update(jfa_desc_s=self.jfa.source(f_s, y_s))
-            if self.proto is not None:
-                # only the (K, C) prototypes outlive this step; the source memory is updated here, once per iteration
-                self.out.update(proto_s=self.proto.source(f_s, y_s))
+            for t in self.terms():
+                self.out.update(t.step_a(f_s, y_s))
             # the coefficients of train1.py:384-387 ride inside the loss kernels (scale=), the total's gradient is the unit scalar
             loss_s = c['kl'](y_s, b['label_s'], b['w_s'], scale=2) + \
                 c['rd2'](y_s, y_s_adv2, None, b['w_s'], mode='min', scale=4) + \
@@ -368,8 +361,8 @@ class DAStep:
                 f_t = m.features(b['x_t'])
                 y_t_grad = m.head(f_t)
                 y_t = y_t_grad.detach()           # only ever used detached (pseudo-labels) in B and C ...
-                if self.mt is None and self.mmd is None:
-                    y_t_grad = None               # ... but for the consistency / MMD term of step C: else the head's graph is freed here
+                if not any(t.needs_head_graph for t in self.terms()):
+                    y_t_grad = None               # ... but for a term of step C that goes through the head: else its graph is freed here
             self._shared = (f_t, y_t, y_t_grad)
             y_t_adv, y_t_adv2, y_t_adv3 = m.adv_heads(f_t.detach())
         else:
@@ -408,29 +401,13 @@ class DAStep:
             loss1 = c['rd2'](y_t, y_t_adv2, None, b['w_t'], mode='min', scale=0.3 * to)
             loss2 = c['rd'](y_t, y_t_adv, None, b['w_t'], mode='min', scale=to)
             loss_gt = loss1 + loss2                     # = 0.3 to rd2 + to rd   (train1.py:443-448)
-            loss_mt = None
-            if self.mt is not None:
-                # the main head's weight gradients of this backward are discarded by the next step A's zero_grad, like the
-                # adversarial heads'; only optimizer_f steps in C
-                x_ema = b['x_t_ema'] if b.get('x_t_ema') is not None else b['x_t']
-                loss_mt = self.mt.term(y_t_grad, x_ema)
-            total = loss_gt if loss_mt is None else loss_gt + loss_mt
-            loss_mmd = None
-            if self.mmd is not None:
-                # as with the mean teacher: only optimizer_f steps in C, the main head's weight gradients are discarded.  y_s lives
-                # in self.out since step A (under capture: produced in the first graph, its storage held by that reference)
-                loss_mmd = self.mmd.term(self.out['y_s'], y_t_grad)
-                total = total + loss_mmd
-            loss_jfa = None
-            if self.jfa is not None:
-                # only f_t gets a gradient, through its GradFanIn beside the heads' input gradients; only optimizer_f steps in C
-                loss_jfa, desc_t = self.jfa.term(f_t, self.out['jfa_desc_s'], y_t)
-                total = total + loss_jfa
-            loss_proto = None
-            if self.proto is not None:
-                # as the JFA term: only f_t gets a gradient, through its GradFanIn; only optimizer_f steps in C
-                loss_proto, proto_t = self.proto.term(f_t, self.out['proto_s'], y_t)
-                total = total + loss_proto
+            # Only optimizer_f steps in C: the weight gradients this backward leaves in the main head (through a term that needs its
+            # graph) are discarded by the next step A's zero_grad, like the adversarial heads'.
+            total, kept = loss_gt, {}
+            for t in self.terms():
+                loss, more = t.step_c(self, b, f_t, y_t, y_t_grad)
+                total = total + loss
+                kept.update(more, **{'loss_' + t.key: loss.detach()})
             with _rt.grouped_wgrads():
                 total.backward(_rt.unit_grad(total))
             _rt.join_side()
@@ -438,15 +415,7 @@ class DAStep:
             if self.skip:
                 for p in self._adv_params:
                     p.requires_grad_(True)
-        self.out.update(loss_gt=loss_gt.detach(), y_t=y_t.detach(), y_t_adv=y_t_adv.detach())
-        if loss_mt is not None:
-            self.out.update(loss_mt=loss_mt.detach())
-        if loss_mmd is not None:
-            self.out.update(loss_mmd=loss_mmd.detach())
-        if loss_jfa is not None:
-            self.out.update(loss_jfa=loss_jfa.detach(), jfa_desc_t=desc_t)
-        if loss_proto is not None:
-            self.out.update(loss_proto=loss_proto.detach(), proto_t=proto_t)
+        self.out.update(kept, loss_gt=loss_gt.detach(), y_t=y_t.detach(), y_t_adv=y_t_adv.detach())
 
     def _update_C(self):
         self.opt['f'].step()

@@ -1224,23 +1224,64 @@ def _chk_desc(who, what, t, shape=None):
                          % (who, what, '' if shape is None else ' of shape %s' % (tuple(shape),), t.dtype, tuple(t.shape), t.stride(), t.data_ptr() % 16))
 
 
+def _pool_args(who, f, xy, radius, axes, out):
+    """The checks of the pooling wrapper `who` (feature map, key points, radius and axes, 16-byte start, room) and its `out`, made
+    when None: (B, K, C, H, W, out)."""
+    _chk_feature(who + ' feature', f)
+    B, C, H, W = f.shape
+    K = _chk_joints(who, xy, B)
+    _chk_jfa(who, C, H, W, radius, axes)
+    if f.data_ptr() % 16:
+        raise Mi355Error('%s: the feature map must start on a 16-byte boundary (offset %d)' % (who, f.data_ptr() % 16))
+    if out is None:
+        out = torch.empty((B, K, C), dtype=torch.float32, device=f.device)
+    _chk_desc(who, 'out', out, (B, K, C))
+    _chk_room(who + ' feature', f, B * C * H * W)
+    _chk_room(who + ' xy', xy, B * K * 2)
+    _chk_room(who + ' out', out, B * K * C)
+    return B, K, C, H, W, out
+
+
+def _gather_args(who, g, what, per_image, xy, out, radius, axes):
+    """The checks of the gather wrapper `who`: the feature gradient `out`, key points, radius and axes, the incoming gradient `g`
+    named `what` ((B, K, C) when `per_image`, else (K, C)), 16-byte start, room: (B, K, C, H, W)."""
+    _chk_feature(who + ' out', out)
+    B, C, H, W = out.shape
+    K = _chk_joints(who, xy, B)
+    _chk_jfa(who, C, H, W, radius, axes)
+    if per_image:
+        _chk_desc(who, what, g, (B, K, C))
+    else:
+        _chk_proto(who, what, g, (K, C))
+    if out.data_ptr() % 16:
+        raise Mi355Error('%s: the feature gradient must start on a 16-byte boundary (offset %d)' % (who, out.data_ptr() % 16))
+    _chk_room('%s %s' % (who, what), g, (B if per_image else 1) * K * C)
+    _chk_room(who + ' out', out, B * C * H * W)
+    return B, K, C, H, W
+
+
+def _kl_buffers(who, chk, a, rows, grads):
+    """rows (one per row of the operand `a`) and the wanted gradients of the KL wrapper `who`, each made when None, the gradients
+    checked with `chk` against `a`; `grads`: (name, tensor or None, wanted) for either side.  Returns (rows, [gradient or None,
+    gradient or None])."""
+    if rows is None:
+        rows = torch.empty(a.shape[:-1], dtype=torch.float32, device=a.device)
+    grads = [(what, torch.empty_like(a) if want and g is None else g, want) for what, g, want in grads]
+    if rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise Mi355Error('%s: rows must be a contiguous fp32 tensor' % who)
+    for what, g, want in grads:
+        if want:
+            chk(who, what, g, a.shape)
+    _chk_room(who + ' rows', rows, a.numel() // a.shape[-1])
+    return rows, [g if want else None for _, g, want in grads]
+
+
 def joint_pool(f, xy, radius=6, axes='ref', divisor=None, out=None):
     """desc (B, K, C) fp32: the box sum of the window of the channels_last feature map f (B, C, H, W; bf16 / fp32) around each key
     point xy (B, K, 2) = (x, y), divided by `divisor` ((2 radius + 1)^2 when None): the reference's loss1
     (uda/model/loss.py:331-365)."""
     _chk_dev(f, xy, out)
-    _chk_feature('joint_pool feature', f)
-    B, C, H, W = f.shape
-    K = _chk_joints('joint_pool', xy, B)
-    _chk_jfa('joint_pool', C, H, W, radius, axes)
-    if f.data_ptr() % 16:
-        raise Mi355Error('joint_pool: the feature map must start on a 16-byte boundary (offset %d)' % (f.data_ptr() % 16))
-    if out is None:
-        out = torch.empty((B, K, C), dtype=torch.float32, device=f.device)
-    _chk_desc('joint_pool', 'out', out, (B, K, C))
-    _chk_room('joint_pool feature', f, B * C * H * W)
-    _chk_room('joint_pool xy', xy, B * K * 2)
-    _chk_room('joint_pool out', out, B * K * C)
+    B, K, C, H, W, out = _pool_args('joint_pool', f, xy, radius, axes, out)
     call('mi355_jfa_pool', ptr(f), ptr(xy), ptr(out), B, K, C, H, W, int(radius), joint_divisor(radius) if divisor is None else float(divisor),
          JFA_AXES[axes], dtype_code(f.dtype), stream_ptr())
     return out
@@ -1257,21 +1298,10 @@ def joint_kl(a, b, want_a, want_b, scale=1.0, rows=None, grad_a=None, grad_b=Non
     B, K, C = a.shape
     if B < 1 or K < 1 or C < 8 or C % 8:
         raise Mi355Error('joint_kl: B=%d K=%d C=%d (C a multiple of 8, at least 8)' % (B, K, C))
-    if rows is None:
-        rows = torch.empty((B, K), dtype=torch.float32, device=a.device)
-    if want_a and grad_a is None:
-        grad_a = torch.empty_like(a)
-    if want_b and grad_b is None:
-        grad_b = torch.empty_like(b)
-    if rows.dtype != torch.float32 or not rows.is_contiguous():
-        raise Mi355Error('joint_kl: rows must be a contiguous fp32 tensor')
-    for what, g, want in (('grad_a', grad_a, want_a), ('grad_b', grad_b, want_b)):
-        if want:
-            _chk_desc('joint_kl', what, g, a.shape)
-    _chk_room('joint_kl rows', rows, B * K)
+    rows, (grad_a, grad_b) = _kl_buffers('joint_kl', _chk_desc, a, rows, (('grad_a', grad_a, want_a), ('grad_b', grad_b, want_b)))
     call('mi355_jfa_kl', ptr(a), ptr(b), ptr(rows), ptr(grad_a) if want_a else 0, ptr(grad_b) if want_b else 0, B * K, C,
          float(scale) / (B * K), stream_ptr())
-    return rows, (grad_a if want_a else None), (grad_b if want_b else None)
+    return rows, grad_a, grad_b
 
 
 def joint_scatter(gd, xy, out, accumulate, radius=6, axes='ref', divisor=None):
@@ -1279,15 +1309,7 @@ def joint_scatter(gd, xy, out, accumulate, radius=6, axes='ref', divisor=None):
     divisor over the joints whose window holds the pixel (ascending j, fp32).  accumulate=False writes it (zeros outside every
     window); accumulate=True adds it onto what `out` holds, one rounding, and leaves uncovered pixels alone."""
     _chk_dev(gd, xy, out)
-    _chk_feature('joint_scatter out', out)
-    B, C, H, W = out.shape
-    K = _chk_joints('joint_scatter', xy, B)
-    _chk_jfa('joint_scatter', C, H, W, radius, axes)
-    _chk_desc('joint_scatter', 'gd', gd, (B, K, C))
-    if out.data_ptr() % 16:
-        raise Mi355Error('joint_scatter: the feature gradient must start on a 16-byte boundary (offset %d)' % (out.data_ptr() % 16))
-    _chk_room('joint_scatter gd', gd, B * K * C)
-    _chk_room('joint_scatter out', out, B * C * H * W)
+    B, K, C, H, W = _gather_args('joint_scatter', gd, 'gd', True, xy, out, radius, axes)
     call('mi355_jfa_scatter', ptr(gd), ptr(xy), ptr(out), int(bool(accumulate)), B, K, C, H, W, int(radius),
          joint_divisor(radius) if divisor is None else float(divisor), JFA_AXES[axes], dtype_code(out.dtype), stream_ptr())
     return out
@@ -1330,18 +1352,7 @@ def proto_pool(f, xy, radius=6, axes='ref', out=None):
     point xy (B, K, 2) = (x, y), divided by the window's own s_row * s_col, s = hi - lo + 1 (the reference's lossx.loss1 up to its
     stack, uda/model/loss.py:402-433)."""
     _chk_dev(f, xy, out)
-    _chk_feature('proto_pool feature', f)
-    B, C, H, W = f.shape
-    K = _chk_joints('proto_pool', xy, B)
-    _chk_jfa('proto_pool', C, H, W, radius, axes)
-    if f.data_ptr() % 16:
-        raise Mi355Error('proto_pool: the feature map must start on a 16-byte boundary (offset %d)' % (f.data_ptr() % 16))
-    if out is None:
-        out = torch.empty((B, K, C), dtype=torch.float32, device=f.device)
-    _chk_desc('proto_pool', 'out', out, (B, K, C))
-    _chk_room('proto_pool feature', f, B * C * H * W)
-    _chk_room('proto_pool xy', xy, B * K * 2)
-    _chk_room('proto_pool out', out, B * K * C)
+    B, K, C, H, W, out = _pool_args('proto_pool', f, xy, radius, axes, out)
     call('mi355_proto_pool', ptr(f), ptr(xy), ptr(out), B, K, C, H, W, int(radius), JFA_AXES[axes], dtype_code(f.dtype), stream_ptr())
     return out
 
@@ -1379,21 +1390,10 @@ def proto_kl(pt, ps, want_t, want_s, mode='kl', scale=1.0, rows=None, grad_t=Non
     _chk_proto('proto_kl', 'pt', pt)
     _chk_proto('proto_kl', 'ps', ps, pt.shape)
     K, C = pt.shape
-    if rows is None:
-        rows = torch.empty((K,), dtype=torch.float32, device=pt.device)
-    if want_t and grad_t is None:
-        grad_t = torch.empty_like(pt)
-    if want_s and grad_s is None:
-        grad_s = torch.empty_like(ps)
-    if rows.dtype != torch.float32 or not rows.is_contiguous():
-        raise Mi355Error('proto_kl: rows must be a contiguous fp32 tensor')
-    for what, g, want in (('grad_t', grad_t, want_t), ('grad_s', grad_s, want_s)):
-        if want:
-            _chk_proto('proto_kl', what, g, pt.shape)
-    _chk_room('proto_kl rows', rows, K)
+    rows, (grad_t, grad_s) = _kl_buffers('proto_kl', _chk_proto, pt, rows, (('grad_t', grad_t, want_t), ('grad_s', grad_s, want_s)))
     call('mi355_proto_kl', ptr(pt), ptr(ps), ptr(rows), ptr(grad_t) if want_t else 0, ptr(grad_s) if want_s else 0, K, C,
          PROTO_MODES[mode], float(scale) / K if mode == 'kl' else float(scale), stream_ptr())
-    return rows, (grad_t if want_t else None), (grad_s if want_s else None)
+    return rows, grad_t, grad_s
 
 
 def proto_scatter(gp, xy, blend, out, accumulate, radius=6, axes='ref'):
@@ -1402,16 +1402,8 @@ def proto_scatter(gp, xy, blend, out, accumulate, radius=6, axes='ref'):
     gradient w.r.t. the prototypes, the same for every image.  accumulate=False writes it (zeros outside every window);
     accumulate=True adds it onto what `out` holds, one rounding, and leaves uncovered pixels alone."""
     _chk_dev(gp, xy, blend, out)
-    _chk_feature('proto_scatter out', out)
-    B, C, H, W = out.shape
-    K = _chk_joints('proto_scatter', xy, B)
-    _chk_jfa('proto_scatter', C, H, W, radius, axes)
-    _chk_proto('proto_scatter', 'gp', gp, (K, C))
     _chk_blend('proto_scatter', blend)
-    if out.data_ptr() % 16:
-        raise Mi355Error('proto_scatter: the feature gradient must start on a 16-byte boundary (offset %d)' % (out.data_ptr() % 16))
-    _chk_room('proto_scatter gp', gp, K * C)
-    _chk_room('proto_scatter out', out, B * C * H * W)
+    B, K, C, H, W = _gather_args('proto_scatter', gp, 'gp', False, xy, out, radius, axes)
     call('mi355_proto_scatter', ptr(gp), ptr(xy), ptr(blend), ptr(out), int(bool(accumulate)), B, K, C, H, W, int(radius),
          JFA_AXES[axes], dtype_code(out.dtype), stream_ptr())
     return out

@@ -220,9 +220,16 @@ class MeanTeacher:
         if self.shape is not None:
             self.loss.set(self.m(), self.k(), self.shape)
 
-    def term(self, y_t, x_t_ema):
-        """m * mt_loss(y_t, teacher(x_t_ema)) with y_t's autograd graph."""
+    # one of DAStep's optional terms (mi355.da_step._Term)
+    key, needs_head_graph = 'mt', True
+
+    def step_a(self, f_s, y_s):
+        return {}
+
+    def step_c(self, step, batch, f_t, y_t, y_t_grad):
+        """m * mt_loss(y_t, teacher(x_t_ema)) with y_t's autograd graph; x_t_ema is x_t itself when the batch has none."""
+        x_t_ema = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
         y_ema = self.teacher.forward(x_t_ema)
         if not torch.cuda.is_current_stream_capturing():
-            self.sync(y_t.shape)
-        return self.loss(y_t, y_ema)
+            self.sync(y_t_grad.shape)
+        return self.loss(y_t_grad, y_ema), {}

@@ -53,9 +53,10 @@ from torch.utils.data.distributed import DistributedSampler
 import mi355
 import uda.model as models
 from mi355 import ops as _ops
-from mi355.da_step import build_training, broadcast_module, _allreduce_mean
+from mi355.da_step import JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
 from mi355.optim import EMATeacher, FusedSGD
-from uda.model.loss import JointsKLLoss
+from mi355.teacher import MeanTeacher
+from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
 from uda.model.regda_7 import MainOutput, PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
 from utils.data import ForeverDataIterator, DevicePrefetcher, DeviceAugmentIterator, ragged_collate
@@ -206,22 +207,14 @@ def main(args):
     if args.ema_update != 'off':
         # the teacher follows the model after every iteration (uda/model/loss.py:252-261 at train1.py:461), on the device
         ema = step.ema = EMATeacher(model, model_ema, opts, args.ema_decay, warmup=args.ema_update == 'warmup')
+    # the optional terms of step C's loss (what each adds: the classes' docstrings)
     if args.mt_loss == 'on':
-        # step C gains m * mt_loss(y_t, model_ema(x_t_ema)) (train1.py:351-364); the teacher runs inside the iteration
-        from mi355.teacher import MeanTeacher
-        step.mt = MeanTeacher(ema, weight=args.mt_weight, k=args.mt_k)
+        step.mt = MeanTeacher(ema, weight=args.mt_weight, k=args.mt_k)          # the teacher runs inside the iteration
     if args.mmd_loss == 'on':
-        # step C gains w * MMD_loss3(y_s.detach(), y_t) (uda/model/loss.py:1061-1104): a non-adversarial alignment term
-        from mi355.da_step import MMDAlign
         step.mmd = MMDAlign(weight=args.mmd_weight, kernel_mul=args.mmd_mul, kernel_num=args.mmd_kernels)
     if args.jfa_loss == 'on':
-        # step C gains w * loss3(f_t, <source descriptors>, xy_t, .) (uda/model/loss.py:331-378): alignment on the neck features
-        from mi355.da_step import JointFeatureAlign
         step.jfa = JointFeatureAlign(weight=args.jfa_weight, radius=args.jfa_radius, axes=args.jfa_axes)
     if args.proto_loss != 'off':
-        # step C gains w * lossx / lossx3 on the per-joint class prototypes of the neck features, blended with a running memory
-        # per domain (uda/model/loss.py:381-466, 560-652)
-        from mi355.da_step import PrototypeAlign
         step.proto = PrototypeAlign(weight=args.proto_weight, radius=args.proto_radius, axes=args.proto_axes, m=args.proto_m,
                                     criterion=args.proto_loss)
     start_epoch = 0
@@ -364,19 +357,10 @@ def _pck(dists, thr=0.5):
 def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     names = ['Time', 'Data', 'Loss (s)', 'Loss (t, false)', 'Loss (t, truth)', 'Acc (s)', 'Acc (t)', 'Acc (s, adv)', 'Acc (t, adv)']
     fmts = [':4.2f', ':3.1f', ':.2e', ':.2e', ':.2e', ':3.2f', ':3.2f', ':3.2f', ':3.2f']
-    mt = getattr(step, 'mt', None)
+    mt, terms = step.mt, step.terms()
     if mt is not None:
         mt.set_epoch(epoch)                              # m and k are functions of the epoch (train1.py:351-353)
-        names, fmts = names + ['Loss (mt)'], fmts + [':.2e']
-    mmd = getattr(step, 'mmd', None)
-    if mmd is not None:
-        names, fmts = names + ['Loss (mmd)'], fmts + [':.2e']
-    jfa = getattr(step, 'jfa', None)
-    if jfa is not None:
-        names, fmts = names + ['Loss (jfa)'], fmts + [':.2e']
-    proto = getattr(step, 'proto', None)
-    if proto is not None:
-        names, fmts = names + ['Loss (proto)'], fmts + [':.2e']
+    names, fmts = names + ['Loss (%s)' % t.key for t in terms], fmts + [':.2e'] * len(terms)
     meters = [AverageMeter(n, f) for n, f in zip(names, fmts)]
     progress = ProgressMeter(args.iters_per_epoch, meters, prefix="Epoch: [{}]".format(epoch))
     end = time.time()
@@ -420,14 +404,8 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
                 m.update(float(out[k]), args.batch_size)
             for m, k in zip(meters[5:9], ('pck_s', 'pck_t', 'pck_s_adv', 'pck_t_adv')):
                 a, c = _pck(out[k]); m.update(a, c)
-            if mt is not None:
-                meters[9].update(float(out['loss_mt']), args.batch_size)
-            if mmd is not None:
-                meters[names.index('Loss (mmd)')].update(float(out['loss_mmd']), args.batch_size)
-            if jfa is not None:
-                meters[names.index('Loss (jfa)')].update(float(out['loss_jfa']), args.batch_size)
-            if proto is not None:
-                meters[names.index('Loss (proto)')].update(float(out['loss_proto']), args.batch_size)
+            for m, t in zip(meters[9:], terms):
+                m.update(float(out['loss_' + t.key]), args.batch_size)
             meters[0].update(time.time() - end)
             progress.display(i)
         end = time.time()
@@ -681,27 +659,22 @@ class _Parser(argparse.ArgumentParser):
         args = super().parse_args(*a, **kw)
         if getattr(args, 'mt_loss', 'off') == 'on' and getattr(args, 'ema_update', 'off') == 'off':
             self.error('--mt-loss on needs a moving teacher: add --ema-update const (or warmup)')
-        if getattr(args, 'mmd_loss', 'off') == 'on':
-            if not args.mmd_weight > 0:
-                self.error('--mmd-weight must be positive, got %r' % (args.mmd_weight,))
-            if not 1 <= args.mmd_kernels <= 8:
-                self.error('--mmd-kernels must be 1 .. 8, got %d' % args.mmd_kernels)
-            if not args.mmd_mul > 0:
-                self.error('--mmd-mul must be positive, got %r' % (args.mmd_mul,))
-            if args.batch_size > 128:
-                self.error('--mmd-loss on takes at most 128 images per domain and GPU (the kernels hold n = 2 B <= 256 rows), got -b %d' % args.batch_size)
-        if getattr(args, 'jfa_loss', 'off') == 'on':
-            if not args.jfa_weight > 0:
-                self.error('--jfa-weight must be positive, got %r' % (args.jfa_weight,))
-            if not 1 <= args.jfa_radius <= 16:
-                self.error('--jfa-radius must be 1 .. 16, got %d' % args.jfa_radius)
-        if getattr(args, 'proto_loss', 'off') != 'off':
-            if not args.proto_weight > 0:
-                self.error('--proto-weight must be positive, got %r' % (args.proto_weight,))
-            if not 1 <= args.proto_radius <= 16:
-                self.error('--proto-radius must be 1 .. 16, got %d' % args.proto_radius)
-            if not 0 < args.proto_m <= 1:
-                self.error('--proto-m must be in (0, 1], got %r' % (args.proto_m,))
+        try:                                             # (the checks the term classes make, under the flags' names)
+            if getattr(args, 'mmd_loss', 'off') == 'on':
+                check_positive('--mmd-weight', args.mmd_weight)
+                check_whole('--mmd-kernels', args.mmd_kernels, 8)
+                check_positive('--mmd-mul', args.mmd_mul)
+                if args.batch_size > 128:
+                    self.error('--mmd-loss on takes at most 128 images per domain and GPU (the kernels hold n = 2 B <= 256 rows), got -b %d' % args.batch_size)
+            if getattr(args, 'jfa_loss', 'off') == 'on':
+                check_positive('--jfa-weight', args.jfa_weight)
+                check_whole('--jfa-radius', args.jfa_radius, 16)
+            if getattr(args, 'proto_loss', 'off') != 'off':
+                check_positive('--proto-weight', args.proto_weight)
+                check_whole('--proto-radius', args.proto_radius, 16)
+                check_blend_weight('--proto-m', args.proto_m)
+        except ValueError as e:
+            self.error(str(e))
         if getattr(args, 'dump_preds', None):
             args.metrics = 'full'                        # (test.py: predictions are what --metrics full decodes)
         if getattr(args, 'decode', 'argmax') != 'argmax' and getattr(args, 'metrics', 'pck') != 'full':

@@ -250,6 +250,36 @@ def _fan_in_scatter(fan, like, scatter):
     return dx
 
 
+def _keep_for_scatter(ctx, feature, fan, args, *tensors):
+    """What the backward of a pooling function needs: the feature map's shape, dtype and device (the map itself is not kept), its
+    fan-in, the window arguments and the small tensors."""
+    ctx.args, ctx.fan = args, fan
+    ctx.like = (tuple(feature.shape), feature.dtype, feature.device)
+    ctx.save_for_backward(*tensors)
+
+
+def _scatter_backward(ctx, g, scatter):
+    """The feature gradient of a pooling function, or None: ``scatter(g, out, accumulate)`` gathers the fp32 contiguous incoming
+    gradient ``g`` into ``out`` (``_fan_in_scatter``)."""
+    if g is None or not ctx.needs_input_grad[0]:
+        return None
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        g = g.float().contiguous()
+    return _fan_in_scatter(ctx.fan, ctx.like, lambda out, acc: scatter(g, out, acc))
+
+
+def _kl_backward(ctx, gout):
+    """The two gradients a KL function's forward saved (either may be None), times the incoming gradient unless it is the unit
+    scalar."""
+    ga, gb = ctx.saved_tensors
+    if gout is None or (ga is None and gb is None):
+        return None, None
+    if not _rt.is_unit_grad(gout):
+        gout = gout.contiguous().float()
+        ga, gb = (None if g is None else ops.scale_by_dev(g, gout) for g in (ga, gb))
+    return ga, gb
+
+
 class _JointPoolFn(torch.autograd.Function):
     """desc = joint_pool(feature, xy).  The backward is the gather ``jfa_scatter``.  A feature tensor that carries a
     ``mi355.nn.GradFanIn`` (the neck output, which the heads consume as well) gets its gradient through that protocol: when the
@@ -258,21 +288,13 @@ class _JointPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feature, xy, radius, axes, divisor, fan):
-        ctx.args, ctx.fan = (radius, axes, divisor), fan
-        ctx.like = (tuple(feature.shape), feature.dtype, feature.device)      # (the feature map itself is not kept)
-        ctx.save_for_backward(xy)
+        _keep_for_scatter(ctx, feature, fan, (radius, axes, divisor), xy)
         return ops.joint_pool(feature, xy, radius, axes, divisor)
 
     @staticmethod
     def backward(ctx, gdesc):
         xy, = ctx.saved_tensors
-        if gdesc is None or not ctx.needs_input_grad[0]:
-            return None, None, None, None, None, None
-        radius, axes, divisor = ctx.args
-        if gdesc.dtype != torch.float32 or not gdesc.is_contiguous():
-            gdesc = gdesc.float().contiguous()
-        dx = _fan_in_scatter(ctx.fan, ctx.like, lambda out, acc: ops.joint_scatter(gdesc, xy, out, acc, radius, axes, divisor))
-        return dx, None, None, None, None, None
+        return (_scatter_backward(ctx, gdesc, lambda g, out, acc: ops.joint_scatter(g, xy, out, acc, *ctx.args)),) + (None,) * 5
 
 
 class _JointKLFn(torch.autograd.Function):
@@ -288,13 +310,7 @@ class _JointKLFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        ga, gb = ctx.saved_tensors
-        if gout is None or (ga is None and gb is None):
-            return None, None, None
-        if not _rt.is_unit_grad(gout):
-            gout = gout.contiguous().float()
-            ga, gb = (None if g is None else ops.scale_by_dev(g, gout) for g in (ga, gb))
-        return ga, gb, None
+        return _kl_backward(ctx, gout) + (None,)
 
 
 def loss1(feature, pre, radius=6, axes='ref', scale=1.0):
@@ -345,27 +361,17 @@ class _ProtoFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feature, xy, memory, blend, radius, axes, fan):
-        ctx.args, ctx.fan = (radius, axes), fan
-        ctx.like = (tuple(feature.shape), feature.dtype, feature.device)
-        ctx.save_for_backward(xy, blend)
+        _keep_for_scatter(ctx, feature, fan, (radius, axes), xy, blend)
         return ops.proto_update(ops.proto_pool(feature, xy, radius, axes), memory, blend)
 
     @staticmethod
     def backward(ctx, gp):
         xy, blend = ctx.saved_tensors
-        if gp is None or not ctx.needs_input_grad[0]:
-            return None, None, None, None, None, None, None
-        radius, axes = ctx.args
-        if gp.dtype != torch.float32 or not gp.is_contiguous():
-            gp = gp.float().contiguous()
-        dx = _fan_in_scatter(ctx.fan, ctx.like, lambda out, acc: ops.proto_scatter(gp, xy, blend, out, acc, radius, axes))
-        return dx, None, None, None, None, None, None
+        return (_scatter_backward(ctx, gp, lambda g, out, acc: ops.proto_scatter(g, xy, blend, out, acc, *ctx.args)),) + (None,) * 6
 
 
 class _ProtoKLFn(torch.autograd.Function):
-    """loss = scale * mean_j rows ('kl') or scale * sum_j rows ('softkl') on prototypes pt, ps (K, C).  As _JointKLFn: the kernel
-    writes d loss / d pt and / d ps in the forward, for whichever needs a gradient; the backward hands them on when the incoming
-    gradient is the unit scalar."""
+    """loss = scale * mean_j rows ('kl') or scale * sum_j rows ('softkl') on prototypes pt, ps (K, C).  Gradients as _JointKLFn's."""
 
     @staticmethod
     def forward(ctx, pt, ps, mode, scale):
@@ -375,13 +381,7 @@ class _ProtoKLFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        gt, gs = ctx.saved_tensors
-        if gout is None or (gt is None and gs is None):
-            return None, None, None, None
-        if not _rt.is_unit_grad(gout):
-            gout = gout.contiguous().float()
-            gt, gs = (None if g is None else ops.scale_by_dev(g, gout) for g in (gt, gs))
-        return gt, gs, None, None
+        return _kl_backward(ctx, gout) + (None, None)
 
 
 def prototype(feature, pre, memory, blend, radius=6, axes='ref'):
@@ -444,39 +444,75 @@ class PrototypeMemory:
             self.val = float(val)
 
 
+# The range checks of the alignment terms' options: one text each, under the name `what` of whoever asks (a class's argument or a
+# command-line flag).
+def check_positive(what, v):
+    if not v > 0:
+        raise ValueError('%s must be positive, got %r' % (what, v))
+
+
+def check_whole(what, n, most=None):
+    """A whole number from 1 on (to `most`): a radius, a kernel count."""
+    if not 1 <= int(n) <= (most or int(n)) or int(n) != n:
+        raise ValueError('%s must be %s, got %r' % (what, '1 .. %d' % most if most else 'an integer of at least 1', n))
+
+
+def check_axes(what, axes):
+    if axes not in ops.JFA_AXES:
+        raise ValueError("%s must be 'xy' or 'ref', got %r" % (what, axes))
+
+
+def check_blend_weight(what, m):
+    if not 0.0 < float(m) <= 1.0:
+        raise ValueError('%s must be in (0, 1], got %r' % (what, m))
+
+
+class PrototypeState:
+    """What a prototype term carries from call to call: the running memory of either side (``mems``), the window arguments, m and
+    its device record.  ``who`` names the owner in messages; ``max_radius``: the owner's bound on the radius, if it has one."""
+
+    def __init__(self, who, radius, axes, m, max_radius=None):
+        check_whole(who + ': the radius', radius, max_radius)
+        check_axes(who + ': axes', axes)
+        check_blend_weight(who + ': m', m)
+        self.who, self.radius, self.axes, self.m = who, int(radius), axes, float(m)
+        self.mems, self.blend = (PrototypeMemory(), PrototypeMemory()), None
+
+    def set_m(self, m):
+        """Change m (outside graph capture): the device record is rewritten in place, so a captured graph that contains the loss
+        follows."""
+        check_blend_weight(self.who + ': m', m)
+        self.m = float(m)
+        if self.blend is not None:
+            ops.proto_blend(self.m, out=self.blend)
+
+    def reset(self):
+        for mem in self.mems:
+            mem.reset()
+
+    def prototype(self, side, f, pre):
+        """``prototype(f, pre, .)`` against the memory of ``side`` (0 or 1), which it updates."""
+        if self.blend is None or self.blend.device != f.device:
+            self.blend = ops.proto_blend(self.m, device=f.device)
+        return prototype(f, pre, self.mems[side].tensor(pre.shape[1], f.shape[1], f.device), self.blend, self.radius, self.axes)
+
+
 class _ProtoLoss(nn.Module):
     criterion = None
 
     def __init__(self, reduction='mean', epsilon=0., radius=6, axes='ref', m=0.999, scale=1.0):
         super().__init__()
-        if not 1 <= int(radius) or int(radius) != radius:
-            raise ValueError('%s: the radius must be an integer of at least 1, got %r' % (type(self).__name__, radius))
-        if axes not in ops.JFA_AXES:
-            raise ValueError("%s: axes must be 'ref' or 'xy', got %r" % (type(self).__name__, axes))
-        if not 0.0 < float(m) <= 1.0:
-            raise ValueError('%s: m must be in (0, 1], got %r' % (type(self).__name__, m))
         self.reduction, self.epsilon = reduction, epsilon            # (kept for the signature; the reference ignores both)
-        self.radius, self.axes, self.m, self.scale = int(radius), axes, float(m), float(scale)
-        self._mem1, self._mem2, self._blend = PrototypeMemory(), PrototypeMemory(), None
+        self.state, self.scale = PrototypeState(type(self).__name__, radius, axes, m), float(scale)
+        self.reset, self.set_m = self.state.reset, self.state.set_m
 
-    val1 = property(lambda self: self._mem1.val)
-    val2 = property(lambda self: self._mem2.val)
-
-    def reset(self):
-        self._mem1.reset()
-        self._mem2.reset()
+    val1 = property(lambda self: self.state.mems[0].val)
+    val2 = property(lambda self: self.state.mems[1].val)
+    m = property(lambda self: self.state.m)
 
     def updata(self, val1, val2):
-        self._mem1.set(val1)
-        self._mem2.set(val2)
-
-    def set_m(self, m):
-        """Change m: the device record is rewritten in place, so a captured graph that contains the loss follows."""
-        if not 0.0 < float(m) <= 1.0:
-            raise ValueError('%s: m must be in (0, 1], got %r' % (type(self).__name__, m))
-        self.m = float(m)
-        if self._blend is not None:
-            ops.proto_blend(self.m, out=self._blend)
+        self.state.mems[0].set(val1)
+        self.state.mems[1].set(val2)
 
     def forward(self, f1, f2, pre1, pre2):
         for f, pre in ((f1, pre1), (f2, pre2)):                  # (both sides are checked before anything is launched)
@@ -486,12 +522,7 @@ class _ProtoLoss(nn.Module):
         if pre1.shape[1] != pre2.shape[1] or f1.shape[1] != f2.shape[1]:
             raise ValueError('%s: the two sides must have one channel count and joint count, got features %s / %s, key points %s / %s'
                              % (type(self).__name__, tuple(f1.shape), tuple(f2.shape), tuple(pre1.shape), tuple(pre2.shape)))
-        K, C = pre1.shape[1], f1.shape[1]
-        if self._blend is None or self._blend.device != f1.device:
-            self._blend = ops.proto_blend(self.m, device=f1.device)
-        p1 = prototype(f1, pre1, self._mem1.tensor(K, C, f1.device), self._blend, self.radius, self.axes)
-        p2 = prototype(f2, pre2, self._mem2.tensor(K, C, f2.device), self._blend, self.radius, self.axes)
-        return prototype_kl_loss(p1, p2, self.criterion, self.scale)
+        return prototype_kl_loss(self.state.prototype(0, f1, pre1), self.state.prototype(1, f2, pre2), self.criterion, self.scale)
 
 
 class lossx(_ProtoLoss):

@@ -781,6 +781,72 @@ def test_step_with_the_jfa_and_mmd_terms(gpu):
         mi355.set_compute_dtype('bf16')
 
 
+def test_step_with_all_four_terms_eager_and_replay(gpu):
+    """The mean-teacher, MMD, JFA and prototype terms in one step: an eager iteration and a replayed one give the same four losses
+    and the same weights bit for bit, and step C issues the terms' kernels in the order mt, mmd, jfa, proto (the labels of a
+    term's forward kernels; the gathers of the backward follow behind all of them)."""
+    import mi355
+    from mi355 import ops
+    from mi355.da_step import JointFeatureAlign, MMDAlign
+    from mi355.optim import EMATeacher
+    from mi355.teacher import MeanTeacher
+    from uda.model.regda_7 import PoseResNetx10
+    from utils.synthetic import make_batch
+    from test_gpu_ema import _pose
+    keys = ('loss_mt', 'loss_mmd', 'loss_jfa', 'loss_proto')
+
+    def iterate(capture_at, log_at=None):
+        model, step, scheds = _training(gpu, 'on', jfa=JointFeatureAlign(weight=0.5, radius=3, axes='xy'), mmd=MMDAlign(weight=0.1))
+        teacher = _pose(gpu, PoseResNetx10, 5)
+        teacher.load_state_dict(model.state_dict())
+        for p in teacher.parameters():
+            p.requires_grad = False
+        step.ema = EMATeacher(model, teacher, step.opt, 0.8, warmup=True)
+        step.mt = MeanTeacher(step.ema, weight=0.5, k='all')
+        assert [t.key for t in step.terms()] == ['mt', 'mmd', 'jfa', 'proto']
+        batch = make_batch(2, 128, 32, seed=3, device=gpu)
+        losses, labels = [], None
+        for i in range(3):
+            if i == capture_at:
+                step.capture(batch, warmup=0)
+            if i == log_at:                            # the labels of step C alone
+                inner = step._fwdbwd_C
+
+                def logged_C(b):
+                    torch.cuda.synchronize()
+                    ops.prof_reset()
+                    inner(b)
+                    torch.cuda.synchronize()
+                    seen.extend(e['label'] for e in ops.prof_launches())
+                    ops.prof_reset()
+                seen, step._fwdbwd_C = [], logged_C
+                ops.prof_reset(); ops.prof_enable(2)
+            try:
+                out = step.run(batch)
+                torch.cuda.synchronize()
+            finally:
+                if i == log_at:
+                    ops.prof_enable(0); ops.prof_reset()
+                    step._fwdbwd_C, labels = inner, seen
+            for s in scheds.values():
+                s.step()
+            losses.append(tuple(float(out[k]) for k in keys))
+        return losses, _host(model), labels
+
+    try:
+        eager, w_eager, labels = iterate(None, log_at=2)
+        graph, w_graph, _ = iterate(2)                 # iteration 2 is a replay
+        assert eager == graph and all(np.isfinite(v) and v > 0 for it in eager for v in it), (eager, graph)
+        for k in w_eager:
+            assert _same(w_eager[k], w_graph[k]), k
+        terms = [l.split()[0] for l in labels if l.startswith(('mse_heatmap', 'mmd_', 'jfa_', 'proto_')) and '_scatter' not in l]
+        families = [t.split('_')[0] for t in terms]
+        assert [f for i, f in enumerate(families) if i == 0 or f != families[i - 1]] == ['mse', 'mmd', 'jfa', 'proto'], terms
+        assert terms[-5:] == ['jfa_pool', 'jfa_kl', 'proto_pool', 'proto_update', 'proto_kl'], terms
+    finally:
+        mi355.set_compute_dtype('bf16')
+
+
 def test_step_launch_log(gpu):
     """An iteration with `proto` on holds one proto_pool and one proto_update in step A (the source prototypes) and one proto_pool,
     one proto_update, one proto_kl (the gradient of the target side only) and one proto_scatter in step C; with `proto` off an
