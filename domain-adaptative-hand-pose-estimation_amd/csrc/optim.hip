@@ -4,18 +4,33 @@
 
 // torch.optim.SGD semantics (train1.py:141-148): g' = g + wd*p; buf = mu*buf + g' (buf starts at 0, which equals
 // torch's "first step: buf = g'"); p -= lr * (nesterov ? g' + mu*buf : buf)
-template <typename L>
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
-                                                   const float* __restrict__ lr_dev, float mu, float wd, int nesterov, L* __restrict__ lowp) {
+// CLIP (mi355_sgd_nesterov_clipped): the same step on g_c = fl32(g * coef), coef and skip read once per block from the record
+// mi355_grad_clip_coef wrote; with skip set the block returns before its first store.
+__device__ __forceinline__ float clip1(float g, float coef) {
+#pragma clang fp contract(off)
+  const float gc = g * coef;          // rounded on its own: never contracted into gc + wd * p
+  return gc;
+}
+
+template <typename L, bool CLIP>
+__device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
+                                         const float* __restrict__ lr_dev, float mu, float wd, int nesterov, L* __restrict__ lowp,
+                                         const mi355_clip_rec* __restrict__ rec) {
+  float coef = 1.f;
+  if constexpr (CLIP) {
+    if (rec->skip) return;
+    coef = rec->coef;
+  }
   const float lr = *lr_dev;
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
     float4 pv = reinterpret_cast<float4*>(p)[i];
     const float4 gv = reinterpret_cast<const float4*>(g)[i];
     float4 bv = reinterpret_cast<float4*>(buf)[i];
-    float pp[4] = {pv.x, pv.y, pv.z, pv.w}; const float gg[4] = {gv.x, gv.y, gv.z, gv.w}; float bb[4] = {bv.x, bv.y, bv.z, bv.w};
+    float pp[4] = {pv.x, pv.y, pv.z, pv.w}; float gg[4] = {gv.x, gv.y, gv.z, gv.w}; float bb[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
+      if constexpr (CLIP) gg[e] = clip1(gg[e], coef);
       const float d = gg[e] + wd * pp[e];
       bb[e] = mu * bb[e] + d;
       pp[e] -= lr * (nesterov ? d + mu * bb[e] : bb[e]);
@@ -29,11 +44,25 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   }
   // tail
   for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const float d = g[i] + wd * p[i];
+    const float gi = CLIP ? clip1(g[i], coef) : g[i];
+    const float d = gi + wd * p[i];
     const float b = mu * buf[i] + d; buf[i] = b;
     const float np = p[i] - lr * (nesterov ? d + mu * b : b); p[i] = np;
     if (lowp) lowp[i] = (L)np;
   }
+}
+
+template <typename L>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
+                                                   const float* __restrict__ lr_dev, float mu, float wd, int nesterov, L* __restrict__ lowp) {
+  sgd_body<L, false>(p, g, buf, n, lr_dev, mu, wd, nesterov, lowp, nullptr);
+}
+
+template <typename L>
+__global__ __launch_bounds__(256) void sgd_clipped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
+                                                           const float* __restrict__ lr_dev, float mu, float wd, int nesterov,
+                                                           L* __restrict__ lowp, const mi355_clip_rec* __restrict__ rec) {
+  sgd_body<L, true>(p, g, buf, n, lr_dev, mu, wd, nesterov, lowp, rec);
 }
 
 extern "C" int mi355_sgd_nesterov(float* p, const float* g, float* buf, long n, const float* lr_dev, float momentum, float wd,
@@ -43,6 +72,114 @@ extern "C" int mi355_sgd_nesterov(float* p, const float* g, float* buf, long n, 
   int grid = (int)((n / 4 + 255) / 256); if (grid < 1) grid = 1; if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(sgd_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), p, g, buf, n, lr_dev, momentum, wd, nesterov, (bf16_t*)p_lowp);
   MI_CHECK_LAUNCH("sgd");
+  return MI355_OK;
+}
+
+extern "C" int mi355_sgd_nesterov_clipped(float* p, const float* g, float* buf, long n, const float* lr_dev, const mi355_clip_rec* rec_dev,
+                                          float momentum, float wd, int nesterov, void* p_lowp, void* stream) {
+  if (!p || !g || !buf || !lr_dev || !rec_dev) MI_FAIL(MI355_EINVAL, "sgd_clipped: null pointer");
+  if (n < 1) MI_FAIL(MI355_EINVAL, "sgd_clipped: n=%ld", n);
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) MI_FAIL(MI355_EINVAL, "sgd_clipped: pointers must be 16-byte aligned");
+  if ((uintptr_t)rec_dev & 7) MI_FAIL(MI355_EINVAL, "sgd_clipped: the record must be 8-byte aligned");
+  int grid = (int)((n / 4 + 255) / 256); if (grid < 1) grid = 1; if (grid > 4096) grid = 4096;
+  hipLaunchKernelGGL(sgd_clipped_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), p, g, buf, n, lr_dev, momentum, wd, nesterov,
+                     (bf16_t*)p_lowp, rec_dev);
+  MI_CHECK_LAUNCH("sgd_clipped");
+  return MI355_OK;
+}
+
+// ---- global gradient norm (mi355pose.h: mi355_grad_sumsq_batched / mi355_grad_clip_coef) ---------------------------------------
+// wave_sum of common.h on doubles: the same fixed xor tree, so every lane ends with the same bits.
+__device__ inline double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// 4 waves; the result is valid in thread 0 only (the one that stores it): waves are added in wave order.
+__device__ inline double block_sum_f64(double v, double* red) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Block b finds its item by binary search over blk0 (as ema_batched_kernel) and owns elements [i0, i0 + len) of it, at most
+// MI355_GN_CHUNK: GN_V float4 per lane, lane-interleaved (float4 number j * 256 + lane of the slice), ALL issued before the first
+// use -- 64 KB in flight per block -- then squared and added in fp64 in index order (the square of an fp32 value is exact in
+// fp64, so a contracted and an uncontracted build give the same bits).  The up to three floats behind the last whole quad go to
+// lanes 0..2.
+#define GN_V (MI355_GN_CHUNK / 4 / 256)
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const mi355_gn_item* __restrict__ items, int nitems, double* __restrict__ partials) {
+  __shared__ double red[4];
+  int lo = 0, hi = nitems - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (items[mid].blk0 <= b) lo = mid; else hi = mid - 1; }
+  const mi355_gn_item it = items[lo];
+  const long i0 = (long)(b - it.blk0) * MI355_GN_CHUNK;
+  const long len = it.n - i0 < MI355_GN_CHUNK ? it.n - i0 : MI355_GN_CHUNK;      // (<= 0 only for a malformed table: nothing is read)
+  const float* __restrict__ g = it.g + i0;
+  const int n4 = len > 0 ? (int)(len >> 2) : 0;
+  float4 v[GN_V];
+  if (n4 > 0) {
+    // a quad past the slice's end re-reads the slice's last whole quad (a clamped address, no branch: the loads stay
+    // back to back) and is zeroed below
+#pragma unroll
+    for (int j = 0; j < GN_V; ++j) {
+      const int q = j * 256 + threadIdx.x;
+      v[j] = reinterpret_cast<const float4*>(g)[q < n4 ? q : n4 - 1];
+    }
+  }
+  const int t = (n4 << 2) + threadIdx.x;
+  const float tail = (threadIdx.x < 3 && t < len) ? g[t] : 0.f;
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < GN_V; ++j) {
+    if (j * 256 + (int)threadIdx.x >= n4) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    acc += (double)v[j].x * (double)v[j].x; acc += (double)v[j].y * (double)v[j].y;
+    acc += (double)v[j].z * (double)v[j].z; acc += (double)v[j].w * (double)v[j].w;
+  }
+  acc += (double)tail * (double)tail;
+  const double s = block_sum_f64(acc, red);
+  if (threadIdx.x == 0) partials[b] = s;
+}
+
+extern "C" int mi355_grad_sumsq_batched(const mi355_gn_item* items_dev, int count, int total_blocks, double* partials_dev, void* stream) {
+  if (!items_dev || !partials_dev) MI_FAIL(MI355_EINVAL, "grad_sumsq_batched: null pointer");
+  if (count < 1 || total_blocks < 1) MI_FAIL(MI355_EINVAL, "grad_sumsq_batched: count=%d total_blocks=%d", count, total_blocks);
+  if (total_blocks < count) MI_FAIL(MI355_EINVAL, "grad_sumsq_batched: total_blocks=%d for count=%d items (each owns a block)", total_blocks, count);
+  if (((uintptr_t)items_dev | (uintptr_t)partials_dev) & 7) MI_FAIL(MI355_EINVAL, "grad_sumsq_batched: items and partials must be 8-byte aligned");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(total_blocks), dim3(256), 0, as_stream(stream), items_dev, count, partials_dev);
+  MI_CHECK_LAUNCH("grad_sumsq_batched");
+  return MI355_OK;
+}
+
+// One block: lane t adds partials[t], partials[t + 256], ... in that order, then the tree; thread 0 fills the record.
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __restrict__ partials, int nblocks, mi355_clip_rec* __restrict__ rec) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nblocks; i += 256) acc += partials[i];
+  const double sumsq = block_sum_f64(acc, red);
+  if (threadIdx.x != 0) return;
+  rec->sumsq = sumsq;
+  if (!isfinite(sumsq)) {
+    rec->norm = (float)sumsq;          // inf or NaN, as torch's total_norm would be
+    rec->coef = 0.f;
+    rec->skip = 1;
+    rec->n_skipped = rec->n_skipped + 1;
+  } else {
+    const float norm = (float)__dsqrt_rn(sumsq);
+    rec->norm = norm;
+    rec->coef = fminf(1.0f, __fdiv_rn(rec->max_norm, norm + 1e-6f));
+    rec->skip = 0;
+  }
+}
+
+extern "C" int mi355_grad_clip_coef(const double* partials_dev, int total_blocks, mi355_clip_rec* rec_dev, void* stream) {
+  if (!partials_dev || !rec_dev) MI_FAIL(MI355_EINVAL, "grad_clip_coef: null pointer");
+  if (total_blocks < 1) MI_FAIL(MI355_EINVAL, "grad_clip_coef: total_blocks=%d", total_blocks);
+  if (((uintptr_t)partials_dev | (uintptr_t)rec_dev) & 7) MI_FAIL(MI355_EINVAL, "grad_clip_coef: partials and the record must be 8-byte aligned");
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, as_stream(stream), partials_dev, total_blocks, rec_dev);
+  MI_CHECK_LAUNCH("grad_clip_coef");
   return MI355_OK;
 }
 

@@ -246,8 +246,12 @@ class DAStep:
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
     def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None,
-                 proto=None):
+                 proto=None, clip=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
+        # optional mi355.optim.GradClipper (may also be assigned after construction): each of the three updates takes the global
+        # gradient norm of everything it steps (A: f and the four heads, B: the adversarial heads, C: f), behind the gradient
+        # exchange, and steps on the clipped gradients -- or not at all when the norm is not finite.  None: nothing is launched.
+        self.clip = clip
         self.ema = ema               # optional mi355.optim.EMATeacher: updated behind step C's optimizer (train1.py:461)
         # the optional terms of step C's loss (`_Term`; any of them may also be assigned after construction): a
         # mi355.teacher.MeanTeacher, whose folded operands are refreshed behind the EMA update, an MMDAlign, a JointFeatureAlign,
@@ -348,9 +352,19 @@ class DAStep:
         _rt.join_side()
         self.out.update(loss_s=loss_s.detach(), y_s=y_s.detach(), y_s_adv=y_s_adv.detach())
 
+    def _step(self, keys, slot):
+        """Step the optimizers `keys` in that order; with a clipper, on the gradients clipped to one norm over all of them."""
+        if self.clip is None:
+            for k in keys:
+                self.opt[k].step()
+            return
+        rec = self.clip.measure([self.opt[k] for k in keys], slot)
+        self.out['gn_' + slot] = rec
+        for k in keys:
+            self.opt[k].step(clip=rec)
+
     def _update_A(self):
-        for k in ('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'):
-            self.opt[k].step()
+        self._step(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'), 'a')
 
     def _fwdbwd_B(self, b):
         m, c, to = self.model, self.crit, self.trade_off
@@ -381,8 +395,7 @@ class DAStep:
         self.out.update(loss_gf=loss_gf.detach())
 
     def _update_B(self):
-        for k in ('h_adv2', 'h_adv', 'h_adv3'):
-            self.opt[k].step()
+        self._step(('h_adv2', 'h_adv', 'h_adv3'), 'b')
 
     def _fwdbwd_C(self, b):
         m, c, to = self.model, self.crit, self.trade_off
@@ -418,7 +431,7 @@ class DAStep:
         self.out.update(kept, loss_gt=loss_gt.detach(), y_t=y_t.detach(), y_t_adv=y_t_adv.detach())
 
     def _update_C(self):
-        self.opt['f'].step()
+        self._step(('f',), 'c')
         if self.ema is not None:
             self.ema.update()
             if self.mt is not None:
@@ -466,6 +479,8 @@ class DAStep:
         from uda.model.regda_4 import _CENTRES
         _CENTRES.clear()
         self.model.train()
+        if self.clip is not None:
+            self.clip.sync()
         self._begin_reduce(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'))
         self._fwdbwd_A(batch)
         self._end_reduce(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'))
@@ -487,7 +502,7 @@ class DAStep:
     def capture(self, batch, warmup=3):
         """Capture the iteration as six HIP graphs (fwd+bwd and update of A, B, C) over static copies of
         `batch`; the gradient all-reduces run eagerly between them.  Everything that changes per iteration
-        (inputs, learning rates, GL lambda, the EMA coefficients) is read from device memory.  With an EMA teacher attached its
+        (inputs, learning rates, GL lambda, the EMA coefficients, the clipper's max_norm) is read from device memory.  With an EMA teacher attached its
         update is captured into the last update graph, behind optimizer_f's step, where the eager iteration has it."""
         self.model.train()
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
@@ -569,6 +584,8 @@ class DAStep:
             self.ema.sync()
         if self.mt is not None:
             self.mt.sync()
+        if self.clip is not None:
+            self.clip.sync()
 
     def replay(self, batch=None):
         if batch is not None and batch is not self.static:

@@ -1054,6 +1054,82 @@ def ema_update_batched(table, count, total_blocks, coef_dev):
     call('mi355_ema_update_batched', ptr(table), int(count), int(total_blocks), ptr(coef_dev), stream_ptr())
 
 
+GN_CHUNK = 16384                                    # MI355_GN_CHUNK
+GN_ITEM_BYTES, CLIP_REC_BYTES = 24, 32
+
+
+def clip_rec_dtype():
+    """numpy layout of mi355_clip_rec."""
+    import numpy as np
+    return np.dtype([('sumsq', '<f8'), ('max_norm', '<f4'), ('norm', '<f4'), ('coef', '<f4'), ('skip', '<i4'), ('n_skipped', '<i8')])
+
+
+def clip_records(count, max_norm, device):
+    """`count` zeroed mi355_clip_rec records with their max_norm field set, as one uint8 device tensor; record i is the view
+    [i * CLIP_REC_BYTES : (i + 1) * CLIP_REC_BYTES]."""
+    import numpy as np
+    rec = np.zeros(count, dtype=clip_rec_dtype())
+    assert rec.dtype.itemsize == CLIP_REC_BYTES
+    rec['max_norm'] = np.float32(max_norm)
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(device)
+
+
+def gn_table(ranges, device):
+    """ranges: 1-D dense fp32 device tensors (views of the gradient buffers), 16-byte aligned -> (uint8 device tensor of
+    mi355_gn_item records, their number, total blocks): the arguments of grad_sumsq_batched.  The table holds addresses only:
+    the caller keeps the buffers alive."""
+    import numpy as np
+    rec = np.zeros(len(ranges), dtype=[('g', '<u8'), ('n', '<i8'), ('blk0', '<i4'), ('pad', '<i4')])
+    assert rec.dtype.itemsize == GN_ITEM_BYTES
+    if not len(ranges):
+        raise Mi355Error('gn_table: no ranges')
+    blk = 0
+    for i, g in enumerate(ranges):
+        _chk_dev(g)
+        n = g.numel()
+        if g.dtype != torch.float32 or g.dim() != 1 or n < 1 or g.stride(0) != 1 or g.data_ptr() % 16:
+            raise Mi355Error('gn_table: range %d needs a dense 1-D fp32 tensor of at least one element on a 16-byte boundary' % i)
+        rec[i] = (g.data_ptr(), n, blk, 0)
+        blk += (n + GN_CHUNK - 1) // GN_CHUNK
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(device), len(ranges), blk
+
+
+def _chk_clip_rec(what, rec):
+    _chk_room(what + ' rec', rec, CLIP_REC_BYTES)
+    if rec.dtype != torch.uint8 or not rec.is_contiguous():
+        raise Mi355Error('%s rec: needs a contiguous uint8 tensor holding one mi355_clip_rec' % what)
+
+
+def grad_sumsq_batched(table, count, total_blocks, partials):
+    """partials[b] = fp64 sum of squares of block b's slice of the ranges in `table` (gn_table); partials: float64, one per block."""
+    _chk_dev(table, partials)
+    _chk_room('grad_sumsq_batched table', table, count * GN_ITEM_BYTES)
+    _chk_room('grad_sumsq_batched partials', partials, total_blocks)
+    if partials.dtype != torch.float64 or not partials.is_contiguous():
+        raise Mi355Error('grad_sumsq_batched partials: needs a contiguous float64 tensor')
+    call('mi355_grad_sumsq_batched', ptr(table), int(count), int(total_blocks), ptr(partials), stream_ptr())
+
+
+def grad_clip_coef(partials, total_blocks, rec):
+    """Fold partials[0 .. total_blocks) into the mi355_clip_rec `rec` (uint8 view): sumsq, norm, coef, skip, n_skipped."""
+    _chk_dev(partials, rec)
+    _chk_room('grad_clip_coef partials', partials, total_blocks)
+    if partials.dtype != torch.float64 or not partials.is_contiguous():
+        raise Mi355Error('grad_clip_coef partials: needs a contiguous float64 tensor')
+    _chk_clip_rec('grad_clip_coef', rec)
+    call('mi355_grad_clip_coef', ptr(partials), int(total_blocks), ptr(rec), stream_ptr())
+
+
+def sgd_nesterov_clipped(p, g, buf, lr_dev, rec, momentum, wd, nesterov, p_lowp=None):
+    """sgd_nesterov on fl32(g * rec.coef); writes nothing when rec.skip is set.  g is only read."""
+    _chk_dev(p, g, buf, lr_dev, rec, p_lowp)
+    for what, t in (('g', g), ('buf', buf), ('p_lowp', p_lowp)):
+        _chk_room('sgd_nesterov_clipped ' + what, t, p.numel())
+    _chk_clip_rec('sgd_nesterov_clipped', rec)
+    call('mi355_sgd_nesterov_clipped', ptr(p), ptr(g), ptr(buf), p.numel(), ptr(lr_dev), ptr(rec), float(momentum), float(wd),
+         int(nesterov), ptr(p_lowp), stream_ptr())
+
+
 # ---------------------------------------------------------------- mean-teacher consistency (csrc/teacher.hip)
 FOLD_CHUNK = 2048                                   # MI355_FOLD_CHUNK
 FOLD_ITEM_BYTES = 88

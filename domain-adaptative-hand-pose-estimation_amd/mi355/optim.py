@@ -156,12 +156,9 @@ class FusedSGD(Optimizer):
         return [p for g in self.param_groups for p in g['params']
                 if p.requires_grad and p.grad is not None and id(p) not in known]
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _settle(self):
+        """What step() does before it looks at the gradients: the side stream has landed, the flat layout holds every parameter
+        that owns a gradient (laid out again, outside capture, when one got its first gradient late)."""
         _rt.join_side()              # weight gradients computed on the side stream must have landed
         self.ensure_flat()
         if self._late_params():      # first gradient arrived after the flat layout was fixed: lay it out again
@@ -170,32 +167,58 @@ class FusedSGD(Optimizer):
                                    'step with every parameter active before capturing')
             self._flat = None
             self.ensure_flat()
+
+    def _runs(self):
+        """(flat group, lo, hi) for every contiguous run of parameters that received a gradient since zero_grad(): the ranges
+        step() updates -- and the ranges a gradient norm over "what this step touches" is taken over (GradClipper)."""
+        for f in self._flat:
+            if f is None:
+                continue
+            stale = [self._stale(p) for p in f['params']]
+            if not any(stale):
+                yield f, 0, f['P'].numel()
+                continue
+            lo = None                # step the contiguous runs of parameters that did receive a gradient
+            for p, st in zip(f['params'], stale):
+                o, n = f['offs'][id(p)]
+                if st:
+                    if lo is not None:
+                        yield f, lo, o
+                        lo = None
+                elif lo is None:
+                    lo = o
+            if lo is not None:
+                yield f, lo, f['P'].numel()
+
+    @torch.no_grad()
+    def step(self, closure=None, clip=None):
+        """`clip`: a mi355_clip_rec on the device (GradClipper.measure): every run is stepped on fl32(g * coef), or not at all when
+        the record says skip.  The gradient buffers are only read, so ``p.grad`` keeps the unclipped values and the zeros
+        nn._zero_grad_once holds in them stay zeros.  A skipped step is a skipped GradScaler step: everything below the kernel
+        launches (packed copies, fp8 scales) proceeds as usual."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._settle()
         if not torch.cuda.is_current_stream_capturing():
             self.sync_lr()
+        runs = {}
+        for f, lo, hi in self._runs():
+            runs.setdefault(id(f), []).append((lo, hi))
         for f in self._flat:
             if f is None:
                 continue
             g = self.param_groups[f['gi']]
-            stale = [self._stale(p) for p in f['params']]
-            if not any(stale):
-                runs = [(0, f['P'].numel())]
-            else:                    # step the contiguous runs of parameters that did receive a gradient
-                runs, lo = [], None
-                for p, st in zip(f['params'], stale):
-                    o, n = f['offs'][id(p)]
-                    if st:
-                        if lo is not None:
-                            runs.append((lo, o))
-                            lo = None
-                    elif lo is None:
-                        lo = o
-                if lo is not None:
-                    runs.append((lo, f['P'].numel()))
-            for lo, hi in runs:
-                ops.sgd_nesterov(f['P'][lo:hi], f['G'][lo:hi], f['M'][lo:hi], f['lr_dev'], g['momentum'], g['weight_decay'],
-                                 g['nesterov'])
-            for p, st in zip(f['params'], stale):
-                if not st:
+            for lo, hi in runs.get(id(f), ()):
+                if clip is None:
+                    ops.sgd_nesterov(f['P'][lo:hi], f['G'][lo:hi], f['M'][lo:hi], f['lr_dev'], g['momentum'], g['weight_decay'],
+                                     g['nesterov'])
+                else:
+                    ops.sgd_nesterov_clipped(f['P'][lo:hi], f['G'][lo:hi], f['M'][lo:hi], f['lr_dev'], clip, g['momentum'],
+                                             g['weight_decay'], g['nesterov'])
+            for p in f['params']:
+                if not self._stale(p):
                     p._mi_epoch = getattr(p, '_mi_epoch', 0) + 1
             repack_params(f['params'], f.setdefault('pack_cache', {}))     # packed conv copies: one launch per group
             repack_params_fp8(f['params'], f['pack_cache'])
@@ -224,6 +247,84 @@ class FusedSGD(Optimizer):
                 st['momentum_buffer'] = mv
                 off += (n + 3) // 4 * 4
         self.sync_lr(force=True)
+
+
+class GradClipper:
+    """Global gradient-norm clipping with a non-finite step guard for FusedSGD optimizers, entirely on the device:
+    ``torch.nn.utils.clip_grad_norm_(parameters stepped in this update, max_norm)`` in front of the optimizers' ``step()``, in two
+    launches (``mi355_grad_sumsq_batched`` over every fresh run of every optimizer, ``mi355_grad_clip_coef``) that fill one
+    ``mi355_clip_rec``; ``FusedSGD.step(clip=record)`` applies the coefficient inside the SGD kernel.  Nothing is read by the
+    host, so the launches sit in captured graphs beside the optimizer's.
+
+    Differences from torch's in-place clip: the gradient buffers are never written -- ``p.grad`` keeps the unclipped values
+    after the step, and the zeros ``nn._zero_grad_once`` holds in the flat buffers cannot go stale; parameters that received no
+    gradient since ``zero_grad()`` are outside the norm (torch: ``grad is None``).  A non-finite sum of squares skips the update
+    (parameters, momentum and low-precision copies keep their values; ``n_skipped`` counts it) while everything else of the
+    iteration proceeds, like a skipped ``GradScaler`` step.  ``max_norm = inf`` measures and guards and never scales.
+
+    One record per slot ('a', 'b', 'c': the three updates of a DAStep iteration) in one small device buffer; ``max_norm`` is a
+    field of the records, written by ``sync()`` outside capture, so it may change between replays.  With several ranks call
+    ``measure`` behind the gradient all-reduce: every rank then derives the same coefficient from the same bytes."""
+    SLOTS = ('a', 'b', 'c')
+
+    def __init__(self, max_norm, device):
+        max_norm = float(max_norm)
+        if not max_norm > 0:                       # (NaN fails the comparison too)
+            raise ValueError('GradClipper: max_norm must be positive (inf: measure and guard only), got %r' % (max_norm,))
+        self.max_norm, self.device = max_norm, torch.device(device)
+        self.recs = ops.clip_records(len(self.SLOTS), max_norm, self.device)
+        self._f32 = self.recs.view(torch.float32)          # 8 floats per record; max_norm is float 2
+        self._synced = max_norm
+        self._tables = {}                          # slot -> dict(sig, table, count, blocks, partials)
+
+    def record(self, slot):
+        """The mi355_clip_rec of `slot` as a uint8 view of the device buffer."""
+        i = self.SLOTS.index(slot)
+        return self.recs[i * ops.CLIP_REC_BYTES:(i + 1) * ops.CLIP_REC_BYTES]
+
+    def sync(self):
+        """Write max_norm into the records when it changed (call outside graph capture)."""
+        if self.max_norm != self._synced:
+            m = float(self.max_norm)
+            if not m > 0:
+                raise ValueError('GradClipper: max_norm must be positive, got %r' % (m,))
+            self._f32[2::8].fill_(m)
+            self._synced = m
+
+    @torch.no_grad()
+    def measure(self, optimizers, slot):
+        """Enqueue the norm of everything `optimizers` (FusedSGD) are about to step into the record of `slot` and return that
+        record, for ``step(clip=...)``.  The range table is keyed by the runs' (buffer address, lo, hi) and rebuilt -- outside
+        capture only -- when that changes."""
+        optimizers = list(optimizers)
+        for o in optimizers:
+            if not isinstance(o, FusedSGD):
+                raise TypeError('GradClipper handles FusedSGD optimizers only, got %s' % type(o).__name__)
+        rec = self.record(slot)
+        for o in optimizers:
+            o._settle()
+        runs = [(f['G'], lo, hi) for o in optimizers for f, lo, hi in o._runs()]
+        sig = tuple((G.data_ptr(), lo, hi) for G, lo, hi in runs)
+        t = self._tables.get(slot)
+        if t is None or t['sig'] != sig:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('GradClipper: the set of gradient ranges of update %r changed during graph capture; run one eager '
+                                   'iteration with the clipper attached before capturing' % (slot,))
+            t = dict(sig=sig)
+            if runs:
+                t['table'], t['count'], t['blocks'] = ops.gn_table([G[lo:hi] for G, lo, hi in runs], self.device)
+                t['partials'] = torch.zeros(t['blocks'], dtype=torch.float64, device=self.device)
+            self._tables[slot] = t
+        if runs:                                   # (no fresh gradient at all: no optimizer launch will read the record)
+            ops.grad_sumsq_batched(t['table'], t['count'], t['blocks'], t['partials'])
+            ops.grad_clip_coef(t['partials'], t['blocks'], rec)
+        return rec
+
+    def read(self):
+        """({slot: (norm, coef, skip)}, n_skipped over all slots): the one device read, for a progress line."""
+        r = self.recs.cpu().numpy().view(ops.clip_rec_dtype())
+        return ({s: (float(r['norm'][i]), float(r['coef'][i]), int(r['skip'][i])) for i, s in enumerate(self.SLOTS)},
+                int(r['n_skipped'].sum()))
 
 
 class EMATeacher:

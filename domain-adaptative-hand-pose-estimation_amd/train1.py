@@ -12,7 +12,8 @@ uda/model/loss.py:1061-1104), ``--jfa-loss {off,on}`` with ``--jfa-weight`` / ``
 neck features pooled around the predicted key points of the target batch with those of the source batch in step C: the
 reference's unused ``loss3``, train1.py:25 and uda/model/loss.py:331-378), ``--proto-loss {off,kl,softkl}`` with ``--proto-weight`` /
 ``--proto-radius`` / ``--proto-axes`` / ``--proto-m`` (alignment of per-joint class prototypes of those features, blended with a running
-memory per domain: the reference's unused ``lossx`` / ``lossx3``, uda/model/loss.py:381-466 and 560-652), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
+memory per domain: the reference's unused ``lossx`` / ``lossx3``, uda/model/loss.py:381-466 and 560-652), ``--clip-grad-norm FLOAT``
+(global gradient-norm clipping of each of the three updates with a non-finite step guard, on the device; not in the reference), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
 sub-pixel decodes ``quarter`` and ``taylor`` are not in the reference), ``--flip-test`` with ``--flip-shift`` (validation averages
@@ -54,7 +55,7 @@ import mi355
 import uda.model as models
 from mi355 import ops as _ops
 from mi355.da_step import JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
-from mi355.optim import EMATeacher, FusedSGD
+from mi355.optim import EMATeacher, FusedSGD, GradClipper
 from mi355.teacher import MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
@@ -217,6 +218,9 @@ def main(args):
     if args.proto_loss != 'off':
         step.proto = PrototypeAlign(weight=args.proto_weight, radius=args.proto_radius, axes=args.proto_axes, m=args.proto_m,
                                     criterion=args.proto_loss)
+    if args.clip_grad_norm > 0:
+        # each update clips the global norm of what it steps and skips itself when that norm is not finite (mi355.optim.GradClipper)
+        step.clip = GradClipper(args.clip_grad_norm, device)
     start_epoch = 0
     if args.resume is None:
         if args.pretrain is None or (args.synthetic and not os.path.exists(args.pretrain)):
@@ -226,9 +230,10 @@ def main(args):
             optimizer = FusedSGD(pre.get_parameters(lr=args.lr), lr=args.lr, momentum=args.momentum, weight_decay=args.wd, nesterov=True)
             lr_scheduler = MultiStepLR(optimizer, args.lr_step, args.lr_factor)
             best_acc = -1
+            pre_clip = GradClipper(args.clip_grad_norm, device) if args.clip_grad_norm > 0 else None
             for epoch in range(args.pretrain_epochs):
                 lr_scheduler.step()                      # the reference steps the schedule before the epoch (train1.py:167)
-                pretrain(train_source_iter, pre, criterion, optimizer, epoch, args)
+                pretrain(train_source_iter, pre, criterion, optimizer, epoch, args, clip=pre_clip)
                 acc = validate(val_source_loader, pre, criterion, args)
                 _ops.bn_resident_check('pre-training epoch %d' % epoch)   # (validation has synchronised: the poll is free)
                 if acc['all'] > best_acc:
@@ -281,6 +286,8 @@ def main(args):
         logger.set_epoch(epoch)
         print(*[scheds[k].get_last_lr() for k in ('f', 'h', 'h_adv', 'h_adv2')])
         train(train_source_iter, train_target_iter, step, scheds, epoch, args)
+        if step.clip is not None:
+            print('skipped steps: %d' % step.clip.read()[1])       # (a count since the start of this process: not checkpointed)
         s_acc = validate(val_source_loader, model, criterion, args)
         t_acc = validate(val_target_loader, model, criterion, args)
         e_acc = validate(val_target_loader, MainOutput(model_ema), criterion, args) if ema is not None else None   # (validate2, :243)
@@ -322,7 +329,7 @@ def main(args):
         dist.destroy_process_group()
 
 
-def pretrain(train_source_iter, model, criterion, optimizer, epoch, args):
+def pretrain(train_source_iter, model, criterion, optimizer, epoch, args, clip=None):
     batch_time, data_time = AverageMeter('Time', ':4.2f'), AverageMeter('Data', ':3.1f')
     losses_s, acc_s = AverageMeter('Loss (s)', ":.2e"), AverageMeter("Acc (s)", ":3.2f")
     progress = ProgressMeter(args.iters_per_epoch, [batch_time, data_time, losses_s, acc_s], prefix="Epoch: [{}]".format(epoch))
@@ -338,7 +345,10 @@ def pretrain(train_source_iter, model, criterion, optimizer, epoch, args):
         loss_s.backward()
         if WORLD > 1:
             _allreduce_mean(optimizer.flat_grads())     # gradient mean over ranks (the flat buffers are the buckets)
-        optimizer.step()
+        if clip is None:
+            optimizer.step()
+        else:
+            optimizer.step(clip=clip.measure([optimizer], 'a'))
         if i % args.print_freq == 0:                    # host reads only when something is printed
             _, avg_acc_s, cnt_s, _ = accuracy(y_s.detach(), label_s)
             acc_s.update(avg_acc_s, cnt_s); losses_s.update(float(loss_s), cnt_s)
@@ -361,6 +371,9 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     if mt is not None:
         mt.set_epoch(epoch)                              # m and k are functions of the epoch (train1.py:351-353)
     names, fmts = names + ['Loss (%s)' % t.key for t in terms], fmts + [':.2e'] * len(terms)
+    clip, n_fixed = step.clip, 9 + len(terms)
+    if clip is not None:                                 # the gradient norms of the three updates, read when a line is printed
+        names, fmts = names + ['GradNorm (%s)' % s.upper() for s in clip.SLOTS], fmts + [':.2e'] * len(clip.SLOTS)
     meters = [AverageMeter(n, f) for n, f in zip(names, fmts)]
     progress = ProgressMeter(args.iters_per_epoch, meters, prefix="Epoch: [{}]".format(epoch))
     end = time.time()
@@ -406,6 +419,10 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
                 a, c = _pck(out[k]); m.update(a, c)
             for m, t in zip(meters[9:], terms):
                 m.update(float(out['loss_' + t.key]), args.batch_size)
+            if clip is not None:
+                norms = clip.read()[0]
+                for m, s in zip(meters[n_fixed:], clip.SLOTS):
+                    m.update(norms[s][0], 1)
             meters[0].update(time.time() - end)
             progress.display(i)
         end = time.time()
@@ -551,6 +568,13 @@ def _mt_weight(text):
     return 'ref' if text == 'ref' else float(text)
 
 
+def _clip_norm(text):
+    v = float(text)
+    if not v >= 0:                                       # (NaN fails the comparison too)
+        raise argparse.ArgumentTypeError('a gradient norm cannot be %s: 0 (off), a positive number or inf' % text)
+    return v
+
+
 _OPTIONS = [
     (('--source_root',), dict(default='data/RHD', help='source dataset directory')),
     (('target_root',), dict(help='target dataset directory')),
@@ -629,6 +653,11 @@ _OPTIONS = [
                             "reference's indexing, x selects the rows (uda/model/loss.py:421)")),
     (('--proto-m',), dict(default=0.999, type=float, metavar='FLOAT', help="weight m of the current batch in the prototype, the memory "
                          "gets 1 - m (0 < m <= 1; 0.999 is the reference's constant, uda/model/loss.py:400)")),
+    (('--clip-grad-norm',), dict(default=0.0, type=_clip_norm, metavar='FLOAT', help="global gradient-norm clipping with a non-finite "
+                                "step guard: each of the updates A, B, C (and the pre-training step) clips over everything it steps, as "
+                                "clip_grad_norm_(those parameters, FLOAT) before the optimizers would, in two launches per update and "
+                                "inside the SGD kernels; an update whose norm is inf or NaN is skipped and counted ('skipped steps:'); "
+                                "'inf' measures and guards without scaling; 0: off, nothing is launched")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--metrics',), dict(default='pck', choices=['pck', 'full'], help="'full': validation also decodes key points in image pixels "
                          "and reports the mean end-point error, the PCK curve's AUC and per-group EPEs (on the device, one read at "

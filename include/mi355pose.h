@@ -491,6 +491,29 @@ int mi355_ema_update(float* e, const float* p, long n, const float* coef_dev, vo
 #define MI355_EMA_COPY64 1
 typedef struct mi355_ema_item { const void* src; void* dst; long n; int kind; int blk0; } mi355_ema_item;
 int mi355_ema_update_batched(const mi355_ema_item* items_dev, int count, int total_blocks, const float* coef_dev, void* stream);
+/* Global gradient-norm clipping with a non-finite step guard, on the device (no host read between backward and step; all three
+ * entry points capture).  torch.nn.utils.clip_grad_norm_(params, max_norm) followed by the optimizer step, except that the
+ * scale is applied inside the SGD kernel: the gradients themselves are never written.
+ *   mi355_grad_sumsq_batched: items = DEVICE array of gradient ranges (g 16-byte aligned, n >= 1 floats; blk0 = first block of the
+ *     item = sum over earlier items of ceil(n / MI355_GN_CHUNK); total_blocks = that sum over all).  Block b owns one
+ *     MI355_GN_CHUNK slice of its item and writes  partials[b] = sum (double)g * (double)g  over it: every lane accumulates its
+ *     elements in index order in fp64, the lanes are folded by a fixed xor tree, the four waves in wave order.  No atomics:
+ *     the same bytes give the same bits, eagerly or replayed.  Nothing outside [g, g + n) of any item is read.
+ *   mi355_grad_clip_coef: ONE block folds partials[0 .. total_blocks) (lane-strided, then the same tree) and fills the record:
+ *       sumsq = the fp64 sum;  norm = (float)sqrt(sumsq), the fp64 root rounded once;
+ *       coef  = fminf(1.0f, max_norm / (norm + 1e-6f))   in fp32 (torch: max_norm / (total_norm + 1e-6), clamp(max=1.0));
+ *       sumsq not finite:  skip = 1, coef = 0, n_skipped += 1;  else skip = 0.
+ *     max_norm is an INPUT field: the host writes it (outside capture); +inf measures and guards without ever scaling.
+ *   mi355_sgd_nesterov_clipped: mi355_sgd_nesterov on g_c = fl32(g * rec->coef) -- the product is rounded on its own, never
+ *     contracted into the weight-decay multiply-add, so coef == 1.0f gives the bits of mi355_sgd_nesterov.  With rec->skip set
+ *     the launch writes nothing: p, buf and p_lowp keep their values (a skipped GradScaler step).  g is only read. */
+#define MI355_GN_CHUNK 16384        /* floats per block */
+typedef struct mi355_gn_item { const float* g; long n; int blk0; int pad; } mi355_gn_item;
+typedef struct mi355_clip_rec { double sumsq; float max_norm; float norm; float coef; int skip; long long n_skipped; } mi355_clip_rec;
+int mi355_grad_sumsq_batched(const mi355_gn_item* items_dev, int count, int total_blocks, double* partials_dev, void* stream);
+int mi355_grad_clip_coef(const double* partials_dev, int total_blocks, mi355_clip_rec* rec_dev, void* stream);
+int mi355_sgd_nesterov_clipped(float* p, const float* g, float* buf, long n, const float* lr_dev, const mi355_clip_rec* rec_dev,
+                               float momentum, float wd, int nesterov, void* p_lowp, void* stream);
 
 /* ---------------------------------------------------------------- mean-teacher consistency (csrc/teacher.hip)
  * Eval-mode BatchNorm folded into the conv in front of it, for many (conv, bn) pairs in ONE launch and into caller-owned

@@ -1,0 +1,434 @@
+"""Global gradient-norm clipping with the non-finite step guard on the GPU (include/mi355pose.h: mi355_grad_sumsq_batched,
+mi355_grad_clip_coef, mi355_sgd_nesterov_clipped; mi355.optim.GradClipper; DAStep(clip=...); train1.py --clip-grad-norm):
+
+  1. exact operands: integer gradients, so every partial sum is exact in float64 -- the record equals tests/gradclip_ref.py bit
+     for bit at every range length around the chunk size, each range surrounded by NaN;
+  2. random data: the norm within one float32 rounding plus the worst case of a float64 summation; the same bits from run to run
+     and from a replayed graph;
+  3. the clipped SGD kernel bit for bit against the unclipped one fed g * coef;
+  4. the guard: an inf or a NaN in the gradients skips the update and counts it;
+  5. FusedSGD + GradClipper beside a float64 network under clip_grad_norm_ + torch.optim.SGD, eager and replayed;
+  6. DAStep: clip=GradClipper(inf) changes nothing bit for bit; a finite max_norm records the float64 norm of the flat
+     gradients, changes the parameters, and replays as it runs eagerly;
+  7. the command line.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import gradclip_ref as ref
+from conftest import PKG
+from seeded import randn
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture
+def rt(gpu):
+    import mi355
+    mi355.load()
+    mi355.set_compute_dtype('bf16')
+    yield mi355
+    mi355.set_compute_dtype('bf16')
+
+
+def _ops():
+    from mi355 import ops
+    return ops
+
+
+def _host_rec(rec):
+    """A device mi355_clip_rec as a numpy record."""
+    return rec.cpu().numpy().view(_ops().clip_rec_dtype())[0].copy()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+class _Measure:
+    """The two launches over `ranges` (device views) into one record."""
+
+    def __init__(self, ranges, max_norm, gpu):
+        ops = _ops()
+        self.ranges = ranges
+        self.table, self.count, self.blocks = ops.gn_table(ranges, gpu)
+        self.partials = torch.zeros(self.blocks, dtype=torch.float64, device=gpu)
+        self.rec = ops.clip_records(1, max_norm, gpu)
+
+    def set_max_norm(self, max_norm):
+        self.rec.view(torch.float32)[2].fill_(max_norm)
+
+    def launch(self):
+        ops = _ops()
+        ops.grad_sumsq_batched(self.table, self.count, self.blocks, self.partials)
+        ops.grad_clip_coef(self.partials, self.blocks, self.rec)
+
+    def __call__(self):
+        self.launch()
+        torch.cuda.synchronize()
+        return _host_rec(self.rec)
+
+
+# ---------------------------------------------------------------- 1. exact operands
+def _lens():
+    C = _ops().GN_CHUNK
+    return [1, 3, 4, 5, C - 4, C, C + 4, 2 * C + 8]
+
+
+def _int_range(seed, n, gpu):
+    """(device view [4 : 4 + n] of a buffer that is NaN everywhere else, its integer values in [-8, 8])."""
+    vals = np.random.default_rng(seed).integers(-8, 9, n).astype(np.float32)
+    vals[0] = 5.0                                   # (never an all-zero range)
+    buf = np.full(n + 8, np.nan, dtype=np.float32)
+    buf[4:4 + n] = vals
+    return torch.from_numpy(buf).to(gpu)[4:4 + n], vals
+
+
+@pytest.mark.parametrize('case', list(range(8)) + ['all'])
+def test_exact_integer_gradients_give_the_reference_record_bit_for_bit(rt, gpu, case):
+    lens = _lens()
+    pick = lens if case == 'all' else [lens[case]]
+    views, vals = zip(*[_int_range(50 + i, n, gpu) for i, n in enumerate(pick)])
+    want_ss = int(sum(int((v.astype(np.int64) ** 2).sum()) for v in vals))
+    norm64 = float(np.sqrt(np.float64(want_ss)))
+    m = _Measure(list(views), 1.0, gpu)
+    assert m.blocks == sum((n + _ops().GN_CHUNK - 1) // _ops().GN_CHUNK for n in pick)
+    for max_norm in (0.5 * norm64, 2.0 * norm64 + 1.0, float('inf')):
+        m.set_max_norm(max_norm)
+        got = m()
+        ss, norm, coef, skip = ref.clip_record(vals, np.float32(max_norm))
+        assert ss == want_ss and got['sumsq'] == want_ss, (case, got['sumsq'], want_ss)          # (nothing NaN was read)
+        assert _bits(got['norm']) == _bits(norm) and _bits(got['coef']) == _bits(coef), (case, max_norm, got, norm, coef)
+        assert got['skip'] == skip == 0 and got['n_skipped'] == 0
+        assert _bits(got['max_norm']) == _bits(np.float32(max_norm))
+    assert (coef == 1.0) and ref.clip_record(vals, np.float32(0.5 * norm64))[2] < 1.0
+
+
+# ---------------------------------------------------------------- 2. random data
+def test_random_gradients_within_the_summation_bound_and_reproducible(rt, gpu):
+    lens = [100000, 150001, 50003]
+    host = [(randn(60 + i, n + 8, scale=0.3 * (i + 1))).numpy() for i, n in enumerate(lens)]
+    views = [torch.from_numpy(h).to(gpu)[4:4 + n] for h, n in zip(host, lens)]
+    n_tot = sum(lens)
+    ref64 = float(np.sqrt(sum(np.sum(h[4:4 + n].astype(np.float64) ** 2) for h, n in zip(host, lens))))
+    m = _Measure(views, 0.5 * ref64, gpu)
+    a = m()
+    bound = ref64 * (2.0 ** -24 + n_tot * 2.0 ** -52)       # one float32 rounding + the worst case of a float64 summation
+    print('norm %.9g  float64 reference %.17g  |difference| %.3g  bound %.3g' % (a['norm'], ref64, abs(float(a['norm']) - ref64), bound))
+    assert abs(float(a['norm']) - ref64) <= bound
+    assert a['skip'] == 0 and 0.0 < a['coef'] < 1.0
+    m.partials.zero_()
+    b = m()
+    assert _bits(a) == _bits(b)
+    # captured and replayed: the same bits as the eager launches
+    m.partials.fill_(-1.0)
+    m.rec.copy_(_ops().clip_records(1, 0.5 * ref64, gpu))
+    g = torch.cuda.CUDAGraph()
+    with rt.no_gc_in_capture():
+        with torch.cuda.graph(g, capture_error_mode=rt.graph_capture_mode()):
+            m.launch()
+    torch.cuda.synchronize()
+    assert _host_rec(m.rec)['sumsq'] == 0.0            # (capture executed nothing)
+    g.replay()
+    torch.cuda.synchronize()
+    assert _bits(_host_rec(m.rec)) == _bits(a)
+
+
+# ---------------------------------------------------------------- 3. the clipped SGD kernel
+def _make_rec(coef, skip, gpu, n_skipped=0):
+    ops = _ops()
+    r = np.zeros(1, dtype=ops.clip_rec_dtype())
+    r['coef'], r['skip'], r['n_skipped'], r['max_norm'] = np.float32(coef), skip, n_skipped, 1.0
+    return torch.from_numpy(r.view(np.uint8).copy()).to(gpu)
+
+
+def _sgd_state(seed, n, gpu):
+    """p, g, buf (float32) and a bf16 copy, each a view [4 : 4 + n] of a buffer with sentinels around it."""
+    full = [randn(seed + i, n + 8).to(gpu) for i in range(3)] + [torch.full((n + 8,), 7.0, dtype=torch.bfloat16, device=gpu)]
+    return full, [t[4:4 + n] for t in full]
+
+
+@pytest.mark.parametrize('n', [4, 5, 1023, 4100])
+def test_clipped_sgd_equals_the_unclipped_kernel_on_scaled_gradients(rt, gpu, n):
+    ops = _ops()
+    lr = torch.tensor(0.05, device=gpu)
+    for coef in (np.float32(0.3712345), np.float32(1.0)):
+        rec = _make_rec(coef, 0, gpu)
+        for nesterov in (True, False):
+            for wd in (0.0, 1e-4):
+                for lowp in (True, False):
+                    fa, (pa, ga, ba, la) = _sgd_state(70, n, gpu)
+                    fb, (pb, gb, bb, lb) = _sgd_state(70, n, gpu)
+                    before = [t.clone() for t in fa]
+                    for _ in range(2):                       # (the second step reads a non-zero momentum written by the first)
+                        ops.sgd_nesterov_clipped(pa, ga, ba, lr, rec, 0.9, wd, nesterov, la if lowp else None)
+                        scaled = gb if coef == 1.0 else gb * torch.tensor(coef, dtype=torch.float32, device=gpu)
+                        ops.sgd_nesterov(pb, scaled, bb, lr, 0.9, wd, nesterov, lb if lowp else None)
+                    torch.cuda.synchronize()
+                    what = (n, float(coef), nesterov, wd, lowp)
+                    for x, y, z in zip(fa, fb, before):
+                        assert torch.equal(x.view(torch.int16 if x.dtype == torch.bfloat16 else torch.int32),
+                                           y.view(torch.int16 if y.dtype == torch.bfloat16 else torch.int32)), what
+                        assert torch.equal(x[:4], z[:4]) and torch.equal(x[4 + n:], z[4 + n:]), what       # outside the view: untouched
+                    assert not torch.equal(fa[0][4:4 + n], before[0][4:4 + n]) and torch.equal(fa[1], before[1]), what
+                    assert torch.equal(fa[3], before[3]) != lowp, what
+
+
+# ---------------------------------------------------------------- 4. the guard
+def test_non_finite_gradients_skip_the_update_and_are_counted(rt, gpu):
+    ops = _ops()
+    C = ops.GN_CHUNK
+    lens = [1000, C + 5, 37]
+    offs = np.cumsum([0] + [(n + 3) // 4 * 4 for n in lens])
+    total = int(offs[-1])
+    P, G, M = randn(80, total).to(gpu), randn(81, total, scale=0.1).to(gpu), randn(82, total).to(gpu)
+    L = P.to(torch.bfloat16)
+    views = [G[o:o + n] for o, n in zip(offs[:-1], lens)]
+    m = _Measure(views, 1.0, gpu)
+    lr = torch.tensor(0.05, device=gpu)
+
+    def step():
+        m.launch()
+        for o, n in zip(offs[:-1], lens):
+            ops.sgd_nesterov_clipped(P[o:o + n], G[o:o + n], M[o:o + n], lr, m.rec, 0.9, 1e-4, True, L[o:o + n])
+        torch.cuda.synchronize()
+        return _host_rec(m.rec)
+
+    state = lambda: [t.clone() for t in (P, M, L)]
+    same = lambda a, b: all(torch.equal(x.view(torch.int16 if x.dtype == torch.bfloat16 else torch.int32),
+                                        y.view(torch.int16 if y.dtype == torch.bfloat16 else torch.int32)) for x, y in zip(a, b))
+    s0 = state()
+    r = step()
+    assert r['skip'] == 0 and r['n_skipped'] == 0 and 0.0 < r['coef'] < 1.0 and not same(s0, state())
+    # the fault is in the data only: one element of the middle range
+    at = int(offs[1]) + C + 2
+    good = float(G[at])
+    for k, bad in enumerate((float('inf'), float('nan'))):
+        G[at] = bad
+        s1 = state()
+        r = step()
+        assert r['skip'] == 1 and r['coef'] == 0.0 and r['n_skipped'] == k + 1, r
+        assert not np.isfinite(r['sumsq']) and not np.isfinite(r['norm'])
+        assert same(s1, state())
+    G[at] = good
+    s2 = state()
+    r = step()
+    assert r['skip'] == 0 and r['n_skipped'] == 2 and 0.0 < r['coef'] < 1.0 and not same(s2, state())
+    assert all(bool(torch.isfinite(t.float()).all()) for t in state())
+
+
+# ---------------------------------------------------------------- 5. FusedSGD + GradClipper beside torch
+MAX_NORM_NET = 20.0                # between the gradient norms of the two output-gradient scales below, thousands and below 5 in the
+                                   # float64 reference (asserted on the reference: it clips in some iterations and not in others)
+DY_SCALES = (1.0, 0.001, 1.0, 0.001, 0.001, 1.0)
+
+
+@pytest.mark.parametrize('replayed', [False, True])
+def test_fused_sgd_with_grad_clipper_follows_torch(rt, gpu, replayed):
+    """conv (bias) -> BatchNorm -> ReLU -> conv (tests/test_gpu_layer_state.py's small network) under TWO FusedSGD optimizers and
+    one GradClipper, next to a float64 copy under clip_grad_norm_ + one torch.optim.SGD.  A further parameter receives a gradient
+    in the first iteration only: afterwards it is outside the norm and is not stepped, as a parameter whose grad is None.  Replayed:
+    forward + backward and the update captured as two graphs after two eager iterations."""
+    from mi355.optim import FusedSGD, GradClipper
+    from test_gpu_layer_state import _small_net, _near, REL
+    rt.set_compute_dtype('f32')
+    mine, net64 = _small_net(gpu, 9)
+    mine.train(); net64.train()
+    extra = torch.nn.Parameter(randn(402, 37).to(gpu))
+    extra64 = torch.nn.Parameter(extra.detach().double().cpu())
+    kw = dict(lr=0.05, momentum=0.9, weight_decay=1e-4, nesterov=True)
+    opt1 = FusedSGD(list(mine[0].parameters()) + list(mine[1].parameters()), **kw)
+    opt2 = FusedSGD(list(mine[3].parameters()) + [extra], **kw)
+    params64 = list(net64.parameters()) + [extra64]
+    opt64 = torch.optim.SGD(params64, **kw)
+    clip = GradClipper(MAX_NORM_NET, gpu)
+    x64 = randn(400, 4, 32, 12, 12).double()
+    dy64 = randn(401, 4, 32, 12, 12).double()
+    x = x64.float().to(gpu).contiguous(memory_format=torch.channels_last)
+    dy1 = dy64.float().to(gpu).contiguous(memory_format=torch.channels_last)
+    dy = dy1.clone()
+    g_extra = randn(403, 37)
+
+    def fwdbwd():
+        opt1.zero_grad(); opt2.zero_grad()
+        mine(x).backward(dy)
+        rt.join_side()
+
+    def update():
+        rec = clip.measure([opt1, opt2], 'a')
+        opt1.step(clip=rec); opt2.step(clip=rec)
+
+    clipped, g_fb = [], None
+    for i, s in enumerate(DY_SCALES):
+        if replayed and i == 2:
+            torch.cuda.synchronize()
+            mode = rt.graph_capture_mode()
+            g_fb, g_st = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with rt.no_gc_in_capture():
+                with torch.cuda.graph(g_fb, capture_error_mode=mode):
+                    fwdbwd()
+                with torch.cuda.graph(g_st, capture_error_mode=mode):
+                    update()
+        dy.copy_(dy1 * s)
+        if g_fb is not None:
+            g_fb.replay(); g_st.replay()
+        else:
+            fwdbwd()
+            if i == 0:
+                extra.grad = g_extra.to(gpu)
+            update()
+        opt64.zero_grad()
+        net64(x64).backward(dy64 * s)
+        if i == 0:
+            extra64.grad = g_extra.double()
+        total = float(torch.nn.utils.clip_grad_norm_(params64, MAX_NORM_NET))
+        opt64.step()
+        clipped.append(total > MAX_NORM_NET)
+        torch.cuda.synchronize()
+        norm, coef, skip = clip.read()[0]['a']
+        what = 'iteration %d%s' % (i, ' (replayed)' if g_fb is not None else '')
+        print('%s: float64 norm %.6g, device norm %.6g coef %.6g' % (what, total, norm, coef))
+        assert skip == 0 and (coef < 1.0) == clipped[-1], what
+        got = dict(mine.named_parameters())
+        for k, p in net64.named_parameters():
+            _near('%s: %s' % (what, k), got[k], p, REL['f32'])
+        _near(what + ': extra', extra, extra64, REL['f32'])
+        # the gradients are only read: after a clipped step the flat buffers still hold the unclipped norm
+        fresh = [G[lo:hi] for o in (opt1, opt2) for f, lo, hi in o._runs() for G in (f['G'],)]
+        unclipped = float(torch.sqrt(sum((t.double() ** 2).sum() for t in fresh)))
+        assert abs(unclipped - norm) <= 1e-6 * norm, what
+        if i >= 1:          # `extra` got no gradient since zero_grad(): outside the table, one run less in its optimizer
+            covered = sum(hi - lo for _, lo, hi in clip._tables['a']['sig'])
+            assert covered == sum(f['P'].numel() for o in (opt1, opt2) for f in o._flat if f is not None) - 40, what
+    assert any(clipped) and not all(clipped), clipped
+    assert clip.read()[1] == 0
+
+
+# ---------------------------------------------------------------- 6. DAStep
+def _da_run(gpu, clip_norm, iters=4, capture_at=2):
+    """resnet18, B = 2, 64 x 64 images, 16 x 16 heat-maps, synthetic: `iters` iterations, the last ones replayed."""
+    import mi355
+    from mi355.da_step import DAStep, build_training
+    from mi355.optim import GradClipper
+    from uda.model.regda_7 import PoseResNetx9
+    from utils.synthetic import make_batch
+    from test_gpu_ema import _pose
+    mi355.set_compute_dtype('bf16')
+    model = _pose(gpu, PoseResNetx9, 731)
+    step, opts, scheds = build_training(model, heatmap_size=16)
+    clip = GradClipper(clip_norm, gpu) if clip_norm is not None else None
+    if clip is not None:
+        step = DAStep(model, opts, step.crit, step.trade_off, step.skip, step.track_acc, clip=clip)
+    assert step.clip is clip
+    for c in step.crit.values():
+        if hasattr(c, 'guard_empty_maps'):
+            c.guard_empty_maps = True
+    batch = make_batch(2, 64, 16, seed=3, device=gpu)
+    recs, f_norm = [], []
+    for i in range(iters):
+        if capture_at is not None and i == capture_at:
+            step.capture(batch, warmup=0)
+        out = step.run(batch)
+        for s in scheds.values():
+            s.step()
+        torch.cuda.synchronize()
+        if clip is not None:
+            recs.append({s: _host_rec(clip.record(s)) for s in clip.SLOTS})
+            f_norm.append((float(torch.sqrt(sum((G.double() ** 2).sum() for G in opts['f'].flat_grads()))),
+                           sum(G.numel() for G in opts['f'].flat_grads())))
+    params = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    outs = {k: v.detach().clone() for k, v in out.items() if torch.is_tensor(v)}
+    return dict(params=params, out=outs, recs=recs, f_norm=f_norm, graphs=step.graphs, skipped=clip.read()[1] if clip else 0)
+
+
+@pytest.fixture(scope='module')
+def da_runs(gpu):
+    import mi355
+    try:
+        plain = _da_run(gpu, None)
+        inf = _da_run(gpu, float('inf'))
+        for i, r in enumerate(inf['recs']):
+            print('iteration %d: ' % i + '  '.join('gn_%s %.6g' % (s, r[s]['norm']) for s in 'abc'))
+        # a tenth of the smallest norm the run has seen that is not zero (update C's gradient is exactly zero in the first iteration
+        # of this synthetic set-up and of the order of 1e-3 afterwards; A's is of the order of 10, B's of 1)
+        seen = [float(r[s]['norm']) for r in inf['recs'] for s in 'abc' if r[s]['norm'] > 0]
+        assert len(seen) >= 9
+        max_norm = 0.1 * min(seen)
+        eager = _da_run(gpu, max_norm, capture_at=None)
+        graph = _da_run(gpu, max_norm)
+    finally:
+        mi355.set_compute_dtype('bf16')
+    return dict(plain=plain, inf=inf, eager=eager, graph=graph, max_norm=max_norm)
+
+
+def _same_tensors(a, b, keys):
+    """The keys at which the two dicts of tensors differ in any bit."""
+    raw = lambda t: t.contiguous().view(-1).view(torch.uint8)
+    return [k for k in keys if a[k].shape != b[k].shape or not torch.equal(raw(a[k]), raw(b[k]))]
+
+
+def test_da_step_with_an_infinite_max_norm_changes_nothing(da_runs):
+    plain, inf = da_runs['plain'], da_runs['inf']
+    assert plain['graphs'] is not None and len(inf['graphs']) == 6
+    assert _same_tensors(plain['params'], inf['params'], plain['params']) == []
+    shared = sorted(set(plain['out']) & set(inf['out']))
+    assert {'loss_s', 'loss_gf', 'loss_gt', 'y_s', 'y_t'} <= set(shared) and 'gn_a' not in plain['out']
+    assert _same_tensors(plain['out'], inf['out'], shared) == []
+    assert {'gn_a', 'gn_b', 'gn_c'} <= set(inf['out']) and inf['skipped'] == 0
+    for r in inf['recs']:
+        for s in 'abc':
+            assert r[s]['coef'] == 1.0 and r[s]['skip'] == 0 and np.isfinite(r[s]['norm']) and r[s]['norm'] >= 0
+
+
+def test_da_step_records_the_float64_norm_and_clips(da_runs):
+    plain, eager = da_runs['plain'], da_runs['eager']
+    assert eager['graphs'] is None and eager['skipped'] == 0
+    for r, (ref64, n) in zip(eager['recs'], eager['f_norm']):
+        got = float(r['c']['norm'])
+        bound = ref64 * (2.0 ** -24 + n * 2.0 ** -52)
+        print('gn_c %.9g  float64 norm of the flat gradients %.17g  |difference| %.3g  bound %.3g' % (got, ref64, abs(got - ref64), bound))
+        assert abs(got - ref64) <= bound
+        for s in 'abc':
+            want = ref.norm_coef_skip(r[s]['sumsq'], np.float32(da_runs['max_norm']))
+            assert r[s]['skip'] == 0 and _bits(r[s]['coef']) == _bits(want[1]) and _bits(r[s]['norm']) == _bits(want[0])
+        print('  '.join('gn_%s %.6g coef %.6g' % (s, r[s]['norm'], r[s]['coef']) for s in 'abc'))
+    # updates A and B see norms orders of magnitude above max_norm in every iteration: both clip throughout
+    assert all(r[s]['coef'] < 1.0 for r in eager['recs'] for s in 'ab')
+    assert _same_tensors(plain['params'], eager['params'], plain['params']) != []
+
+
+def test_da_step_with_the_clip_replays_as_it_runs_eagerly(da_runs):
+    eager, graph = da_runs['eager'], da_runs['graph']
+    assert graph['graphs'] is not None and len(graph['graphs']) == 6
+    assert _same_tensors(eager['params'], graph['params'], eager['params']) == []
+    assert _same_tensors(eager['out'], graph['out'], sorted(eager['out'])) == [] and sorted(eager['out']) == sorted(graph['out'])
+    for a, b in zip(eager['recs'], graph['recs']):
+        for s in 'abc':
+            assert _bits(a[s]) == _bits(b[s])
+
+
+# ---------------------------------------------------------------- 7. the command line
+def test_train_cli_prints_the_gradient_norms_and_the_skipped_steps(gpu, tmp_path):
+    log = str(tmp_path / 'run')
+    pre = str(tmp_path / 'pre.pth')
+    common = ['data/none', '-t', 'Hand3DStudio', '--synthetic', '-a', 'resnet18', '-b', '4', '-i', '6', '-p', '2', '-j', '0', '--epochs', '1',
+              '--pretrain_epochs', '1', '--pretrain', pre]
+    env = dict(os.environ, PYTHONPATH=PKG)
+
+    def run(extra):
+        r = subprocess.run([sys.executable, os.path.join(PKG, 'train1.py')] + common + extra, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        return r.stdout
+
+    out = run(['--log', log, '--clip-grad-norm', '1.0'])
+    assert 'GradNorm (A)' in out and 'GradNorm (B)' in out and 'GradNorm (C)' in out and 'skipped steps: 0' in out
+    assert 'HIP graphs captured' in out and 'Target(best)' in out
+    assert os.path.exists(os.path.join(log, 'checkpoints', 'pretrain.pth'))
+    os.replace(os.path.join(log, 'checkpoints', 'pretrain.pth'), pre)          # (the second run starts from it: no second pre-training)
+    out = run(['--log', str(tmp_path / 'run2')])
+    assert 'GradNorm' not in out and 'skipped steps' not in out and 'Target(best)' in out
