@@ -1,6 +1,7 @@
 // SGD (momentum, weight decay, Nesterov) over a flat fp32 range + the low-precision parameter copy,
-// and the plain cast kernel.  Pure streaming: float4 per lane.
+// Adam / AdamW over a table of parameters, the gradient norm, the EMA update and the plain cast kernel.  Pure streaming: float4 per lane.
 #include "common.h"
+#include "adam_slice.h"
 
 // torch.optim.SGD semantics (train1.py:141-148): g' = g + wd*p; buf = mu*buf + g' (buf starts at 0, which equals
 // torch's "first step: buf = g'"); p -= lr * (nesterov ? g' + mu*buf : buf)
@@ -180,6 +181,129 @@ extern "C" int mi355_grad_clip_coef(const double* partials_dev, int total_blocks
   if (((uintptr_t)partials_dev | (uintptr_t)rec_dev) & 7) MI_FAIL(MI355_EINVAL, "grad_clip_coef: partials and the record must be 8-byte aligned");
   hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, as_stream(stream), partials_dev, total_blocks, rec_dev);
   MI_CHECK_LAUNCH("grad_clip_coef");
+  return MI355_OK;
+}
+
+// ---- Adam / AdamW (mi355pose.h: mi355_adam_step_batched / mi355_adam_tick_batched) ---------------------------------------------
+// The per-block scalars of one item; every fp32 operation of adam1 is rounded on its own, whatever the build's flags say.  sqrtf
+// and `/` are the correctly rounded forms under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt (__fsqrt_rn is the
+// hardware's 1-ulp root unless OCML_BASIC_ROUNDED_OPERATIONS is defined, which this build does not do).
+struct adam_consts { float coef, wd, decay, omb1, beta2, omb2, step_size, bc2s, eps; int clip, l2, decoupled; };
+
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const adam_consts& c) {
+#pragma clang fp contract(off)
+  float gc = c.clip ? g * c.coef : g;
+  float pp = p;
+  if (c.decoupled) pp = pp * c.decay;
+  else if (c.l2) { const float t = c.wd * pp; gc = gc + t; }
+  const float d = gc - m;
+  const float e = c.omb1 * d;
+  const float mm = m + e;
+  const float a = c.beta2 * v;
+  const float s = c.omb2 * gc;
+  const float q = s * gc;
+  const float vv = a + q;
+  const float den = sqrtf(vv) / c.bc2s + c.eps;
+  const float u = c.step_size * (mm / den);
+  p = pp - u; m = mm; v = vv;
+}
+
+// x^t for a whole t >= 1 by squaring in fp64: exact where the powers are (t = 1, dyadic x), otherwise within a few dozen fp64 ulps
+// of pow() -- far below the fp32 rounding of the values derived from it -- and the same bits on every lane and in every launch.
+__device__ __forceinline__ double ipow64(double x, unsigned t) {
+  double r = 1.0;
+  while (t) { if (t & 1u) r *= x; x *= x; t >>= 1; }
+  return r;
+}
+
+// Block b owns elements [i0, i0 + len) of its item (adam_slice.h), len <= MI355_ADAM_CHUNK: float4 number j * 256 + lane of the
+// slice per pass, then the up to three floats behind the last whole quad in lanes 0..2.  step and lr are only read.  The four
+// streams' addresses come out of the table, so they are told to be global memory (address space 1): global_load / global_store
+// instead of flat ones, which would count against the LDS counter as well.
+typedef float adam_v4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) adam_v4 adam_gv4;
+typedef __attribute__((address_space(1))) float adam_gf;
+__global__ __launch_bounds__(256) void adam_step_kernel(const mi355_adam_item* __restrict__ items, int nitems,
+                                                         const mi355_clip_rec* __restrict__ rec) {
+  adam_consts c;
+  c.clip = rec != nullptr; c.coef = 1.f;
+  if (rec) {
+    if (rec->skip) return;
+    c.coef = rec->coef;
+  }
+  const adam_slice sl = adam_block_slice(items, nitems, blockIdx.x);
+  if (sl.len <= 0) return;               // (only for a malformed table: nothing is touched)
+  const mi355_adam_item it = items[sl.item];
+  const long i0 = sl.i0;
+  const int len = sl.len;
+  {
+    const unsigned t = (unsigned)*it.step + 1u;
+    const double lr = (double)*it.lr;
+    const double bc1 = 1.0 - ipow64(it.beta1, t);
+    const double bc2 = 1.0 - ipow64(it.beta2, t);
+    c.step_size = (float)(lr / bc1);
+    c.bc2s = (float)sqrt(bc2);
+    c.decay = (float)(1.0 - lr * (double)it.wd);
+    c.omb1 = (float)(1.0 - it.beta1);
+    c.omb2 = (float)(1.0 - it.beta2);
+    c.beta2 = (float)it.beta2; c.eps = it.eps; c.wd = it.wd;
+    c.decoupled = it.decoupled != 0;
+    c.l2 = !c.decoupled && it.wd != 0.f;
+  }
+  adam_gf* __restrict__ p = (adam_gf*)(it.p + i0);
+  const adam_gf* __restrict__ g = (const adam_gf*)(it.g + i0);
+  adam_gf* __restrict__ m = (adam_gf*)(it.m + i0);
+  adam_gf* __restrict__ v = (adam_gf*)(it.v + i0);
+  const int n4 = len >> 2;
+  for (int q = threadIdx.x; q < n4; q += 256) {
+    adam_v4 pv = ((const adam_gv4*)p)[q];
+    const adam_v4 gv = ((const adam_gv4*)g)[q];
+    adam_v4 mv = ((const adam_gv4*)m)[q];
+    adam_v4 vv = ((const adam_gv4*)v)[q];
+    float pp[4] = {pv.x, pv.y, pv.z, pv.w}; const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+    float mm[4] = {mv.x, mv.y, mv.z, mv.w}; float ww[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) adam1(pp[e], gg[e], mm[e], ww[e], c);
+    pv.x = pp[0]; pv.y = pp[1]; pv.z = pp[2]; pv.w = pp[3];
+    mv.x = mm[0]; mv.y = mm[1]; mv.z = mm[2]; mv.w = mm[3];
+    vv.x = ww[0]; vv.y = ww[1]; vv.z = ww[2]; vv.w = ww[3];
+    ((adam_gv4*)p)[q] = pv; ((adam_gv4*)m)[q] = mv; ((adam_gv4*)v)[q] = vv;
+  }
+  const int t = (n4 << 2) + threadIdx.x;
+  if (threadIdx.x < 3 && t < len) {
+    float pt = p[t], mt = m[t], vt = v[t];
+    adam1(pt, g[t], mt, vt, c);
+    p[t] = pt; m[t] = mt; v[t] = vt;
+  }
+}
+
+// One thread per item: *step += 1 (fp32: exact up to 2^24), behind the step launch on the same stream.
+__global__ __launch_bounds__(256) void adam_tick_kernel(const mi355_adam_item* __restrict__ items, int nitems,
+                                                         const mi355_clip_rec* __restrict__ rec) {
+  if (rec && rec->skip) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < nitems) { float* s = items[i].step; *s = *s + 1.0f; }
+}
+
+extern "C" int mi355_adam_step_batched(const mi355_adam_item* items_dev, int count, int total_blocks, const mi355_clip_rec* rec_dev,
+                                       void* stream) {
+  if (!items_dev) MI_FAIL(MI355_EINVAL, "adam_step_batched: null table");
+  if (count < 1 || total_blocks < 1) MI_FAIL(MI355_EINVAL, "adam_step_batched: count=%d total_blocks=%d", count, total_blocks);
+  if (total_blocks < count) MI_FAIL(MI355_EINVAL, "adam_step_batched: total_blocks=%d for count=%d items (each owns a block)", total_blocks, count);
+  if ((uintptr_t)items_dev & 7) MI_FAIL(MI355_EINVAL, "adam_step_batched: the table must be 8-byte aligned");
+  if ((uintptr_t)rec_dev & 7) MI_FAIL(MI355_EINVAL, "adam_step_batched: the record must be 8-byte aligned");
+  hipLaunchKernelGGL(adam_step_kernel, dim3(total_blocks), dim3(256), 0, as_stream(stream), items_dev, count, rec_dev);
+  MI_CHECK_LAUNCH("adam_step_batched");
+  return MI355_OK;
+}
+
+extern "C" int mi355_adam_tick_batched(const mi355_adam_item* items_dev, int count, const mi355_clip_rec* rec_dev, void* stream) {
+  if (!items_dev) MI_FAIL(MI355_EINVAL, "adam_tick_batched: null table");
+  if (count < 1) MI_FAIL(MI355_EINVAL, "adam_tick_batched: count=%d", count);
+  if ((uintptr_t)items_dev & 7) MI_FAIL(MI355_EINVAL, "adam_tick_batched: the table must be 8-byte aligned");
+  if ((uintptr_t)rec_dev & 7) MI_FAIL(MI355_EINVAL, "adam_tick_batched: the record must be 8-byte aligned");
+  hipLaunchKernelGGL(adam_tick_kernel, dim3((unsigned)(((long)count + 255) / 256)), dim3(256), 0, as_stream(stream), items_dev, count, rec_dev);
+  MI_CHECK_LAUNCH("adam_tick_batched");
   return MI355_OK;
 }
 

@@ -128,6 +128,8 @@ SIGNATURES = {
     'mi355_grad_sumsq_batched': (_I, [_P, _I, _I, _P, _P]),
     'mi355_grad_clip_coef': (_I, [_P, _I, _P, _P]),
     'mi355_sgd_nesterov_clipped': (_I, [_P, _P, _P, _L, _P, _P, _F, _F, _I, _P, _P]),
+    'mi355_adam_step_batched': (_I, [_P, _I, _I, _P, _P]),
+    'mi355_adam_tick_batched': (_I, [_P, _I, _P, _P]),
     'mi355_bn_fold_batched': (_I, [_P, _P, _I, _I, _P]),
     'mi355_mse_heatmap': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'mi355_mmd_workspace': (_Z, [_I, _I]),

@@ -614,21 +614,23 @@ class DAStep:
 
 
 def build_training(model, heatmap_size=64, lr=0.01, momentum=0.9, wd=1e-4, lr_gamma=1e-4, lr_decay=0.75,
-                   trade_off=1.0, num_keypoints=21, skip_discarded=True, track_accuracy=True):
+                   trade_off=1.0, num_keypoints=21, skip_discarded=True, track_accuracy=True, optimizer='sgd',
+                   adam_betas=(0.9, 0.999), adam_eps=1e-8):
     """Criteria, the five SGD optimizers and their LambdaLR schedules exactly as train1.py:131-154 builds them.
-    Returns (DAStep, optimizers dict, schedulers dict)."""
+    `optimizer`: 'sgd' (the reference), 'adam' (FusedAdam, L2 weight decay `wd`) or 'adamw' (decoupled weight decay `wd`) for all
+    five; `momentum` is not used by the last two.  Returns (DAStep, optimizers dict, schedulers dict)."""
     from torch.optim.lr_scheduler import LambdaLR
     from uda.model.loss import JointsKLLoss
     from uda.model.regda_4 import PseudoLabelGenerator
     from uda.model.regda_7 import (PseudoLabelGenerator01, PseudoLabelGenerator03, RegressionDisparityx1,
                                    RegressionDisparityx5, RegressionDisparityx6)
-    from .optim import FusedSGD
+    from .optim import make_optimizer
     crit = dict(
         kl=JointsKLLoss(),
         rd=RegressionDisparityx6(PseudoLabelGenerator(num_keypoints, heatmap_size, heatmap_size), JointsKLLoss(epsilon=1e-7)),
         rd2=RegressionDisparityx5(PseudoLabelGenerator03(num_keypoints, heatmap_size // 2, heatmap_size // 2), JointsKLLoss(epsilon=1e-7)),
         rd1=RegressionDisparityx1(PseudoLabelGenerator01(num_keypoints, heatmap_size // 4, heatmap_size // 4), JointsKLLoss(epsilon=1e-7)))
-    mk = lambda ps: FusedSGD(ps, lr=0.1, momentum=momentum, weight_decay=wd, nesterov=True)
+    mk = lambda ps: make_optimizer(optimizer, ps, lr=0.1, momentum=momentum, weight_decay=wd, betas=adam_betas, eps=adam_eps)
     opts = dict(
         f=mk([{'params': model.backbone.parameters(), 'lr': 0.1}, {'params': model.upsampling.parameters(), 'lr': 0.1}]),
         h=mk(model.head.parameters()), h_adv=mk(model.head_adv.parameters()),

@@ -1130,6 +1130,63 @@ def sgd_nesterov_clipped(p, g, buf, lr_dev, rec, momentum, wd, nesterov, p_lowp=
          int(nesterov), ptr(p_lowp), stream_ptr())
 
 
+ADAM_CHUNK = 16384                                  # MI355_ADAM_CHUNK
+ADAM_ITEM_BYTES = 88
+
+
+def adam_item_dtype():
+    """numpy layout of mi355_adam_item."""
+    import numpy as np
+    return np.dtype([(k, '<u8') for k in ('p', 'g', 'm', 'v', 'step', 'lr')] + [('n', '<i8')] +
+                    [('beta1', '<f8'), ('beta2', '<f8'), ('eps', '<f4'), ('wd', '<f4'), ('decoupled', '<i4'), ('blk0', '<i4')])
+
+
+def adam_table(items, device):
+    """items: (p, g, m, v, step, lr, beta1, beta2, eps, wd, decoupled) per parameter about to be stepped -- p, g, m, v dense fp32
+    device tensors of one size on 16-byte boundaries, step and lr one fp32 each on the device -> (uint8 device tensor of
+    mi355_adam_item records, their number, total blocks): the arguments of adam_step_batched / adam_tick_batched.  The table
+    holds addresses only: the caller keeps the tensors alive."""
+    import numpy as np
+    rec = np.zeros(len(items), dtype=adam_item_dtype())
+    assert rec.dtype.itemsize == ADAM_ITEM_BYTES
+    if not len(items):
+        raise Mi355Error('adam_table: no items')
+    blk = 0
+    for i, (p, g, m, v, step, lr, beta1, beta2, eps, wd, decoupled) in enumerate(items):
+        _chk_dev(p, g, m, v, step, lr)
+        n = p.numel()
+        for what, t in (('p', p), ('g', g), ('m', m), ('v', v)):
+            if t.dtype != torch.float32 or t.numel() != n or n < 1 or t.data_ptr() % 16 or \
+                    1 + sum((s - 1) * st for s, st in zip(t.shape, t.stride())) != n:
+                raise Mi355Error('adam_table: item %d %s needs a dense fp32 tensor of %d element(s) on a 16-byte boundary' % (i, what, n))
+        for what, t in (('step', step), ('lr', lr)):
+            if t.dtype != torch.float32 or t.numel() != 1:
+                raise Mi355Error('adam_table: item %d %s needs one fp32 value on the device' % (i, what))
+        rec[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), step.data_ptr(), lr.data_ptr(), n,
+                  beta1, beta2, eps, wd, int(bool(decoupled)), blk)
+        blk += (n + ADAM_CHUNK - 1) // ADAM_CHUNK
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(device), len(items), blk
+
+
+def adam_step_batched(table, count, total_blocks, rec=None):
+    """One Adam / AdamW step of every item in `table` (adam_table) on fl32(g * rec.coef), or on g when rec is None; writes nothing
+    when rec.skip is set.  The step counts are only read: adam_tick_batched advances them."""
+    _chk_dev(table, rec)
+    _chk_room('adam_step_batched table', table, count * ADAM_ITEM_BYTES)
+    if rec is not None:
+        _chk_clip_rec('adam_step_batched', rec)
+    call('mi355_adam_step_batched', ptr(table), int(count), int(total_blocks), ptr(rec), stream_ptr())
+
+
+def adam_tick_batched(table, count, rec=None):
+    """*step += 1 for every item in `table` unless rec.skip is set: the launch behind adam_step_batched."""
+    _chk_dev(table, rec)
+    _chk_room('adam_tick_batched table', table, count * ADAM_ITEM_BYTES)
+    if rec is not None:
+        _chk_clip_rec('adam_tick_batched', rec)
+    call('mi355_adam_tick_batched', ptr(table), int(count), ptr(rec), stream_ptr())
+
+
 # ---------------------------------------------------------------- mean-teacher consistency (csrc/teacher.hip)
 FOLD_CHUNK = 2048                                   # MI355_FOLD_CHUNK
 FOLD_ITEM_BYTES = 88

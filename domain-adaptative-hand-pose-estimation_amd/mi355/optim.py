@@ -5,6 +5,10 @@ Drop-in for ``torch.optim.SGD`` in the reference's training script: same constru
 ``param_groups`` / ``state_dict()`` layout (``momentum_buffer`` per parameter), so LambdaLR / MultiStepLR and
 the reference checkpoint keys keep working.  Parameters that have never received a gradient (e.g. the unused
 ``backbone.fc``) are skipped exactly as torch does.
+
+FusedAdam: torch.optim.Adam / AdamW semantics on the same flat storage, in two launches per ``step()`` whatever the number of
+parameters and groups.  Both share ``_FlatOptimizer``: the flat layout, the device-side learning rates, the fresh / stale
+bookkeeping of ``zero_grad()`` and the refresh of the packed weight copies behind every step.
 """
 import torch
 from torch.optim import Optimizer
@@ -14,11 +18,19 @@ from . import ops
 from .nn import mark_grads_fresh, repack_params, repack_params_fp8, repack_params_mx
 
 
-class FusedSGD(Optimizer):
-    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0, weight_decay=0.0, nesterov=False):
-        if dampening != 0:
-            raise NotImplementedError('dampening is not used by the reference and not built')
-        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
+class _FlatOptimizer(Optimizer):
+    """What FusedSGD and FusedAdam know about flat storage.  A subclass names its per-parameter state tensors:
+
+    ``_BUFFERS``: ((state key, key of the flat record), ...) -- one flat fp32 buffer per group beside P and G for each, the
+                  state tensor of a parameter being a view of it at the parameter's offset;
+    ``_COUNTER``: the state key of a per-parameter fp32 scalar -- a 0-dim view into one device array per group (record key
+                  'S', one float per parameter in layout order) -- or None;
+
+    and launches its kernels from ``_step_begin`` (once per step) or ``_step_group`` (once per flat group)."""
+    _BUFFERS = ()
+    _COUNTER = None
+
+    def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._flat = None          # list of per-group dicts once flattened
         self._lr_cache = {}
@@ -29,7 +41,7 @@ class FusedSGD(Optimizer):
         return self._flat is not None
 
     def ensure_flat(self):
-        """Move every parameter that owns a gradient into flat (param, grad, momentum) buffers.  Parameter
+        """Move every parameter that owns a gradient into flat (param, grad, state) buffers.  Parameter
         objects keep their identity; only their storage moves.  Called on the first step()."""
         if self._flat is not None:
             return
@@ -46,30 +58,47 @@ class FusedSGD(Optimizer):
                 total += (p.numel() + 3) // 4 * 4          # 16-byte aligned slots
             P = torch.zeros(total, dtype=torch.float32, device=dev)
             G = torch.zeros(total, dtype=torch.float32, device=dev)
-            M = torch.zeros(total, dtype=torch.float32, device=dev)
+            bufs = {fk: torch.zeros(total, dtype=torch.float32, device=dev) for _, fk in self._BUFFERS}
+            S = torch.zeros(len(ps), dtype=torch.float32, device=dev) if self._COUNTER else None
             zeroed = {}              # offset -> length of the bias gradients nn._zero_grad_once holds at zero (see zero_grad)
-            for p, o in zip(ps, offs):
+            for i, (p, o) in enumerate(zip(ps, offs)):
                 n = p.numel()
                 if p.dtype != torch.float32:
-                    raise TypeError('FusedSGD handles fp32 master parameters only')
+                    raise TypeError('%s handles fp32 master parameters only' % type(self).__name__)
                 pv = P[o:o + n].as_strided(p.shape, p.stride())
                 gv = G[o:o + n].as_strided(p.shape, p.stride())
-                mv = M[o:o + n].as_strided(p.shape, p.stride())
                 pv.copy_(p.data)
                 gv.copy_(p.grad)
                 st = self.state[p]
-                if 'momentum_buffer' in st and st['momentum_buffer'] is not None:
-                    mv.copy_(st['momentum_buffer'])
+                for sk, fk in self._BUFFERS:
+                    bv = bufs[fk][o:o + n].as_strided(p.shape, p.stride())
+                    if st.get(sk) is not None:
+                        bv.copy_(st[sk])
+                    st[sk] = bv
+                if self._COUNTER:
+                    self._alias_counter(st, S[i])
                 p.data = pv
                 p.grad = gv
                 gv._mi_flat = (zeroed, o, n)
-                st['momentum_buffer'] = mv
                 p._mi_epoch = getattr(p, '_mi_epoch', 0) + 1     # packed copies must be rebuilt (storage moved)
             lr_dev = torch.zeros((), dtype=torch.float32, device=dev)
-            flat.append(dict(P=P, G=G, M=M, params=ps, lr_dev=lr_dev, gi=gi, zeroed=zeroed, zero_idx=(None, None),
-                             offs={id(p): (o, (p.numel() + 3) // 4 * 4) for p, o in zip(ps, offs)}))
+            f = dict(P=P, G=G, params=ps, lr_dev=lr_dev, gi=gi, zeroed=zeroed, zero_idx=(None, None),
+                     offs={id(p): (o, (p.numel() + 3) // 4 * 4) for p, o in zip(ps, offs)}, **bufs)
+            if S is not None:
+                f['S'] = S
+            flat.append(f)
         self._flat = flat
         self.sync_lr(force=True)
+
+    def _alias_counter(self, st, sv):
+        """Make the 0-dim device view `sv` the counter of the state `st`, keeping a value the state already holds."""
+        old = st.get(self._COUNTER)
+        if torch.is_tensor(old):
+            if old.data_ptr() != sv.data_ptr():
+                sv.copy_(old.detach().reshape(()))
+        elif old is not None:
+            sv.fill_(float(old))
+        st[self._COUNTER] = sv
 
     def flat_range(self, params):
         """(G buffer, lo, hi) covering `params` -- which must be neighbours inside one flat group -- or None when the
@@ -163,8 +192,8 @@ class FusedSGD(Optimizer):
         self.ensure_flat()
         if self._late_params():      # first gradient arrived after the flat layout was fixed: lay it out again
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError('FusedSGD: a parameter received its first gradient during graph capture; run one eager '
-                                   'step with every parameter active before capturing')
+                raise RuntimeError('%s: a parameter received its first gradient during graph capture; run one eager '
+                                   'step with every parameter active before capturing' % type(self).__name__)
             self._flat = None
             self.ensure_flat()
 
@@ -190,6 +219,12 @@ class FusedSGD(Optimizer):
             if lo is not None:
                 yield f, lo, f['P'].numel()
 
+    def _step_begin(self, runs, clip):
+        """Launches of one step that span the flat groups.  runs: {id(flat record): [(lo, hi), ...]}."""
+
+    def _step_group(self, f, group, runs, clip):
+        """Launches of one step for the flat record `f` of `group`; runs: its [(lo, hi), ...]."""
+
     @torch.no_grad()
     def step(self, closure=None, clip=None):
         """`clip`: a mi355_clip_rec on the device (GradClipper.measure): every run is stepped on fl32(g * coef), or not at all when
@@ -206,17 +241,11 @@ class FusedSGD(Optimizer):
         runs = {}
         for f, lo, hi in self._runs():
             runs.setdefault(id(f), []).append((lo, hi))
+        self._step_begin(runs, clip)
         for f in self._flat:
             if f is None:
                 continue
-            g = self.param_groups[f['gi']]
-            for lo, hi in runs.get(id(f), ()):
-                if clip is None:
-                    ops.sgd_nesterov(f['P'][lo:hi], f['G'][lo:hi], f['M'][lo:hi], f['lr_dev'], g['momentum'], g['weight_decay'],
-                                     g['nesterov'])
-                else:
-                    ops.sgd_nesterov_clipped(f['P'][lo:hi], f['G'][lo:hi], f['M'][lo:hi], f['lr_dev'], clip, g['momentum'],
-                                             g['weight_decay'], g['nesterov'])
+            self._step_group(f, self.param_groups[f['gi']], runs.get(id(f), ()), clip)
             for p in f['params']:
                 if not self._stale(p):
                     p._mi_epoch = getattr(p, '_mi_epoch', 0) + 1
@@ -231,29 +260,180 @@ class FusedSGD(Optimizer):
         super().load_state_dict(state_dict)
         if self._flat is None:
             return
-        for f in self._flat:          # re-alias loaded momentum buffers onto the flat storage
+        for f in self._flat:          # re-alias loaded state tensors onto the flat storage
             if f is None:
                 continue
-            off = 0
-            for p in f['params']:
-                n = p.numel()
-                mv = f['M'][off:off + n].as_strided(p.shape, p.stride())
+            for i, p in enumerate(f['params']):
+                o, n = f['offs'][id(p)][0], p.numel()
                 st = self.state[p]
-                buf = st.get('momentum_buffer')
-                if buf is None:
-                    mv.zero_()
-                elif buf.data_ptr() != mv.data_ptr():
-                    mv.copy_(buf)
-                st['momentum_buffer'] = mv
-                off += (n + 3) // 4 * 4
+                for sk, fk in self._BUFFERS:
+                    bv = f[fk][o:o + n].as_strided(p.shape, p.stride())
+                    buf = st.get(sk)
+                    if buf is None:
+                        bv.zero_()
+                    elif buf.data_ptr() != bv.data_ptr():
+                        bv.copy_(buf)
+                    st[sk] = bv
+                if self._COUNTER:
+                    if st.get(self._COUNTER) is None:
+                        f['S'][i].zero_()
+                    self._alias_counter(st, f['S'][i])
         self.sync_lr(force=True)
 
 
+class FusedSGD(_FlatOptimizer):
+    _BUFFERS = (('momentum_buffer', 'M'),)
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0, weight_decay=0.0, nesterov=False):
+        if dampening != 0:
+            raise NotImplementedError('dampening is not used by the reference and not built')
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
+        super().__init__(params, defaults)
+
+    def _step_group(self, f, g, runs, clip):
+        for lo, hi in runs:
+            if clip is None:
+                ops.sgd_nesterov(f['P'][lo:hi], f['G'][lo:hi], f['M'][lo:hi], f['lr_dev'], g['momentum'], g['weight_decay'],
+                                 g['nesterov'])
+            else:
+                ops.sgd_nesterov_clipped(f['P'][lo:hi], f['G'][lo:hi], f['M'][lo:hi], f['lr_dev'], clip, g['momentum'],
+                                         g['weight_decay'], g['nesterov'])
+
+
+class FusedAdam(_FlatOptimizer):
+    """torch.optim.Adam (``decoupled=False``: L2 weight decay) / torch.optim.AdamW (``decoupled=True``) on flat fp32 buffers:
+    ``mi355_adam_step_batched`` over one table of every parameter that received a gradient since ``zero_grad()``, of every group,
+    then ``mi355_adam_tick_batched`` for their step counts -- two launches per ``step()``.  Same defaults, ``param_groups`` keys and
+    ``state_dict()`` layout as torch (``exp_avg``, ``exp_avg_sq`` and ``step``, an fp32 scalar, per parameter), so schedulers and
+    checkpoints move between the two.  The learning rates are read from the groups' device scalars and the step counts live on
+    the device (0-dim views into one array per flat group), so ``step()`` captures into a HIP graph and a replay sees the
+    schedule; betas, eps and weight decay are constants of the table, rebuilt -- outside capture only -- when they or the set of
+    fresh parameters change.  A parameter without a fresh gradient is not stepped and its count does not advance (torch:
+    ``grad is None``).  That holds for the parameters of mi355.nn modules, which mark their gradients themselves.  Caveat for
+    parameters of torch-native modules (``nn.Linear``, ``nn.Conv2d``): their flat gradient views share one version counter per group, so
+    such a parameter counts as untouched since ``zero_grad()`` only if nothing else of its group was written since -- otherwise it is
+    stepped on its zeroed gradient (moments decay, ``step`` advances), unlike torch.  Give a torch-native parameter that may sit out
+    steps a param group of its own.  ``weight_decay=None`` is the default of the torch class it stands for: 0 (Adam), 1e-2 (``decoupled=True``,
+    AdamW).  Arithmetic and its differences from torch: include/mi355pose.h."""
+    _BUFFERS = (('exp_avg', 'M'), ('exp_avg_sq', 'V'))
+    _COUNTER = 'step'
+    _TORCH_ONLY = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, decoupled=False, **torch_only):
+        for k, v in torch_only.items():
+            if k not in self._TORCH_ONLY:
+                raise TypeError('FusedAdam got an unexpected keyword argument %r' % k)
+            if v is not self._TORCH_ONLY[k] and v != self._TORCH_ONLY[k]:
+                raise NotImplementedError('FusedAdam: %s=%r is not built (only torch\'s default, %r)' % (k, v, self._TORCH_ONLY[k]))
+        if weight_decay is None:
+            weight_decay = 1e-2 if decoupled else 0.0       # torch.optim.AdamW's / torch.optim.Adam's default
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, **self._TORCH_ONLY,
+                        decoupled_weight_decay=bool(decoupled))
+        super().__init__(params, defaults)
+        self._tables = {}            # sig -> dict(sig, table, count, blocks): the few sets of fresh parameters a loop alternates between
+        self._retired = []           # tables no step() will use again, kept alive for the graphs that captured them (88 bytes an item)
+        self._table = None           # the one the last step() used
+
+    def ensure_flat(self):
+        if self._flat is None:
+            self._retired.extend(self._tables.values())
+            self._tables, self._table = {}, None         # (the tables hold addresses of the layout that is about to be replaced)
+        super().ensure_flat()
+
+    def _step_begin(self, runs, clip):
+        picked, sig = [], []         # (flat record, index in it, offset, length, hyper-parameters) of every parameter to step
+        for f in self._flat:
+            if f is None or id(f) not in runs:
+                continue
+            g = self.param_groups[f['gi']]
+            for k, v in self._TORCH_ONLY.items():
+                if g.get(k, v) is not v and g.get(k, v) != v:
+                    raise NotImplementedError('FusedAdam: %s=%r is not built' % (k, g[k]))
+            hyper = (float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']),
+                     bool(g.get('decoupled_weight_decay', False)))
+            for i, p in enumerate(f['params']):
+                o, n = f['offs'][id(p)][0], p.numel()
+                if any(lo <= o < hi for lo, hi in runs[id(f)]):
+                    picked.append((f, i, o, n, hyper))
+                    sig.append((f['P'].data_ptr(), o, n) + hyper)
+        sig = tuple(sig)
+        t = self._tables.get(sig)
+        if t is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('FusedAdam: the set of parameters to step (or a hyper-parameter of their groups) changed during '
+                                   'graph capture; run one eager step with the same parameters active before capturing')
+            if len(self._tables) >= 8:           # (a loop alternates between a few sets; anything more is churn: start over --
+                self._retired.extend(self._tables.values())      # but a captured graph may still read a table: none is freed)
+                self._tables.clear()
+            t = self._tables[sig] = dict(sig=sig)
+            if picked:
+                items = [(f['P'][o:o + n], f['G'][o:o + n], f['M'][o:o + n], f['V'][o:o + n], f['S'][i], f['lr_dev']) + hyper
+                         for f, i, o, n, hyper in picked]
+                t['table'], t['count'], t['blocks'] = ops.adam_table(items, items[0][0].device)
+        self._table = t
+        if picked:                   # (no fresh gradient at all: nothing to step)
+            ops.adam_step_batched(t['table'], t['count'], t['blocks'], clip)
+            ops.adam_tick_batched(t['table'], t['count'], clip)
+
+    def state_dict(self):
+        """torch.optim.Adam's layout: ``step`` leaves as an fp32 scalar on the host, as torch keeps it, and never as a view of the
+        device array the kernels count in."""
+        sd = super().state_dict()
+        sd['state'] = {k: ({**st, 'step': st['step'].detach().to('cpu', copy=True)} if torch.is_tensor(st.get('step')) else st)
+                       for k, st in sd['state'].items()}
+        return sd
+
+
+OPTIMIZERS = ('sgd', 'adam', 'adamw')
+
+
+def make_optimizer(kind, params, lr, momentum=0.9, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8):
+    """The training scripts' optimizer of `kind`: 'sgd' = FusedSGD with Nesterov momentum (the reference, train1.py:141-148),
+    'adam' = FusedAdam with L2 weight decay, 'adamw' = FusedAdam with decoupled weight decay (`momentum` unused by both)."""
+    if kind == 'sgd':
+        return FusedSGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=True)
+    if kind in ('adam', 'adamw'):
+        return FusedAdam(params, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, decoupled=kind == 'adamw')
+    raise ValueError('optimizer must be one of %s, got %r' % (', '.join(OPTIMIZERS), kind))
+
+
+def state_dict_kind(state_dict):
+    """'sgd' or 'adam' -- the family of optimizer that wrote `state_dict` (AdamW is Adam with another group flag) --, told from
+    the keys of its param_groups; None when neither."""
+    groups = state_dict.get('param_groups') or [{}]
+    if 'betas' in groups[0]:
+        return 'adam'
+    if 'momentum' in groups[0]:
+        return 'sgd'
+    return None
+
+
+def check_state_dict_kind(optimizer, state_dict, what='optimizer state'):
+    """Raise a ValueError that names both kinds when `state_dict` was written by the other family of optimizer than `optimizer`
+    (loading it would end in a KeyError deep inside step())."""
+    want = 'adam' if isinstance(optimizer, FusedAdam) else 'sgd'
+    got = state_dict_kind(state_dict)
+    if got is not None and got != want:
+        names = {'sgd': 'SGD (--optimizer sgd)', 'adam': 'Adam / AdamW (--optimizer adam | adamw)'}
+        raise ValueError('%s was written by %s but this run builds %s; resume with the optimizer the checkpoint was trained with'
+                         % (what, names[got], names[want]))
+
+
 class GradClipper:
-    """Global gradient-norm clipping with a non-finite step guard for FusedSGD optimizers, entirely on the device:
+    """Global gradient-norm clipping with a non-finite step guard for FusedSGD / FusedAdam optimizers, entirely on the device:
     ``torch.nn.utils.clip_grad_norm_(parameters stepped in this update, max_norm)`` in front of the optimizers' ``step()``, in two
     launches (``mi355_grad_sumsq_batched`` over every fresh run of every optimizer, ``mi355_grad_clip_coef``) that fill one
-    ``mi355_clip_rec``; ``FusedSGD.step(clip=record)`` applies the coefficient inside the SGD kernel.  Nothing is read by the
+    ``mi355_clip_rec``; ``step(clip=record)`` applies the coefficient inside the SGD / Adam kernel.  Nothing is read by the
     host, so the launches sit in captured graphs beside the optimizer's.
 
     Differences from torch's in-place clip: the gradient buffers are never written -- ``p.grad`` keeps the unclipped values
@@ -293,13 +473,13 @@ class GradClipper:
 
     @torch.no_grad()
     def measure(self, optimizers, slot):
-        """Enqueue the norm of everything `optimizers` (FusedSGD) are about to step into the record of `slot` and return that
+        """Enqueue the norm of everything `optimizers` (FusedSGD / FusedAdam) are about to step into the record of `slot` and return that
         record, for ``step(clip=...)``.  The range table is keyed by the runs' (buffer address, lo, hi) and rebuilt -- outside
         capture only -- when that changes."""
         optimizers = list(optimizers)
         for o in optimizers:
-            if not isinstance(o, FusedSGD):
-                raise TypeError('GradClipper handles FusedSGD optimizers only, got %s' % type(o).__name__)
+            if not isinstance(o, (FusedSGD, FusedAdam)):
+                raise TypeError('GradClipper handles FusedSGD and FusedAdam optimizers only, got %s' % type(o).__name__)
         rec = self.record(slot)
         for o in optimizers:
             o._settle()

@@ -55,7 +55,7 @@ import mi355
 import uda.model as models
 from mi355 import ops as _ops
 from mi355.da_step import JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
-from mi355.optim import EMATeacher, FusedSGD, GradClipper
+from mi355.optim import EMATeacher, GradClipper, check_state_dict_kind, make_optimizer
 from mi355.teacher import MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
@@ -197,7 +197,8 @@ def main(args):
     criterion = JointsKLLoss()
     step, opts, scheds = build_training(model, heatmap_size=args.heatmap_size, lr=args.lr, momentum=args.momentum, wd=args.wd,
                                         lr_gamma=args.lr_gamma, lr_decay=args.lr_decay, trade_off=args.trade_off,
-                                        num_keypoints=num_keypoints)
+                                        num_keypoints=num_keypoints, optimizer=args.optimizer, adam_betas=tuple(args.adam_betas),
+                                        adam_eps=args.adam_eps)
     if args.synthetic:
         # noise images make the target predictions collapse within a few dozen iterations; the reference's per-map
         # max-normalisation then divides 0 by 0 (regda_7.py:3623-3625).  Synthetic runs keep such maps at zero instead.
@@ -227,7 +228,8 @@ def main(args):
             print("Pretraining the model on source domain.")
             args.pretrain = logger.get_checkpoint_path('pretrain')
             pre = PoseResNet(backbone, upsampling, 256, num_keypoints, True).to(device)
-            optimizer = FusedSGD(pre.get_parameters(lr=args.lr), lr=args.lr, momentum=args.momentum, weight_decay=args.wd, nesterov=True)
+            optimizer = make_optimizer(args.optimizer, pre.get_parameters(lr=args.lr), lr=args.lr, momentum=args.momentum,
+                                       weight_decay=args.wd, betas=tuple(args.adam_betas), eps=args.adam_eps)
             lr_scheduler = MultiStepLR(optimizer, args.lr_step, args.lr_factor)
             best_acc = -1
             pre_clip = GradClipper(args.clip_grad_norm, device) if args.clip_grad_norm > 0 else None
@@ -251,6 +253,12 @@ def main(args):
     else:
         ck = torch.load(args.resume, map_location='cpu', weights_only=False)
         model.load_state_dict(ck['model']); model_ema.load_state_dict(ck['model'])
+        try:                                             # (SGD state under --optimizer adam, or the reverse: say so, no KeyError later)
+            for k in opts:
+                if 'optimizer_' + k in ck:
+                    check_state_dict_kind(opts[k], ck['optimizer_' + k], '%s: optimizer_%s' % (args.resume, k))
+        except ValueError as e:
+            raise SystemExit('--resume ' + str(e))
         for k, name in (('f', 'optimizer_f'), ('h', 'optimizer_h'), ('h_adv', 'optimizer_h_adv')):
             opts[k].load_state_dict(ck[name]); scheds[k].load_state_dict(ck['lr_scheduler' + name[len('optimizer'):]])
         for k in ('h_adv2', 'h_adv3'):                    # additive keys (the reference never saved these two)
@@ -595,7 +603,7 @@ _OPTIONS = [
     (('--trade-off',), dict(default=1., type=float, help='weight of the target-domain disparity losses')),
     (('-b', '--batch-size'), dict(default=32, type=int, metavar='N', help='images per domain per iteration')),
     (('--lr', '--learning-rate'), dict(default=0.01, type=float, metavar='LR', dest='lr', help='base learning rate')),
-    (('--momentum',), dict(default=0.9, type=float, metavar='M')),
+    (('--momentum',), dict(default=0.9, type=float, metavar='M', help='SGD momentum (ignored with --optimizer adam | adamw)')),
     (('--wd', '--weight-decay'), dict(default=0.0001, type=float, metavar='W')),
     (('--lr-gamma',), dict(default=0.0001, type=float, help='inverse-decay schedule: lr * (1 + gamma * it) ** -decay')),
     (('--lr-decay',), dict(default=0.75, type=float)),
@@ -658,6 +666,16 @@ _OPTIONS = [
                                 "clip_grad_norm_(those parameters, FLOAT) before the optimizers would, in two launches per update and "
                                 "inside the SGD kernels; an update whose norm is inf or NaN is skipped and counted ('skipped steps:'); "
                                 "'inf' measures and guards without scaling; 0: off, nothing is launched")),
+    (('--optimizer',), dict(default='sgd', choices=['sgd', 'adam', 'adamw'], help="every optimizer of the run, the pre-training one "
+                           "included: 'sgd' = SGD with Nesterov momentum (the reference); 'adam' = Adam with --wd as L2 weight decay; "
+                           "'adamw' = Adam with --wd as decoupled weight decay -- both in two launches per update over the flat "
+                           "buffers (mi355.optim.FusedAdam), with the same schedules, --clip-grad-norm, --ema-update and --*-loss "
+                           "terms; --momentum is ignored by both.  The learning rate reached through --lr is a placeholder under "
+                           "adam / adamw (recipes use about 1e-3): its effect on convergence has not been measured, and cannot be "
+                           "without the data sets.  --resume takes a checkpoint of the same kind only")),
+    (('--adam-betas',), dict(default=(0.9, 0.999), type=float, nargs=2, metavar=('B1', 'B2'), help='Adam coefficients of the running '
+                            'averages of the gradient and of its square (--optimizer adam | adamw; each in [0, 1))')),
+    (('--adam-eps',), dict(default=1e-8, type=float, metavar='FLOAT', help="term added to Adam's denominator (--optimizer adam | adamw)")),
     (('--no-graph',), dict(action='store_true', help='launch kernels eagerly instead of replaying HIP graphs')),
     (('--metrics',), dict(default='pck', choices=['pck', 'full'], help="'full': validation also decodes key points in image pixels "
                          "and reports the mean end-point error, the PCK curve's AUC and per-group EPEs (on the device, one read at "
@@ -702,6 +720,12 @@ class _Parser(argparse.ArgumentParser):
                 check_positive('--proto-weight', args.proto_weight)
                 check_whole('--proto-radius', args.proto_radius, 16)
                 check_blend_weight('--proto-m', args.proto_m)
+            if getattr(args, 'optimizer', 'sgd') != 'sgd':
+                for i, b in enumerate(args.adam_betas):
+                    if not 0.0 <= b < 1.0:
+                        raise ValueError('--adam-betas: Invalid beta parameter at index %d: %r' % (i, b))
+                if not 0.0 <= args.adam_eps:
+                    raise ValueError('--adam-eps: Invalid epsilon value: %r' % (args.adam_eps,))
         except ValueError as e:
             self.error(str(e))
         if getattr(args, 'dump_preds', None):

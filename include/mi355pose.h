@@ -514,6 +514,50 @@ int mi355_grad_sumsq_batched(const mi355_gn_item* items_dev, int count, int tota
 int mi355_grad_clip_coef(const double* partials_dev, int total_blocks, mi355_clip_rec* rec_dev, void* stream);
 int mi355_sgd_nesterov_clipped(float* p, const float* g, float* buf, long n, const float* lr_dev, const mi355_clip_rec* rec_dev,
                                float momentum, float wd, int nesterov, void* p_lowp, void* stream);
+/* Adam / AdamW over many parameters in two launches (mi355.optim.FusedAdam): torch.optim.Adam / AdamW of the installed torch,
+ * torch/optim/adam.py `_single_tensor_adam` with amsgrad, maximize, capturable and differentiable off, which does per parameter
+ *     step_t += 1
+ *     weight_decay != 0:  decoupled ? param.mul_(1 - lr * weight_decay) : grad = grad.add(param, alpha=weight_decay)
+ *     exp_avg.lerp_(grad, 1 - beta1)
+ *     exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+ *     bias_correction1 = 1 - beta1 ** step;  bias_correction2 = 1 - beta2 ** step          (Python floats: fp64)
+ *     step_size = lr / bias_correction1;     bias_correction2_sqrt = bias_correction2 ** 0.5
+ *     denom = (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+ *     param.addcdiv_(exp_avg, denom, value=-step_size)
+ * Here: items = DEVICE array, one item per parameter about to be stepped (p, g, m, v 16-byte aligned, n >= 1 floats each; blk0 =
+ * first block of the item = sum over earlier items of ceil(n / MI355_ADAM_CHUNK); total_blocks = that sum over all).  Block b owns
+ * one MI355_ADAM_CHUNK slice of its item (256 threads, a float4 per lane, a scalar tail; no atomics) and computes once, in fp64,
+ * from t = *step + 1 and lr = *item.lr:
+ *     bc1 = 1 - beta1^t;  bc2s = sqrt(1 - beta2^t);  step_size = fl32((double)lr / bc1);  bc2s_f = fl32(bc2s);
+ *     decay = fl32(1 - (double)lr * wd)
+ * then per element in fp32, every operation rounded on its own (nothing is contracted into an FMA), divide and square root
+ * correctly rounded:
+ *     gc = rec ? fl32(g * rec->coef) : g
+ *     decoupled ? p *= decay : gc = gc + wd * p          (the second only when wd != 0)
+ *     m = m + (1 - beta1) * (gc - m)
+ *     v = beta2 * v + (1 - beta2) * gc * gc              (((1 - beta2) * gc) * gc, the order of addcmul_)
+ *     p = p - step_size * (m / (sqrt(v) / bc2s_f + eps))
+ * The betas travel as fp64, as torch keeps them: beta^t and 1 - beta are formed in fp64 ((1 - beta) and beta2 are then rounded to
+ * fp32 once, as torch's scalar arguments are) -- from an fp32 beta2 = 0.999 both 1 - beta2 and 1 - beta2^t at small t would be off
+ * by 3e-5 of their value.  Differences from torch: lr is an fp32 value on the device (rounded before the division), and lerp_ is
+ * always the form above (torch switches to  gc - (gc - m) * beta1  when 1 - beta1 >= 0.5).  With rec->skip set the
+ * launch writes nothing: p, m and v keep their bits; rec->coef == 1.0f gives the bits of the rec == NULL launch.  g, step and lr
+ * are only read, nothing outside [x, x + n) of any item is touched, and blocks of one parameter never race on its step count:
+ * mi355_adam_tick_batched, one tiny launch BEHIND the step, does  *step += 1  for every item unless rec->skip.  The counts are
+ * fp32 (torch's state_dict dtype): exact up to 2^24 steps.  Host validation happens before any launch (null table, count < 1,
+ * total_blocks < 1 or < count, table not 8-byte aligned, record not 8-byte aligned).  Never allocates; capturable. */
+#define MI355_ADAM_CHUNK 16384      /* floats per block */
+typedef struct mi355_adam_item {
+  float* p; const float* g; float* m; float* v;      /* 16-byte aligned, n >= 1 floats each */
+  float* step;                                       /* this parameter's step count, one fp32 on the device */
+  const float* lr;                                   /* its group's learning rate, one fp32 on the device */
+  long n; double beta1, beta2;                       /* fp64, as torch keeps them: see above */
+  float eps, wd; int decoupled; int blk0;
+} mi355_adam_item;
+int mi355_adam_step_batched(const mi355_adam_item* items_dev, int count, int total_blocks,
+                            const mi355_clip_rec* rec_dev /* NULL: no clipping */, void* stream);
+int mi355_adam_tick_batched(const mi355_adam_item* items_dev, int count,
+                            const mi355_clip_rec* rec_dev /* NULL */, void* stream);
 
 /* ---------------------------------------------------------------- mean-teacher consistency (csrc/teacher.hip)
  * Eval-mode BatchNorm folded into the conv in front of it, for many (conv, bn) pairs in ONE launch and into caller-owned
