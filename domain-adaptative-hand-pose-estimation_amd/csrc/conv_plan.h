@@ -482,3 +482,97 @@ static inline WgradPlan plan_wgrad(const mi355_conv_desc* d, const ConvKnobs& k)
 }
 // the kernel a single weight-gradient launch runs, as the launch log names it
 static inline const char* wgrad_kernel_name(const WgradPlan& w) { return w.kw2 ? "wgrad_kw2" : w.kw3 ? "wgrad_kw" : "wgrad"; }
+
+// ------------------------------------------------------------------------------------ grouped weight-gradient plans
+// mi355_conv_wgrad_grouped: which items share a launch (walk_wgrad_groups) and the split counts and slab offsets of one grouped
+// launch (group_plan).  igemm.hip launches from these; tests/conv_dispatch_probe.cpp prints them without a GPU.
+#define WG_MAX 24        // items of one launch of the generic / the 256 x 256-tile grouped kernel
+#define WGK_MAX 16       // items of one launch of the grouped 3x3 / stride-1 kernel
+static inline bool group_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
+  return !w.kw2 && !w.kw3 && (long)w.nto * w.nti < 384;
+}
+// ... and of those, the ones the 256 x 256-tile kernel takes (wgrad_group256_kernel): bf16, whole 256-wide tiles both ways
+static inline bool group256_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
+  return conv_knobs().wgrad_group256 && d->dtype == MI355_BF16 && d->kh == 1 && d->kw == 1 && d->pad == 0 && d->Co % 256 == 0 && d->Ci % 256 == 0;
+}
+// 3x3 / stride-1 problems (wgrad_kw_kernel) small enough to share a launch: fewer than 24 K steps per block at 768 blocks
+static inline bool kw_group_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
+  if (!conv_knobs().wgrad_kw_group || !w.kw3) return false;
+  const long M = (long)d->N * d->Ho * d->Wo, ksteps = (M + 63) / 64;
+  return (long)w.nto * 3 * w.nti * ksteps < 768L * 24;
+}
+static inline long group_tiles(int kind, const mi355_conv_desc* d, const WgradPlan& w) {
+  return kind == 3 ? (long)(d->Co / 256) * (w.ldw / 256) : kind == 2 ? (long)w.nto * 3 * w.nti : (long)w.nto * w.nti;
+}
+struct GroupPlan { int S, rps; size_t ws_off; };
+// Split counts and slab offsets of the items of one grouped launch of `kind`; returns its blocks.
+static inline long group_plan(const mi355_wgrad_item* items, const int* idx, int n, GroupPlan* gp, size_t* ws_bytes, int kind) {
+  const ConvKnobs& kn = conv_knobs();
+  const int target = kind == 3 ? kn.wg_group256_blocks : kind == 2 ? kn.wg_kw_group_blocks : kn.wg_group_blocks;
+  auto rows = [](const mi355_conv_desc* d) { return (long)d->N * d->Ho * d->Wo; };
+  auto kstep = [](const mi355_conv_desc* d) { return d->dtype == MI355_BF16 ? 64 : 32; };
+  // equal work per block: block-steps W = sum tiles_i * ksteps_i; aim at 3 blocks per CU, never fewer than 16 K-steps per block
+  // (256-wide tiles: one 8-wave block per CU)
+  double W = 0;
+  for (int k = 0; k < n; ++k) {
+    const mi355_conv_desc* d = &items[idx[k]].d;
+    W += (double)group_tiles(kind, d, plan_wgrad(d, kn)) * ((rows(d) + kstep(d) - 1) / kstep(d));
+  }
+  long per = (long)(W / target) + 1; if (per < 16) per = 16;
+  auto plan_at = [&](long per, GroupPlan* out, size_t* ws_end) {      // blocks of the group when every block runs `per` K steps
+    long blocks = 0; size_t off = 0;
+    for (int k = 0; k < n; ++k) {
+      const mi355_wgrad_item& it = items[idx[k]]; const mi355_conv_desc* d = &it.d; const WgradPlan w = plan_wgrad(d, kn);
+      const WgradSplit s = wgrad_split(rows(d), kstep(d), ((rows(d) + kstep(d) - 1) / kstep(d) + per - 1) / per);
+      if (out) { out[k].S = s.S; out[k].rps = s.rows; out[k].ws_off = off; }
+      if (s.S > 1 || it.accumulate) off += (size_t)s.S * d->Co * w.ldw * sizeof(float);
+      blocks += group_tiles(kind, d, w) * s.S;
+    }
+    if (ws_end) *ws_end = off;
+    return blocks;
+  };
+  // 256-wide tiles run one block per CU: a grid of 294 blocks on 256 CUs would take two rounds, the second nearly empty -- lengthen
+  // the blocks until the group fits the target (rounding the split counts up is what overshoots it)
+  for (int trial = 0; kind == 3 && trial < 64; ++trial) {
+    if (plan_at(per, nullptr, nullptr) <= target) break;
+    per += per / 16 + 1;
+  }
+  return plan_at(per, gp, ws_bytes);
+}
+// The launches mi355_conv_wgrad_grouped makes of `items`, in order, handed to `fn(kind, idx, m)`: kind 0 = one item through
+// mi355_conv_wgrad, 1 = a group of the generic kernel, 2 = a group of the 3x3 / stride-1 kernel, 3 = a group of the 256 x 256-tile kernel.  One walk for the launcher and
+// for the workspace size, so the two cannot disagree.  Two items that write the same dw (one conv used twice in a backward:
+// overwrite, then accumulate) must neither share a launch -- the overwrite and the read-modify-write would race -- nor change
+// their order: whatever is pending goes first.
+template <typename F>
+static inline int walk_wgrad_groups(const mi355_wgrad_item* items, int n, F&& fn) {
+  int gi[WG_MAX], ki[WGK_MAX], bi[WG_MAX]; int gm = 0, km = 0, bm = 0;
+  auto flush_g = [&]() -> int { if (!gm) return 0; int e = fn(1, gi, gm); gm = 0; return e; };
+  auto flush_k = [&]() -> int { if (!km) return 0; int e = fn(2, ki, km); km = 0; return e; };
+  auto flush_b = [&]() -> int { if (!bm) return 0; int e = fn(3, bi, bm); bm = 0; return e; };
+  for (int i = 0; i < n; ++i) {
+    const mi355_wgrad_item& it = items[i];
+    WgradPlan w = plan_wgrad(&it.d, conv_knobs());
+    bool shares = false;
+    for (int k = 0; k < gm; ++k) shares = shares || items[gi[k]].dw == it.dw;
+    for (int k = 0; k < km; ++k) shares = shares || items[ki[k]].dw == it.dw;
+    for (int k = 0; k < bm; ++k) shares = shares || items[bi[k]].dw == it.dw;
+    if (shares) { if (int e = flush_g()) return e; if (int e = flush_k()) return e; if (int e = flush_b()) return e; }
+    if (kw_group_eligible(&it.d, w)) {
+      if (km && (km == WGK_MAX || plan_wgrad(&items[ki[0]].d, conv_knobs()).mt != w.mt)) { if (int e = flush_k()) return e; }
+      ki[km++] = i;
+    } else if (group_eligible(&it.d, w) && group256_eligible(&it.d, w)) {
+      if (bm == WG_MAX) { if (int e = flush_b()) return e; }
+      bi[bm++] = i;
+    } else if (group_eligible(&it.d, w)) {
+      if (gm && (gm == WG_MAX || items[gi[0]].d.dtype != it.d.dtype)) { if (int e = flush_g()) return e; }
+      gi[gm++] = i;
+    } else {
+      int one = i;
+      if (int e = fn(0, &one, 1)) return e;
+    }
+  }
+  if (int e = flush_g()) return e;
+  if (int e = flush_b()) return e;
+  return flush_k();
+}

@@ -818,7 +818,6 @@ __global__ __launch_bounds__(256, 3) void wgrad_gemm_kernel(const WgradArgs p) {
 // pays for it with as many fp32 slabs plus a reduce launch).  Grouped, the tiles of all problems fill the chip together:
 // 2 .. 4 splits per problem, long K loops, one launch + one grouped slab reduce for the whole stage.  The argument blocks
 // travel by value in the kernel-argument segment (graph-capturable, no device table).
-#define WG_MAX 24
 struct WgradGroupArgs { WgradArgs p[WG_MAX]; int bstart[WG_MAX + 1]; int n; };
 template <typename T>
 __global__ __launch_bounds__(256, 3) void wgrad_group_kernel(const WgradGroupArgs g) {
@@ -1152,7 +1151,6 @@ __global__ __launch_bounds__(256, 3) void wgrad_kw_kernel(const WgradKwArgs p) {
 // half the CUs carry two), run 8 .. 16 K steps each (mostly prologue and fp32 slab stores) and leave 16 .. 256 slabs to a reduce
 // launch of their own.  Grouped, the tiles of all the stage's layers fill the chip together with a few long splits per layer and
 // one grouped slab reduction.  Argument blocks by value in the kernel-argument segment (graph-capturable), as wgrad_group_kernel.
-#define WGK_MAX 16
 struct WgradKwGroupArgs { WgradKwArgs p[WGK_MAX]; int bstart[WGK_MAX + 1]; int n; };
 template <int MT>
 __global__ __launch_bounds__(256, 3) void wgrad_kw_group_kernel(const WgradKwGroupArgs g) {
@@ -1854,58 +1852,8 @@ extern "C" int mi355_conv_wgrad(const mi355_conv_desc* d, const void* x, const v
 // items: HOST array.  Problems the specialised kernels take (3x3 stride 1 -> wgrad_kw, 3x3 / 4x4 stride 2 -> wgrad_kw2), and
 // any problem that fills the chip on its own, run through mi355_conv_wgrad one by one; the rest -- the generic kernel's
 // small problems -- are launched in groups of up to WG_MAX with a split count chosen for the GROUP.
-// (`kind` below: the launch kinds of walk_wgrad_groups.)
-static bool group_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
-  return !w.kw2 && !w.kw3 && (long)w.nto * w.nti < 384;
-}
-// ... and of those, the ones the 256 x 256-tile kernel takes (wgrad_group256_kernel): bf16, whole 256-wide tiles both ways
-static bool group256_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
-  return conv_knobs().wgrad_group256 && d->dtype == MI355_BF16 && d->kh == 1 && d->kw == 1 && d->pad == 0 && d->Co % 256 == 0 && d->Ci % 256 == 0;
-}
-// 3x3 / stride-1 problems (wgrad_kw_kernel) small enough to share a launch: fewer than 24 K steps per block at 768 blocks
-static bool kw_group_eligible(const mi355_conv_desc* d, const WgradPlan& w) {
-  if (!conv_knobs().wgrad_kw_group || !w.kw3) return false;
-  const long M = (long)d->N * d->Ho * d->Wo, ksteps = (M + 63) / 64;
-  return (long)w.nto * 3 * w.nti * ksteps < 768L * 24;
-}
-static long group_tiles(int kind, const mi355_conv_desc* d, const WgradPlan& w) {
-  return kind == 3 ? (long)(d->Co / 256) * (w.ldw / 256) : kind == 2 ? (long)w.nto * 3 * w.nti : (long)w.nto * w.nti;
-}
-struct GroupPlan { int S, rps; size_t ws_off; };
-// Split counts and slab offsets of the items of one grouped launch of `kind`; returns its blocks.
-static long group_plan(const mi355_wgrad_item* items, const int* idx, int n, GroupPlan* gp, size_t* ws_bytes, int kind) {
-  const ConvKnobs& kn = conv_knobs();
-  const int target = kind == 3 ? kn.wg_group256_blocks : kind == 2 ? kn.wg_kw_group_blocks : kn.wg_group_blocks;
-  auto rows = [](const mi355_conv_desc* d) { return (long)d->N * d->Ho * d->Wo; };
-  auto kstep = [](const mi355_conv_desc* d) { return d->dtype == MI355_BF16 ? 64 : 32; };
-  // equal work per block: block-steps W = sum tiles_i * ksteps_i; aim at 3 blocks per CU, never fewer than 16 K-steps per block
-  // (256-wide tiles: one 8-wave block per CU)
-  double W = 0;
-  for (int k = 0; k < n; ++k) {
-    const mi355_conv_desc* d = &items[idx[k]].d;
-    W += (double)group_tiles(kind, d, plan_wgrad(d, kn)) * ((rows(d) + kstep(d) - 1) / kstep(d));
-  }
-  long per = (long)(W / target) + 1; if (per < 16) per = 16;
-  auto plan_at = [&](long per, GroupPlan* out, size_t* ws_end) {      // blocks of the group when every block runs `per` K steps
-    long blocks = 0; size_t off = 0;
-    for (int k = 0; k < n; ++k) {
-      const mi355_wgrad_item& it = items[idx[k]]; const mi355_conv_desc* d = &it.d; const WgradPlan w = plan_wgrad(d, kn);
-      const WgradSplit s = wgrad_split(rows(d), kstep(d), ((rows(d) + kstep(d) - 1) / kstep(d) + per - 1) / per);
-      if (out) { out[k].S = s.S; out[k].rps = s.rows; out[k].ws_off = off; }
-      if (s.S > 1 || it.accumulate) off += (size_t)s.S * d->Co * w.ldw * sizeof(float);
-      blocks += group_tiles(kind, d, w) * s.S;
-    }
-    if (ws_end) *ws_end = off;
-    return blocks;
-  };
-  // 256-wide tiles run one block per CU: a grid of 294 blocks on 256 CUs would take two rounds, the second nearly empty -- lengthen
-  // the blocks until the group fits the target (rounding the split counts up is what overshoots it)
-  for (int trial = 0; kind == 3 && trial < 64; ++trial) {
-    if (plan_at(per, nullptr, nullptr) <= target) break;
-    per += per / 16 + 1;
-  }
-  return plan_at(per, gp, ws_bytes);
-}
+// Which items share a launch (walk_wgrad_groups, whose launch kinds are the `kind` below) and the split counts and slab offsets of
+// a group (group_plan) are in conv_plan.h.
 // The slab reductions of a grouped launch, one launch for all of them.
 static void slab_group_add(SlabGroupArgs& sg, int& nblocks, const float* slabs, float* out, long slab_stride, int S, int accumulate) {
   SlabItem& q = sg.it[sg.n];
@@ -1921,43 +1869,6 @@ static int launch_slab_reduce_group(SlabGroupArgs& sg, int nblocks, hipStream_t 
   ProfScope ps(st, 0.0, sb, 2, prof_on() ? lab : nullptr);
   hipLaunchKernelGGL(slab_reduce_group_kernel, dim3(nblocks), dim3(256), 0, st, sg); MI_CHECK_LAUNCH("slab_reduce_group");
   return MI355_OK;
-}
-// The launches mi355_conv_wgrad_grouped makes of `items`, in order, handed to `fn(kind, idx, m)`: kind 0 = one item through
-// mi355_conv_wgrad, 1 = a group of the generic kernel, 2 = a group of the 3x3 / stride-1 kernel, 3 = a group of the 256 x 256-tile kernel.  One walk for the launcher and
-// for the workspace size, so the two cannot disagree.  Two items that write the same dw (one conv used twice in a backward:
-// overwrite, then accumulate) must neither share a launch -- the overwrite and the read-modify-write would race -- nor change
-// their order: whatever is pending goes first.
-template <typename F>
-static int walk_wgrad_groups(const mi355_wgrad_item* items, int n, F&& fn) {
-  int gi[WG_MAX], ki[WGK_MAX], bi[WG_MAX]; int gm = 0, km = 0, bm = 0;
-  auto flush_g = [&]() -> int { if (!gm) return 0; int e = fn(1, gi, gm); gm = 0; return e; };
-  auto flush_k = [&]() -> int { if (!km) return 0; int e = fn(2, ki, km); km = 0; return e; };
-  auto flush_b = [&]() -> int { if (!bm) return 0; int e = fn(3, bi, bm); bm = 0; return e; };
-  for (int i = 0; i < n; ++i) {
-    const mi355_wgrad_item& it = items[i];
-    WgradPlan w = plan_wgrad(&it.d, conv_knobs());
-    bool shares = false;
-    for (int k = 0; k < gm; ++k) shares = shares || items[gi[k]].dw == it.dw;
-    for (int k = 0; k < km; ++k) shares = shares || items[ki[k]].dw == it.dw;
-    for (int k = 0; k < bm; ++k) shares = shares || items[bi[k]].dw == it.dw;
-    if (shares) { if (int e = flush_g()) return e; if (int e = flush_k()) return e; if (int e = flush_b()) return e; }
-    if (kw_group_eligible(&it.d, w)) {
-      if (km && (km == WGK_MAX || plan_wgrad(&items[ki[0]].d, conv_knobs()).mt != w.mt)) { if (int e = flush_k()) return e; }
-      ki[km++] = i;
-    } else if (group_eligible(&it.d, w) && group256_eligible(&it.d, w)) {
-      if (bm == WG_MAX) { if (int e = flush_b()) return e; }
-      bi[bm++] = i;
-    } else if (group_eligible(&it.d, w)) {
-      if (gm && (gm == WG_MAX || items[gi[0]].d.dtype != it.d.dtype)) { if (int e = flush_g()) return e; }
-      gi[gm++] = i;
-    } else {
-      int one = i;
-      if (int e = fn(0, &one, 1)) return e;
-    }
-  }
-  if (int e = flush_g()) return e;
-  if (int e = flush_b()) return e;
-  return flush_k();
 }
 extern "C" size_t mi355_conv_wgrad_grouped_workspace(const mi355_wgrad_item* items, int n) {
   if (!items || n < 1) return 0;

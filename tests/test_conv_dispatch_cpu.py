@@ -150,3 +150,87 @@ def test_every_case_belongs_to_a_group_that_runs():
         assert set(v[0] for v in table.values()) <= groups
     assert set(R.CASES) == set(R.EXPECT) and set(R.CAT_CASES) == set(R.CAT_EXPECT) and set(R.FP8_CASES) == set(R.FP8_EXPECT)
     assert set(R.PGEMM_CASES) == set(R.PGEMM_EXPECT) and set(R.ROUNDING_CASES) == set(R.ROUNDING_EXPECT)
+
+
+# ---------------------------------------------------------------------------------------------- what the guard buffers need
+def _probe(probe, lines, group='default'):
+    """{line number: [texts]} of the probe for `lines` under the environment of `group`."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith('MI355_')}
+    env.update(R.GROUPS.get(group, {}), ASAN_OPTIONS='detect_leaks=1:halt_on_error=1', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
+    r = subprocess.run([probe], input=''.join(l + '\n' for l in lines), capture_output=True, text=True, env=env, timeout=120)
+    report = (r.stdout[-2000:] + r.stderr[-4000:])
+    assert 'Sanitizer' not in report and 'runtime error:' not in report and r.returncode == 0, report
+    got = {}
+    for row in r.stdout.splitlines():
+        n, text = row.split('\t')
+        got.setdefault(int(n), []).append(text)
+    return got
+
+
+# The cases of conv_exact_ref.py that give the poisoned guard buffers of test_gpu_conv_exact.py (tests/guarded.py) something to
+# find, named so that a table edit which loses one fails here: (a) weight gradients whose last split is ragged, (b) one slab
+# with accumulate (the slab path with a single slab), (c) a grouped launch with more than one slab-reduced item, (d) statistics
+# epilogues that fill fewer slices than their buffer holds.
+GUARD_COVERAGE = {
+    'ragged':       [('small7', 'bf16'), ('t64x128', 'f32'), ('kg2_64', 'bf16'), ('wkw2_wo8', 'bf16')],
+    'single_slab':  [('wkw_direct', 'bf16'), ('wkw2_direct', 'bf16'), ('wgen_direct', 'bf16')],
+    'grouped':      [('wgrad_group', 'f32', 0), ('wgrad_kw_group', 'bf16', 1)],        # (form, format, index of the launch)
+    'slices':       ['small7', 't64x128', 'kg2_128', 't256d', 'kw3_256x128'],
+}
+
+
+def test_the_cases_give_the_guard_buffers_something_to_find(probe):
+    # (a), (b): plan_wgrad / wgrad_split of the single launches
+    names = sorted(set(GUARD_COVERAGE['ragged'] + GUARD_COVERAGE['single_slab']))
+    lines = []
+    for name, dt in names:
+        g, N, Ci, H, W, Co, k, s, p, out_hw, dgrad = R.CASES[name]
+        assert g == 'default'
+        Ho, Wo = out_hw if out_hw is not None else R.out_size(H, W, k, k, s, p)
+        lines.append('wplan %s %d %d %d %d %d %d %d %d %d %d' % (dt, N, H, W, Ci, Co, k, s, p, Ho, Wo))
+    got = _probe(probe, lines)
+    plan = {}
+    for i, key in enumerate(names):
+        m = re.match(r'(\w+) S(\d+) rows(\d+) M(\d+) ws(\d+)$', got[i + 1][0])
+        assert m, got[i + 1]
+        plan[key] = (m.group(1),) + tuple(int(v) for v in m.groups()[1:])
+        kernel, S, rows, M, ws = plan[key]
+        assert '%s S%d' % (kernel, S) == R.EXPECT[key[0]][0 if key[1] == 'bf16' else 1][4]          # the launch the GPU test pins
+        assert (S - 1) * rows < M <= S * rows                                                        # no empty split
+    for key in GUARD_COVERAGE['ragged']:
+        kernel, S, rows, M, ws = plan[key]
+        assert S > 1 and M % rows != 0, (key, plan[key])          # the last split holds fewer rows than the others
+    assert len(set(plan[key][0] for key in GUARD_COVERAGE['ragged'])) == 3          # ... on each of the three kernels
+    for key in GUARD_COVERAGE['single_slab']:
+        kernel, S, rows, M, ws = plan[key]
+        assert S == 1 and ws > 0, (key, plan[key])          # with accumulate (every case runs it) the one slab goes through the workspace
+    assert len(set(plan[key][0] for key in GUARD_COVERAGE['single_slab'])) == 3
+
+    # (c): walk_wgrad_groups / group_plan of the grouped calls
+    for form, dt, launch in GUARD_COVERAGE['grouped']:
+        fmts, shapes = R.GROUPED_CASES[form]
+        assert dt in fmts
+        lines, dw = [], {}
+        for i, (N, H, W, Ci, Co, k, s, p, acc, share) in enumerate(shapes):
+            Ho, Wo = R.out_size(H, W, k, k, s, p)
+            dw[i] = dw[share] if share is not None else i
+            lines.append('gitem %s %d %d %d %d %d %d %d %d %d %d acc=%d dw=%d' % (dt, N, H, W, Ci, Co, k, s, p, Ho, Wo, int(acc), dw[i]))
+        got = _probe(probe, lines + ['gplan'])[len(lines) + 1]
+        head, items = got[launch].split(' | ')[0], got[launch].split(' | ')[1:]
+        assert head.startswith('kind') and head[4] in '123', got
+        slabbed = [it for it in items if it.endswith(' slab1')]
+        assert len(slabbed) > 1, (form, got)          # two slab regions of one workspace side by side, one grouped reduction
+        split = [it for it in slabbed if int(re.search(r' S(\d+) ', it).group(1)) > 1]
+        print('\nGROUPED %s/%s launch %d: %s (%d slab-reduced, %d of them split)' % (form, dt, launch, got[launch], len(slabbed), len(split)))
+
+    # (d): plan_tile_grid of the statistics epilogues
+    lines = []
+    for name in GUARD_COVERAGE['slices']:
+        g, N, Ci, H, W, Co, k, s, p, out_hw, dgrad = R.CASES[name]
+        Ho, Wo = out_hw if out_hw is not None else R.out_size(H, W, k, k, s, p)
+        lines.append('fwd bf16 %d %d %d %d %d %d %d %d %d %d stats=1 slices=1' % (N, H, W, Ci, Co, k, s, p, Ho, Wo))
+    got = _probe(probe, lines)
+    for i, name in enumerate(GUARD_COVERAGE['slices']):
+        m = re.search(r'^(.*) epi1 slices=(\d+)/(\d+)$', got[i + 1][0])
+        assert m and m.group(1) == R.EXPECT[name][0][0], got[i + 1]
+        assert 1 <= int(m.group(2)) < int(m.group(3)), got[i + 1]          # slices behind the last written one: they must stay untouched

@@ -5,7 +5,10 @@ Every comparison here is one of three kinds, named next to it:
   [bound]  the derived bound B of the roundings that remain (ragged row counts, the forward's apply pass);
   [stats]  the project's own tightest statistics tolerances (test_conv_fwd_concat_k): rtol 1e-5 / atol 1e-6 on means,
            rtol 2e-5 / atol 1e-6 on invstd and variances.
-Operands go to the device with plain torch; the float64 references are the functions test_bn_exact_cpu.py holds against
+Operands are plain torch casts of exact values, copied into 0xFF-filled guard buffers (tests/guarded.py); every call runs inside
+a guard window, so the tensors the wrappers allocate (y, dx, dres, mean, invstd, ss, coeff, masks) and the workspace -- of exactly
+mi355_bn_workspace bytes -- are guard buffers too: a store outside a result changes a flank, an element a launch skipped stays a
+NaN, and a chunk load past an operand reads NaN.  The float64 references are the functions test_bn_exact_cpu.py holds against
 torch on the CPU, evaluated with torch's float64 on the device so that the 16 M-element cases stay within seconds.  The form
 of the backward that ran (reduce + finalize + apply, or the one-launch LDS-resident kernel) is read from the launch log, so a
 silent fallback cannot make two runs of one path pass as two paths.  Nothing here provokes a give-up of the resident kernel."""
@@ -13,6 +16,7 @@ import pytest
 import torch
 
 import bn_exact_ref as R
+import guarded as G
 
 pytestmark = pytest.mark.gpu
 
@@ -38,6 +42,14 @@ def launch_log(gpu):
     assert ops.bn_resident_timeouts() == 0
 
 
+@pytest.fixture(autouse=True)
+def guards():
+    """No guard buffer of one test is charged to the next (tests/guarded.py); the operands _HOLD keeps stay under watch."""
+    yield
+    torch.cuda.synchronize()
+    G.check('end of test')
+
+
 _HOLD = {}       # the operands and references of the (rows, C) in hand: consecutive cases of one shape share them
 
 
@@ -46,13 +58,28 @@ def _case(gpu, rows, C, mirror=False):
     if key not in _HOLD:
         _HOLD.clear()
         c = R.make_case(rows, C, device=gpu, mirror=mirror)
+        G.row_pitch(C * 4)          # the widest row of the case (fp32): the flanks of its vectors and of the workspace hold 256 of them
         c['dev'], c['ref'] = {}, {}
         _HOLD[key] = c
     return _HOLD[key]
 
 
 def _put(mat, dt):
-    return R.nchw(mat).to(R.TDT[dt]).contiguous(memory_format=torch.channels_last)
+    """A [rows][C] matrix as a channels_last feature map of type dt, inside a guard buffer (tests/guarded.py)."""
+    return G.place(R.nchw(mat).to(R.TDT[dt]).contiguous(memory_format=torch.channels_last), 'feature map')
+
+
+def _vec(t, what='vector'):
+    """A per-channel vector, a mask, a partials buffer or an fp8 record, inside a guard buffer."""
+    return G.place(t.contiguous(), what)
+
+
+def _whole(what, *ts):
+    """The launch wrote all of each tensor: no element is still the guard fill (a NaN no result here may be)."""
+    for t in ts:
+        if t is not None:
+            assert t.data_ptr() % G.BOUNDARY == G.START, '%s: not in a guard buffer' % what          # (the allocator's own blocks start on the boundary)
+            assert G.unwritten(t) == 0, '%s: %d bytes were never written' % (what, G.unwritten(t))
 
 
 def _dev(c, dt, residual=True):
@@ -60,9 +87,9 @@ def _dev(c, dt, residual=True):
     key = (dt, residual)
     if key not in c['dev']:
         y = R.fwd_y(c, residual, True)
-        d = dict(x=_put(c['x'], dt), dy=_put(c['dy'], dt), res=_put(c['res'], dt), y=_put(y, dt), mask=R.pack_mask(y > 0, R.PER[dt]))
+        d = dict(x=_put(c['x'], dt), dy=_put(c['dy'], dt), res=_put(c['res'], dt), y=_put(y, dt), mask=_vec(R.pack_mask(y > 0, R.PER[dt]), 'mask'))
         for k in ('gamma', 'beta', 'mean', 'invstd'):
-            d[k] = c[k].float()
+            d[k] = _vec(c[k].float(), k)
         for k in ('x', 'dy', 'res', 'y'):
             assert torch.equal(R.rows_of(d[k]).double(), c[k] if k != 'y' else y)          # the casts lost nothing
         c['dev'][key] = d
@@ -78,10 +105,15 @@ def _ref(c, source, residual=True):
 
 
 def _labels(ops, fn):
+    """fn() with the labels of its launches, inside a guard window: every tensor the wrapper allocates and its workspace are
+    0xFF-filled buffers between 0xFF flanks, and no flank byte -- theirs or an operand's -- may have changed afterwards."""
     ops.prof_reset()
-    out = fn()
+    with G.window(ops, 'bn call'):
+        out = fn()
     torch.cuda.synchronize()
-    return out, [l['label'] for l in ops.prof_launches()]
+    labels = [l['label'] for l in ops.prof_launches()]
+    G.check(' | '.join(labels))
+    return out, labels
 
 
 def _backward(ops, c, dt, form, relu, dres, acc, partial=None, q8=None, residual=True):
@@ -89,8 +121,8 @@ def _backward(ops, c, dt, form, relu, dres, acc, partial=None, q8=None, residual
     (accumulate) or from a sentinel the kernel must overwrite."""
     d = _dev(c, dt, residual)
     C, gpu = c['C'], c['x'].device
-    dg = R.int_prior(C, 'dg', gpu).float() if acc else torch.full((C,), 777.0, device=gpu)
-    db = R.int_prior(C, 'db', gpu).float() if acc else torch.full((C,), -777.0, device=gpu)
+    dg = _vec(R.int_prior(C, 'dg', gpu).float() if acc else torch.full((C,), 777.0, device=gpu), 'dgamma')
+    db = _vec(R.int_prior(C, 'db', gpu).float() if acc else torch.full((C,), -777.0, device=gpu), 'dbeta')
     prev = ops.bn_set_resident(1 if form == 'resident' else 0)
     try:
         (dx, dr), labels = _labels(ops, lambda: ops.bn_bwd(d['dy'], d['x'], d['y'] if relu == 1 else None, d['gamma'], d['mean'], d['invstd'],
@@ -98,6 +130,7 @@ def _backward(ops, c, dt, form, relu, dres, acc, partial=None, q8=None, residual
                                                           relu_mask=d['mask'] if relu == 3 else None, q8=q8))
     finally:
         ops.bn_set_resident(prev)
+    _whole('dx / dres', dx, dr)
     return dx, dr, dg, db, labels
 
 
@@ -163,7 +196,7 @@ def test_backward_from_crafted_partials(gpu, case):
     ops = _ops()
     c = _case(gpu, rows, C)
     r = _ref(c, relu)
-    p = R.bwd_partials(r['s1'], r['s2'], ns, relu).float().contiguous()
+    p = _vec(R.bwd_partials(r['s1'], r['s2'], ns, relu).float(), 'partials')
     dx, dr, dg, db, labels = _backward(ops, c, dt, 'three', relu, dres, acc, partial=(p, ns))
     _assert_sums(c, r, dr, dg, db, dres, acc, dt)
     assert torch.equal(R.rows_of(dx).double(), R.rne(r['dx'], dt)), 'dx'       # [equal]
@@ -182,9 +215,10 @@ def test_forward_statistics(gpu, shape, updates):
     s = R.stats_case(rows, C, device=gpu)
     rm0, rv0 = _running_start(C, gpu)
     f = R.train_fwd(s['x'], s['gamma'], s['beta'], rm0=rm0, rv0=rv0, repeats=updates)
-    rm, rv, nbt = rm0.float(), rv0.float(), torch.full((), 5, dtype=torch.int64, device=gpu)
-    y, mean, invstd = ops.bn_train_fwd(_put(s['x'], dt), None, s['gamma'].float(), s['beta'].float(), rm, rv, nbt, R.EPS, R.MOMENTUM, False,
-                                       stat_updates=updates)
+    rm, rv, nbt = _vec(rm0.float(), 'running_mean'), _vec(rv0.float(), 'running_var'), _vec(torch.full((), 5, dtype=torch.int64, device=gpu), 'nbt')
+    x, gamma, beta = _put(s['x'], dt), _vec(s['gamma'].float(), 'gamma'), _vec(s['beta'].float(), 'beta')
+    (y, mean, invstd), _ = _labels(ops, lambda: ops.bn_train_fwd(x, None, gamma, beta, rm, rv, nbt, R.EPS, R.MOMENTUM, False, stat_updates=updates))
+    _whole('y / mean / invstd', y, mean, invstd)
     assert torch.allclose(mean.double(), f['mean'], **MEAN_TOL), float((mean.double() - f['mean']).abs().max())          # [stats]
     assert torch.allclose(invstd.double(), f['invstd'], **VAR_TOL), float((invstd.double() / f['invstd'] - 1).abs().max())   # [stats]
     assert int(nbt) == 5 + updates
@@ -208,10 +242,15 @@ def test_forward_apply_eval_and_mask_bits(gpu, shape, res, relu):
     d = _dev(c, dt)
     rd = d['res'] if res else None
     rm0, rv0 = _running_start(C, gpu)
-    nbt = torch.zeros((), dtype=torch.int64, device=gpu)
-    mask = ops.bn_relu_mask(d['x'])
-    y, mean_k, invstd_k = ops.bn_train_fwd(d['x'], rd, d['gamma'], d['beta'], rm0.float(), rv0.float(), nbt, R.EPS, R.MOMENTUM, relu, relu_mask=mask)
-    y2, mean2, invstd2 = ops.bn_train_fwd(d['x'], rd, d['gamma'], d['beta'], rm0.float(), rv0.float(), nbt, R.EPS, R.MOMENTUM, relu)
+    nbt = _vec(torch.zeros((), dtype=torch.int64, device=gpu), 'nbt')
+    rm, rv = lambda: _vec(rm0.float(), 'running_mean'), lambda: _vec(rv0.float(), 'running_var')
+    with G.window(ops, 'bn_relu_mask'):
+        mask = ops.bn_relu_mask(d['x'])          # 0xFF bytes between flanks: the forward must write every one of them
+    (y, mean_k, invstd_k), _ = _labels(ops, lambda: ops.bn_train_fwd(d['x'], rd, d['gamma'], d['beta'], rm(), rv(), nbt, R.EPS, R.MOMENTUM, relu, relu_mask=mask))
+    (y2, mean2, invstd2), _ = _labels(ops, lambda: ops.bn_train_fwd(d['x'], rd, d['gamma'], d['beta'], rm(), rv(), nbt, R.EPS, R.MOMENTUM, relu))
+    _whole('y / mean / invstd', y, mean_k, invstd_k, y2, mean2, invstd2)
+    if dt == 'f32':
+        _whole('mask', mask)         # (an fp32 mask byte holds four bits: 0xFF is not one; a bf16 byte of eight set bits is)
     assert torch.equal(y, y2) and torch.equal(mean_k, mean2) and torch.equal(invstd_k, invstd2)        # [equal]
     # the statistics the kernel saved (held to float64 by test_forward_statistics) define the reference of the apply pass
     # [bound] sc = g * invstd and sh = b - mean * sc are rounded, then x * sc + sh (+ res): at most five roundings touch each
@@ -231,7 +270,9 @@ def test_forward_apply_eval_and_mask_bits(gpu, shape, res, relu):
     assert torch.equal(bits[sure], (pre > 0)[sure])               # [bound] the bit is y > 0 wherever the bound leaves no doubt
     # eval forward: running_mean integers, running_var powers of four
     rmean, rvar = c['mean'], 1.0 / (c['invstd'] * c['invstd'])
-    ye = ops.bn_eval_fwd(d['x'], rd, d['gamma'], d['beta'], rmean.float(), rvar.float(), R.EPS, relu)
+    rmean_d, rvar_d = _vec(rmean.float(), 'running_mean'), _vec(rvar.float(), 'running_var')
+    ye, _ = _labels(ops, lambda: ops.bn_eval_fwd(d['x'], rd, d['gamma'], d['beta'], rmean_d, rvar_d, R.EPS, relu))
+    _whole('eval y', ye)
     sce = c['gamma'] / torch.sqrt(rvar + R.EPS)
     pree = (c['x'] - rmean) * sce + c['beta'] + (c['res'] if res else 0)
     Be = 8 * R.U32 * ((c['x'] * sce).abs() + (rmean * sce).abs() + c['beta'].abs() + (c['res'].abs() if res else 0))
@@ -252,12 +293,14 @@ def test_forward_from_crafted_partials(gpu, case):
     p = R.sliced_stats_partials(ns, C, device=gpu)
     n, mean, m2 = R.combine_fwd_partials(p)
     x = _put(R.stats_case(16, C, device=gpu)['x'], dt)              # tiny: only the statistics are under test
-    gamma, beta = torch.ones(C, device=gpu), torch.zeros(C, device=gpu)
+    gamma, beta = _vec(torch.ones(C, device=gpu), 'gamma'), _vec(torch.zeros(C, device=gpu), 'beta')
     rm0, rv0 = _running_start(C, gpu)
+    pd = _vec(p.float(), 'partials')
     for updates in (1, 3):
-        rm, rv, nbt = rm0.float(), rv0.float(), torch.full((), 7, dtype=torch.int64, device=gpu)
-        y, mean_k, invstd_k = ops.bn_train_fwd(x, None, gamma, beta, rm, rv, nbt, R.EPS, R.MOMENTUM, False, stat_updates=updates,
-                                               partial=(p.float().contiguous(), ns))
+        rm, rv, nbt = _vec(rm0.float(), 'running_mean'), _vec(rv0.float(), 'running_var'), _vec(torch.full((), 7, dtype=torch.int64, device=gpu), 'nbt')
+        (y, mean_k, invstd_k), _ = _labels(ops, lambda: ops.bn_train_fwd(x, None, gamma, beta, rm, rv, nbt, R.EPS, R.MOMENTUM, False, stat_updates=updates,
+                                                                         partial=(pd, ns)))
+        _whole('y / mean / invstd', y, mean_k, invstd_k)
         rmr, rvr = R.running(mean, m2, float(n[0]), rm0, rv0, R.MOMENTUM, updates)
         assert torch.allclose(mean_k.double(), mean, **MEAN_TOL), float((mean_k.double() - mean).abs().max())        # [stats]
         assert torch.allclose(invstd_k.double(), 1.0 / torch.sqrt(m2 / n + R.EPS), **VAR_TOL)                          # [stats]
@@ -272,12 +315,12 @@ def test_colsum_bit_for_bit(gpu, shape):
     ops = _ops()
     c = _case(gpu, rows, C)
     d = _dev(c, dt)
-    out = torch.full((C,), 777.0, device=gpu)
-    ops.colsum(d['dy'], out, False)
+    out = _vec(torch.full((C,), 777.0, device=gpu), 'out')
+    _labels(ops, lambda: ops.colsum(d['dy'], out, False))
     assert torch.equal(out.double(), R.colsum(c['dy']))                 # [equal]
     prior = R.int_prior(C, 'colsum', gpu)
-    out = prior.float()
-    ops.colsum(d['dy'], out, True)
+    out = _vec(prior.float(), 'out')
+    _labels(ops, lambda: ops.colsum(d['dy'], out, True))
     assert torch.equal(out.double(), R.colsum(c['dy'], prior))          # [equal]
 
 
@@ -290,16 +333,16 @@ def test_apply_relu_mask_bit_for_bit(gpu, shape):
     c = _case(gpu, rows, C)
     per = R.PER[dt]
     b = R.mask_bytes(rows * C // per, 'apply').to(gpu)
-    g = _put(c['dy'], dt)
-    out = ops.apply_relu_mask(g, b)
+    g, bd = _put(c['dy'], dt), _vec(b, 'mask')
+    out, _ = _labels(ops, lambda: ops.apply_relu_mask(g, bd))
     assert torch.equal(R.rows_of(out).double(), R.apply_relu_mask(c['dy'], b, per))          # [equal]
 
 
 # ---------------------------------------------------------------- h. fp8 side outputs (bf16 only)
 def _q8(d, gpu):
     N, C, H, W = d['x'].shape
-    q = torch.zeros((N, H, W, C), dtype=torch.uint8, device=gpu).permute(0, 3, 1, 2)
-    st = torch.tensor([1.0, 1.0, 0.0, 0.0], device=gpu)           # {scale, descale, amax bits, pad}: scale 1, y * scale is exact
+    q = G.empty((N, H, W, C), torch.uint8, gpu, 'fp8 copy').permute(0, 3, 1, 2)         # nothing but the guard fill (an e4m3 / e5m2 NaN)
+    st = _vec(torch.tensor([1.0, 1.0, 0.0, 0.0], device=gpu), 'fp8 state')           # {scale, descale, amax bits, pad}: scale 1, y * scale is exact
     return q, st
 
 
@@ -315,11 +358,13 @@ def test_fp8_side_output_of_the_forward(gpu, rows, C):
     c = _case(gpu, rows, C, mirror=True)
     d = _dev(c, 'bf16', residual=False)
     rm0, rv0 = _running_start(C, gpu)
-    nbt = torch.zeros((), dtype=torch.int64, device=gpu)
+    nbt = _vec(torch.zeros((), dtype=torch.int64, device=gpu), 'nbt')
     for relu in (False, True):
         q, st = _q8(d, gpu)
-        y, _, _ = ops.bn_train_fwd(d['x'], None, d['gamma'], d['beta'], rm0.float(), rv0.float(), nbt, R.EPS, R.MOMENTUM, relu, q8=(q, st))
-        y0, _, _ = ops.bn_train_fwd(d['x'], None, d['gamma'], d['beta'], rm0.float(), rv0.float(), nbt, R.EPS, R.MOMENTUM, relu)
+        rm, rv = lambda: _vec(rm0.float(), 'running_mean'), lambda: _vec(rv0.float(), 'running_var')
+        (y, _, _), _ = _labels(ops, lambda: ops.bn_train_fwd(d['x'], None, d['gamma'], d['beta'], rm(), rv(), nbt, R.EPS, R.MOMENTUM, relu, q8=(q, st)))
+        (y0, _, _), _ = _labels(ops, lambda: ops.bn_train_fwd(d['x'], None, d['gamma'], d['beta'], rm(), rv(), nbt, R.EPS, R.MOMENTUM, relu))
+        _whole('y / fp8 copy', y, y0, q)
         assert torch.equal(y, y0)                                      # [equal]
         assert float(y.float().abs().max()) < 448
         assert torch.equal(q.view(torch.uint8), y.float().to(torch.float8_e4m3fn).view(torch.uint8))      # [equal]
@@ -339,6 +384,7 @@ def test_fp8_side_output_of_the_backward(gpu, rows, C, relu, dres):
     q, st = _q8(d, gpu)
     dx, dr, dg, db, labels = _backward(ops, c, 'bf16', 'resident', relu, dres, False, q8=(q, st), residual=False)
     _assert_form(labels, 'three')
+    _whole('fp8 copy', q)
     _assert_sums(c, r, dr, dg, db, dres, False, 'bf16')
     assert float(r['s1'].abs().max()) == 0 and float(r['s2'].abs().max()) == 0
     assert torch.equal(R.rows_of(dx).double(), r['dx'])               # [equal] (exact in bf16 without rounding)

@@ -9,6 +9,16 @@ testing something else.  The tables are read from choose_conv / choose_pgemm / c
 this commit, and test_conv_dispatch_cpu.py holds them against those functions without a GPU;
 profiles/conv_exact_labels.txt holds the full labels of one run for diffing.
 
+Every call runs in hostile memory (tests/guarded.py): the operands a test builds -- feature maps, packed weights, biases, masks,
+accumulate bases, weight gradients, the items of a grouped call -- are copies inside 0xFF-filled guard buffers, and while a wrapper
+runs, every tensor it allocates (outputs, statistics partials, fp8 / MX copies and their scale arrays) and the workspace it asks
+for -- of exactly the size the library's own *_workspace function returned -- are such buffers too.  0xFF.. is a NaN in every
+element type here, so a store outside a result changes a flank (checked after every call), a launch or a split that writes
+nothing leaves NaN where the comparison looks (an output must have no unwritten element before it is compared: with plain
+torch.empty the block of the previous, identical call would come back with the right bits in it), and a read past an operand
+through a plain pointer poisons the sum it enters.  test_conv_dispatch_cpu.py holds, from the plans, that the cases include ragged
+last splits, single slabs with accumulate, grouped launches with several slab-reduced items and statistics buffers with slack.
+
 Builds behind switches that are read once per process (MI355_DMA, MI355_KW3, MI355_PHASES, MI355_T256D_*, MI355_FP8_TILE)
 run in child processes, one per entry of GROUPS, strictly one after another, each with its own timeout and no retry.
 
@@ -34,6 +44,7 @@ import pytest
 import torch
 
 import conv_exact_ref as R
+import guarded as G
 from mx_ref import mx_dequantize
 
 pytestmark = pytest.mark.gpu
@@ -63,12 +74,45 @@ def launch_log(gpu):
     ops.prof_enable(0)
 
 
+@pytest.fixture(autouse=True)
+def guards():
+    """Every test starts and ends without guard buffers of another test (tests/guarded.py)."""
+    G.reset()
+    yield
+    G.reset()
+
+
 def _run(ops, fn):
-    """fn() with the labels of the conv-family launches it made."""
+    """fn() with the labels of the conv-family launches it made.  The call runs inside a guard window (tests/guarded.py): every
+    tensor the wrapper allocates and the workspace it asks for are 0xFF-filled buffers between 0xFF flanks, and after the launch
+    no flank byte -- theirs, or of any operand a test placed -- may have changed."""
     ops.prof_reset()
-    out = fn()
+    with G.window(ops, 'conv call'):
+        out = fn()
     torch.cuda.synchronize()
-    return out, [l['label'] for l in ops.prof_launches() if l['family'] == 0]
+    labels = [l['label'] for l in ops.prof_launches() if l['family'] == 0]
+    G.check(' | '.join(labels))
+    return out, labels
+
+
+def _guarded(ops, what, fn):
+    """fn() in a guard window of its own: operand producers (quantisers, weight packs) and the BatchNorm launches of this module."""
+    with G.window(ops, what):
+        out = fn()
+    torch.cuda.synchronize()
+    G.check(what)
+    return out
+
+
+def _pitch(dtype, *channels):
+    """The widest row of the case, for the flanks of its flat operands (packed weights, vectors, workspace)."""
+    G.row_pitch(max(channels) * (2 if dtype == torch.bfloat16 else 4))
+
+
+def _whole(what, t):
+    """The launch wrote all of `t`: no element is still the guard fill (a NaN, which no reference of this module holds)."""
+    assert t.data_ptr() % G.BOUNDARY == G.START, '%s: not in a guard buffer' % what          # (the allocator's own blocks start on the boundary)
+    assert G.unwritten(t) == 0, '%s: %d bytes of the output were never written' % (what, G.unwritten(t))
 
 
 def _build(label):
@@ -93,17 +137,32 @@ def _check_builds(what, labels, expect):
 
 
 def _same(what, got, ref, dtype):
+    _whole(what, got)
     assert R.same_bits(got, ref, dtype), '%s: %s' % (what, R.first_mismatch(got, ref, dtype))
 
 
 def _dev(t, dtype, gpu):
-    return _ops().to_nhwc(t.to(gpu), dtype)
+    return G.place(_ops().to_nhwc(t.to(gpu), dtype), 'feature map')
+
+
+def _vec(t, gpu, what='vector'):
+    """A bias, a mask, a scale, a per-channel vector or a gradient buffer: onto the device, into a guard buffer."""
+    return G.place(t.to(gpu).contiguous(), what)
+
+
+def _packs(ops, *args):
+    """ops.pack_weights(*args) with both packs in guard buffers."""
+    return tuple(t if t is None else G.place(t, 'packed weights') for t in _guarded(ops, 'pack_weights', lambda: ops.pack_weights(*args)))
 
 
 def _check_stats(what, part, C, ref, rows):
     """(n, mean, M2) slices of a statistics epilogue, folded in float64, against float64 statistics of the exact output: n exact,
     mean and 1 / sqrt(var + eps) within the tolerances of test_conv_epilogue_bn_statistics (1e-5 / 2e-5 relative, 1e-6 absolute)."""
     assert part is not None and part[1] >= 1, what
+    # the slices the launch reports are written, and nothing behind them is (the buffer holds more than any launch fills)
+    used = part[1] * C * 3
+    assert used < part[0].numel(), what
+    assert G.unwritten(part[0][:used]) == 0 and G.unwritten(part[0][used:]) == (part[0].numel() - used) * 4, what
     tot, mean, m2 = R.fold_stats(part[0], part[1], C)
     n, rmean, rm2 = R.bn_stats(ref)
     assert n == rows and torch.equal(tot, torch.full((C,), float(rows), dtype=torch.float64)), what
@@ -128,9 +187,10 @@ if _CONV:
         e_fwd, e_dgrad, e_acc, e_bnb, e_wgrad = EXPECT[name][0 if dt == 'bf16' else 1]
         N, Ci, H, W, Co, k, s, p = c.shape
         desc = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype, out_hw=c.out_hw)
+        _pitch(dtype, Ci, Co)
         xd, dyd = _dev(c.x, dtype, gpu), _dev(c.dy, dtype, gpu)
-        wf, wt = ops.pack_weights(c.w.permute(0, 2, 3, 1).contiguous().to(gpu), Co, k * k, Ci, Ci, dtype)
-        bias, res = c.bias.to(gpu), _dev(c.res, dtype, gpu)
+        wf, wt = _packs(ops, _vec(c.w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, k * k, Ci, Ci, dtype)
+        bias, res = _vec(c.bias, gpu, 'bias'), _dev(c.res, dtype, gpu)
         tag = '%s/%s ' % (name, dt)
 
         for what, fn, ref in (('fwd', lambda: ops.conv_fwd(desc, xd, wf), c.y),
@@ -146,13 +206,13 @@ if _CONV:
         _check_stats(tag + 'fwd+stats', part, Co, c.y_b, N * c.Ho * c.Wo)
 
         if c.has_dgrad:
-            sc = torch.tensor(0.25, device=gpu)
-            base, mask, bias_i = _dev(c.base, dtype, gpu), c.mask[per].to(gpu), c.bias_i.to(gpu)
+            sc = _vec(torch.full((1,), 0.25), gpu, 'scale')
+            base, mask, bias_i = _dev(c.base, dtype, gpu), _vec(c.mask[per], gpu, 'mask'), _vec(c.bias_i, gpu, 'bias')
             for what, fn, ref, exp in (
                     ('dgrad', lambda: ops.conv_dgrad(desc, dyd, wt), c.dx, e_dgrad),
                     ('dgrad*scale', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc), c.dx_q, e_dgrad),
-                    ('dgrad*scale+acc', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc, out=base.clone(), accumulate=True), c.dx_acc, e_acc),
-                    ('dgrad+macc', lambda: ops.conv_dgrad_masked_acc(desc, dyd, wt, base.clone(), mask), c.dx_macc[per], e_acc),
+                    ('dgrad*scale+acc', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc, out=G.place(base, 'base'), accumulate=True), c.dx_acc, e_acc),
+                    ('dgrad+macc', lambda: ops.conv_dgrad_masked_acc(desc, dyd, wt, G.place(base, 'base'), mask), c.dx_macc[per], e_acc),
                     ('deconv+bias', lambda: ops.deconv_fwd_act(desc, dyd, wt, bias_i), c.dx_b, e_dgrad),
                     ('deconv+bias+relu', lambda: ops.deconv_fwd_act(desc, dyd, wt, bias_i, relu=True), c.dx_br, e_dgrad)):
                 dx, labels = _run(ops, fn)
@@ -168,9 +228,10 @@ if _CONV:
                 _check_stats(tag + 'dgrad+stats', part, Ci, c.dx, N * H * W)
             # the input gradient as the dy of a BatchNorm: exact dx, that BatchNorm's reduction partials against its own passes
             xb = _dev(c.base, dtype, gpu)
-            gamma, beta = (1 + c.bias_i / 64).to(gpu), (c.bias_i / 32).to(gpu)
-            rm, rv, nbt = torch.zeros(Ci, device=gpu), torch.ones(Ci, device=gpu), torch.zeros((), dtype=torch.int64, device=gpu)
-            _, mean, invstd = ops.bn_train_fwd(xb, None, gamma, beta, rm, rv, nbt, 1e-5, 0.1, False)
+            gamma, beta = _vec(1 + c.bias_i / 64, gpu, 'gamma'), _vec(c.bias_i / 32, gpu, 'beta')
+            rm, rv, nbt = _vec(torch.zeros(Ci), gpu, 'running_mean'), _vec(torch.ones(Ci), gpu, 'running_var'), _vec(torch.zeros((), dtype=torch.int64), gpu, 'num_batches_tracked')
+            _, mean, invstd = _guarded(ops, 'bn_train_fwd', lambda: ops.bn_train_fwd(xb, None, gamma, beta, rm, rv, nbt, 1e-5, 0.1, False))
+            _whole('mean', mean), _whole('invstd', invstd)
             bn = (xb, None, gamma, beta, mean, invstd, False)
             (dx, part), labels = _run(ops, lambda: ops.conv_dgrad_bnbwd(desc, dyd, wt, bn))
             epi = _check_builds(tag + 'dgrad+bnb', labels, e_bnb)
@@ -179,22 +240,26 @@ if _CONV:
             if s == 1:
                 assert epi == 2
             if part is not None:
+                used = part[1] * Ci * 2          # [slice][C][2] sums: the reported slices written, nothing behind them
+                assert used < part[0].numel()
+                assert G.unwritten(part[0][:used]) == 0 and G.unwritten(part[0][used:]) == (part[0].numel() - used) * 4
                 sums = []
                 for pp in (None, part):
-                    dg, db = torch.zeros(Ci, device=gpu), torch.zeros(Ci, device=gpu)
-                    ops.bn_bwd(dx, xb, None, gamma, mean, invstd, dg, db, False, False, False, beta=beta, partial=pp)
+                    dg, db = G.empty((Ci,), torch.float32, gpu, 'dgamma'), G.empty((Ci,), torch.float32, gpu, 'dbeta')
+                    _guarded(ops, 'bn_bwd', lambda: ops.bn_bwd(dx, xb, None, gamma, mean, invstd, dg, db, False, False, False, beta=beta, partial=pp))
+                    _whole('dgamma', dg), _whole('dbeta', db)
                     sums.append((dg, db))
                 (dga, dba), (dgb, dbb) = sums
                 tol = 2e-5 * (float(dga.abs().max()) + float(dba.abs().max()) + 1.0)     # as test_gemm_epilogue_bn_backward_reduction
                 assert float((dga - dgb).abs().max()) <= tol and float((dba - dbb).abs().max()) <= tol
 
         kind, slabs = e_wgrad.split(' ')
-        dw = torch.full((Co, k, k, Ci), 7.0, dtype=torch.float32, device=gpu)
+        dw = G.empty((Co, k, k, Ci), torch.float32, gpu, 'dw')          # nothing but the guard fill: the launch must overwrite it
         _, labels = _run(ops, lambda: ops.conv_wgrad(desc, xd, dyd, dw, accumulate=False))
         print('\nLABEL %swgrad %s' % (tag, ' | '.join(labels)))
         assert len(labels) == 1 and labels[0].split(' ')[0] == kind and labels[0].split(' ')[-1] == slabs, (labels, e_wgrad)
         _same(tag + 'wgrad', dw, c.dw, torch.float32)
-        dw = c.dw0.to(gpu).contiguous()
+        dw = _vec(c.dw0, gpu, 'dw')
         _, labels = _run(ops, lambda: ops.conv_wgrad(desc, xd, dyd, dw, accumulate=True))
         assert len(labels) == 1 and labels[0].split(' ')[0] == kind and labels[0].split(' ')[-1] == slabs, (labels, e_wgrad)
         _same(tag + 'wgrad+acc', dw, c.dw_acc, torch.float32)
@@ -213,12 +278,13 @@ if _CAT:
         expect = CAT_EXPECT[name][0 if dt == 'bf16' else 1]
         N, Ci, H, W, Co, k, s, p = c.shape
         desc = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype)
+        _pitch(dtype, Ci, Co)
         xd = _dev(c.x, dtype, gpu)
-        wf, _ = ops.pack_weights(c.w.permute(0, 2, 3, 1).contiguous().to(gpu), Co, k * k, Ci, Ci, dtype)
-        b1, b2 = c.b1.to(gpu), c.b2.to(gpu)
+        wf, _ = _packs(ops, _vec(c.w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, k * k, Ci, Ci, dtype)
+        b1, b2 = _vec(c.b1, gpu, 'bias'), _vec(c.b2, gpu, 'bias2')
         for n2 in R.CAT_C2[dtype]:          # one 16-byte chunk of second-operand channels, and three
             R.assert_exact_in(dtype, c.y[n2], c.y_b[n2])
-            x2d, w2 = _dev(c.x2[n2], dtype, gpu), c.w2[n2].to(gpu).to(dtype).contiguous()
+            x2d, w2 = _dev(c.x2[n2], dtype, gpu), _vec(c.w2[n2].to(dtype), gpu, 'w2')
             tag = '%s/%s c2=%d ' % (name, dt, n2)
             y, labels = _run(ops, lambda: ops.conv_fwd_cat(desc, xd, wf, None, x2d, w2, None))
             assert _check_builds(tag + 'cat', labels, expect) == 0
@@ -248,7 +314,8 @@ if GROUP in ROUNDING:
         assert set(int(v) for v in ref.unique()) == set(sums)
         assert not torch.equal(R.to_dtype(ref, torch.bfloat16).double(), ref)         # the case does round
         desc = ops.make_desc(N, H, W, 64, Co, 1, 1, 1, 0, torch.bfloat16)
-        wf, _ = ops.pack_weights(w.permute(0, 2, 3, 1).contiguous().to(gpu), Co, 1, 64, 64, torch.bfloat16)
+        _pitch(torch.bfloat16, 64, Co)
+        wf, _ = _packs(ops, _vec(w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, 1, 64, 64, torch.bfloat16)
         xd = _dev(x, torch.bfloat16, gpu)
         prev = lib.mi355_set_pgemm(pg) if pg is not None else None
         try:
@@ -277,8 +344,9 @@ if GROUP == 'default':
         R.assert_exact_in(dtype, *c.values)
         x, w, bias, res, y, y_b, y_brr = c.x, c.w, c.bias, c.res, c.y, c.y_b, c.y_brr
         desc = ops.make_desc(N, H, W, Ci, Co, 1, 1, 1, 0, dtype)
-        wf, wt = ops.pack_weights(w.permute(0, 2, 3, 1).contiguous().to(gpu), Co, 1, Ci, Ci, dtype)
-        xd, resd, biasd = _dev(x, dtype, gpu), _dev(res, dtype, gpu), bias.to(gpu)
+        _pitch(dtype, Ci, Co)
+        wf, wt = _packs(ops, _vec(w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, 1, Ci, Ci, dtype)
+        xd, resd, biasd = _dev(x, dtype, gpu), _dev(res, dtype, gpu), _vec(bias, gpu, 'bias')
         prev = lib.mi355_set_pgemm(2)
         try:
             for what, fn, ref, exp in (('fwd', lambda: ops.conv_fwd(desc, xd, wf), y, e_fwd[0]),
@@ -293,11 +361,11 @@ if GROUP == 'default':
             _check_stats(name + ' fwd+stats', part, Co, y_b, N * H * W)
             if has_dgrad:
                 dy, base, mask, dx, dx_acc, dx_macc = c.dy, c.base, c.mask, c.dx, c.dx_acc, c.dx_macc
-                dyd, based, sc = _dev(dy, dtype, gpu), _dev(base, dtype, gpu), torch.tensor(0.25, device=gpu)
+                dyd, based, sc, maskd = _dev(dy, dtype, gpu), _dev(base, dtype, gpu), _vec(torch.full((1,), 0.25), gpu, 'scale'), _vec(mask, gpu, 'mask')
                 for what, fn, ref, exp in (
                         ('dgrad', lambda: ops.conv_dgrad(desc, dyd, wt), dx, e_dgrad[0]),
-                        ('dgrad*scale+acc', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc, out=based.clone(), accumulate=True), dx_acc, e_dgrad[1]),
-                        ('dgrad+macc', lambda: ops.conv_dgrad_masked_acc(desc, dyd, wt, based.clone(), mask.to(gpu)), dx_macc, e_dgrad[1])):
+                        ('dgrad*scale+acc', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc, out=G.place(based, 'base'), accumulate=True), dx_acc, e_dgrad[1]),
+                        ('dgrad+macc', lambda: ops.conv_dgrad_masked_acc(desc, dyd, wt, G.place(based, 'base'), maskd), dx_macc, e_dgrad[1])):
                     got, labels = _run(ops, fn)
                     assert _check_builds('%s %s' % (name, what), labels, exp) == 0
                     _same('%s %s' % (name, what), got, ref, dtype)
@@ -315,7 +383,9 @@ if GROUP == 'default':
         N, C, K, H, W = R.HM_CASES[name]
         c = R.build_hm_case(name)
         R.assert_exact_in(torch.float32, c.ref)
-        y, labels = _run(ops, lambda: ops.conv1x1_heatmap(_dev(c.x, dtype, gpu), c.w.view(K, C).to(gpu).to(dtype).contiguous(), c.b.to(gpu), K))
+        _pitch(dtype, C)
+        xd, wd, bd = _dev(c.x, dtype, gpu), _vec(c.w.view(K, C).to(dtype), gpu, 'weights'), _vec(c.b, gpu, 'bias')
+        y, labels = _run(ops, lambda: ops.conv1x1_heatmap(xd, wd, bd, K))
         assert _check_builds('%s/%s' % (name, dt), labels, 'g128x32 hm' if dt == 'bf16' else 'g128x32 f32 hm') == 0
         assert y.is_contiguous()
         _same(name, y, c.ref, torch.float32)
@@ -337,13 +407,14 @@ if GROUP == 'default':
         heads = GROUPED[form]
         cases, refs = R.build_grouped_case(form)
         items = []
+        _pitch(dtype, *[ch for shape, _, _, _ in cases for ch in shape[3:5]])
         for (N, H, W, Ci, Co, k, s, p, acc, share), x, dy, dw0 in cases:
             if share is not None:
                 dw = items[share][3]
             elif acc:
-                dw = dw0.to(gpu).contiguous()
+                dw = _vec(dw0, gpu, 'dw')
             else:
-                dw = torch.full((Co, k, k, Ci), float('nan'), device=gpu)
+                dw = G.empty((Co, k, k, Ci), torch.float32, gpu, 'dw')
             items.append((ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype), _dev(x, dtype, gpu), _dev(dy, dtype, gpu), dw, acc))
         R.assert_exact_in(torch.float32, *[r for r in refs if r is not None])
         _, labels = _run(ops, lambda: ops.conv_wgrad_grouped(items))
@@ -373,14 +444,17 @@ if _FP8:
         e_plain, e_kw3 = FP8_EXPECT[name]
         e_fwd, e_dgrad = e_plain if isinstance(e_plain, tuple) else (e_plain, e_plain)
         desc = ops.make_desc_fp8(N, H, W, Ci, Co, k, k, s, p)
+        _pitch(bf16, Ci, Co)
         xd, dyd, based = _dev(c.x, bf16, gpu), _dev(c.dy, bf16, gpu), _dev(c.base, bf16, gpu)
-        w_conv = c.w.permute(0, 2, 3, 1).contiguous().to(gpu)
-        bias, sc = c.bias.to(gpu), torch.tensor(0.25, device=gpu)
-        sx, sw, sd = ops.fp8_state(gpu), ops.fp8_state(gpu), ops.fp8_state(gpu)
-        x8 = ops.fp8_quantize(xd, sx, ops.E4M3, jit=True)
-        dy8 = ops.fp8_quantize(dyd, sd, ops.E5M2, jit=True)
-        wf8, wt8 = ops.pack_weights_fp8(w_conv, Co, k * k, Ci, sw)
-        torch.cuda.synchronize()
+        w_conv = _vec(c.w.permute(0, 2, 3, 1), gpu, 'master weights')
+        bias, sc = _vec(c.bias, gpu, 'bias'), _vec(torch.full((1,), 0.25), gpu, 'scale')
+        sx, sw, sd = [_vec(ops.fp8_state(gpu), gpu, 'fp8 state') for _ in range(3)]
+        # the fp8 copies are made inside a guard window: the GEMMs below read them with 0xFF on either side
+        x8 = _guarded(ops, 'fp8_quantize x', lambda: ops.fp8_quantize(xd, sx, ops.E4M3, jit=True))
+        dy8 = _guarded(ops, 'fp8_quantize dy', lambda: ops.fp8_quantize(dyd, sd, ops.E5M2, jit=True))
+        wf8, wt8 = _guarded(ops, 'pack_weights_fp8', lambda: ops.pack_weights_fp8(w_conv, Co, k * k, Ci, sw))
+        for what, t in (('x8', x8), ('dy8', dy8), ('wf8', wf8), ('wt8', wt8)):
+            _whole(what, t)
         assert torch.equal((x8.view(torch.float8_e4m3fn).float() * sx[1]).cpu(), c.x)
         assert torch.equal((dy8.view(torch.float8_e5m2).float() * sd[1]).cpu(), c.dy)
         assert torch.equal((wf8.view(torch.float8_e4m3fn).float() * sw[1]).view(Co, k, k, Ci).cpu(), c.w.permute(0, 2, 3, 1))
@@ -408,25 +482,27 @@ if _FP8:
                 assert (epi == 1) == (part is not None) and (epi == 1 or s != 1)
                 if part is not None:
                     _check_stats(tag + 'dgrad8+stats', part, Ci, c.dx, N * H * W)
-                dx, labels = _run(ops, lambda: ops.conv_dgrad_fp8(desc, dy8, sd, wt8, sw, scale_dev=sc, out=based.clone(), accumulate=True))
+                dx, labels = _run(ops, lambda: ops.conv_dgrad_fp8(desc, dy8, sd, wt8, sw, scale_dev=sc, out=G.place(based, 'base'), accumulate=True))
                 assert _check_builds(tag + 'dgrad8*scale+acc', labels, 'f8 ' + ed + ' bf8') == 0
                 _same(tag + 'dgrad8*scale+acc', dx, c.dx_acc, bf16)
         finally:
             lib.mi355_set_fp8_kw3(prev)
-        dw = torch.full((Co, k, k, Ci), float('nan'), device=gpu)
+        dw = G.empty((Co, k, k, Ci), torch.float32, gpu, 'dw')
         _, labels = _run(ops, lambda: ops.conv_wgrad_fp8(desc, x8, sx, dy8, sd, dw, False))
         print('\nLABEL %s wgrad8 %s' % (name, ' | '.join(labels)))
         assert len(labels) == 1 and labels[0].startswith('wgrad8 '), labels
         _same(name + ' wgrad8', dw, c.dw, torch.float32)
-        dw = c.dw0.to(gpu).contiguous()
-        ops.conv_wgrad_fp8(desc, x8, sx, dy8, sd, dw, True)
+        dw = _vec(c.dw0, gpu, 'dw')
+        _run(ops, lambda: ops.conv_wgrad_fp8(desc, x8, sx, dy8, sd, dw, True))
         _same(name + ' wgrad8+acc', dw, c.dw_acc, torch.float32)
 
         # MX: e4m3 elements, one E8M0 scale per 32 contracted channels
-        xq, xs = ops.mx_quantize(xd)
-        dyq, dys = ops.mx_quantize(dyd)
-        wf, sf, wt, st = ops.pack_weights_mx(w_conv, Co, k * k, Ci)
-        torch.cuda.synchronize()
+        # ... and so are the MX copies with their E8M0 scale arrays: a scale load one block off reads 0xFF, the NaN code
+        xq, xs = _guarded(ops, 'mx_quantize x', lambda: ops.mx_quantize(xd))
+        dyq, dys = _guarded(ops, 'mx_quantize dy', lambda: ops.mx_quantize(dyd))
+        wf, sf, wt, st = _guarded(ops, 'pack_weights_mx', lambda: ops.pack_weights_mx(w_conv, Co, k * k, Ci))
+        for what, t in (('xq', xq), ('xs', xs), ('dyq', dyq), ('dys', dys), ('wf', wf), ('sf', sf), ('wt', wt), ('st', st)):
+            _whole(what, t)
         nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().cpu()
         assert torch.equal(mx_dequantize(nhwc(xq), xs.view(N, H, W, Ci // 32).cpu()), c.x.permute(0, 2, 3, 1))
         assert torch.equal(mx_dequantize(nhwc(dyq), dys.view(N, c.Ho, c.Wo, Co // 32).cpu()), c.dy.permute(0, 2, 3, 1))
@@ -448,7 +524,7 @@ if _FP8:
         y, labels = _run(ops, lambda: ops.conv_fwd_mx(desc, xq, xs, wf, sf))
         assert _check_builds(name + ' fwdmx plain', labels, 'mx ' + e_fwd) == 0
         _same(name + ' fwdmx plain', y, c.y, bf16)
-        dx, labels = _run(ops, lambda: ops.conv_dgrad_mx(desc, dyq, dys, wt, st, scale_dev=sc, out=based.clone(), accumulate=True))
+        dx, labels = _run(ops, lambda: ops.conv_dgrad_mx(desc, dyq, dys, wt, st, scale_dev=sc, out=G.place(based, 'base'), accumulate=True))
         assert _check_builds(name + ' dgradmx*scale+acc', labels, 'mx ' + e_dgrad) == 0
         _same(name + ' dgradmx*scale+acc', dx, c.dx_acc, bf16)
 
