@@ -1588,9 +1588,13 @@ class BatchNorm2d(_FastSlots, nn.Module):
                     cctx.bias_grad_zero = True      # (see _bias_grad)
                     tag_dx = bool(getattr(cctx, 'has_bias', False))
             # the identity branch's gradient may be handed on unmasked when its producer is one of ours that knows how to apply
-            # the mask: conv1.forward_skip's alias of the block input, or the downsample BatchNorm
+            # the mask: conv1.forward_skip's alias of the block input, or the downsample BatchNorm.  Any other BatchNorm output
+            # (the block input itself, produced by the previous block's last BatchNorm, when conv1 took no forward_skip) is not
+            # one: its gradient meets conv1's input gradient in an autograd add, which knows nothing of a pending mask
             fn = getattr(residual, 'grad_fn', None) if residual is not None else None
-            lazy_ok = fn is not None and type(fn).__name__ in ('_ConvSkipFnBackward', '_BnFnBackward')
+            kind = type(fn).__name__ if fn is not None else ''
+            lazy_ok = kind == '_ConvSkipFnBackward' or (kind == '_BnFnBackward' and not getattr(fn, 'relu', True) and
+                                                       getattr(fn, 'mask', 0) is None)
             y = _BnFn.apply(x, self.weight, self.bias, residual, self, bool(relu), partial, lazy_ok, tag_dx)
             y._mi_bn_src, self._last_src = self._last_src, None     # lets the consumer conv's dgrad reduce dy for this BN
             q8, self._last_q8 = self._last_q8, None
