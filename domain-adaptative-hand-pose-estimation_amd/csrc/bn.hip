@@ -225,10 +225,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
     if (res) { float w[CH]; Chunk<T>::load(res + off, w);
 #pragma unroll
       for (int e = 0; e < CH; ++e) v[e] += w[e]; }
-    if (mask) {           // one bit per element: y > 0, what the backward's ReLU mask needs instead of re-reading y
+    if (mask) {           // one bit per element: !(y <= 0), what the backward's ReLU mask needs instead of re-reading y
       unsigned m = 0;
 #pragma unroll
-      for (int e = 0; e < CH; ++e) m |= (v[e] > 0.f ? 1u : 0u) << e;
+      for (int e = 0; e < CH; ++e) m |= (v[e] <= 0.f ? 0u : 1u) << e;      // !(v <= 0): a NaN output keeps its gradient, as ATen's threshold_backward
       mask[(size_t)r * cpr + chunk] = (unsigned char)m;
     }
     if (relu) {
@@ -282,14 +282,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
   auto fold = [&](float (&g)[CH], const float (&v)[CH], const float (&o)[CH], unsigned mb) {
     if (relu == 1) {
 #pragma unroll
-      for (int e = 0; e < CH; ++e) g[e] = o[e] > 0.f ? g[e] : 0.f; }
+      for (int e = 0; e < CH; ++e) g[e] = o[e] <= 0.f ? 0.f : g[e]; }
     else if (relu == 3) {
 #pragma unroll
       for (int e = 0; e < CH; ++e) g[e] = ((mb >> e) & 1u) ? g[e] : 0.f; }
     if (XHAT) {
       if (relu == 2) {
 #pragma unroll
-        for (int e = 0; e < CH; ++e) g[e] = (v[e] * sc[e] + sft[e]) > 0.f ? g[e] : 0.f; }
+        for (int e = 0; e < CH; ++e) g[e] = (v[e] * sc[e] + sft[e]) <= 0.f ? 0.f : g[e]; }
 #pragma unroll
       for (int e = 0; e < CH; ++e) { s1[e] += g[e]; s2[e] += g[e] * ((v[e] - mu[e]) * is[e]); }
     } else {
@@ -390,13 +390,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
   auto finish = [&](size_t off, float (&g)[CH], float (&v)[CH], const float (&o)[CH], unsigned mb) {
     if (relu == 1) {
 #pragma unroll
-      for (int e = 0; e < CH; ++e) g[e] = o[e] > 0.f ? g[e] : 0.f; }
+      for (int e = 0; e < CH; ++e) g[e] = o[e] <= 0.f ? 0.f : g[e]; }
     else if (relu == 3) {
 #pragma unroll
       for (int e = 0; e < CH; ++e) g[e] = ((mb >> e) & 1u) ? g[e] : 0.f; }
     else if (relu == 2) {
 #pragma unroll
-      for (int e = 0; e < CH; ++e) g[e] = (v[e] * k0[e] + sh[e]) > 0.f ? g[e] : 0.f; }
+      for (int e = 0; e < CH; ++e) g[e] = (v[e] * k0[e] + sh[e]) <= 0.f ? 0.f : g[e]; }
     if (dres) Chunk<T>::store(dres + off, g);
 #pragma unroll
     for (int e = 0; e < CH; ++e) v[e] = k0[e] * (g[e] - k1[e] - (v[e] - mu[e]) * is[e] * k2[e]);
@@ -532,7 +532,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_resident_kernel(BnResArgs p) {
     float v[CH], gq[CH]; Chunk<T>::unpack(qxv, v); Chunk<T>::unpack(qdv, gq);
 #pragma unroll
     for (int e = 0; e < CH; ++e) {
-      if (RELU == 2) gq[e] = (v[e] * sc[e] + sft[e]) > 0.f ? gq[e] : 0.f;
+      if (RELU == 2) gq[e] = (v[e] * sc[e] + sft[e]) <= 0.f ? 0.f : gq[e];
       if (RELU == 3) gq[e] = ((mb >> e) & 1u) ? gq[e] : 0.f;
       s1[e] += gq[e]; s2[e] += gq[e] * ((v[e] - mu[e]) * is[e]);
     }
@@ -661,7 +661,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_resident_kernel(BnResArgs p) {
     float v[CH], gq[CH]; Chunk<T>::unpack(qxv, v); Chunk<T>::unpack(qdv, gq);
 #pragma unroll
     for (int e = 0; e < CH; ++e) {
-      if (RELU == 2) gq[e] = (v[e] * sc[e] + sft[e]) > 0.f ? gq[e] : 0.f;
+      if (RELU == 2) gq[e] = (v[e] * sc[e] + sft[e]) <= 0.f ? 0.f : gq[e];
       if (RELU == 3) gq[e] = ((mb >> e) & 1u) ? gq[e] : 0.f;
     }
     if (DR) Chunk<T>::store(DR + off, gq);

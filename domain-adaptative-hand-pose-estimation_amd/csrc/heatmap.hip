@@ -281,6 +281,18 @@ __global__ __launch_bounds__(256) void scale_feature_kernel(const T* __restrict_
   }
 }
 
+// A non-finite `extra` goes through the ground-false map as it does through the reference's torch.clip and torch.max: the clip
+// and the running maximum are selects, which keep a NaN where fminf / fmaxf return the other operand.  +-inf clips to 1 / 0; a
+// NaN stays in its pixel and, under normalise == 1, makes the map's maximum and with it the whole map NaN (normalise == 2 leaves
+// such a map unscaled, as it leaves one whose maximum is not positive).
+__device__ __forceinline__ float clip01_nan(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
+__device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }      // (m stays NaN once it is)
+template <int NW> __device__ inline float block_max_nan(float v, float* red) {
+  const int any_nan = __syncthreads_or(v != v);
+  const float m = block_max<NW>(v, red);
+  return any_nan ? NAN : m;
+}
+
 // Pseudo labels (see mi355pose.h).  One block per (b,k) map.
 __global__ __launch_bounds__(256) void pseudo_label_kernel(const float* __restrict__ xy, const float* __restrict__ patch, int radius, int div,
                                                             int S, int kind, const float* __restrict__ extra, int normalise,
@@ -314,13 +326,13 @@ __global__ __launch_bounds__(256) void pseudo_label_kernel(const float* __restri
         if (kind == 0) { for (int j = 0; j < K; ++j) if (j != k) s += gauss(j, px, py); f = fminf(fmaxf(s, 0.f), 1.f); }
         else { for (int j = 0; j < K; ++j) s += gauss(j, px, py); f = fminf(fmaxf(fminf(fmaxf(s, 0.f), 1.f) - g * 10.f, 0.f), 1.f); }
       }
-      if (extra) f = fminf(fmaxf(f + extra[base + i] - g * 100.f, 0.f), 1.f);
+      if (extra) f = clip01_nan(f + extra[base + i] - g * 100.f);
       gf[base + i] = f;
-      mx = fmaxf(mx, f);     // fmaxf drops NaN like torch.max? torch.max propagates NaN; extra is finite in practice
+      mx = max_nan(mx, f);
     }
   }
   if (gf && normalise) {
-    mx = block_max<4>(mx, red);
+    mx = block_max_nan<4>(mx, red);
     __syncthreads();
     if (normalise == 2 && !(mx > 0.f)) return;          // guarded mode: an all-zero map stays zero (block-uniform)
     for (int i = threadIdx.x; i < S * S; i += 256) gf[base + i] = gf[base + i] / mx;   // 0/0 -> NaN as the reference
@@ -372,8 +384,8 @@ __global__ __launch_bounds__(256) void pseudo_label_reg_kernel(const float* __re
           if (kind == 0) { for (int q = 0; q < K; ++q) if (q != k) s += gauss(q, px, py); fv = fminf(fmaxf(s, 0.f), 1.f); }
           else { for (int q = 0; q < K; ++q) s += gauss(q, px, py); fv = fminf(fmaxf(fminf(fmaxf(s, 0.f), 1.f) - g * 10.f, 0.f), 1.f); }
         }
-        if (extra) fv = fminf(fmaxf(fv + exv[e] - g * 100.f, 0.f), 1.f);
-        mx = fmaxf(mx, fv);
+        if (extra) fv = clip01_nan(fv + exv[e] - g * 100.f);
+        mx = max_nan(mx, fv);
       }
       f[4 * j + e] = fv;
     }
@@ -382,7 +394,7 @@ __global__ __launch_bounds__(256) void pseudo_label_reg_kernel(const float* __re
   if (!gf) return;
   bool divide = false;
   if (normalise) {
-    mx = block_max<4>(mx, red);
+    mx = block_max_nan<4>(mx, red);
     divide = !(normalise == 2 && !(mx > 0.f));               // guarded mode: an all-zero map stays zero (block-uniform)
   }
 #pragma unroll

@@ -557,10 +557,10 @@ __global__ __launch_bounds__(64 * WGM * WGN * KG, (KW3 && BM == 256) ? 2 : 1) vo
       for (int e = 0; e < CH; ++e) gq[e] = (float)(T)v[e];
       if (p.bnb_relu == 1) { float yv[CH]; Chunk<T>::unpack(qy[k], yv);
 #pragma unroll
-        for (int e = 0; e < CH; ++e) gq[e] = yv[e] > 0.f ? gq[e] : 0.f; }
+        for (int e = 0; e < CH; ++e) gq[e] = yv[e] <= 0.f ? 0.f : gq[e]; }
       else if (p.bnb_relu == 2) {
 #pragma unroll
-        for (int e = 0; e < CH; ++e) gq[e] = (xv[e] * bsc[e] + bsh[e]) > 0.f ? gq[e] : 0.f; }
+        for (int e = 0; e < CH; ++e) gq[e] = (xv[e] * bsc[e] + bsh[e]) <= 0.f ? 0.f : gq[e]; }
 #pragma unroll
       for (int e = 0; e < CH; ++e) { smean[e] += gq[e]; sm2[e] += gq[e] * ((xv[e] - bmu[e]) * bis[e]); }
     }

@@ -296,7 +296,7 @@ def stem_unpack(gs, prior=None):
 
 
 # ================================================================ C. pw21
-HW_GEOM = {1: (1, 1), 63: (7, 9), 64: (8, 8), 65: (5, 13), 100: (10, 10), 192: (12, 16), 255: (15, 17), 256: (16, 16),
+HW_GEOM = {1: (1, 1), 63: (7, 9), 64: (8, 8), 65: (5, 13), 100: (10, 10), 120: (10, 12), 192: (12, 16), 255: (15, 17), 256: (16, 16),
            257: (1, 257), 4096: (64, 64)}
 PW_K = [1, 21, 32]
 PW_HW = [1, 63, 64, 65, 100]

@@ -402,3 +402,86 @@ def test_heads_against_float64(rt, gpu, switch):
             worst = max(worst, _anchor(bad, tag, _collect(mod, [y.detach() for y in ys], [f.grad]), out64, out32))
     print('heads %s: worst max|err| / max|ref| %.3g' % (switch, worst))
     assert not bad, '\n'.join(bad)
+
+
+# ---------------------------------------------------------------- NaN and Inf through the glue (tests/nonfinite_ref.py)
+NONFINITE_COMPOSITES = ['basic-id', 'bottleneck-down1', 'stem']
+
+
+def _nonfinite_step(mod, what, dt, x32, dy_of, gpu):
+    """One forward + backward of the module under test and of its float64 torch twin on the same operands.  dy_of(y64) -> the
+    float32 output gradient on the CPU, chosen after the float64 forward.  Gradient slots start from a finite sentinel: a
+    skipped write would read as finite.  -> (got, out64): the compared tensors by name."""
+    from mi355.nn import mark_grads_fresh
+    T = R.T64(mod, torch.float64)
+    T.params()
+    x64 = x32.double().requires_grad_(what != 'stem')
+    y64 = _t64_fwd(mod, what)(T, x64)
+    dy32 = dy_of(y64.detach())
+    y64.backward(dy32.double())
+    out64 = {'y': y64.detach()}
+    if what != 'stem':
+        out64['dx'] = x64.grad.detach()
+    for k, p in T.P.items():
+        out64['grad ' + k] = p.grad.detach()
+    if what == 'stem':
+        x = x32.to(gpu)
+    else:
+        x = x32.to(gpu).to(DT[dt]).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    ps = [p for p in mod.parameters() if p.grad is not None]
+    for p in ps:
+        p.grad.fill_(12345.0)
+    mark_grads_fresh(ps)
+    y = mod(x)
+    y.backward(dy32.to(gpu).to(DT[dt]).contiguous(memory_format=torch.channels_last))
+    torch.cuda.synchronize()
+    got = {'y': y.detach().float()}
+    if what != 'stem':
+        got['dx'] = x.grad.float()
+    for k, p in mod.named_parameters():
+        got['grad ' + k] = p.grad
+    return got, out64
+
+
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+@pytest.mark.parametrize('name', NONFINITE_COMPOSITES)
+def test_non_finite_values_reach_the_gradients_as_in_float64(rt, gpu, name, dt):
+    """One +Inf in the input, then one NaN in the output gradient (where the last ReLU passes it), through the lazy ReLU mask and
+    the gradient fan-in of mi355.nn: the output and the input gradient have the float64 torch block's class at EVERY element
+    (pointwise rule), every parameter gradient is finite exactly where torch's is (reduced rule: dgamma / dbeta and weight
+    gradients are sums).  With the NaN in one element of dy, torch keeps the last conv's weight gradient finite in every other
+    output channel and the last BatchNorm's dgamma / dbeta finite in every other channel: so must the glue."""
+    import nonfinite_ref as NF
+    rt.set_compute_dtype(dt)
+    N, H, W = COMPOSITES[name][3][-1]
+    bad = []
+    for case in ('+inf in x', 'nan in dy'):
+        mod, cin, what, _ = _build(name, gpu, 43)
+        _, x32 = _inputs(what, dt, 531, N, cin, H, W, gpu)
+        x32 = x32.clone()
+        if case == '+inf in x':
+            x32[N - 1, cin - 1, H // 2, W // 2] = float('inf')
+
+        def dy_of(y64):
+            d = randn(731, *y64.shape).to(DT[dt]).float()
+            if case == 'nan in dy':
+                d.view(-1)[int(y64.reshape(-1).argmax())] = float('nan')          # the largest output: the ReLU (and the pool) pass it
+            return d
+
+        got, out64 = _nonfinite_step(mod, what, dt, x32, dy_of, gpu)
+        _empty_tables(bad, '%s %s %s' % (name, dt, case))
+        finite = {k: float(torch.isfinite(v).double().mean()) for k, v in out64.items()}
+        print('%s %s %s: finite share in float64: %s' % (name, dt, case, '  '.join('%s %.3g' % kv for kv in sorted(finite.items()))))
+        if case == 'nan in dy':          # the case must not be all-NaN: torch keeps most of the last layers' gradients finite
+            assert bool(torch.isfinite(out64['y']).all()) and any(0.5 < f < 1.0 for k, f in finite.items() if k.startswith('grad '))
+        else:
+            assert not bool(torch.isfinite(out64['y']).all())
+        for k, ref in out64.items():
+            g = got[k].detach().cpu()
+            g = g.permute(0, 3, 1, 2) if (k.startswith('grad ') and g.dim() == 4 and g.shape != ref.shape) else g
+            if k in ('y', 'dx'):
+                if not torch.equal(NF.classes(g), NF.classes(ref)):
+                    bad.append('%s %s %s: %d elements of %s differ in class from float64' % (name, dt, case, int((NF.classes(g) != NF.classes(ref)).sum()), k))
+            elif not torch.equal(torch.isfinite(g), torch.isfinite(ref)):
+                bad.append('%s %s %s: %s is finite in %d elements, float64 in %d' % (name, dt, case, k, int(torch.isfinite(g).sum()), int(torch.isfinite(ref).sum())))
+    assert not bad, '\n'.join(bad)

@@ -11,12 +11,16 @@ mi355_bn_workspace bytes -- are guard buffers too: a store outside a result chan
 NaN, and a chunk load past an operand reads NaN.  The float64 references are the functions test_bn_exact_cpu.py holds against
 torch on the CPU, evaluated with torch's float64 on the device so that the 16 M-element cases stay within seconds.  The form
 of the backward that ran (reduce + finalize + apply, or the one-launch LDS-resident kernel) is read from the launch log, so a
-silent fallback cannot make two runs of one path pass as two paths.  Nothing here provokes a give-up of the resident kernel."""
+silent fallback cannot make two runs of one path pass as two paths.  Nothing here provokes a give-up of the resident kernel.
+
+Section i runs the same kernels with a NaN, a +Inf or a -Inf in one operand (tests/nonfinite_ref.py): a special stays inside its
+channel, a masked one is dropped by a select and changes no bit, and the mask of a NaN forward output lets the gradient through."""
 import pytest
 import torch
 
 import bn_exact_ref as R
 import guarded as G
+import nonfinite_ref as NF
 
 pytestmark = pytest.mark.gpu
 
@@ -391,3 +395,272 @@ def test_fp8_side_output_of_the_backward(gpu, rows, C, relu, dres):
     assert torch.equal(q.view(torch.uint8), dx.float().to(torch.float8_e5m2).view(torch.uint8))          # [equal]
     assert _amax_of(st) == float(dx.float().abs().max()) and _amax_of(st) > 0          # [equal]
     assert ops.bn_resident_timeouts() == 0
+
+
+# ---------------------------------------------------------------- i. NaN, +Inf and -Inf operands (tests/nonfinite_ref.py)
+# One operand at a time holds a special; every other value is the exact operand of the cases above.  A channel's reductions are
+# its own: the channel that holds the special follows the reduced rule (non-finite where the float64 reference is), and every
+# OTHER channel has the bits of the run without the special -- which the sections above hold to float64.
+NF_SHAPES = [(3, 64, 'bf16'), (3, 64, 'f32'), (315, 64, 'bf16'), (315, 64, 'f32'), (315, 192, 'bf16')]          # the smallest ragged shapes
+NF_BWD_SHAPES = [(315, 64, 'bf16'), (315, 64, 'f32'), (256, 64, 'bf16'), (256, 64, 'f32')]      # ragged and one row per block; both forms run
+NF_BWD_CASES = [(rows, C, dt, form, relu, dres) for rows, C, dt in NF_BWD_SHAPES for form in ('three', 'resident')
+                for relu in (0, 1, 2, 3) for dres in (False, True) if not (form == 'resident' and relu == 1) and (dres is False or relu in (1, 3))]
+
+
+def _same_bits(a, b):
+    """Two results of one kernel on operands that differ elsewhere: every bit, NaN payloads included."""
+    if a is None or b is None:
+        return a is None and b is None
+    it = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.uint8: torch.uint8}[a.dtype]
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
+
+
+def _other_channels_unchanged(what, got, clean, bad):
+    """Per-channel vectors [C] or feature maps [N][C][H][W]: outside the channels of `bad`, the bits of the clean run."""
+    keep = [ch for ch in range(got.shape[0] if got.dim() == 1 else got.shape[1]) if ch not in bad]
+    a, b = (got[keep], clean[keep]) if got.dim() == 1 else (got[:, keep], clean[:, keep])
+    assert _same_bits(a, b), '%s: a special in channel(s) %s changed another channel' % (what, sorted(bad))
+
+
+def _seeded(mat, positions):
+    return NF.seed_specials(mat, positions)
+
+
+@pytest.mark.parametrize('updates,res,relu', [(1, False, False), (2, True, True), (1, True, False)])
+@pytest.mark.parametrize('shape', NF_SHAPES, ids=R.case_id)
+def test_training_forward_with_an_inf_and_a_nan_channel(gpu, shape, updates, res, relu):
+    rows, C, dt = shape
+    ops = _ops()
+    G.row_pitch(C * 4)
+    s = R.stats_case(rows, C, device=gpu)
+    c_inf, c_nan = C - 1, 0
+    x2 = _seeded(s['x'], [((rows - 1, c_inf), '+inf'), ((rows // 2, c_nan), 'nan')])
+    resid = R.int_prior(C, 'nf res', gpu).view(1, C).expand(rows, C).contiguous() if res else None
+    rm0, rv0 = _running_start(C, gpu)
+    ref = R.train_fwd(x2, s['gamma'], s['beta'], res=resid, relu=relu, rm0=rm0, rv0=rv0, repeats=updates)
+    yref = NF.relu_keep_nan(ref['ypre']) if relu else ref['ypre']
+    assert bool((yref[:, [c_inf, c_nan]] != yref[:, [c_inf, c_nan]]).all()) and 4 * int(torch.isfinite(yref).sum()) >= yref.numel()
+    for k in ('mean', 'invstd', 'rm', 'rv'):
+        assert not bool(torch.isfinite(ref[k][[c_inf, c_nan]]).any()) and int(torch.isfinite(ref[k]).sum()) == C - 2, k
+    gamma, beta = _vec(s['gamma'].float(), 'gamma'), _vec(s['beta'].float(), 'beta')
+    rd = _put(resid, dt) if res else None
+    runs = []
+    for x in (s['x'], x2):
+        rm, rv, nbt = _vec(rm0.float(), 'running_mean'), _vec(rv0.float(), 'running_var'), _vec(torch.full((), 5, dtype=torch.int64, device=gpu), 'nbt')
+        xd = _put(x, dt)
+        (y, mean, invstd), _ = _labels(ops, lambda: ops.bn_train_fwd(xd, rd, gamma, beta, rm, rv, nbt, R.EPS, R.MOMENTUM, relu, stat_updates=updates))
+        _whole('y / mean / invstd', y, mean, invstd)
+        assert int(nbt) == 5 + updates
+        runs.append((y, mean, invstd, rm, rv))
+    (yc, meanc, invc, rmc, rvc), (y, mean, invstd, rm, rv) = runs
+    bad = {c_inf, c_nan}
+    got = R.rows_of(y)
+    assert bool((got[:, [c_inf, c_nan]] != got[:, [c_inf, c_nan]]).all()), 'the two channels come out entirely NaN'
+    _other_channels_unchanged('y', y, yc, bad)
+    for what, a, b, tol in (('mean', mean, meanc, MEAN_TOL), ('invstd', invstd, invc, VAR_TOL), ('running_mean', rm, rmc, MEAN_TOL), ('running_var', rv, rvc, VAR_TOL)):
+        _other_channels_unchanged(what, a, b, bad)
+        r = ref[{'mean': 'mean', 'invstd': 'invstd', 'running_mean': 'rm', 'running_var': 'rv'}[what]]
+        bad_msg = NF.reduced_mismatch(a, r, **tol)           # [stats] on the finite channels, non-finite in the two others
+        assert bad_msg is None, '%s: %s' % (what, bad_msg)
+
+
+@pytest.mark.parametrize('res,relu', R.APPLY_MODES)
+@pytest.mark.parametrize('shape', NF_SHAPES[2:], ids=R.case_id)
+def test_eval_forward_and_apply_with_specials(gpu, shape, res, relu):
+    """Pointwise: the class of every element is the reference's (the ReLU keeps NaN, -Inf becomes 0, a negative gamma turns the
+    infinities round), the finite elements stay within the [bound] of test_forward_apply_eval_and_mask_bits."""
+    rows, C, dt = shape
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    pos = [((rows - 1, C - 1), 'nan'), ((0, 0), '+inf'), ((rows // 2, C // 2), '-inf')]
+    neg = (c['gamma'] < 0).nonzero().view(-1).tolist()          # x: both infinities under a negative gamma, so that each comes out as the other
+    xpos = [((rows - 1, C - 1), 'nan'), ((0, neg[0]), '+inf'), ((rows // 2, neg[-1]), '-inf')]
+    assert len(neg) >= 2
+    rmean, rvar = c['mean'], 1.0 / (c['invstd'] * c['invstd'])
+    rmean_d, rvar_d = _vec(rmean.float(), 'running_mean'), _vec(rvar.float(), 'running_var')
+    gamma, beta = _vec(c['gamma'].float(), 'gamma'), _vec(c['beta'].float(), 'beta')
+    sce = c['gamma'] / torch.sqrt(rvar + R.EPS)
+    for operand in (('x', 'res') if res else ('x',)):
+        x = _seeded(c['x'], xpos) if operand == 'x' else c['x']
+        rs = _seeded(c['res'], pos) if operand == 'res' else c['res']
+        xd, rd = _put(x, dt), (_put(rs, dt) if res else None)
+        pree = (x - rmean) * sce + c['beta'] + (rs if res else 0)
+        want = NF.relu_keep_nan(pree) if relu else pree
+        NF.case_condition(want, ('nan', '+inf') if relu else NF.KINDS, 'eval %s' % operand)
+        ye, _ = _labels(ops, lambda: ops.bn_eval_fwd(xd, rd, gamma, beta, rmean_d, rvar_d, R.EPS, relu))
+        _whole('eval y', ye)
+        got = R.rows_of(ye).double()
+        assert torch.equal(NF.classes(got), NF.classes(R.rne(want, dt))), 'eval forward, special in %s: %d classes differ' % (operand, int((NF.classes(got) != NF.classes(want)).sum()))
+        fin = torch.isfinite(pree)
+        assert not relu or not bool(got[pree == -NF.INF].ne(0).any())          # (-Inf through the ReLU: an exact zero)
+        Be = 8 * R.U32 * ((x * sce).abs() + (rmean * sce).abs() + c['beta'].abs() + (rs.abs() if res else 0))
+        lo, hi = (torch.clamp(pree - Be, min=0.0), torch.clamp(pree + Be, min=0.0)) if relu else (pree - Be, pree + Be)
+        lo, hi = (lo, hi) if dt == 'f32' else (R.rne(lo, dt), R.rne(hi, dt))
+        assert bool((lo[fin] <= got[fin]).all()) and bool((got[fin] <= hi[fin]).all())          # [bound]
+    if res:
+        # the apply pass of the training forward: the statistics are x's and clean, the special rides in on the residual and
+        # stays in its element; every other element keeps the bits of the clean run
+        rm0, rv0 = _running_start(C, gpu)
+        nbt = _vec(torch.zeros((), dtype=torch.int64, device=gpu), 'nbt')
+        xd = _put(c['x'], dt)
+        outs = []
+        for rs in (c['res'], _seeded(c['res'], pos)):
+            rd = _put(rs, dt)
+            (y, mean, invstd), _ = _labels(ops, lambda: ops.bn_train_fwd(xd, rd, gamma, beta, _vec(rm0.float(), 'running_mean'), _vec(rv0.float(), 'running_var'),
+                                                                     nbt, R.EPS, R.MOMENTUM, relu))
+            _whole('y', y)
+            outs.append((R.rows_of(y), mean, invstd))
+        (yc, mc, ic), (y, m, i) = outs
+        assert _same_bits(m, mc) and _same_bits(i, ic)
+        want = torch.zeros(rows, C, dtype=torch.int8, device=gpu)
+        for (r, ch), kd in pos:
+            want[r, ch] = NF.CLASS_OF[kd] if not (relu and kd == '-inf') else NF.FINITE
+        assert torch.equal(NF.classes(y), want)
+        assert float(y[rows // 2, C // 2]) == 0.0 or not relu
+        seeded = torch.zeros(rows, C, dtype=torch.bool, device=gpu)
+        for (r, ch), _ in pos:
+            seeded[r, ch] = True
+        assert _same_bits(y[~seeded], yc[~seeded])
+
+
+@pytest.mark.parametrize('dt', ['bf16', 'f32'])
+def test_bn_relu_maxpool_with_specials(gpu, dt):
+    """A NaN wins its windows (the last NaN of a window is the kept position), -Inf loses to everything, +Inf wins unless a NaN is
+    there: the one-pass kernel against small_exact_ref.maxpool_fwd of the BatchNorm + ReLU output of the separate pass, on clean
+    statistics partials (crafted from the clean x, so that only the apply + pool part sees the specials)."""
+    import small_exact_ref as S
+    ops = _ops()
+    N, H, W, C = 3, 18, 14, 64
+    rows = N * H * W
+    G.row_pitch(C * 4)
+    s = R.stats_case(256, C, device=gpu)          # per-channel mean / gamma / beta recipe; the values below are this module's own
+    rng = torch.Generator().manual_seed(7)
+    x = (torch.randint(-3, 4, (rows, C), generator=rng).double().to(gpu) + s['mean_c'])
+    bounds = [(r0, min(rows, r0 + 64)) for r0 in range(0, rows, 64)]
+    part = _vec(R.fwd_partials(x, bounds).float().reshape(-1), 'partials')
+    pos = []
+    for i, (n, h, w) in enumerate([(0, 0, 0), (0, 1, 1), (1, 8, 7), (1, 8, 8), (1, 9, 7), (2, 17, 13), (2, 5, 5), (2, 6, 6)]):
+        # (1, 8, 7), (1, 8, 8) and (1, 9, 7) share a channel: windows with two NaN, and with a NaN and a +Inf
+        pos.append((((n * H + h) * W + w, (63, 54, 45, 45, 45, 18, 9, 0)[i]), ('nan', 'nan', 'nan', '+inf', 'nan', '-inf', '+inf', '-inf')[i]))
+    x2 = _seeded(x, pos)
+    xd = G.place(x2.view(N, H, W, C).permute(0, 3, 1, 2).to(R.TDT[dt]).contiguous(memory_format=torch.channels_last), 'feature map')
+    gamma, beta = _vec(s['gamma'].float(), 'gamma'), _vec(s['beta'].float(), 'beta')
+    res = []
+    for fused in (False, True):
+        rm, rv, nbt = _vec(torch.zeros(C, device=gpu), 'running_mean'), _vec(torch.ones(C, device=gpu), 'running_var'), _vec(torch.zeros((), dtype=torch.int64, device=gpu), 'nbt')
+        if fused:
+            (p, arg, mean, invstd), _ = _labels(ops, lambda: ops.bn_relu_maxpool_fwd(xd, gamma, beta, rm, rv, nbt, R.EPS, R.MOMENTUM, 1, (part, len(bounds))))
+        else:
+            (z, mean, invstd), _ = _labels(ops, lambda: ops.bn_train_fwd(xd, None, gamma, beta, rm, rv, nbt, R.EPS, R.MOMENTUM, True, partial=(part, len(bounds))))
+            _whole('z', z)
+        res.append((mean, invstd, rm, rv))
+    _whole('pooled / codes', p, arg)
+    for a, b in zip(*res):
+        assert _same_bits(a, b) and bool(torch.isfinite(a).all())
+    zc = NF.classes(z)
+    assert int((zc == NF.IS_NAN).sum()) == 4 and int((zc == NF.POS_INF).sum()) + int((zc == NF.NEG_INF).sum()) >= 1
+    y_ref, code_ref = S.maxpool_fwd(z.double().cpu())
+    assert 4 * int(torch.isfinite(y_ref).sum()) >= y_ref.numel() and bool((y_ref != y_ref).any())
+    assert S.bits_equal(p.double().cpu().contiguous(), y_ref), 'pooled values'
+    assert torch.equal(arg.cpu(), code_ref.permute(0, 2, 3, 1)), 'window codes'
+
+
+@pytest.mark.parametrize('case', NF_BWD_CASES, ids=R.case_id)
+def test_backward_with_specials(gpu, case):
+    """(a) a NaN in dy where the gradient is live: the channel's dgamma / dbeta are non-finite and its dx is NaN throughout;
+    (b) a NaN in dy where the ReLU mask clears it: nothing changes, bit for bit (a select, as ATen's threshold_backward);
+    (c) a +Inf in x: the channel's dgamma and dx are non-finite.  Every other channel has the bits of the clean run."""
+    rows, C, dt, form, relu, dres = case
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    d = _dev(c, dt)
+    keep = None if relu == 0 else (c['ypre'] > 0 if relu == 2 else R.fwd_y(c, True, True) > 0)
+    clean = _backward(ops, c, dt, form, relu, dres, False)
+    _assert_form(clean[4], form)
+
+    def run(**over):
+        saved = {k: d[k] for k in over}
+        d.update({k: _put(v, dt) for k, v in over.items()})
+        try:
+            out = _backward(ops, c, dt, form, relu, dres, False)
+        finally:
+            d.update(saved)
+        _assert_form(out[4], form)
+        return out
+
+    live = NF.bn_positions(rows, C, keep, True)[0]
+    ch = live[1]
+    dx, dr, dg, db, _ = run(dy=_seeded(c['dy'], [(live, 'nan')]))
+    ref = NF.bn_bwd_select(dict(c, dy=_seeded(c['dy'], [(live, 'nan')])), keep)
+    assert not bool(torch.isfinite(ref['dgamma'][ch])) and not bool(torch.isfinite(ref['dx'][:, ch]).any()) and int(torch.isfinite(ref['dbeta']).sum()) == C - 1
+    assert NF.reduced_mismatch(dg, ref['dgamma']) is None and NF.reduced_mismatch(db, ref['dbeta']) is None, '(a) dgamma / dbeta'
+    got = R.rows_of(dx)
+    assert bool((got[:, ch] != got[:, ch]).all()), '(a) the channel of a live NaN: dx is NaN throughout'
+    for what, a, b in (('dx', dx, clean[0]), ('dgamma', dg, clean[2]), ('dbeta', db, clean[3])):
+        _other_channels_unchanged('(a) ' + what, a, b, {ch})
+    if dres:
+        want = NF.classes(ref['dres'])
+        assert torch.equal(NF.classes(R.rows_of(dr)), want) and int((want != 0).sum()) == 1
+        assert _same_bits(R.rows_of(dr)[want == 0], R.rows_of(clean[1])[want == 0])
+    if keep is not None:
+        masked = NF.bn_positions(rows, C, keep, False)
+        out = run(dy=_seeded(c['dy'], [(p, 'nan') for p in masked]))
+        for what, a, b in zip(('dx', 'dres', 'dgamma', 'dbeta'), out[:4], clean[:4]):
+            assert _same_bits(a, b), '(b) a masked NaN changed %s' % what
+    if relu == 1:
+        # the mask is !(y <= 0), ATen's threshold_backward: a NaN in the stored forward output lets the gradient through (it used to
+        # count as masked: y > 0 is false for NaN, and dbeta stayed finite where torch's is NaN).  At a masked element, a NaN in y
+        # gives the bits of a run with a positive y there.
+        y = R.fwd_y(c, True, True)
+        at = NF.bn_positions(rows, C, keep, False)[0]
+        one = y.clone()
+        one[at] = 1.0
+        a, b = run(y=_seeded(y, [(at, 'nan')])), run(y=one)
+        for what, p, q in zip(('dx', 'dres', 'dgamma', 'dbeta'), a[:4], b[:4]):
+            assert _same_bits(p, q), 'a NaN in y does not let the gradient through: %s' % what
+        assert not _same_bits(a[3], clean[3]) or float(c['dy'][at]) == 0.0
+    xpos = (rows // 2, C - 1)
+    x2 = _seeded(c['x'], [(xpos, '+inf')])
+    dx, dr, dg, db, _ = run(x=x2)
+    keep2 = keep if relu != 2 else ((x2 - c['mean']) * c['invstd'] * c['gamma'] + c['beta']) > 0
+    ref = NF.bn_bwd_select(dict(c, x=x2), keep2)
+    assert not bool(torch.isfinite(ref['dgamma'][C - 1])) and not bool(torch.isfinite(ref['dx'][:, C - 1]).any())
+    assert NF.reduced_mismatch(dg, ref['dgamma']) is None and NF.reduced_mismatch(db, ref['dbeta']) is None, '(c) dgamma / dbeta'
+    got = R.rows_of(dx)
+    assert not bool(torch.isfinite(got[:, C - 1]).any()), '(c) the channel of an Inf in x: dx is non-finite throughout'
+    for what, a, b in (('dx', dx, clean[0]), ('dgamma', dg, clean[2]), ('dbeta', db, clean[3])):
+        _other_channels_unchanged('(c) ' + what, a, b, {C - 1})
+    assert ops.bn_resident_timeouts() == 0
+
+
+@pytest.mark.parametrize('shape', NF_SHAPES, ids=R.case_id)
+def test_colsum_and_mask_apply_with_specials(gpu, shape):
+    rows, C, dt = shape
+    ops = _ops()
+    c = _case(gpu, rows, C)
+    pos = [((rows - 1, C - 1), 'nan'), ((0, 0), '+inf'), ((rows // 2, C // 2), '-inf')]
+    dy2 = _seeded(c['dy'], pos)
+    dyd = _put(dy2, dt)
+    for acc in (False, True):
+        prior = R.int_prior(C, 'colsum', gpu)
+        out = _vec(prior.float() if acc else torch.full((C,), 777.0, device=gpu), 'out')
+        _labels(ops, lambda: ops.colsum(dyd, out, acc))
+        ref = R.colsum(dy2, prior if acc else None)
+        assert int((~torch.isfinite(ref)).sum()) == 3
+        bad = NF.reduced_mismatch(out, ref)                                   # finite sums [equal], the three channels non-finite
+        assert bad is None, bad
+    # apply_relu_mask: a select -- a special under a cleared bit becomes an exact zero, one under a set bit stays
+    per = R.PER[dt]
+    b = R.mask_bytes(rows * C // per, 'apply').to(gpu)
+    bits = R.unpack_mask(b, rows, C, per)
+    pos, used = [], set()
+    for kd, want in (('nan', False), ('nan', True), ('+inf', True), ('-inf', False)):          # each in a channel of its own, from the last one down
+        r, ch = next((int(r), int(ch)) for r, ch in (bits == want).nonzero().flip(0).tolist() if ch not in used)
+        used.add(ch)
+        pos.append(((r, ch), kd))
+    g2 = _seeded(c['dy'], pos)
+    out, _ = _labels(ops, lambda: ops.apply_relu_mask(_put(g2, dt), _vec(b, 'mask')))
+    ref = NF.relu_bwd_select(g2, bits)
+    assert NF.class_counts(ref)[NF.IS_NAN] == 1 and NF.class_counts(ref)[NF.POS_INF] == 1 and NF.class_counts(ref)[NF.NEG_INF] == 0
+    bad = NF.pointwise_mismatch(R.rows_of(out), ref, R.TDT[dt])
+    assert bad is None, bad

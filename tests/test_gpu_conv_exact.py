@@ -19,6 +19,14 @@ torch.empty the block of the previous, identical call would come back with the r
 through a plain pointer poisons the sum it enters.  test_conv_dispatch_cpu.py holds, from the plans, that the cases include ragged
 last splits, single slabs with accumulate, grouped launches with several slab-reduced items and statistics buffers with slack.
 
+NaN, +Inf and -Inf (tests/nonfinite_ref.py, the section at the end): the guard buffers' claim that a NaN read "poisons the sum it
+enters" holds only for kernels that propagate one, and the step guard of the training loop needs the same.  A few elements of one
+operand at a time (x, dy, bias, residual, accumulate base, weights, the weight gradient's base) are special on the smallest case of
+every build; the class of every output element must be the float64 reference's and every finite element must keep its bits.  A NaN
+base under a cleared accumulate-mask bit contributes an exact zero (a select, never base * bit), the statistics and
+BatchNorm-backward epilogues keep a special inside its channel, and a bf16 store rounds an fp32 value beyond the range to Inf and
+keeps a subnormal.
+
 Builds behind switches that are read once per process (MI355_DMA, MI355_KW3, MI355_PHASES, MI355_T256D_*, MI355_FP8_TILE)
 run in child processes, one per entry of GROUPS, strictly one after another, each with its own timeout and no retry.
 
@@ -45,6 +53,7 @@ import torch
 
 import conv_exact_ref as R
 import guarded as G
+import nonfinite_ref as NF
 from mx_ref import mx_dequantize
 
 pytestmark = pytest.mark.gpu
@@ -529,9 +538,309 @@ if _FP8:
         _same(name + ' dgradmx*scale+acc', dx, c.dx_acc, bf16)
 
 
+# ---------------------------------------------------------------------------------------------- NaN, +Inf and -Inf operands
+# tests/nonfinite_ref.py: a few elements of ONE operand are NaN / +Inf / -Inf, every other value stays an exact integer.  The
+# pointwise rule: the class of every output element is the float64 reference's and every finite element has its bits.  The
+# cases, their positions and the condition on the reference are held without a GPU by test_nonfinite_cpu.py.
+def _pointwise(what, got, ref, dtype):
+    _whole(what, got)          # (a NaN a kernel computed or passed through is not the all-ones fill)
+    bad = NF.pointwise_mismatch(got, ref, dtype)
+    assert bad is None, '%s: %s' % (what, bad)
+
+
+_SPECIALS = [(s, dt) for s in NF.CONV_SPECIALS if R.CASES[s[1]][0] == GROUP for dt in ('bf16', 'f32')]
+if _SPECIALS:
+    @pytest.mark.parametrize('spec,dt', _SPECIALS, ids=['%s-%s' % (NF.special_id(s), dt) for s, dt in _SPECIALS])
+    def test_specials_come_out_where_the_reference_has_them(gpu, spec, dt):
+        ops = _ops()
+        mode, name, operand = spec
+        sp = NF.conv_special(mode, name, operand)
+        for what, ref in sp['refs'].items():          # the cap on the case, before any kernel result is read
+            NF.case_condition(ref, sp['expect'][what], '%s %s' % (NF.special_id(spec), what))
+        c, o, refs = sp['case'], sp['ops'], sp['refs']
+        dtype, per = DT[dt], (8 if dt == 'bf16' else 4)
+        e_fwd, e_dgrad, e_acc, e_bnb, e_wgrad = EXPECT[name][0 if dt == 'bf16' else 1]
+        N, Ci, H, W, Co, k, s, p = c.shape
+        desc = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype, out_hw=c.out_hw)
+        _pitch(dtype, Ci, Co)
+        wf, wt = _packs(ops, _vec(o['w'].permute(0, 2, 3, 1), gpu, 'master weights'), Co, k * k, Ci, Ci, dtype)
+        tag = '%s/%s ' % (NF.special_id(spec), dt)
+        if mode == 'fwd':
+            xd, bias, res = _dev(o['x'], dtype, gpu), _vec(o['bias'], gpu, 'bias'), _dev(o['res'], dtype, gpu)
+            for what, relu in (('fwd+bias+res', False), ('fwd+bias+res+relu', True)):
+                y, labels = _run(ops, lambda: ops.conv_fwd(desc, xd, wf, bias, res, relu=relu))
+                assert _check_builds(tag + what, labels, e_fwd) == 0
+                _pointwise(tag + what, y, refs[what], dtype)
+        elif mode == 'dgrad':
+            dyd, base, sc = _dev(o['dy'], dtype, gpu), _dev(o['base'], dtype, gpu), _vec(torch.full((1,), 0.25), gpu, 'scale')
+            for what, fn, exp in (('dgrad', lambda: ops.conv_dgrad(desc, dyd, wt), e_dgrad),
+                                  ('dgrad*scale', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc), e_dgrad),
+                                  ('dgrad*scale+acc', lambda: ops.conv_dgrad(desc, dyd, wt, scale_dev=sc, out=G.place(base, 'base'), accumulate=True), e_acc)):
+                if what in refs:
+                    dx, labels = _run(ops, fn)
+                    assert _check_builds(tag + what, labels, exp) == 0
+                    _pointwise(tag + what, dx, refs[what], dtype)
+        elif mode == 'macc':
+            # a NaN base under a cleared bit contributes an exact zero (a select, as ATen's threshold_backward), under a set bit it stays
+            dyd, base, mask = _dev(o['dy'], dtype, gpu), _dev(o['base'], dtype, gpu), _vec(c.mask[per], gpu, 'mask')
+            what = 'dgrad+macc/%d' % per
+            dx, labels = _run(ops, lambda: ops.conv_dgrad_masked_acc(desc, dyd, wt, G.place(base, 'base'), mask))
+            assert _check_builds(tag + what, labels, e_acc) == 0
+            _pointwise(tag + what, dx, refs[what], dtype)
+        else:
+            xd, dyd = _dev(o['x'], dtype, gpu), _dev(o['dy'], dtype, gpu)
+            kind, slabs = e_wgrad.split(' ')
+            for what, acc in (('wgrad', False), ('wgrad+acc', True)):
+                if what in refs:
+                    dw = _vec(o['dw0'], gpu, 'dw') if acc else G.empty((Co, k, k, Ci), torch.float32, gpu, 'dw')
+                    _, labels = _run(ops, lambda: ops.conv_wgrad(desc, xd, dyd, dw, accumulate=acc))
+                    assert len(labels) == 1 and labels[0].split(' ')[0] == kind and labels[0].split(' ')[-1] == slabs, (labels, e_wgrad)
+                    _pointwise(tag + what, dw, refs[what], torch.float32)
+
+
+def _fold_or_raw(part, C, width):
+    """The written slices of an epilogue's partials [slice][C][width] as float64 on the host."""
+    return part[0][:part[1] * C * width].detach().cpu().double().view(part[1], C, width)
+
+
+if GROUP == 'default':
+    @pytest.mark.parametrize('dt', ['bf16', 'f32'])
+    def test_statistics_epilogue_keeps_an_inf_in_its_channel(gpu, dt):
+        """conv_fwd_stats with +Inf in one bias element and conv_dgrad_stats with +Inf in one weight of one input channel: that
+        channel's partials are non-finite in every slice that holds one of its non-finite outputs, every other channel's partials
+        are the bits of the clean run, and the outputs follow the pointwise rule."""
+        ops = _ops()
+        dtype = DT[dt]
+        for name, side in (('t64_co72', 'fwd'), ('small_dgrad', 'dgrad')):
+            c = R.build_case(name)
+            N, Ci, H, W, Co, k, s, p = c.shape
+            e_fwd, e_dgrad = EXPECT[name][0 if dt == 'bf16' else 1][:2]
+            desc = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype)
+            _pitch(dtype, Ci, Co)
+            xd, dyd = _dev(c.x, dtype, gpu), _dev(c.dy, dtype, gpu)
+            runs = {}
+            for poisoned in (False, True):
+                if side == 'fwd':
+                    C_, ch, rows = Co, Co - 1, N * c.Ho * c.Wo
+                    bias = NF.seed_specials(c.bias, [((ch,), '+inf')]) if poisoned else c.bias
+                    wf, _ = _packs(ops, _vec(c.w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, k * k, Ci, Ci, dtype)
+                    bd = _vec(bias, gpu, 'bias')
+                    (y, part), labels = _run(ops, lambda: ops.conv_fwd_stats(desc, xd, wf, bd))
+                    assert _check_builds('%s fwd+stats' % name, labels, e_fwd) == 1
+                    ref = NF.fwd_epilogue(c.y, bias)
+                else:
+                    C_, ch, rows = Ci, Ci - 1, N * H * W
+                    w = NF.seed_specials(c.w, [((Co - 1, ch, k // 2, k // 2), '+inf')]) if poisoned else c.w
+                    _, wt = _packs(ops, _vec(w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, k * k, Ci, Ci, dtype)
+                    (y, part), labels = _run(ops, lambda: ops.conv_dgrad_stats(desc, dyd, wt))
+                    assert _check_builds('%s dgrad+stats' % name, labels, e_dgrad) == 1
+                    ref = R.conv_dgrad(c.dy, w, s, p, (H, W))
+                if poisoned:
+                    n = NF.class_counts(ref)
+                    assert 4 * n[NF.FINITE] >= ref.numel() and n[NF.FINITE] < ref.numel()
+                    assert bool(torch.isfinite(ref[:, [q for q in range(C_) if q != ch]]).all()) and not bool(torch.isfinite(ref[:, ch]).all())
+                _pointwise('%s %s+stats' % (name, side), y, ref, dtype)
+                assert part is not None
+                runs[poisoned] = (_fold_or_raw(part, C_, 3), R.fold_stats(part[0], part[1], C_), ref)
+            (pc, _, _), (pp, (tot, mean, m2), ref) = runs[False], runs[True]
+            others = [q for q in range(C_) if q != ch]
+            assert torch.equal(pc[:, others], pp[:, others]), '%s: an Inf in channel %d changed the partials of another channel' % (name, ch)
+            assert torch.equal(pc[:, :, 0], pp[:, :, 0])                    # the counts are counts
+            nr, rmean, rm2 = R.bn_stats(ref)
+            assert NF.reduced_mismatch(tot, torch.full((C_,), float(rows), dtype=torch.float64)) is None
+            inv, rinv = 1.0 / torch.sqrt(m2 / tot + 1e-5), 1.0 / torch.sqrt(rm2 / nr + 1e-5)
+            for what, got, want, tol in (('mean', mean, rmean, dict(rtol=1e-5, atol=1e-6)), ('invstd', inv, rinv, dict(rtol=2e-5, atol=1e-6))):
+                bad = NF.reduced_mismatch(got, want, **tol)          # (the tolerances of _check_stats)
+                assert bad is None, '%s %s: %s' % (name, what, bad)
+            assert not bool(torch.isfinite(mean[ch])) and not bool(torch.isfinite(m2[ch]))
+
+    @pytest.mark.parametrize('relu', ['none', 'from_y', 'from_x'])
+    @pytest.mark.parametrize('dt', ['bf16', 'f32'])
+    def test_bn_backward_epilogue_drops_a_masked_nan_and_keeps_a_live_one(gpu, dt, relu):
+        """conv_dgrad_bnbwd (accumulating, the NaN in ONE element of the base, so in one element of the BatchNorm's dy) and
+        conv_fwd_bnbwd (the NaN in x: a window of the BatchNorm's dy in every channel).  A NaN where the ReLU mask clears the
+        gradient changes no partial at all (the bits of the clean run); one where the mask keeps it makes that channel's sums
+        non-finite and no other's.  The stored gradient follows the pointwise rule either way."""
+        ops = _ops()
+        dtype = DT[dt]
+        for name, side in (('small_dgrad', 'dgrad'), ('t64_s2', 'fwd')):
+            c = R.build_case(name)
+            N, Ci, H, W, Co, k, s, p = c.shape
+            e = EXPECT[name][0 if dt == 'bf16' else 1]
+            desc = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype)
+            _pitch(dtype, Ci, Co)
+            wf, wt = _packs(ops, _vec(c.w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, k * k, Ci, Ci, dtype)
+            C_, bshape, bias_c = (Ci, (N, Ci, H, W), c.bias_i) if side == 'dgrad' else (Co, (N, Co, c.Ho, c.Wo), c.bias)
+            xb64 = R.ints(R.seed_of(name + '/bn x'), *bshape, lo=-16, hi=16)
+            xb = _dev(xb64, dtype, gpu)
+            gamma, beta = _vec(1 + bias_c / 64, gpu, 'gamma'), _vec(bias_c / 32, gpu, 'beta')
+            rm, rv, nbt = _vec(torch.zeros(C_), gpu, 'running_mean'), _vec(torch.ones(C_), gpu, 'running_var'), _vec(torch.zeros((), dtype=torch.int64), gpu, 'num_batches_tracked')
+            yb, mean, invstd = _guarded(ops, 'bn_train_fwd', lambda: ops.bn_train_fwd(xb, None, gamma, beta, rm, rv, nbt, 1e-5, 0.1, relu != 'none'))
+            bn = (xb, yb if relu == 'from_y' else None, gamma, beta, mean, invstd, relu != 'none')
+            # where the mask keeps and where it clears, away from the threshold: the stored y for the kept side, the float64
+            # pre-activation (from the kernel's own statistics) for the cleared one
+            pre = (xb64.double() - mean.double().cpu().view(1, -1, 1, 1)) * (gamma.double() * invstd.double()).cpu().view(1, -1, 1, 1) + beta.double().cpu().view(1, -1, 1, 1)
+            kept = (yb.float().cpu() > 0.1) if relu != 'none' else torch.ones(bshape, dtype=torch.bool)
+            cleared = (pre < -0.1) & (yb.float().cpu() == 0) if relu != 'none' else torch.zeros(bshape, dtype=torch.bool)
+            sure = kept | cleared
+            assert relu == 'none' or (bool(kept.any()) and bool(cleared.any()))
+
+            def run(ops_in):
+                if side == 'dgrad':
+                    dyd, base = _dev(c.dy, dtype, gpu), _dev(ops_in, dtype, gpu)
+                    (g, part), labels = _run(ops, lambda: ops.conv_dgrad_bnbwd(desc, dyd, wt, bn, out=G.place(base, 'base'), accumulate=True))
+                    assert _check_builds('%s dgrad+bnb' % name, labels, e[3]) == 2
+                    return g, part, R.dgrad_epilogue(c.dx, 1.0, ops_in)
+                xd = _dev(ops_in, dtype, gpu)
+                (g, part), labels = _run(ops, lambda: ops.conv_fwd_bnbwd(desc, xd, wf, bn))
+                assert _check_builds('%s fwd+bnb' % name, labels, e[0]) == 2
+                return g, part, R.conv_fwd(ops_in, c.w, s, p)
+
+            clean_in = c.base if side == 'dgrad' else c.x
+            g, part, ref = run(clean_in)
+            _same('%s clean' % name, g, ref, dtype)
+            assert part is not None
+            clean = _fold_or_raw(part, C_, 2)
+            for want_live in ((False, True) if relu != 'none' else (True,)):
+                if side == 'fwd' and not want_live:
+                    continue                 # (the window below holds kept and cleared elements at once)
+                if side == 'dgrad':          # one element of the BatchNorm's dy
+                    where = (kept if want_live else cleared).nonzero()
+                    idx = tuple(int(v) for v in where[where.shape[0] // 2])
+                else:                        # an x pixel: the 3x3 window of outputs around it, every channel
+                    idx = (N - 1, Ci - 1, H // 2, W // 2)
+                g, part, ref = run(NF.seed_specials(clean_in, [(idx, 'nan')]))
+                nan = ref != ref
+                assert bool(nan.any()) and 4 * int((~nan).sum()) >= ref.numel()
+                _pointwise('%s %s nan' % (name, side), g, ref, dtype)
+                assert part is not None
+                got = _fold_or_raw(part, C_, 2)
+                per_channel = lambda m: m.permute(1, 0, 2, 3).reshape(C_, -1).any(1)
+                live, doubt = per_channel(nan & kept), per_channel(nan & ~sure)          # (doubt: a NaN where y sits at the threshold)
+                if side == 'dgrad':
+                    assert bool(live.any()) == want_live
+                for ch in range(C_):
+                    if bool(doubt[ch]):
+                        continue
+                    if bool(live[ch]):
+                        assert not bool(torch.isfinite(got[:, ch].sum(0)).any()), '%s: the live NaN of channel %d left a finite sum' % (name, ch)
+                    else:
+                        assert torch.equal(got[:, ch], clean[:, ch]), '%s: a masked NaN (or one of another channel) changed the sums of channel %d' % (name, ch)
+
+    @pytest.mark.parametrize('dt', ['bf16', 'f32'])
+    def test_concat_k_and_heatmap_conv_with_specials(gpu, dt):
+        ops = _ops()
+        dtype, i = DT[dt], (0 if dt == 'bf16' else 1)
+        name = 'cat_64x64'
+        c = R.build_cat_case(name)
+        N, Ci, H, W, Co, k, s, p = c.shape
+        desc = ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype)
+        _pitch(dtype, Ci, Co)
+        xd = _dev(c.x, dtype, gpu)
+        wf, _ = _packs(ops, _vec(c.w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, k * k, Ci, Ci, dtype)
+        b1, b2 = _vec(c.b1, gpu, 'bias'), _vec(c.b2, gpu, 'bias2')
+        for n2 in R.CAT_C2[dtype]:
+            sp = NF.cat_special(name, n2, i)
+            for what, ref in sp['refs'].items():
+                NF.case_condition(ref, sp['kinds'], what)
+            x2d, w2 = _dev(sp['x2'], dtype, gpu), _vec(c.w2[n2].to(dtype), gpu, 'w2')
+            y, labels = _run(ops, lambda: ops.conv_fwd_cat(desc, xd, wf, None, x2d, w2, None))
+            assert _check_builds('%s c2=%d cat' % (name, n2), labels, CAT_EXPECT[name][i]) == 0
+            _pointwise('cat c2=%d' % n2, y, sp['refs']['cat'], dtype)
+            y, labels = _run(ops, lambda: ops.conv_fwd_cat(desc, xd, wf, b1, x2d, w2, b2))
+            assert _check_builds('%s c2=%d cat+bias' % (name, n2), labels, CAT_EXPECT[name][i]) == 0
+            _pointwise('cat+bias c2=%d' % n2, y, sp['refs']['cat+bias'], dtype)
+        sp = NF.hm_special('hm_120')
+        NF.case_condition(sp['refs']['hm'], sp['kinds'], 'hm_120')
+        Nh, Ch, K, Hh, Wh = R.HM_CASES['hm_120']
+        hc = sp['case']
+        _pitch(dtype, Ch)
+        xh, wd, bd = _dev(sp['x'], dtype, gpu), _vec(hc.w.view(K, Ch).to(dtype), gpu, 'weights'), _vec(hc.b, gpu, 'bias')
+        y, labels = _run(ops, lambda: ops.conv1x1_heatmap(xh, wd, bd, K))
+        assert _check_builds('hm_120/%s' % dt, labels, 'g128x32 hm' if dt == 'bf16' else 'g128x32 f32 hm') == 0
+        _pointwise('hm_120', y, sp['refs']['hm'], torch.float32)
+
+    @pytest.mark.parametrize('dt', R.GROUPED_CASES['wgrad_group'][0])
+    def test_grouped_weight_gradients_with_specials(gpu, dt):
+        """The first grouped form: the dy of an overwriting item and the x of a slab-reduced strided 3x3 item carry the specials;
+        the item that accumulates onto the first one's gradient adds a finite term to rows that are already special."""
+        ops = _ops()
+        dtype = DT[dt]
+        cases, refs = NF.grouped_special('wgrad_group')
+        for i in (0, 2):
+            NF.case_condition(refs[i], NF.KINDS, 'wgrad_group item %d' % i)
+        items = []
+        _pitch(dtype, *[ch for shape, _, _, _ in cases for ch in shape[3:5]])
+        for (N, H, W, Ci, Co, k, s, p, acc, share), x, dy, dw0 in cases:
+            dw = items[share][3] if share is not None else (_vec(dw0, gpu, 'dw') if acc else G.empty((Co, k, k, Ci), torch.float32, gpu, 'dw'))
+            items.append((ops.make_desc(N, H, W, Ci, Co, k, k, s, p, dtype), _dev(x, dtype, gpu), _dev(dy, dtype, gpu), dw, acc))
+        _, labels = _run(ops, lambda: ops.conv_wgrad_grouped(items))
+        assert [' '.join(l.split(' ')[:2]) for l in labels] == GROUPED['wgrad_group'], labels
+        for i, ref in enumerate(refs):
+            if ref is not None:
+                _pointwise('wgrad_group item %d' % i, items[i][3], ref, torch.float32)
+
+    @pytest.mark.parametrize('name,operand', NF.PGEMM_SPECIALS, ids=['%s-%s' % s for s in NF.PGEMM_SPECIALS])
+    def test_pgemm_with_specials(gpu, name, operand):
+        """mi355_set_pgemm(2): the plain ring and the addend ring, ReLU off and on."""
+        import mi355
+        ops = _ops()
+        lib = mi355.load()
+        sp = NF.pgemm_special(name, operand)
+        for what, ref in sp['refs'].items():
+            NF.case_condition(ref, sp['expect'][what], '%s %s %s' % (name, operand, what))
+        c, o, refs = sp['case'], sp['ops'], sp['refs']
+        N, Ci, H, W, Co = c.shape
+        e_plain, e_add = PGEMM[name][0]
+        dtype = torch.bfloat16
+        desc = ops.make_desc(N, H, W, Ci, Co, 1, 1, 1, 0, dtype)
+        _pitch(dtype, Ci, Co)
+        wf, _ = _packs(ops, _vec(c.w.permute(0, 2, 3, 1), gpu, 'master weights'), Co, 1, Ci, Ci, dtype)
+        xd, resd, biasd = _dev(o['x'], dtype, gpu), _dev(o['res'], dtype, gpu), _vec(c.bias, gpu, 'bias')
+        prev = lib.mi355_set_pgemm(2)
+        try:
+            for what, fn, exp in (('fwd', lambda: ops.conv_fwd(desc, xd, wf), e_plain),
+                                  ('fwd+relu', lambda: ops.conv_fwd(desc, xd, wf, relu=True), None),
+                                  ('fwd+bias+res', lambda: ops.conv_fwd(desc, xd, wf, biasd, resd), e_add),
+                                  ('fwd+bias+res+relu', lambda: ops.conv_fwd(desc, xd, wf, biasd, resd, relu=True), e_add)):
+                if what not in refs:
+                    continue
+                got, labels = _run(ops, fn)
+                build = _build(labels[0])
+                assert build.startswith('pgemm '), labels
+                if exp is not None:
+                    assert _check_builds('%s %s' % (name, what), labels, exp) == 0
+                _pointwise('%s %s %s' % (name, operand, what), got, refs[what], dtype)
+        finally:
+            lib.mi355_set_pgemm(prev)
+
+    @pytest.mark.parametrize('pg', [0, 2], ids=['gather', 'pgemm'])
+    def test_bf16_store_overflows_to_inf_and_keeps_subnormals(gpu, pg):
+        """Zero weights, the bias carries +-3.4e38 (rounds to +-Inf), the largest finite bf16 and the smallest bf16 subnormal:
+        the stored bf16 is the fp32 value rounded once to nearest even, through the gather epilogue and the pgemm epilogue."""
+        import mi355
+        ops = _ops()
+        lib = mi355.load()
+        c = NF.store_overflow_case()
+        N, Ci, H, W, Co = c['shape']
+        dtype = torch.bfloat16
+        desc = ops.make_desc(N, H, W, Ci, Co, 1, 1, 1, 0, dtype)
+        _pitch(dtype, Ci, Co)
+        wf, _ = _packs(ops, _vec(c['w'].permute(0, 2, 3, 1), gpu, 'master weights'), Co, 1, Ci, Ci, dtype)
+        xd, bd = _dev(c['x'], dtype, gpu), _vec(c['bias'], gpu, 'bias')
+        prev = lib.mi355_set_pgemm(pg)
+        try:
+            y, labels = _run(ops, lambda: ops.conv_fwd(desc, xd, wf, bd))
+        finally:
+            lib.mi355_set_pgemm(prev)
+        print('\nLABEL store overflow pgemm=%d %s' % (pg, ' | '.join(labels)))
+        assert len(labels) == 1 and _build(labels[0]).startswith('pgemm ' if pg else 'g'), labels
+        _pointwise('store overflow', y, c['ref'], dtype)
+
+
 # ---------------------------------------------------------------------------------------------- the forced builds, in children
 if GROUP == 'default':
-    _abnormal = []          # a child that ended by a signal, an abort or its timeout: nothing more is started on the GPU
+    _abnormal = []        # a child that ended by a signal, an abort or its timeout: nothing more is started on the GPU
 
     @pytest.mark.parametrize('group', sorted(GROUPS))
     def test_forced_builds_in_a_child_process(gpu, group):

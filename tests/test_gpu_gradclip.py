@@ -12,6 +12,7 @@ mi355_grad_clip_coef, mi355_sgd_nesterov_clipped; mi355.optim.GradClipper; DASte
      gradients, changes the parameters, and replays as it runs eagerly;
   7. the command line.
 """
+import functools
 import os
 import subprocess
 import sys
@@ -410,6 +411,187 @@ def test_da_step_with_the_clip_replays_as_it_runs_eagerly(da_runs):
     for a, b in zip(eager['recs'], graph['recs']):
         for s in 'abc':
             assert _bits(a[s]) == _bits(b[s])
+
+
+# ---------------------------------------------------------------- 6b. the guard end to end
+# A non-finite value that arises in an image or a label must reach the flat gradient buffers as a non-finite value, through every
+# kernel between them, or the guard of section 4 protects nothing.  resnet18, B = 2, 64 x 64 images, 16 x 16 maps, GradClipper(inf),
+# an EMA teacher attached: two warm-up iterations (the optimizers go flat, the clipper's tables settle, then the capture), and the
+# four iterations clean / poisoned / clean / clean.
+GUARD_POISONS = ['x_s', 'label_s', 'x_t']
+
+
+def _opt_state(opts, keys):
+    """Clones of everything the optimizers `keys` own on the device: flat parameters, momentum / Adam moments, step counts and
+    the packed low-precision working copies of the conv weights."""
+    out = []
+
+    def walk(v):
+        if torch.is_tensor(v):
+            out.append(v.detach().clone())
+        elif isinstance(v, dict):
+            for k in sorted(v, key=repr):
+                walk(v[k])
+        elif isinstance(v, (list, tuple)):
+            for q in v:
+                walk(q)
+
+    for k in keys:
+        for f in opts[k]._flat:
+            if f is not None:
+                for name in ('P', 'M', 'V', 'S'):
+                    if name in f:
+                        out.append(f[name].detach().clone())
+                walk(f.get('pack_cache', {}))
+    return out
+
+
+def _same_state(a, b):
+    raw = lambda t: t.contiguous().view(-1).view(torch.uint8)
+    return len(a) == len(b) and all(x.shape == y.shape and torch.equal(raw(x), raw(y)) for x, y in zip(a, b))
+
+
+@functools.lru_cache(maxsize=None)
+def _reference_says_b_is_non_finite(poisoned=True):
+    """Update B of the float64 torch copy of the step (oracle/train_step.py, its step B on the CPU): are the gradients of the three
+    adversarial heads non-finite when one pixel of x_t is +Inf?  The oracle's label generators are built for 64 x 64 maps, so it
+    runs at its own size (256 x 256 images) with the same poison; whether a gradient is finite does not depend on the size."""
+    from oracle.train_step import build_model, DATrainer
+    from seeded import fill_module_
+    from utils.synthetic import make_batch
+    ref = build_model('resnet18')
+    fill_module_(ref, 731)
+    ref = ref.double()
+    tr = DATrainer(ref)
+    m, to = tr.model, tr.trade_off
+    m.train()
+    batch = make_batch(2, 256, 64, seed=3, device='cpu')
+    if poisoned:
+        batch['x_t'][1, 2, 133, 68] = float('inf')
+    x_t, w_t = batch['x_t'].double(), batch['w_t'].double()
+    y_t, y_t_adv, y_t_adv2, y_t_adv3, _ = m(x_t)
+    H = y_t.shape[-1]
+    up = lambda t, size: torch.nn.Upsample(size=size, mode='bilinear')(t.detach())
+    loss_gf = 0.3 * to * tr.rd1(y_t, y_t_adv3, w_t, mode='max') + to * tr.rd(y_t, y_t_adv, 0.5 * up(y_t_adv3, H) + up(y_t_adv2, H), w_t, mode='max') + \
+        0.3 * to * tr.rd2(y_t, y_t_adv2, up(y_t_adv3, H // 2), w_t, mode='max')
+    loss_gf.backward()
+    grads = [p.grad for h in (m.head_adv, m.head_adv2, m.head_adv3) for p in h.parameters() if p.grad is not None]
+    assert grads
+    return not all(bool(torch.isfinite(g).all()) for g in grads)
+
+
+def _guard_run(gpu, optimizer, replayed, poison):
+    import mi355
+    from mi355.da_step import DAStep, build_training
+    from mi355.optim import GradClipper, EMATeacher
+    from uda.model.regda_7 import PoseResNetx9
+    from utils.synthetic import make_batch
+    from test_gpu_ema import _pose
+    mi355.set_compute_dtype('bf16')
+    model, teacher = _pose(gpu, PoseResNetx9, 731), _pose(gpu, PoseResNetx9, 731)
+    step, opts, scheds = build_training(model, heatmap_size=16, optimizer=optimizer)
+    clip = GradClipper(float('inf'), gpu)
+    ema = EMATeacher(model, teacher, opts, 0.8, warmup=True)
+    step = DAStep(model, opts, step.crit, step.trade_off, step.skip, step.track_acc, ema=ema, clip=clip)
+    for c in step.crit.values():
+        if hasattr(c, 'guard_empty_maps'):
+            c.guard_empty_maps = True
+    clean = make_batch(2, 64, 16, seed=3, device=gpu)
+    bad = {k: v.clone() for k, v in clean.items()}
+    if poison == 'label_s':
+        bad['label_s'][1, 7, 5, 9] = float('nan')
+    else:
+        bad[poison][1, 2, 33, 17] = float('inf')
+    KEYS = {'a': ('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'), 'b': ('h_adv2', 'h_adv', 'h_adv3'), 'c': ('f',)}
+    watch = {}                     # slot -> (state before, state after, record after) of the update, filled while armed
+
+    def around(slot, fn):
+        def wrapped():
+            if not watch.get('armed'):
+                return fn()
+            torch.cuda.synchronize()
+            before = _opt_state(opts, KEYS[slot])
+            out = fn()
+            torch.cuda.synchronize()
+            watch[slot] = (before, _opt_state(opts, KEYS[slot]), _host_rec(clip.record(slot)))
+            return out
+        return wrapped
+
+    class _Graph:
+        def __init__(self, g, slot):
+            self.g, self.slot = g, slot
+            self.replay = around(slot, g.replay)
+
+    def iterate(batch):
+        out = step.run(batch)
+        for s in scheds.values():
+            s.step()
+        torch.cuda.synchronize()
+        return {k: float(out[k]) for k in ('loss_s', 'loss_gf', 'loss_gt')}, {s: _host_rec(clip.record(s)) for s in clip.SLOTS}
+
+    for _ in range(2):
+        iterate(clean)
+    if replayed:
+        step.capture(clean, warmup=0)
+        step.graphs = [g if i % 2 == 0 else _Graph(g, 'abc'[i // 2]) for i, g in enumerate(step.graphs)]
+    else:
+        step._update_A, step._update_B, step._update_C = around('a', step._update_A), around('b', step._update_B), around('c', step._update_C)
+    log = []
+    params = lambda: torch.cat([f['P'] for o in opts.values() for f in o._flat if f is not None]).clone()
+    for it, batch in enumerate((clean, bad, clean, clean)):
+        watch.clear()
+        watch['armed'] = it == 1
+        p0 = params()
+        losses, recs = iterate(batch)
+        moved = not torch.equal(p0, params())
+        teacher_ok = all(bool(torch.isfinite(p).all()) for p in teacher.parameters())
+        stats = sorted(k for k, v in model.state_dict().items() if 'running_' in k and not bool(torch.isfinite(v).all()))
+        log.append(dict(losses=losses, recs=recs, moved=moved, teacher_ok=teacher_ok, bad_stats=stats, watch=dict(watch)))
+    from mi355 import ops
+    return dict(log=log, n_skipped=clip.read()[1], replayed=step.graphs is not None, timeouts=ops.bn_resident_timeouts())
+
+
+@pytest.mark.parametrize('poison', GUARD_POISONS)
+@pytest.mark.parametrize('replayed', [False, True], ids=['eager', 'replayed'])
+@pytest.mark.parametrize('optimizer', ['sgd', 'adamw'])
+def test_a_non_finite_input_skips_its_updates_and_training_goes_on(rt, gpu, optimizer, replayed, poison):
+    """+Inf in one pixel of x_s, NaN in one element of label_s, +Inf in one pixel of x_t, in iteration 2 of 4.
+    x_s / label_s: update A is skipped.  x_t: update C is skipped, and B where the float64 torch step says its gradients are
+    non-finite.  A skipped update leaves everything its optimizers own bit-identical (parameters, momentum or Adam moments and
+    step counts, packed working copies) and is counted; the clean iterations before and after skip nothing, have finite losses
+    and move the parameters; the EMA teacher's weights stay finite.  The BatchNorm running statistics of the poisoned forward
+    may be non-finite (torch's are, tests/test_nonfinite_cpu.py): the guard does not cover them, the layers are recorded and
+    the assertion is only that iterations 3 and 4 do not care (train-mode BatchNorm normalises by batch statistics)."""
+    try:
+        r = _guard_run(gpu, optimizer, replayed, poison)
+    finally:
+        rt.set_compute_dtype('bf16')
+    assert r['replayed'] == replayed and r['timeouts'] == 0
+    want = {'a': poison in ('x_s', 'label_s'), 'b': False, 'c': poison == 'x_t'}
+    if poison == 'x_t':
+        want['b'] = _reference_says_b_is_non_finite()
+        assert want['b']          # (a +Inf pixel makes every feature NaN behind the first BatchNorm, in torch too)
+    log = r['log']
+    for it in (0, 2, 3):
+        e = log[it]
+        assert all(e['recs'][s]['skip'] == 0 and e['recs'][s]['coef'] == 1.0 and np.isfinite(e['recs'][s]['norm']) for s in 'abc'), (it, e['recs'])
+        assert all(np.isfinite(v) for v in e['losses'].values()), (it, e['losses'])
+        assert e['moved'] and e['teacher_ok'], it
+    e = log[1]
+    print('%s %s %s: running statistics non-finite after the poisoned iteration in %d tensors (%s ...); losses %s' % (
+        optimizer, 'replayed' if replayed else 'eager', poison, len(e['bad_stats']), ', '.join(e['bad_stats'][:3]), e['losses']))
+    assert e['teacher_ok']
+    assert set(e['watch']) - {'armed'} == {'a', 'b', 'c'}
+    for s in 'abc':
+        before, after, rec = e['watch'][s]
+        if want[s]:
+            assert rec['skip'] == 1 and rec['coef'] == 0.0 and not np.isfinite(rec['norm']), (s, rec)
+            assert _same_state(before, after), 'the skipped update %s changed what it owns' % s.upper()
+        else:
+            assert rec['skip'] == 0 and rec['coef'] == 1.0 and np.isfinite(rec['norm']), (s, rec)
+            assert not _same_state(before, after), s
+    assert r['n_skipped'] == sum(want.values())
+    assert log[2]['bad_stats'] == log[1]['bad_stats'] or set(log[2]['bad_stats']) <= set(log[1]['bad_stats'])
 
 
 # ---------------------------------------------------------------- 7. the command line
