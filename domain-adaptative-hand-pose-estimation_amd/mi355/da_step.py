@@ -241,12 +241,118 @@ class PrototypeAlign(_Term):
         self.set_m(state.get('m', self.m))
 
 
+class CrossDomainMixup:
+    """What ``DAStep(mixup=...)`` takes: a fourth stage, step M, behind update C.  The reference's ``mixup`` (uda/model/loss.py:13-24,
+    never called there: nothing builds heat-maps for the unlabelled target images) on the batch of the iteration: every source
+    image is blended with the target image of the same index by ``lam = max(mix, 1 - mix)``, ``mix ~ Beta(beta, beta)`` per sample,
+    the labels likewise, and the backbone, the neck and the main head are trained on the 2B blends with ``weight * KL``.  The
+    target heat-maps are the Gaussian at the arg-max (``PseudoLabelGenerator``) of the student's prediction ``y_t`` of step C
+    (``labels='student'``) or of the EMA teacher's on ``x_t_ema`` (``labels='teacher'``; with a ``MeanTeacher`` attached to the step,
+    its forward of step C is reused).  One ``mi355_mixup_pairs`` launch writes the blends into buffers this object owns.
+
+    The coefficients live in device memory at a fixed address (``lam``) and are written from the host before the iteration
+    (``draw``), from an RNG state this object owns -- seeded from ``seed`` and ``rank``; the global RNG is not advanced -- with the
+    reference's own expression (``uda.model.loss.draw_mixup_coefficients``).  ``state_dict()`` is what the epoch checkpoint keeps as
+    ``mixup_state``."""
+    key = 'mix'
+
+    def __init__(self, beta=1.0, weight=1.0, labels='student', ema=None, seed=0, rank=0):
+        from uda.model.loss import check_positive
+        check_positive('CrossDomainMixup: beta', beta)
+        check_positive('CrossDomainMixup: the weight', weight)
+        if labels not in ('student', 'teacher'):
+            raise ValueError("CrossDomainMixup: labels must be 'student' or 'teacher', got %r" % (labels,))
+        if labels == 'teacher' and ema is None:
+            raise ValueError("CrossDomainMixup: labels='teacher' needs an EMATeacher (--ema-update const|warmup)")
+        self.beta, self.weight, self.labels, self.ema = float(beta), float(weight), labels, ema
+        self.seed, self.rank = int(seed or 0), int(rank)
+        self._rng = self._seeded(0)
+        self.draws = 0
+        self.lam = None                  # (B,) fp32 on the device, fixed address
+        self.lam_host = None             # the coefficients of the last draw
+        self._bufs, self._gen, self._teacher = None, None, None
+
+    # ------------------------------------------------------------ coefficients
+    def draw(self, B=None, device=None):
+        """Draw the coefficients of the coming iteration and write them to the device (host work: outside graph capture)."""
+        from uda.model.loss import draw_mixup_coefficients
+        if self.lam is None:
+            if B is None:
+                raise RuntimeError('CrossDomainMixup: run one eager iteration before replaying graphs')
+            self.lam = torch.zeros(int(B), dtype=torch.float32, device=device)
+        with torch.random.fork_rng(devices=[]):          # the global CPU generator is put back as it was
+            torch.set_rng_state(self._rng)
+            lam = draw_mixup_coefficients(self.lam.numel(), self.beta)
+            self._rng = torch.get_rng_state()
+        self.draws += 1
+        self.lam_host = lam
+        self.lam.copy_(lam, non_blocking=True)
+        return lam
+
+    def _seeded(self, draws):
+        """The generator state of a rank that starts (draws = 0) or joins a resumed run whose checkpoint holds another rank's state."""
+        return torch.Generator().manual_seed(self.seed * 1000003 + 7919 * self.rank + 17 + 104729 * int(draws)).get_state()
+
+    def state_dict(self):
+        """The RNG state, the number of draws so far and the last coefficients (a CPU copy): what the checkpoint keeps."""
+        return {'rng_state': self._rng.clone(), 'draws': self.draws, 'beta': self.beta, 'rank': self.rank,
+                'lam': None if self.lam_host is None else self.lam_host.clone()}
+
+    def load_state_dict(self, state):
+        """Go on where the saved run was.  The checkpoint is rank 0's: another rank takes the number of draws and a state seeded
+        from (seed, rank, draws), so that the ranks keep drawing different coefficients."""
+        self.draws = int(state.get('draws', 0))
+        if int(state.get('rank', 0)) == self.rank:
+            self._rng = state['rng_state'].clone().to(torch.uint8).cpu()
+        else:
+            self._rng = self._seeded(self.draws)
+
+    # ------------------------------------------------------------ step M
+    def teacher(self, step):
+        """The in-iteration teacher whose folded operands follow the EMA update: the MeanTeacher's when the step has one."""
+        if step.mt is not None:
+            return step.mt.teacher
+        if self._teacher is None:
+            from .teacher import InIterationTeacher
+            self._teacher = InIterationTeacher(self.ema)
+        return self._teacher
+
+    def target_labels(self, step, batch):
+        """(B, K, H, W) Gaussians at the arg-max of the student's or the teacher's prediction on the target batch."""
+        from uda.model.regda_4 import PseudoLabelGenerator, cached_centres
+        if self.labels == 'student':
+            y = step.out['y_t']
+        else:
+            y = step.out.get('y_t_ema') if step.mt is not None else None      # step C's teacher forward, when there was one
+            if y is None:
+                x = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
+                y = self.teacher(step).forward(x)
+        K, H, W = y.shape[1:]
+        if self._gen is None or (self._gen.num_keypoints, self._gen.height, self._gen.width) != (K, H, W):
+            self._gen = PseudoLabelGenerator(K, H, W)
+        return self._gen.labels(y, kind=0, want_gf=False, xy=cached_centres(y))[0]
+
+    def blend(self, batch, hm_t):
+        """mixup_pairs(x_s, label_s, w_s, x_t, hm_t, w_t, lam) into the buffers of this object -> (x_mix, hm_mix, w_mix)."""
+        f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+        ops_in = [f32(batch[k]) for k in ('x_s', 'label_s', 'w_s', 'x_t')] + [hm_t, f32(batch['w_t'])]
+        sig = tuple(tuple(t.shape) for t in ops_in)
+        if self._bufs is None or self._bufs[0] != sig:
+            if torch.cuda.is_current_stream_capturing():
+                raise _rt.Mi355Error('CrossDomainMixup: the blend buffers would be allocated during graph capture; run one eager iteration first')
+            B, dev = ops_in[0].shape[0], ops_in[0].device
+            self._bufs = (sig, tuple(torch.empty((2 * B,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in ops_in[:3]))
+        if self.lam is None or self.lam.numel() != ops_in[0].shape[0]:
+            raise _rt.Mi355Error('CrossDomainMixup: no coefficients for a batch of %d: draw() first' % ops_in[0].shape[0])
+        return ops.mixup_pairs(*ops_in, self.lam, out=self._bufs[1])
+
+
 class DAStep:
-    """Holds the static batch buffers and runs A/B/C.  ``optimizers`` = dict with keys f, h, h_adv, h_adv2,
+    """Holds the static batch buffers and runs A/B/C (and M, with ``mixup``).  ``optimizers`` = dict with keys f, h, h_adv, h_adv2,
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
     def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None,
-                 proto=None, clip=None):
+                 proto=None, clip=None, mixup=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         # optional mi355.optim.GradClipper (may also be assigned after construction): each of the three updates takes the global
         # gradient norm of everything it steps (A: f and the four heads, B: the adversarial heads, C: f), behind the gradient
@@ -257,6 +363,10 @@ class DAStep:
         # mi355.teacher.MeanTeacher, whose folded operands are refreshed behind the EMA update, an MMDAlign, a JointFeatureAlign,
         # a PrototypeAlign
         self.mt, self.mmd, self.jfa, self.proto = mt, mmd, jfa, proto
+        # optional CrossDomainMixup (may also be assigned after construction): step M behind update C -- one forward and backward
+        # of the 2B blended images through the backbone, the neck and the main head, then update M of optimizer_f and optimizer_h.
+        # The EMA update and the teacher's refresh then move behind update M.  None: nothing is launched, nothing moves.
+        self.mixup = mixup
         if mt is not None and self.ema is None:
             self.ema = mt.ema
         self.trade_off, self.skip, self.track_acc = trade_off, skip_discarded, track_accuracy
@@ -432,10 +542,37 @@ class DAStep:
 
     def _update_C(self):
         self._step(('f',), 'c')
+        if self.mixup is None:
+            self._update_ema()
+
+    def _update_ema(self):
+        """Behind the last optimizer step of the iteration (update C; update M with mixup)."""
         if self.ema is not None:
             self.ema.update()
             if self.mt is not None:
                 self.mt.teacher.refresh()        # the teacher's folded operands follow its weights, in place
+            if self.mixup is not None and self.mixup._teacher is not None:
+                self.mixup._teacher.refresh()    # (labels='teacher' without a MeanTeacher: the mixup's own in-iteration teacher)
+
+    KM = ('f', 'h')                              # what update M steps
+
+    def _fwdbwd_M(self, b):
+        """Step M: the blends of the source and the target batch through backbone, neck and main head, weight * KL against the
+        blended labels.  The adversarial heads never see the blended images."""
+        m, c, mx = self.model, self.crit, self.mixup
+        for k in self.KM:
+            self.opt[k].zero_grad()
+        x_mix, hm_mix, w_mix = mx.blend(b, mx.target_labels(self, b))
+        with _rt.grouped_wgrads():
+            y_mix = m.head(m.features(x_mix))
+            loss_mix = c['kl'](y_mix, hm_mix, w_mix, scale=mx.weight)
+            loss_mix.backward(_rt.unit_grad(loss_mix))
+        _rt.join_side()
+        self.out.update(loss_mix=loss_mix.detach())
+
+    def _update_M(self):
+        self._step(self.KM, 'm')
+        self._update_ema()
 
     def _accuracy(self, b):
         """Device side of the four accuracy() calls of train1.py:464-475: arg-max coordinates + PCK distances."""
@@ -480,7 +617,11 @@ class DAStep:
         _CENTRES.clear()
         self.model.train()
         if self.clip is not None:
+            if self.mixup is not None:
+                self.clip.ensure_slot('m')       # a fourth record for update M (the three-slot layout is untouched without mixup)
             self.clip.sync()
+        if self.mixup is not None:
+            self.mixup.draw(batch['x_s'].shape[0], batch['x_s'].device)
         self._begin_reduce(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'))
         self._fwdbwd_A(batch)
         self._end_reduce(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'))
@@ -494,16 +635,21 @@ class DAStep:
         if self.ema is not None:
             self.ema.sync()
         self._update_C()
+        if self.mixup is not None:
+            self._begin_reduce(self.KM)
+            self._fwdbwd_M(batch)
+            self._end_reduce(self.KM)
+            self._update_M()
         self._accuracy(batch)
         self.model.step()
         return self.out
 
     # ------------------------------------------------------------------ graph capture / replay
     def capture(self, batch, warmup=3):
-        """Capture the iteration as six HIP graphs (fwd+bwd and update of A, B, C) over static copies of
+        """Capture the iteration as six HIP graphs (fwd+bwd and update of A, B, C; eight with `mixup`: those of M) over static copies of
         `batch`; the gradient all-reduces run eagerly between them.  Everything that changes per iteration
         (inputs, learning rates, GL lambda, the EMA coefficients, the clipper's max_norm) is read from device memory.  With an EMA teacher attached its
-        update is captured into the last update graph, behind optimizer_f's step, where the eager iteration has it."""
+        update is captured into the last update graph, behind the iteration's last optimizer step, where the eager iteration has it."""
         self.model.train()
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
         side = torch.cuda.Stream()
@@ -533,6 +679,13 @@ class DAStep:
         else:
             seg_a, seg_b, seg_c = (lambda: self._fwdbwd_A(self.static)), (lambda: self._fwdbwd_B(self.static)), (lambda: self._fwdbwd_C(self.static))
         segs = [seg_a, self._update_A, seg_b, self._update_B, seg_c, lambda: (self._update_C(), self._accuracy(self.static))]
+        if self.mixup is not None:               # two more graphs; the EMA launches sit in the last one, behind update M
+            if self.exchange_captured:
+                def seg_m():
+                    self._begin_reduce(self.KM); self._fwdbwd_M(self.static); self._end_reduce(self.KM)
+            else:
+                seg_m = lambda: self._fwdbwd_M(self.static)
+            segs += [seg_m, self._update_M]
         mode = _rt.graph_capture_mode()        # 'thread_local' beside an RCCL process group (its watchdog thread polls events)
         graphs = []
         with _rt.no_gc_in_capture():
@@ -586,6 +739,8 @@ class DAStep:
             self.mt.sync()
         if self.clip is not None:
             self.clip.sync()
+        if self.mixup is not None:
+            self.mixup.draw()                # the coefficients of this iteration, to their fixed device address
 
     def replay(self, batch=None):
         if batch is not None and batch is not self.static:
@@ -607,8 +762,12 @@ class DAStep:
             g[4].replay()
             _allreduce_mean(self._grads(('f',)))
             g[5].replay()
+            if len(g) > 6:                   # step M
+                g[6].replay()
+                _allreduce_mean(self._grads(self.KM))
+                g[7].replay()
         if self.ema is not None:
-            self.ema.mark_updated()          # the launches sit in the last graph (_update_C)
+            self.ema.mark_updated()          # the launches sit in the last graph (_update_C; _update_M with mixup)
         self.model.step()
         return self.out
 

@@ -1266,6 +1266,49 @@ def mse_heatmap(pred, target, rec, want_grad, rows=None, grad=None):
     return rows, (grad if want_grad else None)
 
 
+# ---------------------------------------------------------------- cross-domain mixup (csrc/mixup.hip)
+def _dense_f32(who, what, t):
+    """`t` must be an fp32 device tensor whose elements lie in memory in index order without gaps (its first byte may sit
+    anywhere: the kernel takes scalar accesses when a base is not 16-byte aligned)."""
+    _chk_dev(t)
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise Mi355Error('%s: %s must be a dense fp32 tensor, got %s %s strides %s' % (who, what, t.dtype, tuple(t.shape), t.stride()))
+
+
+def mixup_pairs(x_s, hm_s, w_s, x_t, hm_t, w_t, lam, out=None):
+    """The two blends of uda/model/loss.py:13-24 in one launch.  x_s, x_t (B, C, S, S); hm_s, hm_t (B, K, H, W); w_s, w_t (B, K) or
+    (B, K, 1); lam: B fp32 values on the device, already max(mix, 1 - mix).  Returns (x_mix (2B, C, S, S), hm_mix (2B, K, H, W),
+    w_mix (2B,) + w_s.shape[1:]): rows [0, B) are a_s * lam + a_t * (1 - lam), rows [B, 2B) a_t * lam + a_s * (1 - lam), w_mix is
+    max(w_s, w_t) twice.  `out`: that triple, to be written in place (a training step keeps it at fixed addresses)."""
+    who = 'mixup_pairs'
+    for what, t in (('x_s', x_s), ('x_t', x_t), ('hm_s', hm_s), ('hm_t', hm_t), ('w_s', w_s), ('w_t', w_t), ('lam', lam)):
+        _dense_f32(who, what, t)
+    if x_s.dim() != 4 or hm_s.dim() != 4 or w_s.dim() not in (2, 3):
+        raise Mi355Error('%s: needs (B, C, S, S) images, (B, K, H, W) heat-maps and (B, K) weights, got %s, %s, %s'
+                         % (who, tuple(x_s.shape), tuple(hm_s.shape), tuple(w_s.shape)))
+    for what, a, b in (('x', x_s, x_t), ('hm', hm_s, hm_t), ('w', w_s, w_t)):
+        if tuple(a.shape) != tuple(b.shape):
+            raise Mi355Error('%s: %s_s %s vs %s_t %s' % (who, what, tuple(a.shape), what, tuple(b.shape)))
+    B, K = x_s.shape[0], hm_s.shape[1]
+    if hm_s.shape[0] != B or w_s.shape[0] != B or w_s.numel() != B * K or lam.numel() != B:
+        raise Mi355Error('%s: %d images, heat-maps %s, weights %s, %d coefficients' % (who, B, tuple(hm_s.shape), tuple(w_s.shape), lam.numel()))
+    if B < 1 or x_s[0].numel() < 1 or hm_s[0].numel() < 1:
+        raise Mi355Error('%s: empty operand (images %s, heat-maps %s)' % (who, tuple(x_s.shape), tuple(hm_s.shape)))
+    shapes = ((2 * B,) + tuple(x_s.shape[1:]), (2 * B,) + tuple(hm_s.shape[1:]), (2 * B,) + tuple(w_s.shape[1:]))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float32, device=x_s.device) for s in shapes)
+    x_mix, hm_mix, w_mix = out
+    for what, t, s in (('x_mix', x_mix, shapes[0]), ('hm_mix', hm_mix, shapes[1]), ('w_mix', w_mix, shapes[2])):
+        _dense_f32(who, what, t)
+        if tuple(t.shape) != s:                      # (dense and of this shape: room for everything the launch writes)
+            raise Mi355Error('%s: %s has shape %s, the launch writes %s' % (who, what, tuple(t.shape), s))
+    if len({t.device for t in (x_s, x_t, hm_s, hm_t, w_s, w_t, lam, x_mix, hm_mix, w_mix)}) != 1:
+        raise Mi355Error('%s: the operands live on different devices' % who)
+    call('mi355_mixup_pairs', ptr(x_s), ptr(x_t), ptr(hm_s), ptr(hm_t), ptr(w_s), ptr(w_t), ptr(lam), ptr(x_mix), ptr(hm_mix),
+         ptr(w_mix), int(B), x_s[0].numel(), hm_s[0].numel(), int(K), stream_ptr())
+    return x_mix, hm_mix, w_mix
+
+
 # ---------------------------------------------------------------- MMD alignment (csrc/mmd.hip)
 MMD_MAX_ROWS, MMD_MAX_KERNELS = 256, 8
 _mmd_ws = {}

@@ -447,6 +447,18 @@ class GradClipper:
     ``measure`` behind the gradient all-reduce: every rank then derives the same coefficient from the same bytes."""
     SLOTS = ('a', 'b', 'c')
 
+    def ensure_slot(self, slot):
+        """One more record behind the existing ones (update M of a DAStep with mixup: 'm'), outside graph capture; the records of
+        the existing slots keep their values.  Nothing happens when the slot exists."""
+        if slot in self.SLOTS:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('GradClipper: slot %r would be added during graph capture; run one eager iteration first' % (slot,))
+        more = ops.clip_records(1, self._synced, self.device)
+        self.recs = torch.cat([self.recs, more])
+        self._f32 = self.recs.view(torch.float32)
+        self.SLOTS = tuple(self.SLOTS) + (slot,)     # (an instance attribute from here on)
+
     def __init__(self, max_norm, device):
         max_norm = float(max_norm)
         if not max_norm > 0:                       # (NaN fails the comparison too)

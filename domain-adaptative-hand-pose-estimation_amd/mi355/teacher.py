@@ -232,4 +232,4 @@ class MeanTeacher:
         y_ema = self.teacher.forward(x_t_ema)
         if not torch.cuda.is_current_stream_capturing():
             self.sync(y_t_grad.shape)
-        return self.loss(y_t_grad, y_ema), {}
+        return self.loss(y_t_grad, y_ema), {'y_t_ema': y_ema}     # (kept: step M's teacher labels reuse this forward)

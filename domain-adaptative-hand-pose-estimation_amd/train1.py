@@ -12,7 +12,9 @@ uda/model/loss.py:1061-1104), ``--jfa-loss {off,on}`` with ``--jfa-weight`` / ``
 neck features pooled around the predicted key points of the target batch with those of the source batch in step C: the
 reference's unused ``loss3``, train1.py:25 and uda/model/loss.py:331-378), ``--proto-loss {off,kl,softkl}`` with ``--proto-weight`` /
 ``--proto-radius`` / ``--proto-axes`` / ``--proto-m`` (alignment of per-joint class prototypes of those features, blended with a running
-memory per domain: the reference's unused ``lossx`` / ``lossx3``, uda/model/loss.py:381-466 and 560-652), ``--clip-grad-norm FLOAT``
+memory per domain: the reference's unused ``lossx`` / ``lossx3``, uda/model/loss.py:381-466 and 560-652), ``--mixup {off,on}`` with ``--mixup-beta`` / ``--mixup-weight`` /
+``--mixup-labels`` (a fourth stage behind update C that trains the backbone and the main head on cross-domain blends of the source
+and the target batch, with Gaussian pseudo-labels for the target side: the reference's unused ``mixup``, uda/model/loss.py:13-24), ``--clip-grad-norm FLOAT``
 (global gradient-norm clipping of each of the three updates with a non-finite step guard, on the device; not in the reference), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
@@ -54,7 +56,7 @@ from torch.utils.data.distributed import DistributedSampler
 import mi355
 import uda.model as models
 from mi355 import ops as _ops
-from mi355.da_step import JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
+from mi355.da_step import CrossDomainMixup, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
 from mi355.optim import EMATeacher, GradClipper, check_state_dict_kind, make_optimizer
 from mi355.teacher import MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
@@ -170,15 +172,17 @@ def main(args):
     print("Source train:", len(train_source_loader)); print("Target train:", len(train_target_loader))
     print("Source test:", len(val_source_loader)); print("Target test:", len(val_target_loader))
     train_source_iter, train_target_iter = ForeverDataIterator(train_source_loader), ForeverDataIterator(train_target_loader)
+    # who reads the teacher's view of the target batch (meta['image_ema']): the consistency term, and mixup labelled by the teacher
+    want_ema = args.mt_loss == 'on' or (args.mixup == 'on' and args.mixup_labels == 'teacher')
     if args.device_augment and not args.synthetic:
         # packed sources -> HBM, augmentation and heat-map labels on the GPU (mi355.augment, utils.labels)
         dev_aug = lambda it, ema=False: DeviceAugmentIterator(it, device, args.image_size, args.heatmap_size, want_ema=ema)
         # (--mt-loss: the target batches also carry meta['image_ema'], the geometry-only image the teacher sees)
-        train_source_iter, train_target_iter = dev_aug(train_source_iter), dev_aug(train_target_iter, args.mt_loss == 'on')
+        train_source_iter, train_target_iter = dev_aug(train_source_iter), dev_aug(train_target_iter, want_ema)
     else:
         # host -> HBM copies of the next batch overlap the current step (pinned, double-buffered, side stream)
         # (--mt-loss: meta['image_ema'] of the target batches travels with them instead of as a blocking copy inside the iteration)
-        ema_keys = ('image_ema',) if args.mt_loss == 'on' and not args.synthetic else ()
+        ema_keys = ('image_ema',) if want_ema and not args.synthetic else ()
         train_source_iter = DevicePrefetcher(train_source_iter, device)
         train_target_iter = DevicePrefetcher(train_target_iter, device, meta_keys=ema_keys)
 
@@ -219,6 +223,10 @@ def main(args):
     if args.proto_loss != 'off':
         step.proto = PrototypeAlign(weight=args.proto_weight, radius=args.proto_radius, axes=args.proto_axes, m=args.proto_m,
                                     criterion=args.proto_loss)
+    if args.mixup == 'on':
+        # step M behind update C: blends of the two batches through backbone, neck and main head (mi355.da_step.CrossDomainMixup)
+        step.mixup = CrossDomainMixup(beta=args.mixup_beta, weight=args.mixup_weight, labels=args.mixup_labels, ema=ema,
+                                      seed=args.seed, rank=RANK)
     if args.clip_grad_norm > 0:
         # each update clips the global norm of what it steps and skips itself when that norm is not finite (mi355.optim.GradClipper)
         step.clip = GradClipper(args.clip_grad_norm, device)
@@ -276,6 +284,8 @@ def main(args):
                 ema.load_state_dict(ck['ema_state'])
         if getattr(step, 'proto', None) is not None and 'proto_state' in ck:
             step.proto.load_state_dict(ck['proto_state'], device)      # both prototype memories and m
+        if step.mixup is not None and 'mixup_state' in ck:
+            step.mixup.load_state_dict(ck['mixup_state'])               # the RNG state of the blend coefficients (rank 0's)
     broadcast_module(model)                              # replicas start bit-identical whatever each rank loaded
     broadcast_module(model_ema)
 
@@ -312,6 +322,8 @@ def main(args):
         ck_extra = {'ema_state': ema.state_dict()} if ema is not None else {}
         if getattr(step, 'proto', None) is not None:
             ck_extra['proto_state'] = step.proto.state_dict()
+        if step.mixup is not None:
+            ck_extra['mixup_state'] = step.mixup.state_dict()
         torch.save({'model': model.state_dict(), **ck_extra,
                     'optimizer_f': opts['f'].state_dict(), 'optimizer_h': opts['h'].state_dict(),
                     'optimizer_h_adv': opts['h_adv'].state_dict(),
@@ -375,12 +387,15 @@ def _pck(dists, thr=0.5):
 def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     names = ['Time', 'Data', 'Loss (s)', 'Loss (t, false)', 'Loss (t, truth)', 'Acc (s)', 'Acc (t)', 'Acc (s, adv)', 'Acc (t, adv)']
     fmts = [':4.2f', ':3.1f', ':.2e', ':.2e', ':.2e', ':3.2f', ':3.2f', ':3.2f', ':3.2f']
-    mt, terms = step.mt, step.terms()
+    mt, terms, mixup = step.mt, step.terms(), step.mixup
     if mt is not None:
         mt.set_epoch(epoch)                              # m and k are functions of the epoch (train1.py:351-353)
-    names, fmts = names + ['Loss (%s)' % t.key for t in terms], fmts + [':.2e'] * len(terms)
-    clip, n_fixed = step.clip, 9 + len(terms)
-    if clip is not None:                                 # the gradient norms of the three updates, read when a line is printed
+    keys = [t.key for t in terms] + (['mix'] if mixup is not None else [])
+    names, fmts = names + ['Loss (%s)' % k for k in keys], fmts + [':.2e'] * len(keys)
+    clip, n_fixed = step.clip, 9 + len(keys)
+    if clip is not None:                                 # the gradient norms of the updates, read when a line is printed
+        if mixup is not None:
+            clip.ensure_slot('m')                        # update M's record
         names, fmts = names + ['GradNorm (%s)' % s.upper() for s in clip.SLOTS], fmts + [':.2e'] * len(clip.SLOTS)
     meters = [AverageMeter(n, f) for n, f in zip(names, fmts)]
     progress = ProgressMeter(args.iters_per_epoch, meters, prefix="Epoch: [{}]".format(epoch))
@@ -390,7 +405,7 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
         x_t, label_t, weight_t, meta_t = next(train_target_iter)
         to = lambda t: t.to(device, non_blocking=True)
         batch = dict(x_s=to(x_s), label_s=to(label_s), w_s=to(weight_s), x_t=to(x_t), w_t=to(weight_t), label_t=to(label_t))
-        if mt is not None:                               # x_t_ema = meta_t['image_ema'] (train1.py:364); synthetic images have no augmentation
+        if mt is not None or (mixup is not None and mixup.labels == 'teacher'):   # x_t_ema = meta_t['image_ema'] (train1.py:364); synthetic images have no augmentation
             batch['x_t_ema'] = batch['x_t'] if args.synthetic else to(meta_t['image_ema'])
         meters[1].update(time.time() - end)
         # HIP-graph replay once this process has run three eager iterations (whatever epoch it resumed at).  With several
@@ -413,7 +428,7 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
                     step.capture(batch, warmup=0)
                 continue                                      # (the timed iteration was a real one)
             step.capture(batch, warmup=0)
-            print('HIP graphs captured: iterations replay six graphs from here on')
+            print('HIP graphs captured: iterations replay %s graphs from here on' % ('six' if len(step.graphs) == 6 else len(step.graphs)))
         elif step.graphs is None and step.eager_iters == 0:
             print('eager kernel launches%s' % (' with the gradient exchange overlapped with the backward' if WORLD > 1 else ''))
         step.eager_iters += 1
@@ -425,8 +440,8 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
                 m.update(float(out[k]), args.batch_size)
             for m, k in zip(meters[5:9], ('pck_s', 'pck_t', 'pck_s_adv', 'pck_t_adv')):
                 a, c = _pck(out[k]); m.update(a, c)
-            for m, t in zip(meters[9:], terms):
-                m.update(float(out['loss_' + t.key]), args.batch_size)
+            for m, k in zip(meters[9:], keys):
+                m.update(float(out['loss_' + k]), args.batch_size)
             if clip is not None:
                 norms = clip.read()[0]
                 for m, s in zip(meters[n_fixed:], clip.SLOTS):
@@ -661,8 +676,26 @@ _OPTIONS = [
                             "reference's indexing, x selects the rows (uda/model/loss.py:421)")),
     (('--proto-m',), dict(default=0.999, type=float, metavar='FLOAT', help="weight m of the current batch in the prototype, the memory "
                          "gets 1 - m (0 < m <= 1; 0.999 is the reference's constant, uda/model/loss.py:400)")),
+    (('--mixup',), dict(default='off', choices=['off', 'on'], help="cross-domain mixup: a fourth stage (step M) behind update C blends "
+                       "every source image with the target image of the same index by max(l, 1 - l), l ~ Beta(b, b), the heat-map "
+                       "labels likewise -- the reference's unused mixup, uda/model/loss.py:13-24, as one mixup_ kernel launch -- and "
+                       "trains the backbone, the neck and the main head on the 2 B blends with w * KL (one more forward and backward, "
+                       "then update M of optimizer_f and optimizer_h; the EMA update moves behind it); the target side is labelled "
+                       "with Gaussians at the arg-max of a prediction (--mixup-labels); the coefficients come from an RNG state of "
+                       "their own, seeded from --seed and the rank, kept in the epoch checkpoint (mixup_state); 'off': nothing is "
+                       "launched")),
+    (('--mixup-beta',), dict(default=1.0, type=float, metavar='FLOAT', help='concentration b of the Beta(b, b) the blend coefficients '
+                            'are drawn from (positive; the default is a placeholder: its effect on convergence has not been measured, '
+                            'and cannot be without the data sets)')),
+    (('--mixup-weight',), dict(default=1.0, type=float, metavar='FLOAT', help='weight w of the mixup loss (constant, positive; the '
+                              'default is a placeholder: its effect on convergence has not been measured, and cannot be without the '
+                              'data sets)')),
+    (('--mixup-labels',), dict(default='student', choices=['student', 'teacher'], help="whose prediction on the target batch labels "
+                              "it for --mixup: 'student' = the model's own y_t of step C; 'teacher' = the EMA teacher's on its view of "
+                              "the target batch (needs --ema-update const|warmup; with --mt-loss on the teacher's forward of step C "
+                              "is reused)")),
     (('--clip-grad-norm',), dict(default=0.0, type=_clip_norm, metavar='FLOAT', help="global gradient-norm clipping with a non-finite "
-                                "step guard: each of the updates A, B, C (and the pre-training step) clips over everything it steps, as "
+                                "step guard: each of the updates A, B, C (M with --mixup on; and the pre-training step) clips over everything it steps, as "
                                 "clip_grad_norm_(those parameters, FLOAT) before the optimizers would, in two launches per update and "
                                 "inside the SGD kernels; an update whose norm is inf or NaN is skipped and counted ('skipped steps:'); "
                                 "'inf' measures and guards without scaling; 0: off, nothing is launched")),
@@ -706,7 +739,13 @@ class _Parser(argparse.ArgumentParser):
         args = super().parse_args(*a, **kw)
         if getattr(args, 'mt_loss', 'off') == 'on' and getattr(args, 'ema_update', 'off') == 'off':
             self.error('--mt-loss on needs a moving teacher: add --ema-update const (or warmup)')
+        if getattr(args, 'mixup', 'off') == 'on' and getattr(args, 'mixup_labels', 'student') == 'teacher' and \
+                getattr(args, 'ema_update', 'off') == 'off':
+            self.error('--mixup-labels teacher needs a moving teacher: add --ema-update const (or warmup)')
         try:                                             # (the checks the term classes make, under the flags' names)
+            if getattr(args, 'mixup', 'off') == 'on':
+                check_positive('--mixup-beta', args.mixup_beta)
+                check_positive('--mixup-weight', args.mixup_weight)
             if getattr(args, 'mmd_loss', 'off') == 'on':
                 check_positive('--mmd-weight', args.mmd_weight)
                 check_whole('--mmd-kernels', args.mmd_kernels, 8)

@@ -14,6 +14,36 @@ from mi355 import ops
 import mi355 as _rt
 
 
+# ---------------------------------------------------------------- cross-domain mixup (reference uda/model/loss.py:13-24)
+def draw_mixup_coefficients(batch, beta):
+    """The B coefficients of the reference's mixup, drawn as it draws them (uda/model/loss.py:14-17): Beta(beta, beta) with
+    float32 concentrations, ``rsample((B, 1, 1, 1))`` on the CPU from the global RNG, then ``max(mix, 1 - mix)``.  (B,) fp32."""
+    check_positive('mixup: beta', beta)
+    m = torch.distributions.beta.Beta(torch.tensor(float(beta)), torch.tensor(float(beta)))
+    mix = m.rsample(sample_shape=(int(batch), 1, 1, 1))
+    return torch.max(mix, 1 - mix).reshape(-1)
+
+
+def mixup(img_src, hm_src, weights_src, img_trg, hm_trg, weights_trg, beta, mix=None):
+    """The reference's ``mixup`` (name, positional signature and 6-tuple), as one ``mi355_mixup_pairs`` launch: returns
+    ``(img_src_mix, hm_src_mix, weights, img_trg_mix, hm_trg_mix, weights)`` with the source-dominant blends ``a_src * mix + a_trg *
+    (1 - mix)``, the target-dominant ones ``a_trg * mix + a_src * (1 - mix)`` and ``weights = max(weights_src, weights_trg)``, the
+    same object twice.  The six results are views into the kernel's three outputs.  ``mix=None`` draws the coefficients as the
+    reference does (``draw_mixup_coefficients``: the same ``torch.manual_seed`` gives the same blends); ``mix=`` B values (any
+    device) are taken as they are -- the reference's ``mix`` behind its ``max(mix, 1 - mix)`` -- and nothing is drawn.  All inputs
+    are data: no autograd graph is built."""
+    B = img_src.size(0)
+    if mix is None:
+        mix = draw_mixup_coefficients(B, beta)
+    lam = torch.as_tensor(mix, dtype=torch.float32).detach().reshape(-1).to(img_src.device).contiguous()
+    if lam.numel() != B:
+        raise ValueError('mixup: %d coefficients for a batch of %d' % (lam.numel(), B))
+    dense = lambda t: t.detach().float().contiguous()
+    x, hm, w = ops.mixup_pairs(dense(img_src), dense(hm_src), dense(weights_src), dense(img_trg), dense(hm_trg), dense(weights_trg), lam)
+    weights = w[:B]
+    return x[:B], hm[:B], weights, x[B:], hm[B:], weights
+
+
 class _KLFn(torch.autograd.Function):
     """loss = coeff * mean(rows).  The kernel already writes d loss / d pred; the backward multiplies it by the incoming
     gradient unless that is the shared unit scalar of ``mi355.unit_grad`` (``loss.backward(mi355.unit_grad(loss))``: the

@@ -682,6 +682,25 @@ int mi355_proto_kl(const float* proto_t, const float* proto_s, float* rows, floa
 int mi355_proto_scatter(const float* grad_proto, const float* xy, const float* blend, void* grad_feature, int accumulate, int B, int K,
                         int C, int H, int W, int radius, int rows_by_x, int dtype, void* stream);
 
+/* ---------------------------------------------------------------- cross-domain mixup (csrc/mixup.hip)
+ * mixup of uda/model/loss.py:13-24, the first function of that file, which the reference never calls: every source sample
+ * blended with the target sample of the same index by a per-sample coefficient, images, heat-maps and joint weights in ONE
+ * launch.  Dense fp32 operands: x_s, x_t [B][img_plane] (img_plane = C * S * S of an NCHW image), hm_s, hm_t [B][hm_plane]
+ * (hm_plane = K * H * W), w_s, w_t [B][K], lam [B] in DEVICE memory, already max(mix, 1 - mix) (:17).  With om = fl(1.0f - lam[b]):
+ *   x_mix[b]      = fl(fl(x_s[b] * lam[b]) + fl(x_t[b] * om))       the source-dominant blend (:19-20), rows [0, B)
+ *   x_mix[B + b]  = fl(fl(x_t[b] * lam[b]) + fl(x_s[b] * om))       the target-dominant blend (:21-22), rows [B, 2B)
+ * and hm_mix [2B][hm_plane] likewise; w_mix [2B][K] = max(w_s, w_t) in both halves (:23-24).  Three fp32 roundings per element
+ * as in torch's expression, nothing contracted into an FMA.  Every input element is read once and feeds both blends.  A stream:
+ * at most MI355_MIXUP_MAX_BLOCKS blocks of 256 lanes with a grid-stride loop, 16-byte accesses when x_s, x_t, x_mix (hm_s, hm_t,
+ * hm_mix) are all 16-byte aligned -- the coefficient is looked up per element, a vector may straddle samples -- and scalar
+ * accesses otherwise; pointers need 4-byte alignment only.  Refused with MI355_EINVAL before any launch: a null pointer, B < 1, a
+ * plane or K below 1, B * plane above 2^40, an output range that overlaps an input range or another output.  Finite operands;
+ * what a NaN weight gives is not part of the contract.  Never allocates; capturable. */
+#define MI355_MIXUP_MAX_BLOCKS 2048
+int mi355_mixup_pairs(const float* x_s, const float* x_t, const float* hm_s, const float* hm_t, const float* w_s, const float* w_t,
+                      const float* lam, float* x_mix, float* hm_mix, float* w_mix, int B, long img_plane, long hm_plane, int K,
+                      void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
