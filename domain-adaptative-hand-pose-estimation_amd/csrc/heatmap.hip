@@ -242,6 +242,114 @@ __global__ __launch_bounds__(256) void kl_heatmap_reg_kernel(const float* __rest
   }
 }
 
+// Coordinate loss on the soft-arg-max (see mi355pose.h).  The soft-arg-max is utils/keypoint_detection.py:209-239; the loss
+// on it and its gradient are NOT in the reference (integral regression, Sun et al. 2018: PAPERS.md).
+// h = smooth-L1 with threshold delta (torch smooth_l1_loss(beta=delta)); delta == 0: L1.  A NaN stays a NaN in both.
+__device__ __forceinline__ float coord_h(float d, float delta) {
+  const float a = fabsf(d);
+  return (delta > 0.f && a < delta) ? 0.5f * d * d / delta : a - 0.5f * delta;
+}
+__device__ __forceinline__ float coord_dh(float d, float delta) {
+  if (delta > 0.f && fabsf(d) < delta) return d / delta;
+  return d > 0.f ? 1.f : (d < 0.f ? -1.f : d);             // sign(d): 0 for +-0, NaN for NaN
+}
+// what every thread of a map holds behind the three sums: the row loss and the two factors of the gradient
+struct CoordRow { float u, v, hx, hy, loss; bool skip; };
+__device__ __forceinline__ CoordRow coord_row(float s, float su, float sv, const float* __restrict__ coord, const float* __restrict__ weight,
+                                              int m, float delta) {
+  CoordRow r;
+  r.u = su / s; r.v = sv / s;
+  const float dx = r.u - coord[2 * m], dy = r.v - coord[2 * m + 1];
+  const float w = weight ? weight[m] : 1.f;
+  r.skip = w == 0.f;                                        // selection, not multiplication: whatever the row holds
+  r.loss = r.skip ? 0.f : w * (coord_h(dx, delta) + coord_h(dy, delta));
+  r.hx = w * coord_dh(dx, delta); r.hy = w * coord_dh(dy, delta);
+  return r;
+}
+
+__global__ __launch_bounds__(256) void coord_heatmap_kernel(const float* __restrict__ pred, const float* __restrict__ coord,
+                                                             const float* __restrict__ weight, float beta, float delta, float coef,
+                                                             float* __restrict__ loss_rows, float* __restrict__ unit_grad,
+                                                             float* __restrict__ uv, unsigned HW, unsigned W) {      // (unsigned: i + 256 stays representable below 2^31 + 256)
+  __shared__ float red[4];
+  const int m = blockIdx.x;
+  const size_t base = (size_t)m * HW;
+  const float* row = pred + base;
+  float mx = -INFINITY;
+  for (unsigned i = threadIdx.x; i < HW; i += 256) mx = fmaxf(mx, row[i] * beta);
+  mx = block_max<4>(mx, red);
+  float s = 0.f, su = 0.f, sv = 0.f;
+  for (unsigned i = threadIdx.x; i < HW; i += 256) {
+    const float e = expf(row[i] * beta - mx);
+    s += e; su += e * (float)(i % W); sv += e * (float)(i / W);
+  }
+  s = block_sum<4>(s, red); su = block_sum<4>(su, red); sv = block_sum<4>(sv, red);
+  const CoordRow r = coord_row(s, su, sv, coord, weight, m, delta);
+  if (threadIdx.x == 0) {
+    loss_rows[m] = r.loss;
+    if (uv) { uv[2 * m] = r.u; uv[2 * m + 1] = r.v; }
+  }
+  if (unit_grad) {
+    float* g = unit_grad + base;
+    const float k = coef * beta;
+    for (unsigned i = threadIdx.x; i < HW; i += 256) {
+      const float p = expf(row[i] * beta - mx) / s;
+      const float t = ((float)(i % W) - r.u) * r.hx + ((float)(i / W) - r.v) * r.hy;
+      g[i] = r.skip ? 0.f : k * p * t;
+    }
+  }
+}
+
+template <int NV, bool WPM>
+__global__ __launch_bounds__(256) void coord_heatmap_reg_kernel(const float* __restrict__ pred, const float* __restrict__ coord,
+                                                                 const float* __restrict__ weight, float beta, float delta, float coef,
+                                                                 float* __restrict__ loss_rows, float* __restrict__ unit_grad,
+                                                                 float* __restrict__ uv, int rows, int W) {
+  using G = RowGeom<NV, WPM>;
+  constexpr int HW = 4 * NV * G::kThreads;
+  __shared__ float red[4];
+  __shared__ float red3[12];
+  const int m = G::map();
+  if (WPM && m >= rows) return;                              // (wave-uniform: a whole wave owns a map)
+  const size_t base = (size_t)m * HW;
+  float v[4 * NV];
+  row_load<NV, WPM>(pred + base, v);
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < 4 * NV; ++k) mx = fmaxf(mx, v[k] * beta);
+  mx = G::max(mx, red);
+  float s = 0.f, su = 0.f, sv = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = row_index<NV, WPM>(j, e);
+      const float ex = expf(v[4 * j + e] * beta - mx);
+      s += ex; su += ex * (float)(i % W); sv += ex * (float)(i / W);
+      v[4 * j + e] = ex;                                     // (kept for the gradient)
+    }
+  G::sum3(s, su, sv, red3);
+  const CoordRow r = coord_row(s, su, sv, coord, weight, m, delta);
+  if (G::tid() == 0) {
+    loss_rows[m] = r.loss;
+    if (uv) { uv[2 * m] = r.u; uv[2 * m + 1] = r.v; }
+  }
+  if (unit_grad) {
+    const float k = coef * beta;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      float o[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int i = row_index<NV, WPM>(j, e);
+        const float t = ((float)(i % W) - r.u) * r.hx + ((float)(i / W) - r.v) * r.hy;
+        o[e] = r.skip ? 0.f : k * (v[4 * j + e] / s) * t;
+      }
+      reinterpret_cast<float4*>(unit_grad + base)[G::tid() + G::kThreads * j] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+  }
+}
+
 // row-kernel dispatch: 0 = no register form for this map size (or unaligned pointers): the loop kernels above
 static int row_form(int HW, const void* a, const void* b = nullptr, const void* c = nullptr) {
   static const bool on = !(getenv("MI355_ROW_REG") && atoi(getenv("MI355_ROW_REG")) == 0);      // A/B switch
@@ -475,6 +583,29 @@ extern "C" int mi355_kl_heatmap(const float* pred, const float* target, const fl
     default: hipLaunchKernelGGL(kl_heatmap_kernel, dim3(rows), dim3(256), 0, st, pred, target, weight, eps, loss_rows, unit_grad, HW, inv_count);
   }
   MI_CHECK_LAUNCH("kl_heatmap");
+  return MI355_OK;
+}
+extern "C" int mi355_coord_heatmap(const float* pred, const float* coord, const float* weight, float beta, float delta, float coef,
+                                   float* loss_rows, float* unit_grad, float* uv, int rows, int H, int W, void* stream) {
+  if (!pred || !coord || !loss_rows) MI_FAIL(MI355_EINVAL, "coord_heatmap: null pred, coord or loss_rows");
+  if (rows < 1 || H < 1 || W < 1) MI_FAIL(MI355_EINVAL, "coord_heatmap: bad shape (rows=%d H=%d W=%d)", rows, H, W);
+  if ((long)H * (long)W >= (1L << 31)) MI_FAIL(MI355_EINVAL, "coord_heatmap: map too large (H=%d W=%d: H*W must be below 2^31)", H, W);
+  if (!__builtin_isfinite(beta) || !(beta > 0.f)) MI_FAIL(MI355_EINVAL, "coord_heatmap: beta must be finite and positive, got %g", (double)beta);
+  if (!__builtin_isfinite(delta) || delta < 0.f) MI_FAIL(MI355_EINVAL, "coord_heatmap: delta must be finite and not negative, got %g", (double)delta);
+  if (!__builtin_isfinite(coef)) MI_FAIL(MI355_EINVAL, "coord_heatmap: coef must be finite, got %g", (double)coef);
+  hipStream_t st = as_stream(stream);
+  const int HW = H * W;
+  const int form = row_form(HW, pred, unit_grad);
+  char lab[80];
+  if (prof_on()) snprintf(lab, sizeof(lab), "coord_heatmap rows%d %dx%d form%d%s", rows, H, W, form, unit_grad ? " +grad" : "");
+  ProfScope ps(st, 0.0, (unit_grad ? 8.0 : 4.0) * rows * HW + 16.0 * rows, 2, prof_on() ? lab : nullptr);
+  switch (form) {
+    case 1: hipLaunchKernelGGL((coord_heatmap_reg_kernel<4, false>), dim3(rows), dim3(256), 0, st, pred, coord, weight, beta, delta, coef, loss_rows, unit_grad, uv, rows, W); break;
+    case 2: hipLaunchKernelGGL((coord_heatmap_reg_kernel<4, true>), dim3(cdiv(rows, 4)), dim3(256), 0, st, pred, coord, weight, beta, delta, coef, loss_rows, unit_grad, uv, rows, W); break;
+    case 3: hipLaunchKernelGGL((coord_heatmap_reg_kernel<1, true>), dim3(cdiv(rows, 4)), dim3(256), 0, st, pred, coord, weight, beta, delta, coef, loss_rows, unit_grad, uv, rows, W); break;
+    default: hipLaunchKernelGGL(coord_heatmap_kernel, dim3(rows), dim3(256), 0, st, pred, coord, weight, beta, delta, coef, loss_rows, unit_grad, uv, (unsigned)HW, (unsigned)W);
+  }
+  MI_CHECK_LAUNCH("coord_heatmap");
   return MI355_OK;
 }
 extern "C" int mi355_reduce_sum(const float* in, float* out, int n, float scale, void* stream) {

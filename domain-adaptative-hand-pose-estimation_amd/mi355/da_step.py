@@ -241,6 +241,59 @@ class PrototypeAlign(_Term):
         self.set_m(state.get('m', self.m))
 
 
+class CoordRegression(_Term):
+    """What ``DAStep(coord=...)`` takes: the integral-regression loss (``uda.model.loss.JointsCoordLoss``; Sun et al., ECCV 2018 --
+    not in the reference) beside the heat-map losses.  Step A's loss gains ``weight * JointsCoordLoss(y_s, batch['kp_s'], w_s)``:
+    the soft-arg-max of ``softmax(beta * y_s)`` against the un-quantised annotation in heat-map pixels, smooth-L1 with threshold
+    ``delta``; it trains the backbone, the neck and the main head through update A.  ``target='teacher'`` also gives step C
+    ``target_weight * JointsCoordLoss(y_t, soft_argmax(teacher(x_t_ema)), w_t)``, a coordinate-space consistency term against the
+    EMA teacher, through the main head's graph.  The teacher's forward is the ``MeanTeacher``'s when the step has one (one forward
+    per iteration), else that of an in-iteration teacher of this object's own, which step M's teacher labels reuse in turn.  Both
+    weights ride inside the kernel (``scale=``)."""
+    key, needs_head_graph = 'coordt', True
+
+    def __init__(self, weight=1.0, beta=1.0, delta=1.0, target='off', target_weight=1.0, ema=None):
+        from uda.model.loss import JointsCoordLoss, check_positive
+        check_positive('CoordRegression: the weight', weight)
+        check_positive('CoordRegression: the target weight', target_weight)
+        if target not in ('off', 'teacher'):
+            raise ValueError("CoordRegression: target must be 'off' or 'teacher', got %r" % (target,))
+        if target == 'teacher' and ema is None:
+            raise ValueError("CoordRegression: target='teacher' needs an EMATeacher (--ema-update const|warmup)")
+        self.weight, self.target, self.target_weight, self.ema = float(weight), target, float(target_weight), ema
+        self.crit = JointsCoordLoss(beta=beta, delta=delta)           # (checks beta and delta)
+        self.crit_t = JointsCoordLoss(beta=beta, delta=delta)
+        self.beta = self.crit.beta
+        self._teacher = None
+
+    def source(self, y_s, batch):
+        """Step A's term; a batch without the continuous key points is an error, not a term left out."""
+        if batch.get('kp_s') is None:
+            raise KeyError("CoordRegression: the batch has no 'kp_s' (the continuous source key points, (B, K, 2) in heat-map pixels)")
+        return self.crit(y_s, batch['kp_s'], batch['w_s'], scale=self.weight)
+
+    def teacher(self, step):
+        """The in-iteration teacher whose folded operands follow the EMA update: the MeanTeacher's when the step has one."""
+        if step.mt is not None:
+            return step.mt.teacher
+        if self._teacher is None:
+            from .teacher import InIterationTeacher
+            self._teacher = InIterationTeacher(self.ema)
+        return self._teacher
+
+    def step_c(self, step, batch, f_t, y_t, y_t_grad):
+        from uda.model.loss import soft_argmax
+        more = {}
+        y_ema = step._kept_c.get('y_t_ema') if step.mt is not None else None      # the MeanTeacher's forward of this very step C
+        if y_ema is None:
+            x = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
+            y_ema = self.teacher(step).forward(x)
+            more['y_t_ema'] = y_ema                                               # (kept: step M's teacher labels reuse it)
+        kp_ema = soft_argmax(y_ema, self.beta)
+        more['kp_t_ema'] = kp_ema
+        return self.crit_t(y_t_grad, kp_ema, batch['w_t'], scale=self.target_weight), more
+
+
 class CrossDomainMixup:
     """What ``DAStep(mixup=...)`` takes: a fourth stage, step M, behind update C.  The reference's ``mixup`` (uda/model/loss.py:13-24,
     never called there: nothing builds heat-maps for the unlabelled target images) on the batch of the iteration: every source
@@ -323,7 +376,8 @@ class CrossDomainMixup:
         if self.labels == 'student':
             y = step.out['y_t']
         else:
-            y = step.out.get('y_t_ema') if step.mt is not None else None      # step C's teacher forward, when there was one
+            shared = step.mt is not None or (step.coord is not None and step.coord.target == 'teacher')
+            y = step.out.get('y_t_ema') if shared else None                   # step C's teacher forward, when there was one
             if y is None:
                 x = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
                 y = self.teacher(step).forward(x)
@@ -352,7 +406,7 @@ class DAStep:
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
     def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None,
-                 proto=None, clip=None, mixup=None):
+                 proto=None, clip=None, mixup=None, coord=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         # optional mi355.optim.GradClipper (may also be assigned after construction): each of the three updates takes the global
         # gradient norm of everything it steps (A: f and the four heads, B: the adversarial heads, C: f), behind the gradient
@@ -367,6 +421,10 @@ class DAStep:
         # of the 2B blended images through the backbone, the neck and the main head, then update M of optimizer_f and optimizer_h.
         # The EMA update and the teacher's refresh then move behind update M.  None: nothing is launched, nothing moves.
         self.mixup = mixup
+        # optional CoordRegression (may also be assigned after construction): step A's loss gains the coordinate loss on the source
+        # batch (batch['kp_s']); with target='teacher' it is also the last of step C's terms.  None: nothing is launched.
+        self.coord = coord
+        self._kept_c = {}
         if mt is not None and self.ema is None:
             self.ema = mt.ema
         self.trade_off, self.skip, self.track_acc = trade_off, skip_discarded, track_accuracy
@@ -443,7 +501,10 @@ class DAStep:
     # ------------------------------------------------------------------ the three steps (fwd+bwd, then update)
     def terms(self):
         """The optional terms that are on, in the order in which step C adds them and issues their kernels."""
-        return [t for t in (self.mt, self.mmd, self.jfa, self.proto) if t is not None]
+        on = [t for t in (self.mt, self.mmd, self.jfa, self.proto) if t is not None]
+        if self.coord is not None and self.coord.target == 'teacher':
+            on.append(self.coord)
+        return on
 
     def _fwdbwd_A(self, b):
         m, c = self.model, self.crit
@@ -458,7 +519,13 @@ class DAStep:
                 c['rd2'](y_s, y_s_adv2, None, b['w_s'], mode='min', scale=4) + \
                 c['rd'](y_s, y_s_adv, None, b['w_s'], mode='min', scale=4) + \
                 c['rd1'](y_s, y_s_adv3, b['w_s'], mode='min', scale=4)
-            loss_s.backward(_rt.unit_grad(loss_s))
+            if self.coord is None:
+                loss_s.backward(_rt.unit_grad(loss_s))
+            else:
+                loss_coord = self.coord.source(y_s, b)
+                total = loss_s + loss_coord
+                total.backward(_rt.unit_grad(total))
+                self.out.update(loss_coord=loss_coord.detach())
         _rt.join_side()
         self.out.update(loss_s=loss_s.detach(), y_s=y_s.detach(), y_s_adv=y_s_adv.detach())
 
@@ -527,6 +594,7 @@ class DAStep:
             # Only optimizer_f steps in C: the weight gradients this backward leaves in the main head (through a term that needs its
             # graph) are discarded by the next step A's zero_grad, like the adversarial heads'.
             total, kept = loss_gt, {}
+            self._kept_c = kept                         # (a later term may reuse what an earlier one kept: the teacher's forward)
             for t in self.terms():
                 loss, more = t.step_c(self, b, f_t, y_t, y_t_grad)
                 total = total + loss
@@ -553,6 +621,8 @@ class DAStep:
                 self.mt.teacher.refresh()        # the teacher's folded operands follow its weights, in place
             if self.mixup is not None and self.mixup._teacher is not None:
                 self.mixup._teacher.refresh()    # (labels='teacher' without a MeanTeacher: the mixup's own in-iteration teacher)
+            if self.coord is not None and self.coord._teacher is not None:
+                self.coord._teacher.refresh()    # (target='teacher' without a MeanTeacher, likewise)
 
     KM = ('f', 'h')                              # what update M steps
 
@@ -610,7 +680,8 @@ class DAStep:
     # ------------------------------------------------------------------ eager iteration
     def run(self, batch):
         """batch: dict x_s, label_s, w_s, x_t, w_t (+ optional label_t for the PCK bookkeeping; with `mt`: x_t_ema, the teacher's
-        view of the target batch -- x_t itself when the key is absent)."""
+        view of the target batch -- x_t itself when the key is absent; with `coord`: kp_s, the continuous source key points (B, K, 2)
+        in heat-map pixels)."""
         if self.graphs is not None:
             return self.replay(batch)
         from uda.model.regda_4 import _CENTRES

@@ -810,6 +810,27 @@ def kl_heatmap(pred, target, weight, eps, want_grad, coeff=1.0):
     return rows, g
 
 
+def coord_heatmap(pred, coord, weight, beta=1.0, delta=1.0, coef=1.0, want_grad=False):
+    """The coordinate loss on the soft-arg-max of ``pred`` (B, K, H, W) against ``coord`` (B, K, 2) = (x, y) in heat-map pixels
+    (mi355_coord_heatmap).  Returns (loss_rows [B,K], unit_grad [B,K,H,W] or None, uv [B,K,2]); ``coef`` is the term's
+    coefficient: unit_grad = d(coef * mean over B*K of the rows)/d pred."""
+    pred = _hm(pred)
+    B, K, H, W = pred.shape
+    if tuple(coord.shape) != (B, K, 2):
+        raise Mi355Error('coord_heatmap: pred %s needs coordinates (%d, %d, 2), got %s' % (tuple(pred.shape), B, K, tuple(coord.shape)))
+    coord = _hm(coord)
+    if weight is not None:
+        if weight.numel() != B * K:
+            raise Mi355Error('coord_heatmap: %d weights for %d maps' % (weight.numel(), B * K))
+        weight = _hm(weight.reshape(B, K))
+    rows = torch.empty((B, K), dtype=torch.float32, device=pred.device)
+    uv = torch.empty((B, K, 2), dtype=torch.float32, device=pred.device)
+    g = torch.empty_like(pred) if want_grad else None
+    call('mi355_coord_heatmap', ptr(pred), ptr(coord), ptr(weight), float(beta), float(delta), float(coef) / (B * K), ptr(rows),
+         ptr(g), ptr(uv), B * K, H, W, stream_ptr())
+    return rows, g, uv
+
+
 def reduce_sum(v, scale=1.0):
     v = v.contiguous()
     out = torch.empty((), dtype=torch.float32, device=v.device)

@@ -14,7 +14,10 @@ reference's unused ``loss3``, train1.py:25 and uda/model/loss.py:331-378), ``--p
 ``--proto-radius`` / ``--proto-axes`` / ``--proto-m`` (alignment of per-joint class prototypes of those features, blended with a running
 memory per domain: the reference's unused ``lossx`` / ``lossx3``, uda/model/loss.py:381-466 and 560-652), ``--mixup {off,on}`` with ``--mixup-beta`` / ``--mixup-weight`` /
 ``--mixup-labels`` (a fourth stage behind update C that trains the backbone and the main head on cross-domain blends of the source
-and the target batch, with Gaussian pseudo-labels for the target side: the reference's unused ``mixup``, uda/model/loss.py:13-24), ``--clip-grad-norm FLOAT``
+and the target batch, with Gaussian pseudo-labels for the target side: the reference's unused ``mixup``, uda/model/loss.py:13-24), ``--coord-loss {off,source,both}`` with ``--coord-weight`` /
+``--coord-target-weight`` / ``--coord-beta`` / ``--coord-delta`` (a coordinate loss on the differentiable soft-arg-max of the source
+heat-maps against the un-quantised annotation, and of the target heat-maps against the EMA teacher's: integral regression, not in
+the reference), ``--clip-grad-norm FLOAT``
 (global gradient-norm clipping of each of the three updates with a non-finite step guard, on the device; not in the reference), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
@@ -56,7 +59,7 @@ from torch.utils.data.distributed import DistributedSampler
 import mi355
 import uda.model as models
 from mi355 import ops as _ops
-from mi355.da_step import CrossDomainMixup, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
+from mi355.da_step import CoordRegression, CrossDomainMixup, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
 from mi355.optim import EMATeacher, GradClipper, check_state_dict_kind, make_optimizer
 from mi355.teacher import MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
@@ -173,7 +176,7 @@ def main(args):
     print("Source test:", len(val_source_loader)); print("Target test:", len(val_target_loader))
     train_source_iter, train_target_iter = ForeverDataIterator(train_source_loader), ForeverDataIterator(train_target_loader)
     # who reads the teacher's view of the target batch (meta['image_ema']): the consistency term, and mixup labelled by the teacher
-    want_ema = args.mt_loss == 'on' or (args.mixup == 'on' and args.mixup_labels == 'teacher')
+    want_ema = args.mt_loss == 'on' or (args.mixup == 'on' and args.mixup_labels == 'teacher') or args.coord_loss == 'both'
     if args.device_augment and not args.synthetic:
         # packed sources -> HBM, augmentation and heat-map labels on the GPU (mi355.augment, utils.labels)
         dev_aug = lambda it, ema=False: DeviceAugmentIterator(it, device, args.image_size, args.heatmap_size, want_ema=ema)
@@ -183,7 +186,8 @@ def main(args):
         # host -> HBM copies of the next batch overlap the current step (pinned, double-buffered, side stream)
         # (--mt-loss: meta['image_ema'] of the target batches travels with them instead of as a blocking copy inside the iteration)
         ema_keys = ('image_ema',) if want_ema and not args.synthetic else ()
-        train_source_iter = DevicePrefetcher(train_source_iter, device)
+        # (--coord-loss: meta['keypoint2d'] of the source batches, the un-quantised key points, travels with them likewise)
+        train_source_iter = DevicePrefetcher(train_source_iter, device, meta_keys=('keypoint2d',) if args.coord_loss != 'off' else ())
         train_target_iter = DevicePrefetcher(train_target_iter, device, meta_keys=ema_keys)
 
     # model (+ the EMA copy the reference builds and checkpoints, train1.py:102-128; frozen unless --ema-update is on)
@@ -227,6 +231,8 @@ def main(args):
         # step M behind update C: blends of the two batches through backbone, neck and main head (mi355.da_step.CrossDomainMixup)
         step.mixup = CrossDomainMixup(beta=args.mixup_beta, weight=args.mixup_weight, labels=args.mixup_labels, ema=ema,
                                       seed=args.seed, rank=RANK)
+    # step A (and, with 'both', step C against the teacher) gains a loss on the soft-arg-max coordinates
+    step.coord = coord_term(args, ema)
     if args.clip_grad_norm > 0:
         # each update clips the global norm of what it steps and skips itself when that norm is not finite (mi355.optim.GradClipper)
         step.clip = GradClipper(args.clip_grad_norm, device)
@@ -384,13 +390,28 @@ def _pck(dists, thr=0.5):
     return (sum(accs) / len(accs) if accs else 0), len(accs)
 
 
+def coord_term(args, ema):
+    """The ``mi355.da_step.CoordRegression`` of --coord-loss source|both; None when the switch is off."""
+    if args.coord_loss == 'off':
+        return None
+    return CoordRegression(weight=args.coord_weight, beta=args.coord_beta, delta=args.coord_delta,
+                           target='teacher' if args.coord_loss == 'both' else 'off', target_weight=args.coord_target_weight, ema=ema)
+
+
+def source_keypoints(meta, image_size, heatmap_size, device):
+    """batch['kp_s']: ``meta['keypoint2d']`` (B, K, 2) in image pixels -> fp32 heat-map pixels on `device`, un-quantised (the labels
+    sit at ``int(. + 0.5)`` of these)."""
+    kp = torch.as_tensor(meta['keypoint2d']).to(device, non_blocking=True)
+    return (kp.float() / (float(image_size) / float(heatmap_size))).contiguous()
+
+
 def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     names = ['Time', 'Data', 'Loss (s)', 'Loss (t, false)', 'Loss (t, truth)', 'Acc (s)', 'Acc (t)', 'Acc (s, adv)', 'Acc (t, adv)']
     fmts = [':4.2f', ':3.1f', ':.2e', ':.2e', ':.2e', ':3.2f', ':3.2f', ':3.2f', ':3.2f']
-    mt, terms, mixup = step.mt, step.terms(), step.mixup
+    mt, terms, mixup, coord = step.mt, step.terms(), step.mixup, step.coord
     if mt is not None:
         mt.set_epoch(epoch)                              # m and k are functions of the epoch (train1.py:351-353)
-    keys = [t.key for t in terms] + (['mix'] if mixup is not None else [])
+    keys = (['coord'] if coord is not None else []) + [t.key for t in terms] + (['mix'] if mixup is not None else [])
     names, fmts = names + ['Loss (%s)' % k for k in keys], fmts + [':.2e'] * len(keys)
     clip, n_fixed = step.clip, 9 + len(keys)
     if clip is not None:                                 # the gradient norms of the updates, read when a line is printed
@@ -401,11 +422,13 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
     progress = ProgressMeter(args.iters_per_epoch, meters, prefix="Epoch: [{}]".format(epoch))
     end = time.time()
     for i in range(args.iters_per_epoch):
-        x_s, label_s, weight_s, _ = next(train_source_iter)
+        x_s, label_s, weight_s, meta_s = next(train_source_iter)
         x_t, label_t, weight_t, meta_t = next(train_target_iter)
         to = lambda t: t.to(device, non_blocking=True)
         batch = dict(x_s=to(x_s), label_s=to(label_s), w_s=to(weight_s), x_t=to(x_t), w_t=to(weight_t), label_t=to(label_t))
-        if mt is not None or (mixup is not None and mixup.labels == 'teacher'):   # x_t_ema = meta_t['image_ema'] (train1.py:364); synthetic images have no augmentation
+        if coord is not None:                            # the un-quantised source key points, image pixels -> heat-map pixels
+            batch['kp_s'] = source_keypoints(meta_s, args.image_size, args.heatmap_size, device)
+        if mt is not None or (mixup is not None and mixup.labels == 'teacher') or (coord is not None and coord.target == 'teacher'):   # x_t_ema = meta_t['image_ema'] (train1.py:364); synthetic images have no augmentation
             batch['x_t_ema'] = batch['x_t'] if args.synthetic else to(meta_t['image_ema'])
         meters[1].update(time.time() - end)
         # HIP-graph replay once this process has run three eager iterations (whatever epoch it resumed at).  With several
@@ -694,6 +717,22 @@ _OPTIONS = [
                               "it for --mixup: 'student' = the model's own y_t of step C; 'teacher' = the EMA teacher's on its view of "
                               "the target batch (needs --ema-update const|warmup; with --mt-loss on the teacher's forward of step C "
                               "is reused)")),
+    (('--coord-loss',), dict(default='off', choices=['off', 'source', 'both'], help="coordinate loss on the differentiable soft-arg-max "
+                            "(integral regression, Sun et al. 2018; not in the reference), one kernel launch per term: 'source' = step A "
+                            "adds w * smooth-L1 between the soft-arg-max of softmax(beta * y_s) and the un-quantised annotation "
+                            "(meta['keypoint2d'] in heat-map pixels), trained beside the heat-map losses through update A; 'both' = step "
+                            "C also adds wt * the same loss between the target prediction and the EMA teacher's soft-arg-max on its "
+                            "view of the target batch (needs --ema-update const|warmup; one teacher forward per iteration whatever "
+                            "else uses it); 'off': nothing is launched.  The pre-training step keeps the KL alone")),
+    (('--coord-weight',), dict(default=1.0, type=float, metavar='FLOAT', help='weight w of the source coordinate loss (constant, positive; '
+                              'the default is a placeholder: its effect on convergence has not been measured, and cannot be without '
+                              'the data sets)')),
+    (('--coord-target-weight',), dict(default=1.0, type=float, metavar='FLOAT', help='weight wt of the target coordinate loss of '
+                                     "--coord-loss both (constant, positive; the default is a placeholder: its effect on convergence "
+                                     'has not been measured, and cannot be without the data sets)')),
+    (('--coord-beta',), dict(default=1.0, type=float, metavar='FLOAT', help='inverse temperature of the softmax under the soft-arg-max '
+                            '(positive; 1 = the distribution the KL loss trains the main head towards)')),
+    (('--coord-delta',), dict(default=1.0, type=float, metavar='FLOAT', help='threshold of the smooth-L1 in heat-map pixels (0: plain L1)')),
     (('--clip-grad-norm',), dict(default=0.0, type=_clip_norm, metavar='FLOAT', help="global gradient-norm clipping with a non-finite "
                                 "step guard: each of the updates A, B, C (M with --mixup on; and the pre-training step) clips over everything it steps, as "
                                 "clip_grad_norm_(those parameters, FLOAT) before the optimizers would, in two launches per update and "
@@ -742,10 +781,18 @@ class _Parser(argparse.ArgumentParser):
         if getattr(args, 'mixup', 'off') == 'on' and getattr(args, 'mixup_labels', 'student') == 'teacher' and \
                 getattr(args, 'ema_update', 'off') == 'off':
             self.error('--mixup-labels teacher needs a moving teacher: add --ema-update const (or warmup)')
+        if getattr(args, 'coord_loss', 'off') == 'both' and getattr(args, 'ema_update', 'off') == 'off':
+            self.error('--coord-loss both needs a moving teacher: add --ema-update const (or warmup)')
         try:                                             # (the checks the term classes make, under the flags' names)
             if getattr(args, 'mixup', 'off') == 'on':
                 check_positive('--mixup-beta', args.mixup_beta)
                 check_positive('--mixup-weight', args.mixup_weight)
+            if getattr(args, 'coord_loss', 'off') != 'off':
+                check_positive('--coord-weight', args.coord_weight)
+                check_positive('--coord-target-weight', args.coord_target_weight)
+                check_positive('--coord-beta', args.coord_beta)
+                if not 0.0 <= args.coord_delta < float('inf'):
+                    raise ValueError('--coord-delta must be finite and not negative, got %r' % (args.coord_delta,))
             if getattr(args, 'mmd_loss', 'off') == 'on':
                 check_positive('--mmd-weight', args.mmd_weight)
                 check_whole('--mmd-kernels', args.mmd_kernels, 8)

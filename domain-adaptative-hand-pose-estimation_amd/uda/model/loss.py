@@ -84,6 +84,56 @@ class JointsKLLoss(nn.Module):
             return rows.detach().mean(dim=-1) * float(scale)     # forward-only, as no caller differentiates it
 
 
+# ---------------------------------------------------------------- coordinate loss on the soft-arg-max (not in the reference)
+class _CoordFn(torch.autograd.Function):
+    """loss = coeff * mean(rows) of the coordinate loss; built like _KLFn: the kernel writes d loss / d pred in the forward, the
+    backward hands it on under the unit scalar of ``mi355.unit_grad`` and multiplies it by the incoming gradient otherwise."""
+
+    @staticmethod
+    def forward(ctx, pred, coord, weight, beta, delta, coeff):
+        ctx.set_materialize_grads(False)
+        rows, g, uv = ops.coord_heatmap(pred, coord, weight, beta, delta, coeff, ctx.needs_input_grad[0])
+        ctx.save_for_backward(g)
+        ctx.mark_non_differentiable(uv)
+        return ops.reduce_sum(rows.view(-1), float(coeff) / rows.numel()), rows, uv
+
+    @staticmethod
+    def backward(ctx, gout, grows, guv):
+        g, = ctx.saved_tensors
+        if g is None or gout is None:
+            return None, None, None, None, None, None
+        if _rt.is_unit_grad(gout):
+            return g, None, None, None, None, None
+        return ops.scale_by_dev(g, gout.contiguous().float()), None, None, None, None, None
+
+
+class JointsCoordLoss(nn.Module):
+    """Integral-regression loss (Sun et al., ECCV 2018; not in the reference): the expectation of ``softmax(beta * output)`` over
+    the pixel grid is a differentiable key point (u, v) in heat-map pixels, compared with the continuous annotation ``coords``
+    (B, K, 2) = (x, y) under smooth-L1 with threshold ``delta`` (``delta=0``: L1), summed over the two axes, times
+    ``target_weight`` (B, K[, 1]), averaged over the B*K maps.  A joint of weight 0 is left out whatever its coordinates hold.
+    One launch computes the loss and its gradient w.r.t. ``output``.  ``uv`` holds the soft-arg-max of the last call, detached."""
+
+    def __init__(self, beta=1.0, delta=1.0):
+        super().__init__()
+        check_positive('JointsCoordLoss: beta', beta)
+        if not 0.0 <= float(delta) < float('inf'):
+            raise ValueError('JointsCoordLoss: delta must be finite and not negative, got %r' % (delta,))
+        self.beta, self.delta = float(beta), float(delta)
+        self.uv = None
+
+    def forward(self, output, coords, target_weight=None, scale=1.0):
+        """``scale``: coefficient of this term in the total loss, folded into the kernel as ``JointsKLLoss``'s."""
+        w = None if target_weight is None else target_weight.detach()
+        loss, _, self.uv = _CoordFn.apply(output, coords.detach(), w, self.beta, self.delta, float(scale))
+        return loss
+
+
+def soft_argmax(output, beta=1.0):
+    """(B, K, 2) soft-arg-max of ``softmax(beta * output)`` in heat-map pixels, (x, y), detached."""
+    return ops.softargmax(output.detach(), beta, 1.0)
+
+
 # ---------------------------------------------------------------- mean-teacher consistency (reference uda/model/loss.py:265-297)
 # the joint curriculum of mt_loss: k < 100 the wrist, then one more joint per finger every 100, all joints from 400 on
 MT_SUBSETS = ((100, (0,)),

@@ -33,25 +33,31 @@ def generate_target(joints, joints_vis, heatmap_size, sigma, image_size):
 
 
 def make_batch(batch_size, image_size=256, heatmap_size=64, num_keypoints=21, seed=1, device='cpu', with_target_labels=True,
-               p_visible=1.0):
-    """dict(x_s, label_s, w_s, x_t, w_t[, label_t]) as fp32 tensors on `device`."""
+               p_visible=1.0, with_keypoints=False):
+    """dict(x_s, label_s, w_s, x_t, w_t[, label_t][, kp_s, kp_t]) as fp32 tensors on `device`.  ``with_keypoints``: the continuous
+    key points the labels are made of, (B, K, 2) = (x, y) in heat-map pixels (the draw divided by the stride); every other entry
+    is the same with and without them."""
     rng = np.random.default_rng(seed)
     S, Hm, K, B = image_size, heatmap_size, num_keypoints, batch_size
 
     def labels():
         lab = np.zeros((B, K, Hm, Hm), np.float32)
         w = np.zeros((B, K, 1), np.float32)
+        kps = np.zeros((B, K, 2), np.float32)
         for b in range(B):
             kp = rng.uniform(8, S - 8, size=(K, 2))
             vis = (rng.random((K, 1)) < p_visible).astype(np.float32)
             lab[b], w[b] = generate_target(kp, vis, (Hm, Hm), 2, (S, S))
-        return torch.from_numpy(lab), torch.from_numpy(w)
+            kps[b] = kp / (S / Hm)
+        return torch.from_numpy(lab), torch.from_numpy(w), torch.from_numpy(kps)
 
     x_s = torch.from_numpy(rng.standard_normal((B, 3, S, S), dtype=np.float32))
     x_t = torch.from_numpy(rng.standard_normal((B, 3, S, S), dtype=np.float32))
-    label_s, w_s = labels()
-    label_t, w_t = labels()
+    label_s, w_s, kp_s = labels()
+    label_t, w_t, kp_t = labels()
     out = dict(x_s=x_s, label_s=label_s, w_s=w_s, x_t=x_t, w_t=w_t)
     if with_target_labels:
         out['label_t'] = label_t
+    if with_keypoints:
+        out['kp_s'], out['kp_t'] = kp_s, kp_t
     return {k: v.to(device) for k, v in out.items()}

@@ -392,6 +392,25 @@ int mi355_softargmax(const float* hm, float* uv, int rows, int H, int W, float b
  */
 int mi355_kl_heatmap(const float* pred, const float* target, const float* weight, float eps,
                      float* loss_rows, float* unit_grad, int rows, int HW, float inv_count, void* stream);
+/* Coordinate loss on a differentiable soft-arg-max, one launch.  The soft-arg-max is utils/keypoint_detection.py:209-239; the
+ * loss on it is NOT in the reference: it is the integral-regression loss of Sun et al., ECCV 2018, trained beside
+ * the heat-map loss.  pred [rows][H][W] fp32, coord [rows][2] = (x, y) in heat-map pixels, weight [rows] (nullable: all ones).
+ * Per row r, x_i = i % W, y_i = i / W:
+ *   m = max_i beta*z_i; e_i = expf(beta*z_i - m); s = sum e_i; p_i = e_i / s
+ *   u = sum p_i x_i; v = sum p_i y_i;  uv[r] (nullable) = (u, v)        (= mi355_softargmax with out_scale 1)
+ *   dx = u - coord[r][0]; dy = v - coord[r][1]
+ *   h(d)  = delta > 0 ? (|d| < delta ? 0.5 d^2 / delta : |d| - 0.5 delta) : |d|     (torch smooth_l1_loss(beta=delta); 0: L1)
+ *   h'(d) = delta > 0 ? (|d| < delta ? d / delta : sign(d)) : sign(d)                (sign(0) = 0)
+ *   loss_rows[r] = w_r * (h(dx) + h(dy))
+ *   unit_grad[r][i] (nullable) = coef * w_r * beta * p_i * ((x_i - u) h'(dx) + (y_i - v) h'(dy))
+ * coef = the term's coefficient / rows: the scalar loss is mi355_reduce_sum(loss_rows, coef) and unit_grad its gradient.
+ * A row with w_r == 0 is skipped by selection: loss 0 and a gradient row of exact zeros whatever pred[r] and coord[r] hold (NaN
+ * and inf included; an invisible joint's coordinates mean nothing); uv[r] is still written.  In a weighted row a NaN of pred or
+ * coord reaches that row's loss and its whole gradient row, and no other row.  No atomics, fixed summation order.
+ * MI355_EINVAL: null pred / coord / loss_rows; rows, H or W < 1; H*W >= 2^31; beta not finite or <= 0; delta NaN, inf or < 0;
+ * coef not finite. */
+int mi355_coord_heatmap(const float* pred, const float* coord, const float* weight, float beta, float delta, float coef,
+                        float* loss_rows, float* unit_grad, float* uv, int rows, int H, int W, void* stream);
 /* out[0] = scale * sum(in[0..n)) in a fixed order (deterministic). */
 int mi355_reduce_sum(const float* in, float* out, int n, float scale, void* stream);
 /* out[i] = in[i] * (*g_dev) : backward of the KL loss (upstream scalar gradient on device). */
