@@ -285,6 +285,7 @@ class _PackedFp8:
     def __init__(self):
         self.key = None
         self.wf = self.wt = self.state = self.rec = None
+        self.restored = None            # the record of a checkpoint (load_fp8_state_dict), until the first pack has used it
 
     def get(self, weight, O, T, I):
         key = (_param_version(weight), O, T, I)
@@ -295,10 +296,21 @@ class _PackedFp8:
                     raise Mi355Error('fp8 weight copies are created on first use: run one eager iteration before capturing')
                 self.wf = torch.empty(O * T * I, dtype=torch.uint8, device=weight.device)
                 self.wt = torch.empty(O * T * I, dtype=torch.uint8, device=weight.device)
-                self.state = _rt.fp8_alloc_state(weight.device, ops.E4M3)
+                if self.restored is None or self.state is None or self.state.device != weight.device:
+                    self.state, self.restored = _rt.fp8_alloc_state(weight.device, ops.E4M3), None
                 self.rec = self.state[2:4]          # [1] of this view = state[3]: the descale of the current pack (fp8_common.h)
-            # first pack: scale from this tensor; afterwards delayed scaling (weights move by lr per step): ONE launch
-            ops.pack_weights_fp8(weight.detach(), O, T, I, self.state, self.wf, self.wt, jit=first)
+            rec, self.restored = self.restored, None
+            if first and rec is not None and float(rec[3]) > 0:
+                # resumed run: the pack that was live when the checkpoint was written was made of these very weights with the
+                # scale 1 / rec[3] (a power of two), one scale refresh before the record's own; make that pack again, then put
+                # the record back as it was saved (the pack kernel has noted the amax and its descale in it)
+                d = float(rec[3])
+                self.state.copy_(torch.tensor([1.0 / d, d, 0.0, d], dtype=torch.float32))
+                ops.pack_weights_fp8(weight.detach(), O, T, I, self.state, self.wf, self.wt, jit=False)
+                self.state.copy_(rec)
+            else:
+                # first pack: scale from this tensor; afterwards delayed scaling (weights move by lr per step): ONE launch
+                ops.pack_weights_fp8(weight.detach(), O, T, I, self.state, self.wf, self.wt, jit=first)
             self.key = key
             weight._mi_pack8 = (self, O, T, I)          # lets the optimizer refresh all fp8 copies of a group in one launch
         return self.wf, self.wt, self.rec             # consumers descale with the pack's own record, not the live scale
@@ -344,6 +356,59 @@ class _Fp8Stream:
         q = ops.fp8_quantize(t, self.state, self.fmt, jit=first)
         t._mi_q8 = (q, q._mi_rec, self.fmt, t._version)       # consumers descale with the copy's own record, not the live state
         return q, q._mi_rec
+
+
+_FP8_OWNERS = ('_packed8', '_q_in', '_q_dy', '_q_out', '_q_dx')      # the attributes of a layer that hold a scaling record
+
+
+def fp8_state_dict(model):
+    """'fp8' mode: the delayed-scaling records of the process-wide pools (mi355.fp8_alloc_state) with the layers of `model` that own
+    them -- per format {fmt, used, buf: a CPU copy of the used records, owners: 'module name/attribute' or None per slot} -- what the
+    epoch checkpoint keeps as ``fp8_state``.  None when no pool exists (any other compute dtype)."""
+    pools = {}
+    for (_, fmt), pool in _rt._fp8_pools.items():
+        if pool['used'] and fmt not in pools:
+            pools[fmt] = (pool, [None] * pool['used'])
+    if not pools:
+        return None
+    for name, mod in model.named_modules():
+        for attr in _FP8_OWNERS:
+            st = getattr(getattr(mod, attr, None), 'state', None)
+            if st is None:
+                continue
+            for pool, owners in pools.values():
+                off = st.data_ptr() - pool['buf'].data_ptr()
+                if st.device == pool['buf'].device and 0 <= off < 16 * pool['used'] and off % 16 == 0:
+                    owners[off // 16] = '%s/%s' % (name, attr)
+    return {'pools': {fmt: {'fmt': fmt, 'used': pool['used'], 'owners': owners,
+                            'buf': pool['buf'][:4 * pool['used']].detach().cpu().clone()}
+                      for fmt, (pool, owners) in sorted(pools.items())}}
+
+
+def load_fp8_state_dict(model, state, device):
+    """Hand every record of ``fp8_state_dict()`` to the layer of `model` that owned it, in the saved slot order, BEFORE the first
+    iteration: the layers then start on the delayed scales of the saved run instead of a just-in-time scale of their first tensor,
+    and the weight packs are made again with the scale the saved run's live packs had (_PackedFp8.get).  A layer that already
+    owns a record (an iteration has run) or a name `model` does not have is refused; records no layer owned are left out."""
+    mods = dict(model.named_modules())
+    todo = []
+    for fmt, pool in sorted(state['pools'].items()):
+        recs = pool['buf'].reshape(-1, 4)
+        for i, owner in enumerate(pool['owners']):
+            if owner is None:
+                continue
+            name, attr = owner.rsplit('/', 1)
+            obj = getattr(mods.get(name), attr, None) if attr in _FP8_OWNERS else None
+            if obj is None:
+                raise ValueError('fp8_state: the checkpoint holds a scaling record of %s, which this model does not have' % owner)
+            if obj.state is not None:
+                raise ValueError('fp8_state: %s owns a scaling record already; load the checkpoint before the first iteration' % owner)
+            todo.append((obj, int(fmt), recs[i].to(torch.float32).clone()))
+    for obj, fmt, rec in todo:
+        obj.state = _rt.fp8_alloc_state(device, fmt)
+        obj.state.copy_(rec)
+        if isinstance(obj, _PackedFp8):
+            obj.restored = rec
 
 
 class _PackedMx:

@@ -60,11 +60,12 @@ import mi355
 import uda.model as models
 from mi355 import ops as _ops
 from mi355.da_step import CoordRegression, CrossDomainMixup, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
-from mi355.optim import EMATeacher, GradClipper, check_state_dict_kind, make_optimizer
+from mi355.optim import EMATeacher, GradClipper, make_optimizer
 from mi355.teacher import MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
 from uda.model.regda_7 import MainOutput, PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
+from utils.checkpoint import load_training_state, save_training_state
 from utils.data import ForeverDataIterator, DevicePrefetcher, DeviceAugmentIterator, ragged_collate
 from utils.keypoint_detection import accuracy, accuracy_from_preds, get_max_preds_device, decode_keypoints, PoseMetrics
 from utils.logger import CompleteLogger
@@ -265,33 +266,7 @@ def main(args):
         model.load_state_dict(pretrained_dict, strict=False)
         model_ema.load_state_dict(pretrained_dict, strict=False)
     else:
-        ck = torch.load(args.resume, map_location='cpu', weights_only=False)
-        model.load_state_dict(ck['model']); model_ema.load_state_dict(ck['model'])
-        try:                                             # (SGD state under --optimizer adam, or the reverse: say so, no KeyError later)
-            for k in opts:
-                if 'optimizer_' + k in ck:
-                    check_state_dict_kind(opts[k], ck['optimizer_' + k], '%s: optimizer_%s' % (args.resume, k))
-        except ValueError as e:
-            raise SystemExit('--resume ' + str(e))
-        for k, name in (('f', 'optimizer_f'), ('h', 'optimizer_h'), ('h_adv', 'optimizer_h_adv')):
-            opts[k].load_state_dict(ck[name]); scheds[k].load_state_dict(ck['lr_scheduler' + name[len('optimizer'):]])
-        for k in ('h_adv2', 'h_adv3'):                    # additive keys (the reference never saved these two)
-            if 'optimizer_' + k in ck:
-                opts[k].load_state_dict(ck['optimizer_' + k]); scheds[k].load_state_dict(ck['lr_scheduler_' + k])
-        model.gl_layer.iter_num = ck.get('gl_iter_num', 0)
-        start_epoch = ck['epoch'] + 1
-        if ema is not None:
-            # the teacher: --ema_model, else the model_ema.pth written next to the resumed checkpoint, else the model (above)
-            beside = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'model_ema.pth')
-            ema_path = args.ema_model or (beside if os.path.exists(beside) else None)
-            if ema_path is not None:
-                model_ema.load_state_dict(torch.load(ema_path, map_location='cpu', weights_only=False)['model_ema'])
-            if 'ema_state' in ck:
-                ema.load_state_dict(ck['ema_state'])
-        if getattr(step, 'proto', None) is not None and 'proto_state' in ck:
-            step.proto.load_state_dict(ck['proto_state'], device)      # both prototype memories and m
-        if step.mixup is not None and 'mixup_state' in ck:
-            step.mixup.load_state_dict(ck['mixup_state'])               # the RNG state of the blend coefficients (rank 0's)
+        start_epoch = load_training_state(args.resume, args, model, model_ema, opts, scheds, step, ema, device)
     broadcast_module(model)                              # replicas start bit-identical whatever each rank loaded
     broadcast_module(model_ema)
 
@@ -325,21 +300,7 @@ def main(args):
                 dist.barrier()
             best_acc = max(best_acc, t_acc['all'])
             continue
-        ck_extra = {'ema_state': ema.state_dict()} if ema is not None else {}
-        if getattr(step, 'proto', None) is not None:
-            ck_extra['proto_state'] = step.proto.state_dict()
-        if step.mixup is not None:
-            ck_extra['mixup_state'] = step.mixup.state_dict()
-        torch.save({'model': model.state_dict(), **ck_extra,
-                    'optimizer_f': opts['f'].state_dict(), 'optimizer_h': opts['h'].state_dict(),
-                    'optimizer_h_adv': opts['h_adv'].state_dict(),
-                    'lr_scheduler_f': scheds['f'].state_dict(), 'lr_scheduler_h': scheds['h'].state_dict(),
-                    'lr_scheduler_h_adv': scheds['h_adv'].state_dict(), 'epoch': epoch, 'args': args,
-                    # additive keys: close the reference's resume gaps
-                    'optimizer_h_adv2': opts['h_adv2'].state_dict(), 'optimizer_h_adv3': opts['h_adv3'].state_dict(),
-                    'lr_scheduler_h_adv2': scheds['h_adv2'].state_dict(), 'lr_scheduler_h_adv3': scheds['h_adv3'].state_dict(),
-                    'gl_iter_num': model.gl_layer.iter_num}, logger.get_checkpoint_path(epoch))
-        torch.save({'model_ema': model_ema.state_dict()}, logger.get_checkpoint_path('model_ema'))
+        save_training_state(logger.get_checkpoint_path(epoch), epoch, args, model, model_ema, opts, scheds, step, ema)
         if t_acc['all'] > best_acc:
             shutil.copy(logger.get_checkpoint_path(epoch), logger.get_checkpoint_path('best'))
             best_acc = t_acc['all']
