@@ -401,12 +401,47 @@ class CrossDomainMixup:
         return ops.mixup_pairs(*ops_in, self.lam, out=self._bufs[1])
 
 
+class FourierStyle:
+    """What ``DAStep(fda=...)`` takes: Fourier Domain Adaptation (Yang and Soatto, CVPR 2020; not in the reference) of the source
+    batch at the head of step A.  The amplitude of the ``(2b+1)^2`` lowest frequencies of every source image, ``b = floor(min(H, W) *
+    beta)``, is replaced by that of the target image of the same index and the phase is kept, so the geometry and the labels stay
+    (``mi355_fda_transfer``: two launches, no FFT).  No learnable parts and no state: nothing joins the checkpoint.  This object
+    owns the stylised batch and the workspace at fixed addresses, keyed by the input signature, so the launches capture."""
+
+    def __init__(self, beta=0.01, mean=ops.MEAN, std=ops.STD):
+        from uda.model.loss import check_positive
+        check_positive('FourierStyle: beta', beta)
+        self.beta = float(beta)
+        self.mean, self.std = tuple(mean), tuple(std)
+        self._bufs = None
+
+    def band(self, H, W):
+        return ops.fda_band(H, W, self.beta)
+
+    def stylise(self, batch):
+        """x_s of `batch` in the style of its x_t, in the buffer of this object; the batch's own tensors are only read."""
+        f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+        x_s, x_t = f32(batch['x_s']), f32(batch['x_t'])
+        sig = (tuple(x_s.shape), tuple(x_t.shape), x_s.device)
+        if self._bufs is None or self._bufs[0] != sig:
+            if torch.cuda.is_current_stream_capturing():
+                raise _rt.Mi355Error('FourierStyle: the stylised batch and the workspace would be allocated during graph capture; run one eager iteration first')
+            if x_s.dim() != 4:
+                raise _rt.Mi355Error('FourierStyle: x_s must be (B, C, H, W), got %s' % (tuple(x_s.shape),))
+            B, C, H, W = x_s.shape
+            need = _rt.load().mi355_fda_workspace_bytes(B, C, H, W, self.band(H, W))
+            if need < 0:
+                raise _rt.Mi355Error('FourierStyle: beta=%g on %s images: %s' % (self.beta, tuple(x_s.shape), _rt.load().mi355_last_error().decode()))
+            self._bufs = (sig, torch.empty_like(x_s), torch.empty(need, dtype=torch.uint8, device=x_s.device))
+        return ops.fda_transfer(x_s, x_t, self.beta, self.mean, self.std, out=self._bufs[1], ws=self._bufs[2])
+
+
 class DAStep:
     """Holds the static batch buffers and runs A/B/C (and M, with ``mixup``).  ``optimizers`` = dict with keys f, h, h_adv, h_adv2,
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
     def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None,
-                 proto=None, clip=None, mixup=None, coord=None):
+                 proto=None, clip=None, mixup=None, fda=None, coord=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         # optional mi355.optim.GradClipper (may also be assigned after construction): each of the three updates takes the global
         # gradient norm of everything it steps (A: f and the four heads, B: the adversarial heads, C: f), behind the gradient
@@ -424,6 +459,10 @@ class DAStep:
         # optional CoordRegression (may also be assigned after construction): step A's loss gains the coordinate loss on the source
         # batch (batch['kp_s']); with target='teacher' it is also the last of step C's terms.  None: nothing is launched.
         self.coord = coord
+        # optional FourierStyle (may also be assigned after construction): step A's forward takes the source batch in the style of
+        # the target batch (two launches at the head of step A) instead of batch['x_s'], which is only read; steps B, C and M, the
+        # teacher views and the mixup blend keep the batch's own tensors.  None: nothing is launched.
+        self.fda = fda
         self._kept_c = {}
         if mt is not None and self.ema is None:
             self.ema = mt.ema
@@ -510,8 +549,9 @@ class DAStep:
         m, c = self.model, self.crit
         for o in self.opt.values():
             o.zero_grad()
+        x_s = b['x_s'] if self.fda is None else self.fda.stylise(b)
         with _rt.grouped_wgrads():
-            y_s, y_s_adv, y_s_adv2, y_s_adv3, f_s = m(b['x_s'])
+            y_s, y_s_adv, y_s_adv2, y_s_adv3, f_s = m(x_s)
             for t in self.terms():
                 self.out.update(t.step_a(f_s, y_s))
             # the coefficients of train1.py:384-387 ride inside the loss kernels (scale=), the total's gradient is the unit scalar
@@ -845,10 +885,10 @@ class DAStep:
 
 def build_training(model, heatmap_size=64, lr=0.01, momentum=0.9, wd=1e-4, lr_gamma=1e-4, lr_decay=0.75,
                    trade_off=1.0, num_keypoints=21, skip_discarded=True, track_accuracy=True, optimizer='sgd',
-                   adam_betas=(0.9, 0.999), adam_eps=1e-8):
+                   adam_betas=(0.9, 0.999), adam_eps=1e-8, fda=None):
     """Criteria, the five SGD optimizers and their LambdaLR schedules exactly as train1.py:131-154 builds them.
     `optimizer`: 'sgd' (the reference), 'adam' (FusedAdam, L2 weight decay `wd`) or 'adamw' (decoupled weight decay `wd`) for all
-    five; `momentum` is not used by the last two.  Returns (DAStep, optimizers dict, schedulers dict)."""
+    five; `momentum` is not used by the last two.  `fda`: an optional FourierStyle, handed to the DAStep.  Returns (DAStep, optimizers dict, schedulers dict)."""
     from torch.optim.lr_scheduler import LambdaLR
     from uda.model.loss import JointsKLLoss
     from uda.model.regda_4 import PseudoLabelGenerator
@@ -867,4 +907,4 @@ def build_training(model, heatmap_size=64, lr=0.01, momentum=0.9, wd=1e-4, lr_ga
         h_adv2=mk(model.head_adv2.parameters()), h_adv3=mk(model.head_adv3.parameters()))
     fn = lambda x: lr * (1. + lr_gamma * float(x)) ** (-lr_decay)
     scheds = {k: LambdaLR(o, fn) for k, o in opts.items()}
-    return DAStep(model, opts, crit, trade_off, skip_discarded, track_accuracy), opts, scheds
+    return DAStep(model, opts, crit, trade_off, skip_discarded, track_accuracy, fda=fda), opts, scheds

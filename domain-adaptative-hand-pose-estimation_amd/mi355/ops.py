@@ -5,6 +5,7 @@ tensors in channels_last memory (= the NHWC layout the kernels use), dtype bf16 
 are contiguous NCHW fp32.  Nothing here falls back to torch math.
 """
 import ctypes
+import math
 
 import torch
 
@@ -1328,6 +1329,57 @@ def mixup_pairs(x_s, hm_s, w_s, x_t, hm_t, w_t, lam, out=None):
     call('mi355_mixup_pairs', ptr(x_s), ptr(x_t), ptr(hm_s), ptr(hm_t), ptr(w_s), ptr(w_t), ptr(lam), ptr(x_mix), ptr(hm_mix),
          ptr(w_mix), int(B), x_s[0].numel(), hm_s[0].numel(), int(K), stream_ptr())
     return x_mix, hm_mix, w_mix
+
+
+# ---------------------------------------------------------------- Fourier-domain stylisation (csrc/fda.hip)
+from .augment import MEAN, STD          # noqa: E402  (the normalisation the loaders apply)
+
+FDA_MAX_B = 32
+
+
+def fda_band(H, W, beta):
+    """b of the (2b+1)^2 window: int(floor(min(H, W) * beta)) in Python doubles, as the published low_freq_mutate takes it."""
+    return int(math.floor(min(int(H), int(W)) * float(beta)))
+
+
+def fda_transfer(x_s, x_t, beta, mean=MEAN, std=STD, out=None, ws=None):
+    """Fourier Domain Adaptation (Yang and Soatto, CVPR 2020) of a source batch: the amplitude of the (2b+1)^2 lowest frequencies
+    of every plane of x_s replaced by that of the same plane of x_t, the phase kept (mi355_fda_transfer, include/mi355pose.h).
+    x_s, x_t: (B, C, H, W) dense fp32, normalised with `mean` / `std` (default: those of mi355.augment); b = fda_band(H, W, beta).
+    Returns `out`; `out` and the workspace `ws` (a uint8 tensor) are allocated only when not given, and never during graph capture."""
+    who = 'fda_transfer'
+    for what, t in (('x_s', x_s), ('x_t', x_t)):
+        _dense_f32(who, what, t)
+    if x_s.dim() != 4 or tuple(x_s.shape) != tuple(x_t.shape):
+        raise Mi355Error('%s: x_s %s and x_t %s must be (B, C, H, W) of one shape' % (who, tuple(x_s.shape), tuple(x_t.shape)))
+    if x_s.device != x_t.device:
+        raise Mi355Error('%s: x_s and x_t live on different devices' % who)
+    B, C, H, W = (int(s) for s in x_s.shape)
+    if not (isinstance(beta, (int, float)) and math.isfinite(beta) and beta >= 0):
+        raise Mi355Error('%s: beta=%r must be a finite number >= 0' % (who, beta))
+    if len(mean) < C or len(std) < C:
+        raise Mi355Error('%s: mean / std hold %d / %d values for C=%d channels' % (who, len(mean), len(std), C))
+    b = fda_band(H, W, beta)
+    need = load().mi355_fda_workspace_bytes(B, C, H, W, b)
+    if need < 0:
+        raise Mi355Error('%s: beta=%r gives b=%d: %s' % (who, beta, b, load().mi355_last_error().decode()))
+    if out is None or ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise Mi355Error('%s: out / the workspace would be allocated during graph capture; run one eager call first' % who)
+        if out is None:
+            out = torch.empty((B, C, H, W), dtype=torch.float32, device=x_s.device)
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=x_s.device)
+    _dense_f32(who, 'out', out)
+    if tuple(out.shape) != (B, C, H, W):
+        raise Mi355Error('%s: out has shape %s, the launch writes %s' % (who, tuple(out.shape), (B, C, H, W)))
+    _chk_dev(ws)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or out.device != x_s.device or ws.device != x_s.device:
+        raise Mi355Error('%s: ws must be a dense uint8 tensor on the device of x_s (and out on it too)' % who)
+    fl = ctypes.c_float * C
+    call('mi355_fda_transfer', ptr(x_s), ptr(x_t), ptr(out), fl(*[float(v) for v in mean[:C]]), fl(*[float(v) for v in std[:C]]),
+         B, C, H, W, b, ptr(ws), ws.numel(), stream_ptr())
+    return out
 
 
 # ---------------------------------------------------------------- MMD alignment (csrc/mmd.hip)

@@ -17,7 +17,8 @@ memory per domain: the reference's unused ``lossx`` / ``lossx3``, uda/model/loss
 and the target batch, with Gaussian pseudo-labels for the target side: the reference's unused ``mixup``, uda/model/loss.py:13-24), ``--coord-loss {off,source,both}`` with ``--coord-weight`` /
 ``--coord-target-weight`` / ``--coord-beta`` / ``--coord-delta`` (a coordinate loss on the differentiable soft-arg-max of the source
 heat-maps against the un-quantised annotation, and of the target heat-maps against the EMA teacher's: integral regression, not in
-the reference), ``--clip-grad-norm FLOAT``
+the reference), ``--fda {off,on}`` with ``--fda-beta`` (step A sees the source batch with the low-frequency amplitude of the target batch:
+Fourier Domain Adaptation, not in the reference), ``--clip-grad-norm FLOAT``
 (global gradient-norm clipping of each of the three updates with a non-finite step guard, on the device; not in the reference), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
@@ -59,7 +60,8 @@ from torch.utils.data.distributed import DistributedSampler
 import mi355
 import uda.model as models
 from mi355 import ops as _ops
-from mi355.da_step import CoordRegression, CrossDomainMixup, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
+from mi355.ops import FDA_MAX_B, fda_band
+from mi355.da_step import CoordRegression, CrossDomainMixup, FourierStyle, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
 from mi355.optim import EMATeacher, GradClipper, make_optimizer
 from mi355.teacher import MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
@@ -232,6 +234,9 @@ def main(args):
         # step M behind update C: blends of the two batches through backbone, neck and main head (mi355.da_step.CrossDomainMixup)
         step.mixup = CrossDomainMixup(beta=args.mixup_beta, weight=args.mixup_weight, labels=args.mixup_labels, ema=ema,
                                       seed=args.seed, rank=RANK)
+    if args.fda == 'on':
+        # step A sees the source batch in the style of the target batch (mi355.da_step.FourierStyle); no state, nothing to checkpoint
+        step.fda = FourierStyle(beta=args.fda_beta)
     # step A (and, with 'both', step C against the teacher) gains a loss on the soft-arg-max coordinates
     step.coord = coord_term(args, ema)
     if args.clip_grad_norm > 0:
@@ -678,6 +683,17 @@ _OPTIONS = [
                               "it for --mixup: 'student' = the model's own y_t of step C; 'teacher' = the EMA teacher's on its view of "
                               "the target batch (needs --ema-update const|warmup; with --mt-loss on the teacher's forward of step C "
                               "is reused)")),
+    (('--fda',), dict(default='off', choices=['off', 'on'], help="Fourier-domain stylisation of the source batch (Fourier Domain "
+                     "Adaptation, Yang and Soatto 2020; not in the reference): step A's forward takes every source image with the "
+                     "amplitude of its (2b+1)^2 lowest frequencies replaced by that of the target image of the same index, the "
+                     "phase -- and with it the geometry and the labels -- kept; two kernel launches at the head of step A, no "
+                     "FFT, no extra pass through the network, no state.  Steps B, C and M and the pre-training step see the "
+                     "images as the loaders deliver them.  Its effect on convergence has not been measured, and cannot be "
+                     "without the data sets; 'off': nothing is launched")),
+    (('--fda-beta',), dict(default=0.01, type=float, metavar='FLOAT', help='half-width of the swapped band as a fraction of the image '
+                          'side: b = floor(--image-size * FLOAT) (positive; with --fda on, b <= 32 and 2b+1 <= --image-size; 0.01 is '
+                          "the paper's smallest band and a placeholder: its effect on convergence has not been measured, and cannot "
+                          'be without the data sets)')),
     (('--coord-loss',), dict(default='off', choices=['off', 'source', 'both'], help="coordinate loss on the differentiable soft-arg-max "
                             "(integral regression, Sun et al. 2018; not in the reference), one kernel launch per term: 'source' = step A "
                             "adds w * smooth-L1 between the soft-arg-max of softmax(beta * y_s) and the un-quantised annotation "
@@ -748,6 +764,16 @@ class _Parser(argparse.ArgumentParser):
             if getattr(args, 'mixup', 'off') == 'on':
                 check_positive('--mixup-beta', args.mixup_beta)
                 check_positive('--mixup-weight', args.mixup_weight)
+            if getattr(args, 'fda_beta', None) is not None:
+                check_positive('--fda-beta', args.fda_beta)
+                if getattr(args, 'fda', 'off') == 'on':
+                    side = int(args.image_size)
+                    b = fda_band(side, side, args.fda_beta)
+                    if b > FDA_MAX_B:
+                        raise ValueError('--fda-beta: beta = %g gives b = %d at --image-size %d, above the limit of %d' % (args.fda_beta, b, side, FDA_MAX_B))
+                    if 2 * b + 1 > side:
+                        raise ValueError('--fda-beta: beta = %g gives b = %d: the window 2b+1 = %d is wider than the limit of --image-size %d'
+                                         % (args.fda_beta, b, 2 * b + 1, side))
             if getattr(args, 'coord_loss', 'off') != 'off':
                 check_positive('--coord-weight', args.coord_weight)
                 check_positive('--coord-target-weight', args.coord_target_weight)

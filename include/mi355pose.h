@@ -720,6 +720,35 @@ int mi355_mixup_pairs(const float* x_s, const float* x_t, const float* hm_s, con
                       const float* lam, float* x_mix, float* hm_mix, float* w_mix, int B, long img_plane, long hm_plane, int K,
                       void* stream);
 
+/* ---------------------------------------------------------------- Fourier-domain stylisation (csrc/fda.hip)
+ * Fourier Domain Adaptation (Yang and Soatto, "FDA: Fourier Domain Adaptation for Semantic Segmentation", CVPR 2020).  The
+ * reference has no such function, so there is no file:line to cite; the semantics are those of the paper's published
+ * low_freq_mutate (fft2 -> fftshift -> swap the centre window of the amplitude -> ifftshift -> ifft2 -> real), stated here.
+ * x_s, x_t, out [B][C][H][W] dense fp32 (NCHW), normalised as the loaders deliver them ((p - mean_c) / std_c); source image i
+ * is paired with target image i.  b = floor(min(H, W) * beta) is computed by the caller; the window is u, v in [-b, b].
+ * Spectra are those of the DE-NORMALISED planes p = x * std_c + mean_c (non-negative pixels, so the DC term has phase 0); the
+ * affine is folded into the coefficients, not applied per pixel: F01[u,v] = std_c * Fnorm[u,v], plus mean_c * H * W at [0,0].
+ *   D[u,v]    = (|Ft[u,v]| - |Fs[u,v]|) * Fs[u,v] / |Fs[u,v]|        (phase factor 1 where |Fs[u,v]| == 0, as np.angle(0) = 0)
+ *   out[y,x]  = fl32(x_s[y,x] + 1 / (H W std_c) * Re sum_{u,v} D[u,v] e^{+2 pi i (u y / H + v x / W)})
+ * No clamp to the pixel range (the published code has none).  x_s and x_t are only read.  Twiddles (arguments reduced in
+ * integers, from a table built per block), sums, magnitudes and the inverse sum are fp64 on the fp32 operands; the only
+ * rounding to fp32 is the store.  D is Hermitian: only v >= 0 is computed and doubled, and the v = 0 column is summed from
+ * u >= 0 alone, so the result is real by construction.  Two launches whatever B is: (1) per stripe of 32 rows of a plane, the
+ * partial (2b+1) x (b+1) window of both spectra into ws; (2) per block the stripe partials folded in stripe order, D, and the
+ * output rows.  No atomics, fixed summation orders: the same bits on every run, eagerly and under graph replay.  Rows are read
+ * and written as 16-byte vectors when the bases are 16-byte aligned and W % 4 == 0, float by float otherwise.
+ * mean, std: HOST arrays of C floats, passed to the kernels by value.  ws: mi355_fda_workspace_bytes(B, C, H, W, b) bytes of
+ * device memory, 16-byte aligned, written by launch 1 and read by launch 2.  Refused with MI355_EINVAL before any launch,
+ * the message naming the argument (mi355_fda_workspace_bytes returns -1): b < 0, b > MI355_FDA_MAX_B, 2b+1 > min(H, W), C
+ * outside 1..4, B < 1 (or B * C * ceil(H / 32) above 2^31 - 1), H or W outside 1..1024, std_c <= 0 or not finite, mean_c not
+ * finite, a null pointer, x_s / x_t / out not 4-byte aligned, ws not 16-byte aligned or smaller than needed, out or ws
+ * overlapping an input or each other.  A non-finite pixel makes every pixel of that output plane non-finite and leaves the
+ * other planes as they are.  Never allocates; capturable. */
+#define MI355_FDA_MAX_B 32
+long mi355_fda_workspace_bytes(int B, int C, int H, int W, int b);
+int mi355_fda_transfer(const float* x_s, const float* x_t, float* out, const float* mean, const float* std, int B, int C, int H,
+                       int W, int b, void* ws, long ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
