@@ -12,7 +12,7 @@ pitch of every buffer made after it, flat ones included.  `lean=True` (window) g
 plus one row tile instead; nothing uses it unless the run time demands it.
 
 Start alignment.  The payload starts START = 16 bytes past a 256-byte boundary -- the least alignment every entry point the
-exact conv and BatchNorm suites reach accepts -- not at the allocator's 256- / 512-byte boundary.  What each kernel family
+guarded suites reach accepts -- not at the allocator's 256- / 512-byte boundary.  What each kernel family
 assumes of an operand's first byte, read from its address arithmetic (csrc/ at this commit):
 
   * gather loads of the implicit GEMMs (igemm.hip gather_kernel, igemm_fp8.hip gather_fp8_kernel, register-staged builds):
@@ -42,10 +42,49 @@ assumes of an operand's first byte, read from its address arithmetic (csrc/ at t
     the workspace (partials [slice][C][3], then coeff) as floats: 4 bytes; mask bytes one by one; the fp8 side output as one
     uint4 per pair of lanes (16 e4m3, C % 16 == 0 checked): 16 bytes.  The granules of the one-launch backward live in a buffer
     of the library's own, not in an operand.  mi355_colsum and mi355_apply_relu_mask: the same 16-byte chunks.
+  * max-pool, layout, space-to-depth, stem pack (pool_layout.hip): the feature maps x, y, dy, dx as Chunk<T>::load / store
+    (uint4) at (pixel * C + chunk), C a whole number of chunks ("bad args (C=...)"): 16 bytes; the window codes as ONE load /
+    store of CH bytes (load_bytes / store_bytes of common.h: 8 bytes in bf16, 4 in fp32) at the same element offsets: 8 bytes;
+    the NCHW fp32 side of the layout kernels, the stem weights and their gradient float by float: 4 bytes.
+  * pw21 (pw21.hip): the feature maps x, the residual and the output in 16-byte chunks: 16 bytes; heat maps, weights, biases,
+    scale_dev, the statistics partials [slice][C][3], the slabs of pw_wgrad's workspace [slice][K][C] and hm_rowsum's [N][K]
+    floats one by one: 4 bytes (the kernels' float4 traffic is on their own LDS arrays, aligned(16)).
+  * SGD, clipped SGD, cast, EMA (optim.hip): p, g, buf of the SGD kernels and e, p of mi355_ema_update as float4 with a scalar
+    tail -- the entry points check 16 bytes themselves ("pointers must be 16-byte aligned"); the bf16 copy and cast's source
+    and destination element by element: 2 / 4 bytes; lr_dev and the coefficient pair: 4 bytes; the clip record (a double
+    first): 8 bytes, checked.  ema_update_batched walks its ranges float by float (4 bytes; the int64 counters 8) and reads
+    records whose first field is a pointer: 8 bytes of the table.
+  * gradient norm and Adam (optim.hip, adam_slice.h): every range / p, g, m, v as float4 per lane behind the item's base
+    (gn_table and adam_table refuse a base off a 16-byte boundary): 16 bytes; the item tables, the partials (doubles) and the
+    clip record: 8 bytes, checked by the entry points; step and lr of an item: one float each, 4 bytes.
+  * MMD (mmd.hip): source, target, the gradients, rows and the workspace through plain float pointers: 4 bytes, checked
+    ("pointers must be 4-byte aligned"); float4 accesses only when HW % 4 == 0 and the bases are 16-byte aligned (the host
+    chooses the scalar build otherwise: the tests run both, at START and at START + 4).  The (K, n, n) workspace float by float.
+  * per-joint pooling, KL, scatter, prototype update (jfa.hip, proto.hip, joint_pool.h): the feature map and its gradient in
+    16-byte chunks (the wrappers refuse another start), descriptors, prototypes, the memory and the KL gradients as float4 rows
+    ("must be 16-byte aligned", checked by the entry points): 16 bytes; key points, rows and the blend record float by float:
+    4 bytes.
+  * consistency MSE (mi355_mse_heatmap, teacher.hip): 4 bytes, checked; float4 only when HW % 4 == 0 and pred, target and the
+    gradient sit on 16-byte boundaries (the scalar build otherwise: tests/test_gpu_mt.py runs it at START + 4).
+  * MX quantiser and packs (mx_fp8.hip): above.  The item table of the batched pack holds pointers: 8 bytes.
+  * training augmentation (augment.hip): the packed sources, the geometry image and the records' bytes one by one (the records
+    are structs whose first field is an int64: 8 bytes); x and image_ema float by float: 4 bytes; the workspace begins with
+    the B luminance sums (unsigned long long, atomicAdd): 8 bytes, the geometry image follows at the next multiple of 256.
 
-No family assumes more than 16 bytes of an operand's first byte, so every payload of the two suites starts at START and no
+No family assumes more than 16 bytes of an operand's first byte, so every payload of these suites starts at START and no
 entry point had to learn a new refusal.  (16 bytes is also what a production run offers: mi355.nn hands the kernels views into
 flat buffers of packed weights and gradients.)
+
+What the window does not guard, and why.  torch.empty, torch.empty_strided, torch.empty_like and ops.workspace are replaced;
+anything a wrapper makes by other means is outside: the device copy of the augmentation records (Tensor.to of a pinned host
+array inside mi355.augment._prepare; tests/test_gpu_augment.py runs the mixed batch a second time through the ABI with a placed
+copy), the item tables of ema_table / gn_table / adam_table / fold_table (torch.from_numpy(...).to(device): the tests place a
+copy and hand that in), proto_blend's and mse_record's two-element records (placed by the tests likewise), and every gradient
+autograd itself allocates in the tests that go through uda.model.loss.  The two caching wrappers (mi355.augment._ws,
+mi355.ops._mmd_ws) allocate with torch.empty: a test empties the cache with monkeypatch, so the buffer is made inside the window
+at exactly the size the library reports.  An all-ones element can be a right answer where the expected value is a NaN (the
+hardware's float -> bf16 conversion keeps no promise about a NaN's payload; 0xFFFF was seen from the max-pool): such tests count
+unwritten elements only where the reference is not a NaN.
 
 What the fill cannot reach: the conv family reads x, w, dy, the second operand pair of the concat-K builds, the MX scale
 arrays and pgemm's addends through buffer resources whose size is the operand's, so a read past the END of one of them returns
@@ -56,7 +95,7 @@ is loaded and never stored) are invisible to this and every other test.
 
 Use.
     v = place(t, 'x')                  # a copy of t inside a guarded buffer, same shape / strides / dtype
-    with window(ops, 'fwd+bias'):      # torch.empty, torch.empty_strided and ops.workspace are guarded while it is open
+    with window(ops, 'fwd+bias'):      # torch.empty, empty_strided, empty_like and ops.workspace are guarded while it is open
         y = ops.conv_fwd(desc, v, w)
     torch.cuda.synchronize()
     check()                            # every flank byte of every buffer since the last check is still 0xFF
@@ -75,7 +114,7 @@ START = 16               # the payload's first byte, past a BOUNDARY
 FLAT_PITCH = 4096        # a flat payload's own pitch is its length, at most this
 LEAN_ABOVE = 64 << 20
 
-_real_empty, _real_empty_strided = torch.empty, torch.empty_strided
+_real_empty, _real_empty_strided, _real_empty_like = torch.empty, torch.empty_strided, torch.empty_like
 
 
 class GuardError(AssertionError):
@@ -188,12 +227,13 @@ def _default_device():
 
 @contextlib.contextmanager
 def window(ops, label='', device=None, pitch=0, start=START, lean=False):
-    """While open: torch.empty and torch.empty_strided of `device`'s type (default: cuda where there is one, else cpu) return views
-    of guarded 0xFF-filled buffers with the requested shape, strides and dtype, and ops.workspace(nbytes, ...) returns a guarded
-    0xFF-filled view of exactly nbytes rounded up to 16, made for this call only.  All three are restored on the way out,
-    whatever happens inside.  pitch: bytes of the widest row a kernel of the call strides by (a lower bound for every flank)."""
+    """While open: torch.empty, torch.empty_strided and torch.empty_like of `device`'s type (default: cuda where there is one, else
+    cpu) return views of guarded 0xFF-filled buffers with the requested shape, strides and dtype (empty_like: those of its
+    argument, which must be dense; dtype= and device= are honoured, anything else goes to the real function), and
+    ops.workspace(nbytes, ...) returns a guarded 0xFF-filled view of exactly nbytes rounded up to 16, made for this call only.
+    All four are restored on the way out, whatever happens inside.  pitch: bytes of the widest row a kernel of the call strides by (a lower bound for every flank)."""
     want = torch.device(device).type if device is not None else ('cuda' if torch.cuda.is_available() else 'cpu')
-    saved = (torch.empty, torch.empty_strided, ops.workspace, dict(_state))
+    saved = (torch.empty, torch.empty_strided, ops.workspace, dict(_state), torch.empty_like)
 
     def empty(*size, **kw):
         dev = kw.get('device', None)
@@ -219,6 +259,18 @@ def window(ops, label='', device=None, pitch=0, start=START, lean=False):
         dtype = kw.get('dtype') or torch.get_default_dtype()
         return _strided(size, stride, dtype, dev, 'empty_strided%s %s' % (tuple(size), dtype), start)[1]
 
+    def empty_like(t, **kw):
+        dev = torch.device(kw['device']) if kw.get('device') is not None else t.device
+        fmt = kw.get('memory_format', torch.preserve_format)
+        layout = kw.get('layout') or t.layout
+        dense = t.dim() == 0 or t.numel() == 0 or _extent(tuple(t.shape), t.stride())[0] == t.numel()
+        if not _guards(dev, want) or kw.get('pin_memory') or layout != torch.strided or t.layout != torch.strided \
+                or fmt != torch.preserve_format or not dense or any(st < 0 for st in t.stride()):
+            return saved[4](t, **kw)                    # not modelled: a gapped or overlapping source, another memory format
+        dtype = kw.get('dtype') or t.dtype
+        v = _strided(t.shape, t.stride(), dtype, dev, 'empty_like%s %s' % (tuple(t.shape), dtype), start)[1]
+        return v.requires_grad_() if kw.get('requires_grad') else v
+
     def workspace(nbytes, device, tag='main'):
         nbytes = int(nbytes)
         size = (nbytes + 15) // 16 * 16
@@ -226,11 +278,12 @@ def window(ops, label='', device=None, pitch=0, start=START, lean=False):
         return b.raw[b.start:b.start + size]
 
     _state.update(label=label, pitch=max(int(pitch), _state['pitch']), lean=bool(lean))
-    torch.empty, torch.empty_strided, ops.workspace = empty, empty_strided, workspace
+    torch.empty, torch.empty_strided, torch.empty_like, ops.workspace = empty, empty_strided, empty_like, workspace
     try:
         yield
     finally:
         torch.empty, torch.empty_strided, ops.workspace = saved[:3]
+        torch.empty_like = saved[4]
         _state.clear()
         _state.update(saved[3])
 

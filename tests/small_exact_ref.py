@@ -94,6 +94,9 @@ def nhwc(t, dtype):
 MP_MAPS = [(1, 1), (1, 2), (2, 1), (3, 3), (4, 4), (5, 7), (7, 5), (18, 14)]
 MP_CASES = {'%s-n%d-c%d-%dx%d' % (dt, N, C, H, W): (dt, N, C, H, W)
             for dt in DTS for N in (1, 3) for C in (PER[dt], 3 * PER[dt]) for H, W in MP_MAPS}
+# two images of one chunk: the last row and column of the last image sit against whatever follows the operand
+MP_EDGE_MAPS = [(1, 1), (1, 2), (2, 1), (3, 3), (4, 5)]
+MP_CASES.update({'%s-n%d-c%d-%dx%d' % (dt, 2, PER[dt], H, W): (dt, 2, PER[dt], H, W) for dt in DTS for H, W in MP_EDGE_MAPS})
 # the grid-stride lap: 182 * 182 * 64 = 2 119 936 output chunks > 8192 blocks * 256, and four laps of the backward
 MP_LAP = ('bf16', 1, 512, 364, 364)
 
@@ -300,7 +303,8 @@ HW_GEOM = {1: (1, 1), 63: (7, 9), 64: (8, 8), 65: (5, 13), 100: (10, 10), 120: (
            257: (1, 257), 4096: (64, 64)}
 PW_K = [1, 21, 32]
 PW_HW = [1, 63, 64, 65, 100]
-PW_N = [1, 3]
+PW_N = [1, 2, 3]
+PW_EDGE_HW = [1, 63, 64, 65]                    # one pixel, a ragged tile, a whole tile, a tile and one pixel
 
 
 def pw_c(dt, *more):
@@ -426,7 +430,7 @@ def check_exact_rowsum(c):
 
 
 # ================================================================ D. optimiser
-SGD_N = [1, 3, 4, 5, 6, 1023, 1025, 4195507]   # n % 4 = 0, 1, 2, 3; the last: one full lap of 4096 * 256 float4, 300 float4 of the second, a tail of 3
+SGD_N = [1, 3, 4, 5, 6, 1023, 1024, 1025, 4195507]   # n % 4 = 0, 1, 2, 3; the last: one full lap of 4096 * 256 float4, 300 float4 of the second, a tail of 3
 SGD_LRS = [2.0 ** -3, 2.0 ** -4, 2.0 ** -3]
 SGD_MU = 0.5
 SGD_CASES = [(n, nesterov, wd) for n in SGD_N for nesterov in (True, False) for wd in (0.25, 0.0)]

@@ -11,6 +11,7 @@ import torch
 from PIL import Image, ImageEnhance, ImageFilter
 
 import augment_ref as R
+import augment_cases as A
 from augment_cases import K0, cpu_chain, labels, ref_from_params, seeded, sources
 
 
@@ -54,6 +55,109 @@ def test_jitter_matches_pillow(order):
 def test_blur_matches_pillow(radius):
     arr = _img(np.random.default_rng(7), 70, 90)
     assert np.array_equal(R.blur(arr, radius), np.asarray(Image.fromarray(arr).filter(ImageFilter.GaussianBlur(radius))))
+
+
+# ------------------------------------------------------------------ the edge cases the GPU suite runs (augment_cases), against Pillow
+def _pillow_stages(arr, p, size):
+    """The chain of augment_cases.ref_stages done by Pillow itself."""
+    enh = [ImageEnhance.Brightness, ImageEnhance.Contrast, ImageEnhance.Color]
+    top, left, side = int(p[1]), int(p[2]), int(p[3])
+    im = Image.fromarray(arr).rotate(p[0]).crop((left, top, left + side, top + side)).resize((size, size), Image.BILINEAR)
+    g = np.asarray(im)
+    for k in [int(o) for o in p[7:10] if o >= 0]:
+        im = enh[k](im).enhance(p[4 + k])
+    j = np.asarray(im)
+    return g, j, np.asarray(im.filter(ImageFilter.GaussianBlur(p[10])))
+
+
+def _agrees_with_pillow(case, size):
+    for i, (arr, row) in enumerate(case):
+        p = np.array(row)
+        for name, a, b in zip(('geometry', 'jitter', 'blur'), A.ref_stages(arr, p, size), _pillow_stages(arr, p, size)):
+            assert np.array_equal(a, b), (name, i, row)
+
+
+@pytest.mark.parametrize('S', A.EDGE_SIDES)
+def test_edge_crop_sides_match_pillow(S):
+    """Output sides 16 and 48, crop sides 1, 2, S - 1, S, S + 1, 2 S + 1, 4 S - 1 and 4 S at both corners under every rotation
+    mode."""
+    from mi355.augment import records
+    assert A.crop_sides(S) == [1, 2, S - 1, S, S + 1, 2 * S + 1, 4 * S - 1, 4 * S]
+    for side in A.crop_sides(S):
+        case = A.geometry_case(S, side)
+        packed, table, params = A.pack(case)
+        rec = records(table, params)
+        assert sorted(rec['rot'].tolist()) == [0, 0, 1, 1, 2, 2, 3, 3, 4, 4] and rec['rot'][0] == rec['rot'][-1] == 1
+        assert int(rec['top'][0]) == int(rec['left'][0]) == 0                        # the first image from its first byte ...
+        assert int(rec['top'][-1] + side) == int(rec['h'][-1]) and int(rec['left'][-1] + side) == int(rec['w'][-1])
+        assert int(rec['offset'][-1]) + int(rec['h'][-1]) * int(rec['w'][-1]) * 3 == packed.numel()    # ... the last to the last byte
+        assert int(packed.max()) < 255
+        _agrees_with_pillow(case, S)
+
+
+def test_the_affine_case_leaves_the_source_on_all_four_sides():
+    from mi355.augment import rotation_record
+    arr, row = A.geometry_case(16, 16)[1]
+    h, w = arr.shape[:2]
+    assert h != w
+    mode, c = rotation_record(row[0], w, h)
+    assert mode == 0
+    y, x = np.mgrid[0:h, 0:w].astype(np.int64)
+    xs, ys = (c[2] + y * c[1] + x * c[0]) >> 16, (c[5] + y * c[4] + x * c[3]) >> 16
+    assert (xs < 0).any() and (xs >= w).any() and (ys < 0).any() and (ys >= h).any()
+
+
+def test_edge_jitter_factors_match_pillow():
+    case = A.jitter_case()
+    rows = np.array([r for _, r in case])
+    assert A.ABOVE_ONE > 1 and np.float32(A.ABOVE_ONE) == np.nextafter(np.float32(1), np.float32(2))
+    for op in range(3):                                   # every factor for each op alone
+        alone = rows[7 * op:7 * op + 7]
+        assert ((alone[:, 7:10] >= 0).sum(1) == 1).all() and (alone[:, 7 + op] == op).all()
+        assert alone[:, 4 + op].tolist() == A.FACTORS
+    for order in A.ORDERS + A.PARTIAL_ORDERS:             # and every order, with every factor in every slot
+        sel = rows[(rows[:, 7:10] == np.array(order)).all(1)]
+        assert len(sel) == len(A.FACTORS) and all(set(sel[:, 4 + k].tolist()) == set(A.FACTORS) for k in range(3))
+    assert all((a == 0).all(2).any() and (a == 255).all(2).any() for a, _ in case)      # rows of 0 and of 255
+    clipped = [A.ref_stages(a, np.array(r), 16)[1] for a, r in case]
+    assert any((j == 0).any() for j in clipped) and any((j == 255).any() for j in clipped)
+    _agrees_with_pillow(case, 16)
+
+
+def test_contrast_tie_rounds_up_and_matches_pillow():
+    case = A.tie_case()
+    L = R.luminance(case[0][0])
+    assert sorted(np.unique(L).tolist()) == [10, 11] and float(L.astype(np.int64).sum()) / L.size == 10.5
+    assert sorted({r[5] for _, r in case}) == [0.5, 1.5]
+    assert A.ref_lsum(case[0][0], np.array(case[0][1]), 16) == 10 * 128 + 11 * 128
+    want = R.blend(np.full_like(case[0][0], 11), case[0][0], 0.5)                   # mean 11, not 10
+    assert np.array_equal(A.ref_stages(case[0][0], np.array(case[0][1]), 16)[1], want) and (want[:8] == 10).all()
+    assert not np.array_equal(want, R.blend(np.full_like(case[0][0], 10), case[0][0], 0.5))      # a mean of 10 would show
+    _agrees_with_pillow(case, 16)
+
+
+@pytest.mark.parametrize('S', A.EDGE_SIDES)
+def test_edge_blur_radii_match_pillow(S):
+    from mi355 import Mi355Error
+    from mi355.augment import blur_record
+    radii = A.blur_radii()
+    lo, hi = A.largest_blur_radius()
+    assert radii[:6] == [0.0, 1e-6, 1e-3, 0.05, 0.8, 1.0] and radii[6] == lo and abs(lo - 1.41421347) < 1e-8
+    assert hi == np.nextafter(lo, 2.0) and int(R.box_radius(lo)) == 0 and int(R.box_radius(hi)) == 1
+    assert blur_record(1e-6) == (1, 1 << 24, 0)            # 255 * 2^24 + 2^23: the largest sum the kernel forms in 32 bits
+    assert 255 * (1 << 24) + (1 << 23) < 1 << 32
+    for r in radii:
+        on, ww, fw = blur_record(r)
+        assert (on, ww, fw) == ((0, 0, 0) if r == 0 else (1,) + R.box_weights(R.box_radius(r))[1:]) and ww + 2 * fw <= 1 << 24
+    with pytest.raises(Mi355Error):
+        blur_record(hi)
+    _agrees_with_pillow(A.blur_case(S), S)
+
+
+def test_mixed_batch_matches_pillow():
+    case = A.mixed_case(48)
+    assert 20 <= len(case) <= 28 and len({a.shape for a, _ in case}) > 8
+    _agrees_with_pillow(case, 48)
 
 
 # ------------------------------------------------------------------ host records of mi355.augment

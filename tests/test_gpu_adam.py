@@ -17,6 +17,12 @@ build_training(optimizer=...); train1.py --optimizer):
 The bound, per tensor: twice the distance of torch.optim.Adam(W) on CPU float32 from the float64 oracle, or 4 float32 ulps of the
 tensor's largest magnitude, whichever is larger (the kernel rounds lr to float32 before the division: one rounding more per
 operation than torch).
+
+Guards (tests/guarded.py).  The kernel-level tests of sections 1 - 3 keep every buffer of an item (p, g, m, v with their sentinel
+bands, the step count, lr), the item table and the clip record in G.place() copies and launch through _launch, which opens a
+window, synchronises and checks every flank.  The kernels work in place (nothing is allocated, so there is no unwritten check);
+the exact comparisons stay.  test_one_table_of_every_tail_length_against_the_flanks has no sentinel bands at all: every buffer
+ends where its flank begins.  FusedAdam, the capture, DAStep and the command line (sections 4 - 7) are not guarded.
 """
 import copy
 import os
@@ -28,11 +34,19 @@ import pytest
 import torch
 
 import adam_ref as ref
+import guarded as G
 from conftest import PKG
 
 pytestmark = pytest.mark.gpu
 
 GUARD, SENTINEL = 4, 7.0
+
+
+@pytest.fixture(autouse=True)
+def guards():
+    G.reset()
+    yield
+    G.reset()
 
 
 @pytest.fixture
@@ -61,17 +75,17 @@ class _Item:
     """p, g, m, v of one parameter, each the view [GUARD : GUARD + n] of a buffer that holds SENTINEL around it, its step count and
     the hyper-parameters of its group."""
 
-    def __init__(self, gpu, p, g, lr_dev, beta1, beta2, eps, wd, decoupled, step=0.0, m=None, v=None):
+    def __init__(self, gpu, p, g, lr_dev, beta1, beta2, eps, wd, decoupled, step=0.0, m=None, v=None, band=GUARD):
         n = len(p)
-        self.n, self.hyper = n, (beta1, beta2, eps, wd, decoupled)
+        self.n, self.hyper, self.band = n, (beta1, beta2, eps, wd, decoupled), band
         zeros = np.zeros(n, dtype=np.float32)
         self.full = []
-        for x in (p, g, zeros if m is None else m, zeros if v is None else v):
-            buf = np.full(n + 2 * GUARD, SENTINEL, dtype=np.float32)
-            buf[GUARD:GUARD + n] = x
-            self.full.append(torch.from_numpy(buf).to(gpu))
-        self.p, self.g, self.m, self.v = (t[GUARD:GUARD + n] for t in self.full)
-        self.step = torch.full((3,), SENTINEL, device=gpu)
+        for x, name in zip((p, g, zeros if m is None else m, zeros if v is None else v), 'pgmv'):
+            buf = np.full(n + 2 * band, SENTINEL, dtype=np.float32)
+            buf[band:band + n] = x
+            self.full.append(G.place(torch.from_numpy(buf).to(gpu), '%s[%d]' % (name, n)))      # band = 0: the flank follows the last element
+        self.p, self.g, self.m, self.v = (t[band:band + n] for t in self.full)
+        self.step = G.place(torch.full((3,), SENTINEL, device=gpu), 'step')
         self.step[1] = step
         self.lr = lr_dev
 
@@ -80,7 +94,8 @@ class _Item:
 
     def guards_intact(self):
         s = torch.tensor(SENTINEL)
-        ok = all(_same(t[:GUARD].cpu(), s.expand(GUARD)) and _same(t[GUARD + self.n:].cpu(), s.expand(GUARD)) for t in self.full)
+        b = self.band
+        ok = all(_same(t[:b].cpu(), s.expand(b)) and _same(t[b + self.n:].cpu(), s.expand(b)) for t in self.full)
         return ok and float(self.step[0]) == SENTINEL and float(self.step[2]) == SENTINEL
 
     def host(self):
@@ -89,11 +104,17 @@ class _Item:
 
 def _launch(items, gpu, rec=None, table=None):
     ops = _ops()
-    table = table or ops.adam_table([it.row() for it in items], gpu)
-    assert table[2] == sum((it.n + ops.ADAM_CHUNK - 1) // ops.ADAM_CHUNK for it in items)
-    ops.adam_step_batched(*table, rec)
-    ops.adam_tick_batched(table[0], table[1], rec)
+    if table is None:
+        table = ops.adam_table([it.row() for it in items], gpu)
+        table = (G.place(table[0], 'adam table'),) + tuple(table[1:])
+    assert table[2] == sum((it.n + ops.ADAM_CHUNK - 1) // ops.ADAM_CHUNK for it in items)      # exactly the blocks the table needs
+    assert table[0].numel() == len(items) * ops.ADAM_ITEM_BYTES
+    label = 'adam_step_batched + adam_tick_batched, items %s' % ([it.n for it in items],)
+    with G.window(ops, label):
+        ops.adam_step_batched(*table, rec)
+        ops.adam_tick_batched(table[0], table[1], rec)
     torch.cuda.synchronize()
+    G.check(label)
     return table
 
 
@@ -101,7 +122,7 @@ def _make_rec(coef, skip, gpu):
     ops = _ops()
     r = np.zeros(1, dtype=ops.clip_rec_dtype())
     r['coef'], r['skip'], r['max_norm'] = np.float32(coef), skip, 1.0
-    return torch.from_numpy(r.view(np.uint8).copy()).to(gpu)
+    return G.place(torch.from_numpy(r.view(np.uint8).copy()).to(gpu), 'clip record')
 
 
 # ---------------------------------------------------------------- 1. exact operands
@@ -116,16 +137,16 @@ def _exact_operands(seed, n):
     return p, g
 
 
-def _exact_item(seed, n, gpu, lr_dev, step=0.0):
+def _exact_item(seed, n, gpu, lr_dev, step=0.0, band=GUARD):
     p, g = _exact_operands(seed, n)
     h = EXACT
-    return _Item(gpu, p, g, lr_dev, h['beta1'], h['beta2'], h['eps'], h['wd'], h['decoupled'], step=step), p, g
+    return _Item(gpu, p, g, lr_dev, h['beta1'], h['beta2'], h['eps'], h['wd'], h['decoupled'], step=step, band=band), p, g
 
 
 @pytest.mark.parametrize('n', EXACT_LENS)
 def test_one_exact_step_bit_for_bit(rt, gpu, n):
     assert _ops().ADAM_CHUNK == 16384
-    lr_dev = torch.tensor(EXACT['lr'], device=gpu)
+    lr_dev = G.place(torch.tensor(EXACT['lr'], device=gpu), 'lr')
     it, p, g = _exact_item(100 + n, n, gpu, lr_dev)
     _launch([it], gpu)
     got_p, got_m, got_v, step = it.host()
@@ -137,7 +158,7 @@ def test_one_exact_step_bit_for_bit(rt, gpu, n):
 
 
 def test_one_table_of_three_items_at_step_counts_0_1_and_9(rt, gpu):
-    lr_dev = torch.tensor(EXACT['lr'], device=gpu)
+    lr_dev = G.place(torch.tensor(EXACT['lr'], device=gpu), 'lr')
     starts, lens = (0.0, 1.0, 9.0), (16385, 5, 1024)
     made = [_exact_item(200 + i, n, gpu, lr_dev, step=s) for i, (n, s) in enumerate(zip(lens, starts))]
     _launch([m[0] for m in made], gpu)
@@ -156,6 +177,25 @@ def test_one_table_of_three_items_at_step_counts_0_1_and_9(rt, gpu):
             assert got_p.tobytes() == o_p.astype(np.float32).tobytes()
 
 
+TAIL_LENS = [1, 3, 4, 5, 1023, 1024, 1025, 1]            # one launch; the first and the last item have one element
+
+
+def test_one_table_of_every_tail_length_against_the_flanks(rt, gpu):
+    """No sentinel bands: p, g, m and v of every item end where their back flank begins, so a float4 that reaches past a tail of
+    1, 3 or 5 elements reads 0xFF bytes or writes into a flank.  Exact operands, one step from zero moments."""
+    lr_dev = G.place(torch.tensor(EXACT['lr'], device=gpu), 'lr')
+    made = [_exact_item(500 + i, n, gpu, lr_dev, band=0) for i, n in enumerate(TAIL_LENS)]
+    assert all(t.data_ptr() % 16 == 0 and t.numel() == it.n for it, _, _ in made for t in it.full)
+    table = _launch([m[0] for m in made], gpu)
+    assert table[2] == len(TAIL_LENS)                     # one block each
+    for it, p, g in made:
+        got_p, got_m, got_v, step = it.host()
+        assert got_p.tobytes() == (p - np.float32(EXACT['lr']) * np.sign(g)).astype(np.float32).tobytes(), it.n
+        assert got_m.tobytes() == (g / 2).astype(np.float32).tobytes() and got_v.tobytes() == (g * g / 4).astype(np.float32).tobytes(), it.n
+        assert step == 1.0 and it.g.cpu().numpy().tobytes() == g.tobytes()
+        assert float(it.step[0]) == SENTINEL and float(it.step[2]) == SENTINEL
+
+
 # ---------------------------------------------------------------- 2. random operands
 GROUPS = (dict(lens=(1000, 16384 + 5, 37), lr=1e-2, betas=(0.9, 0.999), eps=1e-8, wd=0.05),
           dict(lens=(4100, 3), lr=3e-3, betas=(0.8, 0.95), eps=1e-6, wd=0.01))
@@ -171,7 +211,7 @@ def test_five_random_steps_of_two_groups_within_the_bound(rt, gpu, decoupled):
     cls = torch.optim.AdamW if decoupled else torch.optim.Adam
     items, t_params, t_groups, state64, hypers = [], [], [], [], []
     for gr in GROUPS:
-        lr_dev = torch.tensor(gr['lr'], device=gpu)
+        lr_dev = G.place(torch.tensor(gr['lr'], device=gpu), 'lr')
         ps = []
         for n in gr['lens']:
             p = rng.standard_normal(n).astype(np.float32)
@@ -219,7 +259,7 @@ def _random_items(seed, gpu, lr_dev, g_scale=1.0, wd=0.05, decoupled=False):
 
 @pytest.mark.parametrize('decoupled', [False, True])
 def test_clip_coefficient_and_skip(rt, gpu, decoupled):
-    lr_dev = torch.tensor(1e-2, device=gpu)
+    lr_dev = G.place(torch.tensor(1e-2, device=gpu), 'lr')
     state = lambda items: [t.clone() for it in items for t in it.full + [it.step]]
     same = lambda a, b: all(_same(x, y) for x, y in zip(a, b))
     # coef = 0.5 is the unclipped step on g / 2 (halving is exact)
@@ -250,7 +290,7 @@ def test_kernel_equals_the_float32_restatement_bit_for_bit(rt, gpu, decoupled, c
     """tests/adam_ref.py::adam_step32 is the kernel operation for operation (correctly rounded square root and division, nothing
     contracted, the bias corrections in float64 by squaring): three steps on random operands from non-zero moments and step counts
     0, 3 and 1, with and without a clip coefficient whose product with g rounds, give the same bits."""
-    lr_dev = torch.tensor(1e-2, device=gpu)
+    lr_dev = G.place(torch.tensor(1e-2, device=gpu), 'lr')
     items = _random_items(450, gpu, lr_dev, decoupled=decoupled)
     rec = None if coef is None else _make_rec(coef, 0, gpu)
     rng = np.random.default_rng(451)

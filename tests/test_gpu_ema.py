@@ -1,6 +1,11 @@
 """EMA teacher on the GPU (mi355_ema_update, mi355_ema_update_batched, mi355.optim.EMATeacher, DAStep's `ema`, the command
 lines).  Everything is compared bit for bit: the update is three fp32 roundings (tests/ema_ref.py, equal to the reference's
-live functions through tests/golden/g11_ema.npz), so there is no tolerance to choose."""
+live functions through tests/golden/g11_ema.npz), so there is no tolerance to choose.
+
+Guards (tests/guarded.py).  The two kernel-level tests and test_batched_table_of_every_tail_length keep the teacher's and the main
+model's ranges, the coefficient pair, the counters and the item table in G.place() copies, launch inside a window and check
+every flank afterwards.  The kernels update in place (no unwritten check); the comparisons are the ones from before.  The flat
+kernel also runs on a range that ends exactly where its flank begins.  EMATeacher, DAStep and the command lines are not guarded."""
 import os
 import re
 import subprocess
@@ -12,8 +17,25 @@ import torch
 
 from conftest import PKG, golden
 import ema_ref
+import guarded as G
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def guards():
+    G.reset()
+    yield
+    G.reset()
+
+
+def _guard(label, fn, *args):
+    from mi355 import ops
+    with G.window(ops, label):
+        out = fn(*args)
+    torch.cuda.synchronize()
+    G.check(label)
+    return out
 
 GRID_CAP = 4096                       # blocks of one flat launch (as sgd_kernel): 256 lanes x float4 each per pass
 KEYS = ['0.weight', '1.weight', '1.bias', '1.running_mean', '1.running_var', '1.num_batches_tracked']
@@ -44,12 +66,15 @@ def test_flat_kernel_bit_exact(gpu, n, m):
     rng = np.random.default_rng(n % 1000 + int(m * 1000))
     e0 = rng.standard_normal(n + 64).astype(np.float32)
     p0 = rng.standard_normal(n).astype(np.float32)
-    e, p = torch.from_numpy(e0).to(gpu), torch.from_numpy(p0).to(gpu)
-    ops.ema_update(e[:n], p, _coef(m, gpu))
-    torch.cuda.synchronize()
+    e, p = G.place(torch.from_numpy(e0).to(gpu), 'e'), G.place(torch.from_numpy(p0).to(gpu), 'p')
+    coef = G.place(_coef(m, gpu), 'coef')
+    _guard('ema_update n=%d' % n, ops.ema_update, e[:n], p, coef)
     assert _same(e[:n], ema_ref.ema_array(e0[:n], p0, m))
     assert _same(e[n:], e0[n:])                    # the guard band behind the range
     assert _same(p, p0)                            # the main model's side is only read
+    tight = G.place(torch.from_numpy(e0[:n].copy()).to(gpu), 'e, tight')          # ... and a range that ends where its flank begins
+    _guard('ema_update tight n=%d' % n, ops.ema_update, tight, p, coef)
+    assert _same(tight, ema_ref.ema_array(e0[:n], p0, m)) and _same(p, p0)
 
 
 def test_flat_wrapper_checks_room(gpu):
@@ -82,17 +107,18 @@ def test_batched_kernel_bit_exact(gpu):
     total = pos + 16
     d0 = rng.standard_normal(total).astype(np.float32)
     s0 = rng.standard_normal(total).astype(np.float32)
-    dst, src = torch.from_numpy(d0).to(gpu), torch.from_numpy(s0).to(gpu)
+    dst, src = G.place(torch.from_numpy(d0).to(gpu), 'dst'), G.place(torch.from_numpy(s0).to(gpu), 'src')
     assert dst.data_ptr() % 16 == 0 and dst[offs[1]:].data_ptr() % 16 == 4
-    cnt_src = torch.tensor([7, -1, 1 << 40, -1], dtype=torch.int64, device=gpu)
-    cnt_dst = torch.full((4,), -5, dtype=torch.int64, device=gpu)
+    cnt_src = G.place(torch.tensor([7, -1, 1 << 40, -1], dtype=torch.int64, device=gpu), 'counters, main')
+    cnt_dst = G.place(torch.full((4,), -5, dtype=torch.int64, device=gpu), 'counters, teacher')
     recs = [(src[o:o + n], dst[o:o + n], ops.EMA_F32) for o, n in zip(offs, sizes)]
     recs.insert(2, (cnt_src[0], cnt_dst[0], ops.EMA_COPY64))
     recs.append((cnt_src[2], cnt_dst[2], ops.EMA_COPY64))
     table, count, blocks = ops.ema_table(recs, gpu)
     assert count == 8 and blocks == 1 + 1 + 1 + 1 + 1 + 2 + 35 + 1
-    ops.ema_update_batched(table, count, blocks, _coef(m, gpu))
-    torch.cuda.synchronize()
+    table = G.place(table, 'ema table')
+    assert table.numel() == count * ops.EMA_ITEM_BYTES
+    _guard('ema_update_batched', ops.ema_update_batched, table, count, blocks, G.place(_coef(m, gpu), 'coef'))
     want = d0.copy()
     for o, n in zip(offs, sizes):
         want[o:o + n] = ema_ref.ema_array(d0[o:o + n], s0[o:o + n], m)
@@ -100,6 +126,29 @@ def test_batched_kernel_bit_exact(gpu):
     assert _same(dst, want)                        # every record right, every gap untouched
     assert _same(src, s0)
     assert cnt_dst.tolist() == [7, -5, 1 << 40, -5] and cnt_src.tolist() == [7, -1, 1 << 40, -1]
+
+
+def test_batched_table_of_every_tail_length(gpu):
+    """Items of 1, 3, 4, 5, 1023, 1024, 1025 and 1 elements in one launch, each pair of ranges in buffers of its own that end where
+    their flanks begin, and a counter copy between them."""
+    from mi355 import ops
+    m = 0.999
+    sizes = [1, 3, 4, 5, 1023, 1024, 1025, 1]
+    rng = np.random.default_rng(15)
+    d0 = [rng.standard_normal(n).astype(np.float32) for n in sizes]
+    s0 = [rng.standard_normal(n).astype(np.float32) for n in sizes]
+    dst = [G.place(torch.from_numpy(a).to(gpu), 'dst[%d]' % len(a)) for a in d0]
+    src = [G.place(torch.from_numpy(a).to(gpu), 'src[%d]' % len(a)) for a in s0]
+    cnt_src = G.place(torch.tensor([12345678901], dtype=torch.int64, device=gpu), 'counter, main')
+    cnt_dst = G.place(torch.tensor([-5], dtype=torch.int64, device=gpu), 'counter, teacher')
+    recs = [(a, b, ops.EMA_F32) for a, b in zip(src, dst)]
+    recs.insert(4, (cnt_src[0], cnt_dst[0], ops.EMA_COPY64))
+    table, count, blocks = ops.ema_table(recs, gpu)
+    assert count == blocks == 9                          # every item less than a chunk: exactly one block each
+    _guard('ema_update_batched tails', ops.ema_update_batched, G.place(table, 'ema table'), count, blocks, G.place(_coef(m, gpu), 'coef'))
+    for d, a, b0, a0 in zip(dst, src, d0, s0):
+        assert _same(d, ema_ref.ema_array(b0, a0, m)) and _same(a, a0), len(a0)
+    assert cnt_dst.tolist() == [12345678901] and cnt_src.tolist() == [12345678901]
 
 
 # ---------------------------------------------------------------- the golden case through EMATeacher

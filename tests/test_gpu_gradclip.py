@@ -11,6 +11,12 @@ mi355_grad_clip_coef, mi355_sgd_nesterov_clipped; mi355.optim.GradClipper; DASte
   6. DAStep: clip=GradClipper(inf) changes nothing bit for bit; a finite max_norm records the float64 norm of the flat
      gradients, changes the parameters, and replays as it runs eagerly;
   7. the command line.
+
+Guards (tests/guarded.py).  Sections 1 - 4 keep the gradient ranges (with their NaN or sentinel bands), the item table, the
+partials -- a G.empty() buffer of exactly total_blocks doubles, all of them written by grad_sumsq_batched --, the clip record,
+lr, p, buf and the bf16 copy in guarded buffers; the launches run inside a window and every flank is checked after them (the
+captured launches of section 2 run as they did: nothing is allocated there).  test_one_table_of_every_tail_length_against_the_flanks
+has ranges that end where their flanks begin.  FusedSGD + GradClipper, DAStep and the command line are not guarded.
 """
 import functools
 import os
@@ -22,10 +28,26 @@ import pytest
 import torch
 
 import gradclip_ref as ref
+import guarded as G
 from conftest import PKG
 from seeded import randn
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def guards():
+    G.reset()
+    yield
+    G.reset()
+
+
+def _guard(label, fn, *args):
+    with G.window(_ops(), label):
+        out = fn(*args)
+    torch.cuda.synchronize()
+    G.check(label)
+    return out
 
 
 @pytest.fixture
@@ -58,8 +80,10 @@ class _Measure:
         ops = _ops()
         self.ranges = ranges
         self.table, self.count, self.blocks = ops.gn_table(ranges, gpu)
-        self.partials = torch.zeros(self.blocks, dtype=torch.float64, device=gpu)
-        self.rec = ops.clip_records(1, max_norm, gpu)
+        self.table = G.place(self.table, 'gn table')
+        assert self.table.numel() == self.count * ops.GN_ITEM_BYTES
+        self.partials = G.empty((self.blocks,), torch.float64, gpu, 'partials')       # exactly total_blocks doubles
+        self.rec = G.place(ops.clip_records(1, max_norm, gpu), 'clip record')
 
     def set_max_norm(self, max_norm):
         self.rec.view(torch.float32)[2].fill_(max_norm)
@@ -70,8 +94,8 @@ class _Measure:
         ops.grad_clip_coef(self.partials, self.blocks, self.rec)
 
     def __call__(self):
-        self.launch()
-        torch.cuda.synchronize()
+        _guard('grad_sumsq_batched + grad_clip_coef, %d blocks' % self.blocks, self.launch)
+        assert G.unwritten(self.partials) == 0
         return _host_rec(self.rec)
 
 
@@ -81,13 +105,17 @@ def _lens():
     return [1, 3, 4, 5, C - 4, C, C + 4, 2 * C + 8]
 
 
-def _int_range(seed, n, gpu):
-    """(device view [4 : 4 + n] of a buffer that is NaN everywhere else, its integer values in [-8, 8])."""
+def _int_range(seed, n, gpu, band=4):
+    """(device view [band : band + n] of a guarded buffer that is NaN everywhere else, its integer values in [-8, 8]); the view
+    keeps the whole buffer under the flank checks (band = 0: the range ends where its flank begins)."""
     vals = np.random.default_rng(seed).integers(-8, 9, n).astype(np.float32)
     vals[0] = 5.0                                   # (never an all-zero range)
-    buf = np.full(n + 8, np.nan, dtype=np.float32)
-    buf[4:4 + n] = vals
-    return torch.from_numpy(buf).to(gpu)[4:4 + n], vals
+    buf = np.full(n + 2 * band, np.nan, dtype=np.float32)
+    buf[band:band + n] = vals
+    full = G.place(torch.from_numpy(buf).to(gpu), 'g[%d]' % n)
+    view = full[band:band + n]
+    view.whole = full
+    return view, vals
 
 
 @pytest.mark.parametrize('case', list(range(8)) + ['all'])
@@ -110,11 +138,28 @@ def test_exact_integer_gradients_give_the_reference_record_bit_for_bit(rt, gpu, 
     assert (coef == 1.0) and ref.clip_record(vals, np.float32(0.5 * norm64))[2] < 1.0
 
 
+def test_one_table_of_every_tail_length_against_the_flanks(rt, gpu):
+    """Ranges of 1, 3, 4, 5, 1023, 1024, 1025 and 1 elements in one launch, none with a band around it: the float4 a lane loads
+    behind a tail of 1, 3 or 5 elements would read the 0xFF of the flank, a NaN that the sum of squares cannot hide."""
+    lens = [1, 3, 4, 5, 1023, 1024, 1025, 1]
+    views, vals = zip(*[_int_range(90 + i, n, gpu, band=0) for i, n in enumerate(lens)])
+    want_ss = int(sum(int((v.astype(np.int64) ** 2).sum()) for v in vals))
+    m = _Measure(list(views), 1.0, gpu)
+    assert m.blocks == m.count == len(lens) and m.partials.numel() == len(lens)
+    got = m()
+    ss, norm, coef, skip = ref.clip_record(vals, np.float32(1.0))
+    assert ss == want_ss and got['sumsq'] == want_ss
+    assert _bits(got['norm']) == _bits(norm) and _bits(got['coef']) == _bits(coef) and got['skip'] == skip == 0
+    per_block = [float((v.astype(np.float64) ** 2).sum()) for v in vals]
+    assert m.partials.cpu().tolist() == per_block
+
+
 # ---------------------------------------------------------------- 2. random data
 def test_random_gradients_within_the_summation_bound_and_reproducible(rt, gpu):
     lens = [100000, 150001, 50003]
     host = [(randn(60 + i, n + 8, scale=0.3 * (i + 1))).numpy() for i, n in enumerate(lens)]
-    views = [torch.from_numpy(h).to(gpu)[4:4 + n] for h, n in zip(host, lens)]
+    whole = [G.place(torch.from_numpy(h).to(gpu), 'g[%d]' % n) for h, n in zip(host, lens)]
+    views = [w[4:4 + n] for w, n in zip(whole, lens)]
     n_tot = sum(lens)
     ref64 = float(np.sqrt(sum(np.sum(h[4:4 + n].astype(np.float64) ** 2) for h, n in zip(host, lens))))
     m = _Measure(views, 0.5 * ref64, gpu)
@@ -145,19 +190,20 @@ def _make_rec(coef, skip, gpu, n_skipped=0):
     ops = _ops()
     r = np.zeros(1, dtype=ops.clip_rec_dtype())
     r['coef'], r['skip'], r['n_skipped'], r['max_norm'] = np.float32(coef), skip, n_skipped, 1.0
-    return torch.from_numpy(r.view(np.uint8).copy()).to(gpu)
+    return G.place(torch.from_numpy(r.view(np.uint8).copy()).to(gpu), 'clip record')
 
 
 def _sgd_state(seed, n, gpu):
-    """p, g, buf (float32) and a bf16 copy, each a view [4 : 4 + n] of a buffer with sentinels around it."""
+    """p, g, buf (float32) and a bf16 copy, each a view [4 : 4 + n] of a guarded buffer with sentinels around it."""
     full = [randn(seed + i, n + 8).to(gpu) for i in range(3)] + [torch.full((n + 8,), 7.0, dtype=torch.bfloat16, device=gpu)]
+    full = [G.place(t, name) for t, name in zip(full, ('p', 'g', 'buf', 'p_lowp'))]
     return full, [t[4:4 + n] for t in full]
 
 
-@pytest.mark.parametrize('n', [4, 5, 1023, 4100])
+@pytest.mark.parametrize('n', [1, 3, 4, 5, 1023, 1024, 1025, 4100])
 def test_clipped_sgd_equals_the_unclipped_kernel_on_scaled_gradients(rt, gpu, n):
     ops = _ops()
-    lr = torch.tensor(0.05, device=gpu)
+    lr = G.place(torch.tensor(0.05, device=gpu), 'lr')
     for coef in (np.float32(0.3712345), np.float32(1.0)):
         rec = _make_rec(coef, 0, gpu)
         for nesterov in (True, False):
@@ -167,9 +213,9 @@ def test_clipped_sgd_equals_the_unclipped_kernel_on_scaled_gradients(rt, gpu, n)
                     fb, (pb, gb, bb, lb) = _sgd_state(70, n, gpu)
                     before = [t.clone() for t in fa]
                     for _ in range(2):                       # (the second step reads a non-zero momentum written by the first)
-                        ops.sgd_nesterov_clipped(pa, ga, ba, lr, rec, 0.9, wd, nesterov, la if lowp else None)
-                        scaled = gb if coef == 1.0 else gb * torch.tensor(coef, dtype=torch.float32, device=gpu)
-                        ops.sgd_nesterov(pb, scaled, bb, lr, 0.9, wd, nesterov, lb if lowp else None)
+                        _guard('sgd_nesterov_clipped n=%d' % n, ops.sgd_nesterov_clipped, pa, ga, ba, lr, rec, 0.9, wd, nesterov, la if lowp else None)
+                        scaled = gb if coef == 1.0 else G.place(gb * torch.tensor(coef, dtype=torch.float32, device=gpu), 'g * coef')
+                        _guard('sgd_nesterov n=%d' % n, ops.sgd_nesterov, pb, scaled, bb, lr, 0.9, wd, nesterov, lb if lowp else None)
                     torch.cuda.synchronize()
                     what = (n, float(coef), nesterov, wd, lowp)
                     for x, y, z in zip(fa, fb, before):
@@ -187,17 +233,20 @@ def test_non_finite_gradients_skip_the_update_and_are_counted(rt, gpu):
     lens = [1000, C + 5, 37]
     offs = np.cumsum([0] + [(n + 3) // 4 * 4 for n in lens])
     total = int(offs[-1])
-    P, G, M = randn(80, total).to(gpu), randn(81, total, scale=0.1).to(gpu), randn(82, total).to(gpu)
-    L = P.to(torch.bfloat16)
-    views = [G[o:o + n] for o, n in zip(offs[:-1], lens)]
+    P, Gr, M = (G.place(t, name) for t, name in zip((randn(80, total).to(gpu), randn(81, total, scale=0.1).to(gpu), randn(82, total).to(gpu)),
+                                                     ('p', 'g', 'buf')))
+    L = G.place(P.to(torch.bfloat16), 'p_lowp')
+    views = [Gr[o:o + n] for o, n in zip(offs[:-1], lens)]
     m = _Measure(views, 1.0, gpu)
-    lr = torch.tensor(0.05, device=gpu)
+    lr = G.place(torch.tensor(0.05, device=gpu), 'lr')
 
-    def step():
+    def launches():
         m.launch()
         for o, n in zip(offs[:-1], lens):
-            ops.sgd_nesterov_clipped(P[o:o + n], G[o:o + n], M[o:o + n], lr, m.rec, 0.9, 1e-4, True, L[o:o + n])
-        torch.cuda.synchronize()
+            ops.sgd_nesterov_clipped(P[o:o + n], Gr[o:o + n], M[o:o + n], lr, m.rec, 0.9, 1e-4, True, L[o:o + n])
+
+    def step():
+        _guard('measure + three clipped steps', launches)
         return _host_rec(m.rec)
 
     state = lambda: [t.clone() for t in (P, M, L)]
@@ -208,15 +257,15 @@ def test_non_finite_gradients_skip_the_update_and_are_counted(rt, gpu):
     assert r['skip'] == 0 and r['n_skipped'] == 0 and 0.0 < r['coef'] < 1.0 and not same(s0, state())
     # the fault is in the data only: one element of the middle range
     at = int(offs[1]) + C + 2
-    good = float(G[at])
+    good = float(Gr[at])
     for k, bad in enumerate((float('inf'), float('nan'))):
-        G[at] = bad
+        Gr[at] = bad
         s1 = state()
         r = step()
         assert r['skip'] == 1 and r['coef'] == 0.0 and r['n_skipped'] == k + 1, r
         assert not np.isfinite(r['sumsq']) and not np.isfinite(r['norm'])
         assert same(s1, state())
-    G[at] = good
+    Gr[at] = good
     s2 = state()
     r = step()
     assert r['skip'] == 0 and r['n_skipped'] == 2 and 0.0 < r['coef'] < 1.0 and not same(s2, state())

@@ -8,15 +8,57 @@ float32 run of the reference expression from it (the fixture's float32 arrays fo
 otherwise), with the floors jfa_ref.py writes down.  A gradient that is STORED in bf16 (bf16 features) may in addition, element by
 element, be one bf16 rounding from the value before storage: bf16 keeps 8 significant bits, so round-to-nearest moves a value v
 by at most half a unit in the last place, 2^-8 of the power of two below |v|, hence at most 2^-8 |v|; v itself is within the
-bound of the float64 value r, so the allowance of an element is 2^-8 (|r| + bound).  The format, not the kernel's arithmetic."""
+bound of the float64 value r, so the allowance of an element is 2^-8 (|r| + bound).  The format, not the kernel's arithmetic.
+
+Guards (tests/guarded.py).  The kernel-level tests of section 3 and the KL test of section 4 call the wrappers through _guard:
+feature maps, key points, descriptors and gradients are G.place() copies, descriptors, rows and KL gradients the wrappers make
+come from torch.empty / torch.empty_like inside the window, a feature gradient that is written (not accumulated) is a G.empty()
+buffer, and the row pitch is W * C * esize of the feature map.  The tests through uda.model.loss and autograd (sections 1 and 2,
+the two-runs test) go through _run, which keeps one window open over the forward, the backward and the two loss1 calls: the
+wrappers allocate every descriptor and gradient there too, so all of them are guarded and must be written completely.  The
+GradFanIn test and DAStep are not guarded."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden
+import guarded as G
 import jfa_ref
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def guards():
+    G.reset()
+    yield
+    G.reset()
+
+
+def _guard(label, fn, *args, **kw):
+    """One wrapper call inside a guard window; no flank byte of anything placed or allocated has changed afterwards."""
+    from mi355 import ops
+    with G.window(ops, label):
+        out = fn(*args, **kw)
+    torch.cuda.synchronize()
+    G.check(label)
+    return out
+
+
+def _gfeat(gpu, a, dtype, name='feature'):
+    """_feat inside guards, and the row pitch of the calls that follow: one image row of it."""
+    t = _feat(gpu, a, dtype)
+    G.row_pitch(t.shape[3] * t.shape[1] * t.element_size())
+    return G.place(t, name)
+
+
+def _gdev(gpu, a, name):
+    return G.place(torch.from_numpy(np.ascontiguousarray(a)).to(gpu), name)
+
+
+def _gout(gpu, B, C, H, W, dtype, name='out'):
+    """A channels_last feature gradient with nothing but the fill in it."""
+    return G.empty((B, H, W, C), dtype, gpu, name).permute(0, 3, 1, 2)
 
 POISON = -7777.25
 KEYS = ('loss', 'grad_f1', 'grad_f2', 'desc1', 'desc2')
@@ -62,15 +104,22 @@ def _check(tag, got, ref32, ref64, stored_bf16=False):
 
 def _run(gpu, f1, f2, p1, p2, dtype=torch.float32, up=None, **opts):
     """loss3 and loss1 of uda.model.loss through autograd: dict of loss, both feature gradients and both descriptors."""
+    from mi355 import ops
     from uda.model.loss import loss1, loss3
-    a, b = _feat(gpu, f1, dtype, True), _feat(gpu, f2, dtype, True)
-    x1, x2 = torch.from_numpy(np.asarray(p1, np.float32)).to(gpu), torch.from_numpy(np.asarray(p2, np.float32)).to(gpu)
-    loss = loss3(a, b, x1, x2, **opts)
-    (loss if up is None else loss * up).backward()
-    kw = {k: v for k, v in opts.items() if k != 'scale'}
-    with torch.no_grad():
-        d1, d2 = loss1(a, x1, **kw), loss1(b, x2, **kw)
+    # inside guards: the features and key points are placed; the descriptors, rows, KL gradients and the feature gradients are
+    # all made by the wrappers (torch.empty / torch.empty_like) while the window is open, the backward included
+    a, b = _gfeat(gpu, f1, dtype, 'f1').requires_grad_(True), _gfeat(gpu, f2, dtype, 'f2').requires_grad_(True)
+    x1, x2 = _gdev(gpu, np.asarray(p1, np.float32), 'pre1'), _gdev(gpu, np.asarray(p2, np.float32), 'pre2')
+    label = 'loss3 + backward + loss1 %s %s' % (tuple(a.shape), dtype)
+    with G.window(ops, label):
+        loss = loss3(a, b, x1, x2, **opts)
+        (loss if up is None else loss * up).backward()
+        kw = {k: v for k, v in opts.items() if k != 'scale'}
+        with torch.no_grad():
+            d1, d2 = loss1(a, x1, **kw), loss1(b, x2, **kw)
     torch.cuda.synchronize()
+    G.check(label)
+    assert all(G.unwritten(t) == 0 for t in (a.grad, b.grad, d1, d2, loss.detach()))
     assert a.grad.dtype == dtype and ops_is_nhwc(a.grad) and d1.dtype == torch.float32
     return dict(loss=float(loss.detach()), grad_f1=_nchw(a.grad), grad_f2=_nchw(b.grad), desc1=d1.cpu().numpy(), desc2=d2.cpu().numpy())
 
@@ -208,12 +257,12 @@ def _exact(gpu, B=2, K=21, C=40, H=32, W=48, radius=6, axes='xy', seed=8):
 def test_pool_is_bit_identical_on_exact_operands(gpu, axes):
     from mi355 import ops
     rng, f, p = _exact(gpu, axes=axes)
-    xy = torch.from_numpy(p).to(gpu)
+    xy = _gdev(gpu, p, 'xy')
     want = (jfa_ref.pool(f, p, 6, axes, np.float64) * 169).astype(np.float32) / np.float32(169)
     for dtype in (torch.bfloat16, torch.float32):
-        d = ops.joint_pool(_feat(gpu, f, dtype), xy, 6, axes)
-        d2 = ops.joint_pool(_feat(gpu, f, dtype), xy, 6, axes)
-        torch.cuda.synchronize()
+        d = _guard('joint_pool %s %s' % (axes, dtype), ops.joint_pool, _gfeat(gpu, f, dtype), xy, 6, axes)
+        d2 = _guard('joint_pool %s %s again' % (axes, dtype), ops.joint_pool, _gfeat(gpu, f, dtype), xy, 6, axes)
+        assert G.unwritten(d) == 0 and G.unwritten(d2) == 0
         assert _same(d, want) and _same(d, d2), dtype
     assert (want[:, 8] == 0).all() and want.max() > 0.5
 
@@ -224,16 +273,16 @@ def test_scatter_is_bit_identical_with_the_fixed_order_model(gpu, axes, dtype):
     from mi355 import ops
     B, K, C, H, W = 2, 21, 40, 32, 48
     rng, f, p = _exact(gpu, B, K, C, H, W, axes=axes)
-    xy = torch.from_numpy(p).to(gpu)
+    xy = _gdev(gpu, p, 'xy')
     gd = rng.standard_normal((B, K, C)).astype(np.float32)
     rnd = jfa_ref.bf16_round if dtype == torch.bfloat16 else None
     want, cov = jfa_ref.scatter_model(gd, p, (B, H, W, C), 6, axes, round_to=rnd)
     assert cov.any() and not cov.all()
-    gdev = torch.from_numpy(gd).to(gpu)
-    out = ops.nhwc_empty(B, C, H, W, dtype, gpu)
-    out.fill_(POISON)
-    ops.joint_scatter(gdev, xy, out, False, 6, axes)
-    torch.cuda.synchronize()
+    gdev = _gdev(gpu, gd, 'gd')
+    G.row_pitch(W * C * (2 if dtype == torch.bfloat16 else 4))
+    out = _gout(gpu, B, C, H, W, dtype)
+    _guard('joint_scatter = %s %s' % (axes, dtype), ops.joint_scatter, gdev, xy, out, False, 6, axes)
+    assert G.unwritten(out) == 0
     got = out.permute(0, 2, 3, 1).float().cpu().numpy()
     assert _same(got, want)
     assert (got[~cov] == 0).all() and not np.signbit(got[~cov]).any()                      # +0 outside every window
@@ -242,7 +291,7 @@ def test_scatter_is_bit_identical_with_the_fixed_order_model(gpu, axes, dtype):
     base = jfa_ref.bf16_round(base) if dtype == torch.bfloat16 else base
     out.fill_(POISON)
     out.copy_(torch.from_numpy(base).to(gpu).permute(0, 3, 1, 2))
-    ops.joint_scatter(gdev, xy, out, True, 6, axes)
+    _guard('joint_scatter += %s %s' % (axes, dtype), ops.joint_scatter, gdev, xy, out, True, 6, axes)
     again = out.clone()
     torch.cuda.synchronize()
     want_acc, _ = jfa_ref.scatter_model(gd, p, (B, H, W, C), 6, axes, onto=base, round_to=rnd)
@@ -251,9 +300,53 @@ def test_scatter_is_bit_identical_with_the_fixed_order_model(gpu, axes, dtype):
     assert _bits(got[~cov]) == _bits(base[~cov]) and not np.array_equal(got[cov], base[cov])
     # two runs give the same bits
     out.copy_(torch.from_numpy(base).to(gpu).permute(0, 3, 1, 2))
-    ops.joint_scatter(gdev, xy, out, True, 6, axes)
-    torch.cuda.synchronize()
+    _guard('joint_scatter += %s %s again' % (axes, dtype), ops.joint_scatter, gdev, xy, out, True, 6, axes)
     assert _same(out, again)
+
+
+# key points on the four corners of the first and of the last image, windows of one pixel and windows larger than the map
+CORNER_C = [8, 264]               # one chunk; a second channel tile of one bf16 chunk / two fp32 chunks behind 256 channels
+
+
+def _corners(B, K, H, W, axes):
+    assert K == 4
+    p = np.tile(np.array([[0, 0], [W - 1, H - 1], [0, H - 1], [W - 1, 0]], np.float32), (B, 1, 1))
+    return p[..., ::-1].copy() if axes == 'ref' else p
+
+
+@pytest.mark.parametrize('radius', [1, 16])
+@pytest.mark.parametrize('C', CORNER_C)
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32], ids=['bf16', 'f32'])
+@pytest.mark.parametrize('axes', ['xy', 'ref'])
+def test_pool_and_scatter_at_the_corners_of_the_first_and_last_image(gpu, axes, dtype, C, radius):
+    """B = 2, K = 4, a 5 x 7 map: the windows touch the first and the last pixel of the feature map, which sit against the guard
+    flanks; with C = 264 the last thread of the second channel tile idles."""
+    from mi355 import ops
+    B, K, H, W = 2, 4, 5, 7
+    rng = np.random.default_rng(C * 10 + radius)
+    f = (rng.integers(0, 16, (B, C, H, W)) / 8).astype(np.float32)         # every window sum is exact in fp32 in any order
+    p = _corners(B, K, H, W, axes)
+    win = jfa_ref.windows(p, H, W, radius, axes)
+    assert ((win[..., 1] > win[..., 0]) & (win[..., 3] > win[..., 2])).all() and (win[:, 0, [0, 2]] == 0).all()
+    xy = _gdev(gpu, p, 'xy')
+    div = (2 * radius + 1) ** 2
+    want = (jfa_ref.pool(f, p, radius, axes, np.float64) * div).astype(np.float32) / np.float32(div)
+    d = _guard('joint_pool corners', ops.joint_pool, _gfeat(gpu, f, dtype), xy, radius, axes)
+    assert G.unwritten(d) == 0 and _same(d, want) and want.max() > 0
+    gd = rng.standard_normal((B, K, C)).astype(np.float32)
+    rnd = jfa_ref.bf16_round if dtype == torch.bfloat16 else None
+    want_g, cov = jfa_ref.scatter_model(gd, p, (B, H, W, C), radius, axes, round_to=rnd)
+    assert cov[0, 0, 0] and cov[B - 1].any() and not cov.all()
+    gdev = _gdev(gpu, gd, 'gd')
+    out = _gout(gpu, B, C, H, W, dtype)
+    _guard('joint_scatter = corners', ops.joint_scatter, gdev, xy, out, False, radius, axes)
+    assert G.unwritten(out) == 0 and _same(out.permute(0, 2, 3, 1).float().cpu().numpy(), want_g)
+    base = rng.standard_normal((B, H, W, C)).astype(np.float32)
+    base = jfa_ref.bf16_round(base) if dtype == torch.bfloat16 else base
+    acc = G.place(torch.from_numpy(base).to(gpu).to(dtype), 'out +=').permute(0, 3, 1, 2)
+    _guard('joint_scatter += corners', ops.joint_scatter, gdev, xy, acc, True, radius, axes)
+    want_acc, _ = jfa_ref.scatter_model(gd, p, (B, H, W, C), radius, axes, onto=base, round_to=rnd)
+    assert _same(acc.permute(0, 2, 3, 1).float().cpu().numpy(), want_acc)
 
 
 def test_two_runs_give_the_same_bits(gpu):
@@ -270,16 +363,22 @@ def test_gradient_requests(gpu, want):
     from mi355 import ops
     rng = np.random.default_rng(5)
     a, b = rng.random((3, 21, 40)).astype(np.float32), rng.random((3, 21, 40)).astype(np.float32)
-    ad, bd = torch.from_numpy(a).to(gpu), torch.from_numpy(b).to(gpu)
+    ad, bd = _gdev(gpu, a, 'a'), _gdev(gpu, b, 'b')
     # both gradient buffers are handed over whatever is wanted, as neighbours inside one poisoned allocation with guard zones:
     # a side that is not wanted, and everything around a side that is, must keep the poison
     n = ad.numel()
-    flat = torch.full((3 * n + 64,), POISON, device=gpu)
+    flat = G.place(torch.full((3 * n + 64,), POISON, device=gpu), 'gradients')
     ga, gb = flat[32:32 + n].view(ad.shape), flat[32 + n:32 + 2 * n].view(bd.shape)
     assert ga.data_ptr() % 16 == 0 and gb.data_ptr() % 16 == 0
-    rows, ra, rb = ops.joint_kl(ad, bd, want[0], want[1], 0.5, grad_a=ga, grad_b=gb)
-    loss = ops.reduce_sum(rows.view(-1), 0.5 / rows.numel())
-    torch.cuda.synchronize()
+    G.row_pitch(a.shape[-1] * 4)
+    rows, ra, rb = _guard('joint_kl %s' % (want,), ops.joint_kl, ad, bd, want[0], want[1], 0.5, grad_a=ga, grad_b=gb)
+    loss = _guard('reduce_sum', ops.reduce_sum, rows.view(-1), 0.5 / rows.numel())
+    assert G.unwritten(rows) == 0 and G.unwritten(loss) == 0
+    # ... and with the gradients left to the wrapper (torch.empty_like inside the window): the same bits, all of them written
+    rows2, ra2, rb2 = _guard('joint_kl %s, own gradients' % (want,), ops.joint_kl, ad, bd, want[0], want[1], 0.5)
+    assert _same(rows2, rows) and G.unwritten(rows2) == 0
+    for mine, theirs, w in ((ra2, ga, want[0]), (rb2, gb, want[1])):
+        assert (mine is None) == (not w) and (not w or (G.unwritten(mine) == 0 and _same(mine, theirs)))
     assert (ra is None) == (not want[0]) and (rb is None) == (not want[1])
     l64, r64, ga64, gb64 = jfa_ref.kl(a, b, 0.5, np.float64)
     l32, r32, ga32, gb32 = jfa_ref.kl(a, b, 0.5, np.float32)

@@ -5,15 +5,31 @@ the tiling can go wrong and at the workload's row length; their bit-level proper
 The tolerance, everywhere: a kernel result may be as far from the float64 result as 4 times the distance of a float32 run of the
 reference expression from it (the fixture's float32 arrays for the fixture cases, mmd_ref in float32 otherwise), with floors of
 5e-7 relative on the loss and 1e-6 of max |grad| on each gradient (mmd_ref.bounds; tests/test_mmd_cpu.py shows the reference's own
-float32 run to stay below the floors)."""
+float32 run to stay below the floors).
+
+Guards (tests/guarded.py).  Every launch of sections 2 - 4 goes through _kernels: source, target and the gradient buffers of a
+side that is not wanted (poisoned, and required to keep the poison) are G.place() copies, the wanted gradients are G.empty()
+buffers handed in through grad_source= / grad_target=, rows and the scalar come from torch.empty inside the window, and the
+wrapper's workspace cache (ops._mmd_ws) is emptied with monkeypatch for the call, so the (K, n, n) matrices sit in exactly
+mi355_mmd_workspace(B, K) bytes between two flanks.  The row pitch is HW * 4.  The fixture test of section 1 goes through the
+loss classes and autograd with the window open over forward and backward: the wrapper makes rows, both gradients
+(torch.empty_like) and the workspace inside it.  Sections 5 and 6 launch nothing or run DAStep."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden
+import guarded as G
 import mmd_ref
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def guards():
+    G.reset()
+    yield
+    G.reset()
 
 POISON = np.float32(-7777.25)
 
@@ -27,27 +43,43 @@ def _same(a, b):
     return _bits(a) == _bits(b)
 
 
-def _dev(gpu, a, offset=0):
+def _dev(gpu, a, offset=0, name='operand'):
     """`a` on the device; offset 1: as a contiguous view that starts one float behind a 16-byte boundary."""
     a = np.ascontiguousarray(a, np.float32)
-    buf = torch.full((a.size + 8,), float(POISON), device=gpu)
-    v = buf[offset:offset + a.size].view(a.shape)
-    v.copy_(torch.from_numpy(a))
+    v = G.place(torch.from_numpy(a).to(gpu), name, start=G.START + 4 * offset)
     assert v.is_contiguous() and v.data_ptr() % 16 == 4 * offset
     return v
 
 
-def _kernels(gpu, s, t, want=(True, True), offset=0, scale=1.0, **opts):
+def _kernels(gpu, s, t, want=(True, True), offset=0, scale=1.0, own_grads=True, **opts):
     """(loss, rows, grad_source, grad_target) of the launches; the gradient buffers are poisoned first and, when a side is not
     wanted, handed back as they are."""
+    import mi355
     from mi355 import ops
-    sd, td = _dev(gpu, s, offset), _dev(gpu, t, offset)
-    gs, gt = _dev(gpu, np.full(s.shape, POISON), offset), _dev(gpu, np.full(t.shape, POISON), offset)
-    rows, a, b = ops.mmd_heatmap(sd, td, want[0], want[1], scale=scale, grad_source=gs if want[0] else None,
-                                 grad_target=gt if want[1] else None, **opts)
-    loss = ops.reduce_sum(rows, float(scale) / rows.numel())
+    B, K = s.shape[:2]
+    G.row_pitch(int(np.prod(s.shape[2:])) * 4)
+    sd, td = _dev(gpu, s, offset, 'source'), _dev(gpu, t, offset, 'target')
+    gs, gt = [G.empty(x.shape, torch.float32, gpu, n, start=G.START + 4 * offset) if w else _dev(gpu, np.full(x.shape, POISON), offset, n)
+              for x, w, n in ((s, want[0], 'grad_source'), (t, want[1], 'grad_target'))]
+    label = 'mmd_heatmap B%d K%d %s want %s' % (B, K, s.shape[2:], want)
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(ops, '_mmd_ws', {})                   # the workspace is allocated inside the window, at the library's size
+        with G.window(ops, label):
+            rows, a, b = ops.mmd_heatmap(sd, td, want[0], want[1], scale=scale, grad_source=gs if want[0] and own_grads else None,
+                                         grad_target=gt if want[1] and own_grads else None, **opts)
+            loss = ops.reduce_sum(rows, float(scale) / rows.numel())
+        if not own_grads:                                # the wrapper's own torch.empty_like, made inside the window
+            gs, gt = a if want[0] else gs, b if want[1] else gt
+        (work,) = ops._mmd_ws.values()
+    need = int(mi355.load().mi355_mmd_workspace(B, K))
+    assert need == K * 4 * B * B * 4 and work.numel() * 4 == need and G._buf_of(work).n == need      # a guarded buffer of exactly that size
     torch.cuda.synchronize()
+    G.check(label)
+    assert G.unwritten(work) == 0 and G.unwritten(rows) == 0 and G.unwritten(loss) == 0
+    assert all(G.unwritten(g) == 0 for g, w in ((gs, want[0]), (gt, want[1])) if w)
+    assert _same(sd, s) and _same(td, t)                                # the inputs are only read
     assert (a is None) == (not want[0]) and (b is None) == (not want[1])
+    _kernels.work = work
     return float(loss), rows.cpu().numpy(), gs.cpu().numpy(), gt.cpu().numpy()
 
 
@@ -68,13 +100,20 @@ def test_kernels_against_the_reference(gpu, case):
     """Through the public classes and autograd: MMD_loss3 (a - c) and MMD_loss (d), loss and both gradients."""
     from uda.model.loss import MMD_loss, MMD_loss3
     g = golden('g14_mmd')
-    s = torch.from_numpy(g[case + '/source']).to(gpu).requires_grad_(True)
-    t = torch.from_numpy(g[case + '/target']).to(gpu).requires_grad_(True)
+    from mi355 import ops
+    G.row_pitch(int(np.prod(g[case + '/source'].shape[2:] if case != 'd' else g[case + '/source'].shape[1:])) * 4)
+    s = G.place(torch.from_numpy(g[case + '/source']).to(gpu), 'source').requires_grad_(True)
+    t = G.place(torch.from_numpy(g[case + '/target']).to(gpu), 'target').requires_grad_(True)
     crit = MMD_loss() if case == 'd' else MMD_loss3()
     assert (crit.kernel_mul, crit.kernel_num, crit.fix_sigma) == (2.0, 5, None)
-    loss = crit(s, t)
-    loss.backward()
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(ops, '_mmd_ws', {})                   # rows, both gradients (torch.empty_like) and the workspace: inside the window
+        with G.window(ops, 'MMD fixture ' + case):
+            loss = crit(s, t)
+            loss.backward()
     torch.cuda.synchronize()
+    G.check('MMD fixture ' + case)
+    assert G.unwritten(s.grad) == 0 and G.unwritten(t.grad) == 0 and G.unwritten(loss.detach()) == 0
     got = (float(loss.detach()), None, s.grad.cpu().numpy(), t.grad.cpu().numpy())
     ref32 = (g[case + '/loss'], g[case + '/grad_source'], g[case + '/grad_target'])
     ref64 = (g[case + '/loss64'], g[case + '/grad_source64'], g[case + '/grad_target64'])
@@ -142,6 +181,7 @@ def test_gradient_requests(gpu, B, want):
     ref32 = mmd_ref.mmd(s, t, dtype=np.float32)
     both = _kernels(gpu, s, t)
     got = _kernels(gpu, s, t, want=want)
+    assert all(_same(x, y) for x, y in zip(got[1:], _kernels(gpu, s, t, want=want, own_grads=False)[1:]))      # gradients the wrapper allocates
     assert got[0] == both[0] and _same(got[1], both[1])
     for side, g, full in ((0, got[2], both[2]), (1, got[3], both[3])):
         if want[side]:
@@ -185,7 +225,7 @@ def test_distances_are_symmetric_with_a_zero_diagonal(gpu):
     B, K = 17, 3
     s, t = _operands(9, B, K, (5, 7))
     _kernels(gpu, s, t, want=(False, False), kernel_num=1, fix_sigma=64.0, scale=-float(B * B * K))
-    c = ops._mmd_workspace(gpu, B, K).cpu().numpy().reshape(K, 2 * B, 2 * B)
+    c = _kernels.work.cpu().numpy().reshape(K, 2 * B, 2 * B)           # (the cache was emptied for the call: its own buffer)
     assert _same(c, np.ascontiguousarray(c.transpose(0, 2, 1)))
     assert _same(np.diagonal(c, axis1=1, axis2=2), np.full((K, 2 * B), 1.0 / 64.0, np.float32))
     assert (c[:, :B, :B] > 0).all() and (c[:, B:, B:] > 0).all() and (c[:, :B, B:] < 0).all() and (c[:, B:, :B] < 0).all()
@@ -219,6 +259,44 @@ def test_zero_bandwidth_joint(gpu):
     # every joint dead: loss 0
     s3 = np.broadcast_to(s[:1, :, :1, :1], s.shape).copy()
     assert _kernels(gpu, s3, s3.copy())[0] == 0.0
+
+
+# ---------------------------------------------------------------- 4b. the edges of the row count, inside guards
+@pytest.mark.parametrize('B,K,shape', [(1, 1, (3, 5)), (128, 1, (3, 5)), (2, 21, (4, 4))], ids=['n2', 'n256', 'K21-HW16'])
+def test_smallest_and_largest_row_counts(gpu, B, K, shape):
+    """n = 2 and n = 256 = MMD_MAX_ROWS with one joint and 15 pixels (the scalar path), and K = 21 with one float4 chunk."""
+    from mi355 import ops
+    assert 2 * 128 == ops.MMD_MAX_ROWS
+    s, t = _operands(1000 + B, B, K, shape)
+    ref64 = mmd_ref.mmd(s, t, dtype=np.float64)
+    ref32 = mmd_ref.mmd(s, t, dtype=np.float32)
+    got = _kernels(gpu, s, t)
+    _check('B%d K%d %s' % (B, K, shape), got, (ref32[0], ref32[2], ref32[3]), (ref64[0], ref64[2], ref64[3]))
+    assert np.allclose(got[1], ref64[1], rtol=1e-5, atol=1e-6)
+
+
+def test_workspace_one_byte_short_launches_nothing(gpu):
+    """mi355_mmd_heatmap refuses a workspace one byte short (MI355_EINVAL, the message names the workspace) ahead of its launches."""
+    import mi355
+    from mi355 import ops
+    B, K, HW = 3, 2, 16
+    s, t = _operands(5, B, K, (4, 4))
+    sd, td = _dev(gpu, s, 0, 'source'), _dev(gpu, t, 0, 'target')
+    need = int(mi355.load().mi355_mmd_workspace(B, K))
+    with G.window(ops, 'mmd workspace'):
+        work = torch.empty(need // 4, dtype=torch.float32, device=gpu)
+    rows, gs, gt = (G.empty(sh, torch.float32, gpu, n) for sh, n in (((K,), 'rows'), (s.shape, 'grad_source'), (t.shape, 'grad_target')))
+    ops.prof_reset(); ops.prof_enable(2)
+    try:
+        rc = mi355.load().mi355_mmd_heatmap(sd.data_ptr(), td.data_ptr(), work.data_ptr(), need - 1, rows.data_ptr(), gs.data_ptr(),
+                                            gt.data_ptr(), B, K, HW, 2.0, 5, 0.0, 1.0, mi355.stream_ptr())
+        torch.cuda.synchronize()
+        assert rc == -1 and b'workspace' in mi355.load().mi355_last_error()
+        assert ops.prof_launches() == []
+    finally:
+        ops.prof_enable(0); ops.prof_reset()
+    G.check('mmd workspace one byte short')
+    assert all(G.unwritten(x) == x.numel() * 4 for x in (work, rows, gs, gt))
 
 
 # ---------------------------------------------------------------- 5. refused arguments

@@ -1,6 +1,12 @@
 """Mean-teacher consistency on the GPU: mi355_bn_fold_batched and mi355_mse_heatmap against tests/mt_ref.py,
 uda.model.loss.mt_loss against the reference's live function (tests/golden/g12_mt.npz), the in-iteration teacher
-(mi355.teacher.InIterationTeacher) against today's host-folded eval path, DAStep's `mt` and the command lines."""
+(mi355.teacher.InIterationTeacher) against today's host-folded eval path, DAStep's `mt` and the command lines.
+
+Guards (tests/guarded.py).  The two loss-kernel tests place the prediction, the label and the record, call mse_heatmap inside a
+window (rows from torch.empty, the unit gradient from torch.empty_like, both written completely; the row pitch is H * W * 4) and
+check the flanks after every call; the unaligned case places its views 4 bytes off a 16-byte boundary and hands in a G.empty()
+gradient at the same offset.  The fold kernel keeps its own canaries; MeanTeacherLoss, the teacher, DAStep and the command lines
+are not guarded."""
 import os
 import re
 import subprocess
@@ -11,9 +17,26 @@ import pytest
 import torch
 
 from conftest import PKG, golden
+import guarded as G
 import mt_ref
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def guards():
+    G.reset()
+    yield
+    G.reset()
+
+
+def _guard(label, fn, *args, **kw):
+    from mi355 import ops
+    with G.window(ops, label):
+        out = fn(*args, **kw)
+    torch.cuda.synchronize()
+    G.check(label)
+    return out
 
 CANARY = np.float32(-7777.25)
 
@@ -134,13 +157,15 @@ def test_loss_kernel(gpu, B, hw):
     rng = np.random.default_rng(B * 100 + H)
     pre = rng.standard_normal((B, 21, H, W)).astype(np.float32)
     label = rng.random((B, 21, H, W)).astype(np.float32)
-    p, t = torch.from_numpy(pre).to(gpu), torch.from_numpy(label).to(gpu)
+    G.row_pitch(H * W * 4)
+    p, t = G.place(torch.from_numpy(pre).to(gpu), 'pred'), G.place(torch.from_numpy(label).to(gpu), 'target')
     for k, m in ((0, 1.0), (100, 0.05), (200, 1.0), (300, 0.3), (400, 1.0)):
         mask, gs = mt_ref.mask(k), mt_ref.grad_scale(m, pre.shape, k)
-        rec = ops.mse_record(mask, gs, gpu)
-        rows, g = ops.mse_heatmap(p, t, rec, True)
-        rows2, g2 = ops.mse_heatmap(p, t, rec, False)
-        torch.cuda.synchronize()
+        rec = G.place(ops.mse_record(mask, gs, gpu), 'record')
+        rows, g = _guard('mse_heatmap B%d %dx%d k=%d grad' % (B, H, W, k), ops.mse_heatmap, p, t, rec, True)
+        rows2, g2 = _guard('mse_heatmap B%d %dx%d k=%d' % (B, H, W, k), ops.mse_heatmap, p, t, rec, False)
+        assert G.unwritten(rows) == 0 and G.unwritten(g) == 0 and G.unwritten(rows2) == 0
+        assert _same(p, pre) and _same(t, label)                    # the operands are only read
         assert g2 is None and _same(rows, rows2)                    # two launches: the same bits
         assert _same(g, mt_ref.unit_grad(pre, label, mask, gs)), (k, m)
         off = [j for j in range(21) if not (mask >> j) & 1]
@@ -169,15 +194,22 @@ def test_loss_kernel_unaligned_views_take_the_scalar_path(gpu):
     pre = rng.standard_normal((2, 21, 8, 8)).astype(np.float32)
     label = rng.random((2, 21, 8, 8)).astype(np.float32)
     n = pre.size
-    pb, tb, gb = (torch.full((n + 8,), float(CANARY), device=gpu) for _ in range(3))
+    G.row_pitch(64 * 4)
+    pb, tb, gb = (G.place(torch.full((n + 8,), float(CANARY), device=gpu), name) for name in ('pred', 'target', 'grad'))
     pv, tv, gv = (b[1:1 + n].view(2, 21, 8, 8) for b in (pb, tb, gb))
     pv.copy_(torch.from_numpy(pre)); tv.copy_(torch.from_numpy(label))
     assert pv.data_ptr() % 16 == 4 and pv.is_contiguous()
     mask, gs = mt_ref.mask(200), mt_ref.grad_scale(0.3, pre.shape, 200)
-    rec = ops.mse_record(mask, gs, gpu)
-    rows, g = ops.mse_heatmap(pv, tv, rec, True, grad=gv)
-    rows_al, g_al = ops.mse_heatmap(pv.clone(), tv.clone(), rec, True)
-    torch.cuda.synchronize()
+    rec = G.place(ops.mse_record(mask, gs, gpu), 'record')
+    rows, g = _guard('mse_heatmap, views 4 bytes off', ops.mse_heatmap, pv, tv, rec, True, grad=gv)
+    rows_al, g_al = _guard('mse_heatmap, aligned copies', ops.mse_heatmap, G.place(pv.clone(), 'pred'), G.place(tv.clone(), 'target'), rec, True)
+    assert G.unwritten(rows) == 0 and G.unwritten(rows_al) == 0 and G.unwritten(g_al) == 0
+    # ... and with nothing between the operands and their flanks: the views themselves start 4 bytes off
+    off = G.START + 4
+    tight = G.empty(pre.shape, torch.float32, gpu, 'grad, tight', start=off)
+    rows_t, g_t = _guard('mse_heatmap, tight and 4 bytes off', ops.mse_heatmap, G.place(pv.clone(), 'pred', start=off),
+                         G.place(tv.clone(), 'target', start=off), rec, True, grad=tight)
+    assert tight.data_ptr() % 16 == 4 and G.unwritten(tight) == 0 and _same(g_t, g_al) and _same(rows_t, rows)
     assert g.data_ptr() == gv.data_ptr() and _same(g, mt_ref.unit_grad(pre, label, mask, gs)) and _same(g, g_al)
     assert float(gb[0]) == CANARY and _same(gb[1 + n:], np.full(7, CANARY, np.float32))
     assert np.allclose(rows.cpu().numpy(), rows_al.cpu().numpy(), rtol=1e-6)      # (another lane order: not the same bits)

@@ -1,6 +1,12 @@
 """'mxfp8' compute mode: MX (block-scaled e4m3) operands for the K-heavy conv GEMMs (csrc/mx_fp8.hip, the MX build of the fp8
 gather kernel).  Quantiser and weight packs bit-exact against the reference rule (tests/mx_ref.py), the scale-to-lane map
-with exact integer data, the GEMMs against fp64 torch on the dequantised operands, then layer- and model-level behaviour."""
+with exact integer data, the GEMMs against fp64 torch on the dequantised operands, then layer- and model-level behaviour.
+
+Guards (tests/guarded.py).  Sections 1 - 3 (the quantiser, the weight packs, the scale-to-lane map) place every operand and the
+item table, call the wrappers inside a window and check the flanks after each call.  The outputs of sections 1 and 2 are bytes
+(e4m3 elements, E8M0 scales) for which 0xFF is a right answer (a NaN block), so equality with the reference is the check; the
+one-block case and the pack cases assert that their references hold no 0xFF byte, so a skipped byte cannot pass there.  The bf16
+outputs of section 3 must be written completely.  The row pitch is C (times the element size) of the widest operand row."""
 import os
 import subprocess
 import sys
@@ -10,11 +16,27 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import guarded as G
 from conftest import PKG
 from mx_ref import mx_dequantize, mx_pack_weights_ref, mx_quantize_ref
 from seeded import fill_module_, randn
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def guards():
+    G.reset()
+    yield
+    G.reset()
+
+
+def _guard(label, fn, *args, **kw):
+    with G.window(_ops(), label):
+        out = fn(*args, **kw)
+    torch.cuda.synchronize()
+    G.check(label)
+    return out
 
 
 def _ops():
@@ -59,9 +81,10 @@ def test_mx_quantize_is_bit_exact_with_the_reference_rule(gpu, src, C):
     x[2, 32:64] = 1e-3; x[2, 33] = float('nan')                  # NaN: 0xFF scale
     x[2, 64:96] = 3.0; x[2, 90] = -float('inf')                  # -Inf: 0xFF scale
     x[3, :32] = 2.0 ** 100                                       # large exponents
-    xg = x.to(gpu)
-    q, s = ops.mx_quantize(xg)
-    torch.cuda.synchronize()
+    G.row_pitch(C * x.element_size())
+    xg = G.place(x.to(gpu), 'x')
+    q, s = _guard('mx_quantize %s rows=%d C=%d' % (src, rows, C), ops.mx_quantize, xg)
+    assert torch.equal(xg.cpu().view(torch.int16 if src == 'bf16' else torch.int32), x.view(torch.int16 if src == 'bf16' else torch.int32))
     qr, sr = mx_quantize_ref(x)
     assert q.shape == x.shape and s.numel() == rows * C // 32
     _assert_q_equal(q, s.view(rows, C // 32), qr, sr, x)
@@ -73,39 +96,58 @@ def test_mx_quantize_is_bit_exact_with_the_reference_rule(gpu, src, C):
     assert float((d[fin] - x[fin].float()).abs().max()) <= 2.0 ** -4 * float(x[fin].float().abs().max())
 
 
+@pytest.mark.parametrize('src', ['bf16', 'f32'])
+@pytest.mark.parametrize('rows,C', [(1, 32), (3, 32), (1, 64)])
+def test_mx_quantize_smallest_shapes_leave_no_byte_unwritten(gpu, src, rows, C):
+    """One row of one block, and its neighbours: finite data, so the reference holds no 0xFF byte (asserted) and an element or a
+    scale byte the kernel skipped would still be the fill."""
+    ops = _ops()
+    x = (randn(47, rows, C) * 3).to(torch.bfloat16 if src == 'bf16' else torch.float32)
+    qr, sr = mx_quantize_ref(x)
+    assert not bool((qr == 0xFF).any()) and not bool((sr == 0xFF).any())
+    G.row_pitch(C * x.element_size())
+    q, s = _guard('mx_quantize %s rows=%d C=%d' % (src, rows, C), ops.mx_quantize, G.place(x.to(gpu), 'x'))
+    assert q.shape == x.shape and s.numel() == rows * C // 32
+    assert torch.equal(q.cpu(), qr) and torch.equal(s.view(rows, C // 32).cpu(), sr)
+
+
 def test_mx_quantize_nhwc_rows(gpu):
     """an NHWC feature map is blocked along its channels: the [rows][C] memory of the map"""
     ops = _ops()
-    x = _nhwc(randn(43, 3, 256, 9, 11).to(gpu).to(torch.bfloat16))
-    q, s = ops.mx_quantize(x)
+    G.row_pitch(11 * 256 * 2)
+    x = G.place(_nhwc(randn(43, 3, 256, 9, 11).to(gpu).to(torch.bfloat16)), 'x')
+    q, s = _guard('mx_quantize nhwc', ops.mx_quantize, x)
     qr, sr = mx_quantize_ref(_rows(x))
+    assert not bool((qr == 0xFF).any()) and not bool((sr == 0xFF).any())      # finite data: no 0xFF in the reference
     assert q.stride() == x.stride()
     assert torch.equal(_rows(q), qr) and torch.equal(s.view(-1, 8).cpu(), sr)
 
 
 # ---------------------------------------------------------------- 2. weight packs
-@pytest.mark.parametrize('O,T,I', [(128, 9, 128), (256, 16, 128), (64, 9, 96), (136 + 24, 9, 512)])
+@pytest.mark.parametrize('O,T,I', [(32, 1, 32), (128, 9, 128), (256, 16, 128), (64, 9, 96), (136 + 24, 9, 512)])
 def test_mx_weight_packs_are_bit_exact(gpu, O, T, I):
     ops = _ops()
     w = randn(44, O, T, I) * torch.exp(randn(45, O, T, 1) * 3)
     w[0, 0, :32] = 0.0
-    w[1, 1, 7] = 448.0 * 4
-    wg = w.to(gpu).contiguous()
-    got = ops.pack_weights_mx(wg, O, T, I)
+    w[1, min(1, T - 1), 7] = 448.0 * 4
+    G.row_pitch(max(O, I) * 4)
+    wg = G.place(w.to(gpu).contiguous(), 'w')
+    got = _guard('pack_weights_mx %s' % ((O, T, I),), ops.pack_weights_mx, wg, O, T, I)
     ref = mx_pack_weights_ref(w, O, T, I)
     for name, a, b in zip(('wf', 'sf', 'wt', 'st'), got, ref):
+        assert not bool((b == 0xFF).any()), name          # finite weights: no 0xFF in the reference, a skipped byte would show
         assert torch.equal(a.cpu(), b), name
     # the batched form (two items in one launch) writes the same bytes
-    w2 = (randn(46, 128, 9, 256)).to(gpu).contiguous()
-    packs = [[torch.full((n,), 0xAB, dtype=torch.uint8, device=gpu) for n in (o * t * i, o * t * i // 32) * 2]
+    w2 = G.place((randn(46, 128, 9, 256)).to(gpu).contiguous(), 'w2')
+    packs = [[G.empty((n,), torch.uint8, gpu, 'pack') for n in (o * t * i, o * t * i // 32) * 2]
              for (o, t, i) in ((O, T, I), (128, 9, 256))]
     rec = np.zeros(2, dtype=[('w', '<u8'), ('wf', '<u8'), ('sf', '<u8'), ('wt', '<u8'), ('st', '<u8'), ('O', '<i4'), ('T', '<i4'),
                              ('I', '<i4'), ('blk0', '<i4')])
     blk0 = (O // 32) * (I // 32) * T
     rec[0] = (wg.data_ptr(), *[p.data_ptr() for p in packs[0]], O, T, I, 0)
     rec[1] = (w2.data_ptr(), *[p.data_ptr() for p in packs[1]], 128, 9, 256, blk0)
-    tab = torch.from_numpy(rec.view(np.uint8).copy()).to(gpu)
-    ops.pack_weights_mx_batched(tab, 2, blk0 + 4 * 8 * 9)
+    tab = G.place(torch.from_numpy(rec.view(np.uint8).copy()).to(gpu), 'pack table')
+    _guard('pack_weights_mx_batched', ops.pack_weights_mx_batched, tab, 2, blk0 + 4 * 8 * 9)
     for p, b in zip(packs[0], ref):
         assert torch.equal(p.cpu(), b)
     for p, b in zip(packs[1], mx_pack_weights_ref(w2.cpu(), 128, 9, 256)):
@@ -135,14 +177,18 @@ def test_mx_scale_to_lane_map_is_exact(gpu, case):
     wq, ws = _exact_operands(52, Co * k * k, Ci)
     wtq, wts = _exact_operands(53, Ci * k * k, Co)
     desc = ops.make_desc_fp8(N, H, W, Ci, Co, k, k, s, p)
-    y = ops.conv_fwd_mx(desc, xq.to(gpu), xs.to(gpu), wq.to(gpu), ws.to(gpu))
+    G.row_pitch(max(Ci, Co) * 2)
+    pl = lambda t, name: G.place(t.to(gpu), name)
+    y = _guard('conv_fwd_mx %s' % (case,), ops.conv_fwd_mx, desc, pl(xq, 'x8'), pl(xs, 'sx'), pl(wq, 'w8'), pl(ws, 'sw'))
+    assert G.unwritten(y) == 0
     xr = mx_dequantize(xq, xs).view(N, H, W, Ci).permute(0, 3, 1, 2).double()
     wr = mx_dequantize(wq, ws).view(Co, k, k, Ci).permute(0, 3, 1, 2).double()
     ref = F.conv2d(xr, wr, stride=s, padding=p)
     assert torch.equal(y.float().cpu(), ref.float().to(torch.bfloat16).float()), 'fwd %s' % (case,)
     if Co % 128 == 0:
         dq, dsc = _exact_operands(54, N * Ho * Wo, Co)
-        dx = ops.conv_dgrad_mx(desc, dq.to(gpu), dsc.to(gpu), wtq.to(gpu), wts.to(gpu))
+        dx = _guard('conv_dgrad_mx %s' % (case,), ops.conv_dgrad_mx, desc, pl(dq, 'dy8'), pl(dsc, 'sdy'), pl(wtq, 'wT8'), pl(wts, 'swT'))
+        assert G.unwritten(dx) == 0
         dyr = mx_dequantize(dq, dsc).view(N, Ho, Wo, Co).permute(0, 3, 1, 2).double()
         wtr = mx_dequantize(wtq, wts).view(Ci, k, k, Co).permute(3, 0, 1, 2).double()    # -> (Co, Ci, kh, kw)
         xx = torch.zeros(N, Ci, H, W, dtype=torch.float64, requires_grad=True)

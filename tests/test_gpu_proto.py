@@ -9,7 +9,15 @@ distance of a float32 run of the reference expression from it (the fixture's flo
 float32 otherwise), with the floors jfa_ref.py writes down.  A gradient that is STORED in bf16 (bf16 features) may in addition,
 element by element, be one bf16 rounding from the value before storage: bf16 keeps 8 significant bits, so round-to-nearest moves a
 value v by at most 2^-8 |v|; v itself is within the bound of the float64 value r, so the allowance of an element is
-2^-8 (|r| + bound), as tests/test_gpu_jfa.py states it.  The format, not the kernel's arithmetic."""
+2^-8 (|r| + bound), as tests/test_gpu_jfa.py states it.  The format, not the kernel's arithmetic.
+
+Guards (tests/guarded.py), as in tests/test_gpu_jfa.py: the kernel-level tests of section 3 and the KL test of section 5 place
+feature maps, key points, descriptors, the blend record, the memory and the gradients, call the wrappers in a window and check
+the flanks after every call; P, the descriptors and the rows come from torch.empty inside the window and must be written
+completely.  proto_update's memory is rewritten in place: its flanks are checked and its bits compared.  The tests through the
+loss classes and autograd go through _call, which keeps one window open over the forward and the backward: every descriptor,
+prototype and gradient the wrappers allocate is guarded too (the running memories belong to the criterion and are not).  The
+graph replay, the GradFanIn test and DAStep are not guarded."""
 import io
 import os
 import subprocess
@@ -20,8 +28,10 @@ import pytest
 import torch
 
 from conftest import PKG, golden
+import guarded as G
 import proto_ref
-from test_gpu_jfa import POISON, _bits, _same, _feat, _nchw, _points, ops_is_nhwc
+from test_gpu_jfa import (CORNER_C, POISON, _bits, _corners, _feat, _gdev, _gfeat, _gout, _guard, _nchw, _points, _same, guards,  # noqa: F401
+                          ops_is_nhwc)
 
 pytestmark = pytest.mark.gpu
 
@@ -54,17 +64,24 @@ def _call(gpu, crit, f1, f2, p1, p2, dtype=torch.float32, want=(True, True), ont
     """One forward + backward of a lossx / lossx3 instance: dict of loss, both feature gradients and both memories.  `onto`
     (B, C, H, W): the target features carry a GradFanIn whose buffer holds it, so the backward takes the accumulate path."""
     from mi355 import nn as mnn
-    a, b = _feat(gpu, f1, dtype, want[0]), _feat(gpu, f2, dtype, want[1])
+    from mi355 import ops
+    # inside guards: features, key points and the fan-in buffer are placed; descriptors, prototypes, rows and gradients are made
+    # by the wrappers while the window is open, the backward included (the memories are the criterion's own tensors)
+    a, b = _gfeat(gpu, f1, dtype, 'f1').requires_grad_(want[0]), _gfeat(gpu, f2, dtype, 'f2').requires_grad_(want[1])
     fan = None
     if onto is not None:
         fan = mnn.GradFanIn()
-        fan.buf = _feat(gpu, onto, dtype)
+        fan.buf = _gfeat(gpu, onto, dtype, 'fan-in buffer')
         a._mi_fan = fan
-    x1, x2 = torch.from_numpy(np.asarray(p1, np.float32)).to(gpu), torch.from_numpy(np.asarray(p2, np.float32)).to(gpu)
-    loss = crit(a, b, x1, x2)
-    if any(want):
-        (loss if up is None else loss * up).backward()
+    x1, x2 = _gdev(gpu, np.asarray(p1, np.float32), 'pre1'), _gdev(gpu, np.asarray(p2, np.float32), 'pre2')
+    label = 'prototype criterion + backward %s %s' % (tuple(a.shape), dtype)
+    with G.window(ops, label):
+        loss = crit(a, b, x1, x2)
+        if any(want):
+            (loss if up is None else loss * up).backward()
     torch.cuda.synchronize()
+    G.check(label)
+    assert all(G.unwritten(t) == 0 for t in (a.grad, b.grad, loss.detach()) if t is not None)
     if fan is not None:
         assert a.grad is None
     ga = fan.buf if fan is not None else a.grad
@@ -232,22 +249,23 @@ def test_pool_update_and_memory_are_bit_identical_on_exact_operands(gpu, axes):
     memory equal the float32 numpy model that does the same single divisions and products in the same order -- over two calls."""
     from mi355 import ops
     rng, f, p = _exact(axes=axes)
-    xy = torch.from_numpy(p).to(gpu)
+    xy = _gdev(gpu, p, 'xy')
     want_d = proto_ref.pool_model(f.transpose(0, 2, 3, 1), p, 6, axes)
     assert (want_d[:, 8] == 0).all() and want_d.max() > 0.5
     for m in (0.999, 0.5, 1.0):
-        blend = ops.proto_blend(m, device=gpu)
+        blend = G.place(ops.proto_blend(m, device=gpu), 'blend')
         assert _same(blend, np.array(proto_ref.blend_record(m), np.float32))
         for dtype in (torch.bfloat16, torch.float32):
             mem0 = rng.integers(-4, 5, (21, 24)).astype(np.float32)
-            mem = torch.from_numpy(mem0).to(gpu)
-            d = ops.proto_pool(_feat(gpu, f, dtype), xy, 6, axes)
-            P = ops.proto_update(d, mem, blend)
-            torch.cuda.synchronize()
+            mem = _gdev(gpu, mem0, 'memory')
+            d = _guard('proto_pool %s %s' % (axes, dtype), ops.proto_pool, _gfeat(gpu, f, dtype), xy, 6, axes)
+            P = _guard('proto_update m=%g' % m, ops.proto_update, d, mem, blend)
+            assert G.unwritten(d) == 0 and G.unwritten(P) == 0
             want_P = proto_ref.update_model(want_d, mem0, m)
             assert _same(d, want_d) and _same(P, want_P) and _same(mem, want_P) and P.data_ptr() != mem.data_ptr(), (m, dtype)
-            P2 = ops.proto_update(ops.proto_pool(_feat(gpu, f, dtype), xy, 6, axes), mem, blend)      # the second call sees the first's memory
-            torch.cuda.synchronize()
+            d2 = _guard('proto_pool %s %s again' % (axes, dtype), ops.proto_pool, _gfeat(gpu, f, dtype), xy, 6, axes)
+            P2 = _guard('proto_update m=%g again' % m, ops.proto_update, d2, mem, blend)      # the second call sees the first's memory
+            assert G.unwritten(P2) == 0
             want_P2 = proto_ref.update_model(want_d, want_P, m)
             assert _same(P2, want_P2) and _same(mem, want_P2) and (m == 1.0 or not _same(P2, P))
 
@@ -257,13 +275,14 @@ def test_update_adds_the_images_in_ascending_order_at_every_batch_size(gpu):
     workload's 64 (1 + 7 groups + 7), on inexact operands against the fp32 model that adds b = 0, 1, 2, ... in turn."""
     from mi355 import ops
     rng = np.random.default_rng(17)
-    blend = ops.proto_blend(0.999, device=gpu)
+    blend = G.place(ops.proto_blend(0.999, device=gpu), 'blend')
     for B, K, C in ((1, 21, 24), (8, 21, 24), (9, 1, 8), (10, 32, 24), (17, 21, 264), (64, 21, 256)):
         d = rng.standard_normal((B, K, C)).astype(np.float32)
         mem0 = rng.standard_normal((K, C)).astype(np.float32)
-        mem = torch.from_numpy(mem0).to(gpu)
-        P = ops.proto_update(torch.from_numpy(d).to(gpu), mem, blend)
-        torch.cuda.synchronize()
+        G.row_pitch(C * 4)
+        mem = _gdev(gpu, mem0, 'memory')
+        P = _guard('proto_update B%d K%d C%d' % (B, K, C), ops.proto_update, _gdev(gpu, d, 'desc'), mem, blend)
+        assert G.unwritten(P) == 0
         want = proto_ref.update_model(d, mem0, 0.999)
         assert _same(P, want) and _same(mem, want), (B, K, C)
 
@@ -274,16 +293,16 @@ def test_scatter_is_bit_identical_with_the_fixed_order_model(gpu, axes, dtype):
     from mi355 import ops
     B, K, C, H, W, m = 3, 21, 24, 32, 48, 0.999
     rng, f, p = _exact(B, K, C, H, W, axes=axes)
-    xy = torch.from_numpy(p).to(gpu)
+    xy = _gdev(gpu, p, 'xy')
     gp = rng.standard_normal((K, C)).astype(np.float32)
     rnd = proto_ref.bf16_round if dtype == torch.bfloat16 else None
     want, cov = proto_ref.scatter_model(gp, p, (B, H, W, C), m, 6, axes, round_to=rnd)
     assert cov.any() and not cov.all()
-    gdev, blend = torch.from_numpy(gp).to(gpu), ops.proto_blend(m, device=gpu)
-    out = ops.nhwc_empty(B, C, H, W, dtype, gpu)
-    out.fill_(POISON)
-    ops.proto_scatter(gdev, xy, blend, out, False, 6, axes)
-    torch.cuda.synchronize()
+    gdev, blend = _gdev(gpu, gp, 'gp'), G.place(ops.proto_blend(m, device=gpu), 'blend')
+    G.row_pitch(W * C * (2 if dtype == torch.bfloat16 else 4))
+    out = _gout(gpu, B, C, H, W, dtype)
+    _guard('proto_scatter = %s %s' % (axes, dtype), ops.proto_scatter, gdev, xy, blend, out, False, 6, axes)
+    assert G.unwritten(out) == 0
     got = out.permute(0, 2, 3, 1).float().cpu().numpy()
     assert _same(got, want)
     assert (got[~cov] == 0).all() and not np.signbit(got[~cov]).any()                      # +0 outside every window
@@ -292,7 +311,7 @@ def test_scatter_is_bit_identical_with_the_fixed_order_model(gpu, axes, dtype):
     base = proto_ref.bf16_round(base) if dtype == torch.bfloat16 else base
     out.fill_(POISON)
     out.copy_(torch.from_numpy(base).to(gpu).permute(0, 3, 1, 2))
-    ops.proto_scatter(gdev, xy, blend, out, True, 6, axes)
+    _guard('proto_scatter += %s %s' % (axes, dtype), ops.proto_scatter, gdev, xy, blend, out, True, 6, axes)
     again = out.clone()
     torch.cuda.synchronize()
     want_acc, _ = proto_ref.scatter_model(gp, p, (B, H, W, C), m, 6, axes, onto=base, round_to=rnd)
@@ -301,9 +320,40 @@ def test_scatter_is_bit_identical_with_the_fixed_order_model(gpu, axes, dtype):
     assert _bits(got[~cov]) == _bits(base[~cov]) and not np.array_equal(got[cov], base[cov])
     # two runs give the same bits
     out.copy_(torch.from_numpy(base).to(gpu).permute(0, 3, 1, 2))
-    ops.proto_scatter(gdev, xy, blend, out, True, 6, axes)
-    torch.cuda.synchronize()
+    _guard('proto_scatter += %s %s again' % (axes, dtype), ops.proto_scatter, gdev, xy, blend, out, True, 6, axes)
     assert _same(out, again)
+
+
+@pytest.mark.parametrize('radius', [1, 16])
+@pytest.mark.parametrize('C', CORNER_C)
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32], ids=['bf16', 'f32'])
+@pytest.mark.parametrize('axes', ['xy', 'ref'])
+def test_pool_and_scatter_at_the_corners_of_the_first_and_last_image(gpu, axes, dtype, C, radius):
+    """B = 2, K = 4, a 5 x 7 map, key points on the four corners of both images, windows of one pixel and windows larger than the
+    map: the first and the last pixel of the feature map sit against the guard flanks."""
+    from mi355 import ops
+    B, K, H, W, m = 2, 4, 5, 7, 0.999
+    rng = np.random.default_rng(C * 10 + radius)
+    f = rng.integers(0, 16, (B, C, H, W)).astype(np.float32)               # small integers: every sum is exact in fp32 in any order
+    p = _corners(B, K, H, W, axes)
+    xy = _gdev(gpu, p, 'xy')
+    want_d = proto_ref.pool_model(f.transpose(0, 2, 3, 1), p, radius, axes)
+    d = _guard('proto_pool corners', ops.proto_pool, _gfeat(gpu, f, dtype), xy, radius, axes)
+    assert G.unwritten(d) == 0 and _same(d, want_d) and want_d.min() >= 0 and want_d.max() > 0.5
+    gp = rng.standard_normal((K, C)).astype(np.float32)
+    rnd = proto_ref.bf16_round if dtype == torch.bfloat16 else None
+    want, cov = proto_ref.scatter_model(gp, p, (B, H, W, C), m, radius, axes, round_to=rnd)
+    assert cov[0, 0, 0] and cov[B - 1].any() and not cov.all()
+    gdev, blend = _gdev(gpu, gp, 'gp'), G.place(ops.proto_blend(m, device=gpu), 'blend')
+    out = _gout(gpu, B, C, H, W, dtype)
+    _guard('proto_scatter = corners', ops.proto_scatter, gdev, xy, blend, out, False, radius, axes)
+    assert G.unwritten(out) == 0 and _same(out.permute(0, 2, 3, 1).float().cpu().numpy(), want)
+    base = rng.standard_normal((B, H, W, C)).astype(np.float32)
+    base = proto_ref.bf16_round(base) if dtype == torch.bfloat16 else base
+    acc = G.place(torch.from_numpy(base).to(gpu).to(dtype), 'out +=').permute(0, 3, 1, 2)
+    _guard('proto_scatter += corners', ops.proto_scatter, gdev, xy, blend, acc, True, radius, axes)
+    want_acc, _ = proto_ref.scatter_model(gp, p, (B, H, W, C), m, radius, axes, onto=base, round_to=rnd)
+    assert _same(acc.permute(0, 2, 3, 1).float().cpu().numpy(), want_acc)
 
 
 @pytest.mark.parametrize('mode', ['kl', 'softkl'])
@@ -369,16 +419,22 @@ def test_gradient_requests(gpu, want, mode):
     rng = np.random.default_rng(5)
     K, C = 21, 24
     a, b = rng.random((K, C)).astype(np.float32), rng.random((K, C)).astype(np.float32)
-    ad, bd = torch.from_numpy(a).to(gpu), torch.from_numpy(b).to(gpu)
+    ad, bd = _gdev(gpu, a, 'pt'), _gdev(gpu, b, 'ps')
     # both gradient buffers are handed over whatever is wanted, as neighbours inside one poisoned allocation with guard zones:
     # a side that is not wanted, and everything around a side that is, must keep the poison
     n = ad.numel()
-    flat = torch.full((3 * n + 64,), POISON, device=gpu)
+    flat = G.place(torch.full((3 * n + 64,), POISON, device=gpu), 'gradients')
     ga, gb = flat[32:32 + n].view(ad.shape), flat[32 + n:32 + 2 * n].view(bd.shape)
     assert ga.data_ptr() % 16 == 0 and gb.data_ptr() % 16 == 0
-    rows, ra, rb = ops.proto_kl(ad, bd, want[0], want[1], mode, 0.5, grad_t=ga, grad_s=gb)
-    loss = ops.reduce_sum(rows, 0.5 / K if mode == 'kl' else 0.5)
-    torch.cuda.synchronize()
+    G.row_pitch(C * 4)
+    rows, ra, rb = _guard('proto_kl %s %s' % (mode, want), ops.proto_kl, ad, bd, want[0], want[1], mode, 0.5, grad_t=ga, grad_s=gb)
+    loss = _guard('reduce_sum', ops.reduce_sum, rows, 0.5 / K if mode == 'kl' else 0.5)
+    assert G.unwritten(rows) == 0 and G.unwritten(loss) == 0
+    # ... and with the gradients left to the wrapper (torch.empty_like inside the window): the same bits, all of them written
+    rows2, ra2, rb2 = _guard('proto_kl %s %s, own gradients' % (mode, want), ops.proto_kl, ad, bd, want[0], want[1], mode, 0.5)
+    assert _same(rows2, rows) and G.unwritten(rows2) == 0
+    for mine, theirs, w in ((ra2, ga, want[0]), (rb2, gb, want[1])):
+        assert (mine is None) == (not w) and (not w or (G.unwritten(mine) == 0 and _same(mine, theirs)))
     assert (ra is None) == (not want[0]) and (rb is None) == (not want[1])
     l64, r64, ga64, gb64 = proto_ref.criterion(a, b, mode, 0.5, np.float64)
     l32, r32, ga32, gb32 = proto_ref.criterion(a, b, mode, 0.5, np.float32)

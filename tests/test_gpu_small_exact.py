@@ -8,14 +8,53 @@ Every comparison is one of two kinds, named next to it:
   [stats]  the tolerances of test_pointwise_k2c_walks_several_tiles_per_block_at_full_size, 1e-5 * (max |mean| + 1) and
            1e-4 * (max M2 + 1): only the mean and M2 columns of pw_k2c_stats, a Welford recurrence in fp32.
 Operands go to the device as plain torch casts of exact values, and every cast is checked to have lost nothing.  Every kernel is
-called inside its documented contract; section E calls the wrappers outside it and nothing launches there."""
+called inside its documented contract; section E calls the wrappers outside it and nothing launches there.
+
+Guards (tests/guarded.py).  Sections A-D run inside poisoned guard buffers: every operand is a G.place() copy, every wrapper
+call runs in a G.window() (_run), the flanks are checked after the device has been synchronised, and every freshly allocated
+floating-point output has no unwritten element.  The row pitch is W * C * esize of the widest feature map of the shape at hand
+(the windowed kernels step by image rows), set again for every shape a test loops over.  The in-place kernels (SGD, cast into a
+view, = / += of a gradient) have their flanks checked and keep their exact comparison.  The window codes of the max-pool are
+bytes: their references hold no 0xFF (asserted), so equality is the check.  Section F calls the ABI with a workspace one byte
+short.  Outside the windows: test_maxpool_grid_stride_laps and test_to_nhwc_grid_stride_lap (2 M-chunk cases: flanks of 256
+rows would cost time there for nothing new) and section E (nothing launches)."""
+
 import numpy as np
 import pytest
 import torch
 
+import guarded as G
 import small_exact_ref as R
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def guards():
+    G.reset()
+    yield
+    G.reset()
+
+
+def _run(ops, label, fn, *args, **kw):
+    """One wrapper call inside a guard window; the flanks of everything placed or allocated are intact afterwards."""
+    with G.window(ops, label):
+        out = fn(*args, **kw)
+    torch.cuda.synchronize()
+    G.check(label)
+    return out
+
+
+def _written(out, ref):
+    """No element of `out` still holds the fill.  Where the reference `ref` (same logical shape) is a NaN the all-ones pattern is
+    a legitimate result -- 0xFFFF is a bf16 NaN, and the hardware's conversion keeps no promise about the payload -- so those
+    positions are left to the comparison that follows (NaN by position)."""
+    ones = out.view(torch.int16 if out.element_size() == 2 else torch.int32) == -1
+    return not bool((ones.cpu() & ~torch.isnan(ref.reshape(out.shape))).any())
+
+
+def _pitch(W, C, dt):
+    G.row_pitch(W * C * (2 if dt == 'bf16' else 4))
 
 
 def _ops():
@@ -25,17 +64,17 @@ def _ops():
     return ops
 
 
-def _feat(v64, dt, gpu):
+def _feat(v64, dt, gpu, name='feature'):
     """Logical NCHW float64 -> channels_last `dt` on the device; the cast lost nothing."""
     d = R.nhwc(v64, R.TDT[dt]).to(gpu)
     assert R.bits_equal(d.double().cpu().contiguous(), v64.contiguous())
-    return d
+    return G.place(d, name)
 
 
-def _f32(v64, gpu):
+def _f32(v64, gpu, name='f32 operand'):
     d = v64.float().contiguous().to(gpu)
     assert torch.equal(d.double().cpu(), v64)
-    return d
+    return G.place(d, name)
 
 
 def _host(t):
@@ -49,6 +88,7 @@ def _roomy(t, extra, fill):
     flat = t.permute(0, 2, 3, 1).reshape(-1)
     buf = torch.full((flat.numel() + extra,), fill, dtype=t.dtype, device=t.device)
     buf[:flat.numel()] = flat
+    buf = G.place(buf, 'roomy')
     return buf[:flat.numel()].view(N, H, W, C).permute(0, 3, 1, 2), buf
 
 
@@ -61,7 +101,10 @@ def test_maxpool_bit_for_bit(gpu, name):
     N, C, H, W = c['x'].shape
     Ho, Wo = R.mp_out(H, W)
     y_ref, code_ref, dx_ref = R.check_exact_maxpool(c)
-    y, arg = ops.maxpool_fwd(_feat(c['x'], dt, gpu))
+    assert int(code_ref.max()) <= 8                     # no 0xFF in the reference: a code byte nobody wrote cannot pass
+    _pitch(W, C, dt)
+    y, arg = _run(ops, 'maxpool_fwd ' + name, ops.maxpool_fwd, _feat(c['x'], dt, gpu, 'x'))
+    assert _written(y, y_ref)
     assert y.dtype == R.TDT[dt] and ops.is_nhwc(y) and tuple(y.shape) == (N, C, Ho, Wo)
     assert R.bits_equal(_host(y), y_ref), 'pooled values'                                            # [equal], NaN by position
     assert arg.dtype == torch.uint8 and tuple(arg.shape) == (N, Ho, Wo, C)
@@ -69,14 +112,20 @@ def test_maxpool_bit_for_bit(gpu, name):
     # dy and the codes as views of larger buffers whose tails would count if read (code 1, dy = 64): the window rows and columns
     # past Ho and Wo belong to nobody
     room = (Wo + 2) * C
-    dyd, dy_buf = _roomy(_feat(c['dy'], dt, gpu), room, 64.0)
+    dyd, dy_buf = _roomy(_feat(c['dy'], dt, gpu, 'dy'), room, 64.0)
     argd, arg_buf = _roomy(arg.permute(0, 3, 1, 2), room, 1)
-    dx = ops.maxpool_bwd(dyd, argd.permute(0, 2, 3, 1), (N, C, H, W))
+    dx = _run(ops, 'maxpool_bwd roomy ' + name, ops.maxpool_bwd, dyd, argd.permute(0, 2, 3, 1), (N, C, H, W))
+    assert G.unwritten(dx) == 0
     assert dx.dtype == R.TDT[dt] and ops.is_nhwc(dx) and tuple(dx.shape) == (N, C, H, W)
     assert torch.equal(_host(dx), R.rne(dx_ref, dt)), 'dx'                                           # [equal]
     assert bool((dy_buf[-room:] == 64).all()) and bool((arg_buf[-room:] == 1).all())
     own = R.maxpool_bwd_np(c['dy'].numpy(), arg.cpu().permute(0, 3, 1, 2).numpy(), (N, C, H, W))
     assert np.array_equal(own, dx_ref.numpy()), 'dy scattered through the kernel\'s own codes'     # [equal]
+    # the same with dy and the codes ending exactly where their guard flank begins: a window row or column past Ho / Wo that is
+    # read would now be 0xFF (an impossible code, a NaN)
+    dx = _run(ops, 'maxpool_bwd tight ' + name, ops.maxpool_bwd, _feat(c['dy'], dt, gpu, 'dy'), G.place(arg, 'arg'), (N, C, H, W))
+    assert G.unwritten(dx) == 0
+    assert torch.equal(_host(dx), R.rne(dx_ref, dt)), 'dx, tight operands'                           # [equal]
 
 
 def test_maxpool_grid_stride_laps(gpu):
@@ -111,8 +160,10 @@ def test_to_nhwc(gpu, dt, C, cpad):
     for N in (1, 3):
         for H, W in R.TO_NHWC_MAPS:
             x = R.layout_values('to_nhwc', N, C, H, W)
-            out = ops.to_nhwc(x.to(gpu), R.TDT[dt], cpad)
             ref = R.to_nhwc(x, dt, cpad)
+            _pitch(W, ref.shape[1], dt)
+            out = _run(ops, 'to_nhwc %s' % ((N, C, H, W, cpad),), ops.to_nhwc, G.place(x.to(gpu), 'x'), R.TDT[dt], cpad)
+            assert _written(out, ref)
             assert ops.is_nhwc(out) and out.dtype == R.TDT[dt]
             assert R.bits_equal(out.cpu().contiguous(), ref), (N, H, W)                              # [equal], pads +0.0
 
@@ -136,12 +187,17 @@ def test_to_nchw_f32(gpu, dt):
         for C in R.TO_NCHW_C:
             for H, W in R.TO_NCHW_MAPS:
                 x = R.nhwc(R.layout_values('to_nchw', N, C, H, W), R.TDT[dt])
-                xd = x.to(gpu)
+                _pitch(W, C, dt)
+                xd = G.place(x.to(gpu), 'x')
                 assert ops.is_nhwc(xd)
-                y = ops.to_nchw_f32(xd)
+                y = _run(ops, 'to_nchw_f32 %s' % ((N, C, H, W),), ops.to_nchw_f32, xd)
+                assert _written(y, R.to_nchw_f32(x))
                 assert y.dtype == torch.float32 and y.is_contiguous()
                 assert R.bits_equal(y.cpu(), R.to_nchw_f32(x)), (N, C, H, W)                         # [equal]
-                back = ops.to_nhwc(y, R.TDT[dt])
+                back = _run(ops, 'to_nhwc back %s' % ((N, C, H, W),), ops.to_nhwc, y, R.TDT[dt])
+                padded = torch.zeros(back.shape)
+                padded[:, :C] = x.float()
+                assert _written(back, padded)
                 assert R.bits_equal(back[:, :C].cpu().contiguous(), x.contiguous()), (N, C, H, W)    # [equal] round trip
                 assert not bool(back[:, C:].ne(0).any())
 
@@ -153,7 +209,9 @@ def test_to_nhwc_s2d(gpu, dt, N, H, W):
     # input that laps would be more than 200 MB of fp32 image; the loop is the one test_to_nhwc_grid_stride_lap walks.
     ops = _ops()
     x = R.layout_values('s2d', N, 3, H, W)
-    out = ops.to_nhwc_s2d(x.to(gpu), R.TDT[dt])
+    _pitch(W, 3, 'f32')                  # an image row of the NCHW source; the output's W/2 * 16 elements are no wider
+    out = _run(ops, 'to_nhwc_s2d %s' % ((N, H, W),), ops.to_nhwc_s2d, G.place(x.to(gpu), 'x'), R.TDT[dt])
+    assert _written(out, R.s2d(x, dt))
     assert ops.is_nhwc(out) and tuple(out.shape) == (N, 16, H // 2, W // 2)
     assert R.bits_equal(out.cpu().contiguous(), R.s2d(x, dt))                                        # [equal]
 
@@ -163,25 +221,28 @@ def test_to_nhwc_s2d(gpu, dt, N, H, W):
 def test_stem_pack_and_unpack(gpu, dt, Co):
     ops = _ops()
     w = R.layout_values('stem w', Co, 7, 7, 3)
-    out = ops.stem_s2d_pack(w.reshape(-1).to(gpu), R.TDT[dt])
+    out = _run(ops, 'stem_s2d_pack %d' % Co, ops.stem_s2d_pack, G.place(w.reshape(-1).to(gpu), 'w'), R.TDT[dt])
     ref = R.stem_pack(w.double()).float().to(R.TDT[dt])
+    assert _written(out, ref)
     assert R.bits_equal(out.cpu().view(Co, 4, 4, 16), ref)                                           # [equal]
     if dt == 'f32':                     # the gradient is fp32 whatever the activation type
         gs = R.int_values('stem gs', -8, 8, Co, 4, 4, 16)
         prior = R.int_values('stem prior', -8, 8, Co, 7, 7, 3)
         for acc in (False, True):
-            g = _f32(prior, gpu) if acc else torch.full((Co, 7, 7, 3), 777.0, device=gpu)
-            ops.stem_s2d_unpack_grad(_f32(gs, gpu), g, acc)
+            g = _f32(prior, gpu, 'g') if acc else G.empty((Co, 7, 7, 3), torch.float32, gpu, 'g')
+            _run(ops, 'stem_s2d_unpack_grad %d acc=%d' % (Co, acc), ops.stem_s2d_unpack_grad, _f32(gs, gpu, 'gs'), g, acc)
+            assert G.unwritten(g) == 0
             assert torch.equal(g.double().cpu(), R.stem_unpack(gs, prior if acc else None))         # [equal]
 
 
 # ================================================================ C. pw21
 def _pw_dev(c, gpu):
     dt = c['dt']
-    d = dict(x=_feat(c['x'], dt, gpu), res=_feat(c['res'], dt, gpu), y=_f32(c['y'], gpu))
+    _pitch(c['W'], c['C'], dt)
+    d = dict(x=_feat(c['x'], dt, gpu, 'x'), res=_feat(c['res'], dt, gpu, 'res'), y=_f32(c['y'], gpu, 'y'))
     for k in ('wck', 'wkc', 'bias_k', 'bias_c', 'prior_w'):
-        d[k] = _f32(c[k], gpu)
-    d['wck_t'], d['wkc_t'] = _f32(c['wck'].t().contiguous(), gpu), _f32(c['wkc'].t().contiguous(), gpu)
+        d[k] = _f32(c[k], gpu, k)
+    d['wck_t'], d['wkc_t'] = _f32(c['wck'].t().contiguous(), gpu, 'wck_t'), _f32(c['wkc'].t().contiguous(), gpu, 'wkc_t')
     return d
 
 
@@ -199,10 +260,12 @@ def test_pw_c2k(gpu, case):
             for bias in (False, True):
                 ref = R.pw_c2k(c['x'], c['wkc'], c['bias_k'] if bias else None)
                 b = d['bias_k'] if bias else None
-                y = ops.pw_c2k(d['x'], d['wkc'], b, K)
+                y = _run(ops, 'pw_c2k %s' % ((dt, N, C, K, HW, bias),), ops.pw_c2k, d['x'], d['wkc'], b, K)
+                assert G.unwritten(y) == 0
                 assert y.dtype == torch.float32 and y.is_contiguous()
                 assert torch.equal(y.double().cpu(), ref), (N, HW, bias, '[K][C]')                   # [equal]
-                y = ops.pw_c2k(d['x'], d['wkc_t'], b, K, w_transposed=True)
+                y = _run(ops, 'pw_c2k [C][K] %s' % ((dt, N, C, K, HW, bias),), ops.pw_c2k, d['x'], d['wkc_t'], b, K, w_transposed=True)
+                assert G.unwritten(y) == 0
                 assert torch.equal(y.double().cpu(), ref), (N, HW, bias, '[C][K]')                   # [equal]
 
 
@@ -212,7 +275,7 @@ def test_pw_k2c(gpu, case):
     off, both weight layouts.  The bf16 results are real roundings (check_exact_pw counts the exact ties)."""
     ops = _ops()
     dt, C, K = case
-    half, one = torch.tensor(0.5, device=gpu), torch.tensor(1.0, device=gpu)
+    half, one = G.place(torch.tensor(0.5, device=gpu), 'scale_dev 0.5'), G.place(torch.tensor(1.0, device=gpu), 'scale_dev 1')
     for N in R.PW_N:
         for HW in R.PW_HW:
             c = R.pw_case(dt, N, C, K, HW)
@@ -223,32 +286,49 @@ def test_pw_k2c(gpu, case):
                 ref = R.pw_k2c(c['y'], c['wck'], c['bias_c'] if bias else None, c['res'] if res else None, scale)
                 kw = dict(residual=d['res'] if res else None, scale_dev={None: None, 0.5: half, 1.0: one}[scale])
                 b = d['bias_c'] if bias else None
-                out = ops.pw_k2c(d['y'], d['wck'], b, C, R.TDT[dt], **kw)
+                label = 'pw_k2c %s' % ((dt, N, C, K, HW, bias, res, scale),)
+                out = _run(ops, label, ops.pw_k2c, d['y'], d['wck'], b, C, R.TDT[dt], **kw)
+                assert G.unwritten(out) == 0
                 assert out.dtype == R.TDT[dt] and ops.is_nhwc(out)
                 assert torch.equal(_host(out), R.rne(ref, dt)), (N, HW, bias, res, scale, '[C][K]')   # [equal]
-                out = ops.pw_k2c(d['y'], d['wck_t'], b, C, R.TDT[dt], w_transposed=True, **kw)
+                out = _run(ops, label + ' [K][C]', ops.pw_k2c, d['y'], d['wck_t'], b, C, R.TDT[dt], w_transposed=True, **kw)
+                assert G.unwritten(out) == 0
                 assert torch.equal(_host(out), R.rne(ref, dt)), (N, HW, bias, res, scale, '[K][C]')   # [equal]
 
 
-@pytest.mark.parametrize('case', R.K2C_STATS_CASES, ids=R.case_id)
-def test_pw_k2c_stats(gpu, case):
-    ops = _ops()
-    dt, C, N = case
-    K, HW = 21, 100
+def _k2c_stats(ops, gpu, dt, C, N, HW, counts):
+    K = 21
     c = R.pw_case(dt, N, C, K, HW)
     R.check_exact_pw(c)
     d = _pw_dev(c, gpu)
     ref = R.rne(R.pw_k2c(c['y'], c['wck'], c['bias_c'], c['res']), dt)
-    plain = ops.pw_k2c(d['y'], d['wck'], d['bias_c'], C, R.TDT[dt], residual=d['res'])
-    out, (partial, ns) = ops.pw_k2c_stats(d['y'], d['wck'], d['bias_c'], C, R.TDT[dt], residual=d['res'])
+    label = 'pw_k2c_stats %s' % ((dt, N, C, HW),)
+    plain = _run(ops, label + ' plain', ops.pw_k2c, d['y'], d['wck'], d['bias_c'], C, R.TDT[dt], residual=d['res'])
+    out, (partial, ns) = _run(ops, label, ops.pw_k2c_stats, d['y'], d['wck'], d['bias_c'], C, R.TDT[dt], residual=d['res'])
+    assert G.unwritten(plain) == 0 and G.unwritten(out) == 0
     assert torch.equal(out, plain)                                                                   # [equal]
     assert torch.equal(_host(out), ref)                                                              # [equal]
     assert ns == N * ((HW + 63) // 64)
+    assert partial.numel() == ns * C * 3 and G.unwritten(partial) == 0           # ns_max slices, the last of each image ragged
     p = partial[:ns * C * 3].view(ns, C, 3).double().cpu()
     st = R.slice_stats(ref, HW)                           # of the STORED values
-    assert torch.equal(p[:, :, 0], st[:, :, 0]) and set(p[:, :, 0].unique().tolist()) == {64.0, 36.0}    # [equal]
+    assert torch.equal(p[:, :, 0], st[:, :, 0]) and set(p[:, :, 0].unique().tolist()) == counts          # [equal]
     assert float((p[:, :, 1] - st[:, :, 1]).abs().max()) <= 1e-5 * float(st[:, :, 1].abs().max() + 1)    # [stats]
     assert float((p[:, :, 2] - st[:, :, 2]).abs().max()) <= 1e-4 * float(st[:, :, 2].abs().max() + 1)    # [stats]
+
+
+@pytest.mark.parametrize('case', R.K2C_STATS_CASES, ids=R.case_id)
+def test_pw_k2c_stats(gpu, case):
+    dt, C, N = case
+    _k2c_stats(_ops(), gpu, dt, C, N, 100, {64.0, 36.0})
+
+
+@pytest.mark.parametrize('HW', R.PW_EDGE_HW)
+@pytest.mark.parametrize('dt,C', [(dt, C) for dt in R.DTS for C in (24, 264)])
+def test_pw_k2c_stats_two_images_at_the_tile_edges(gpu, dt, C, HW):
+    """N = 2 at H*W = 1, 63, 64, 65: the partials buffer has exactly ns_max slices and the last slice of each image holds 1, 63,
+    64 or 1 pixels."""
+    _k2c_stats(_ops(), gpu, dt, C, 2, HW, {float(HW)} if HW <= 64 else {64.0, float(HW - 64)})
 
 
 @pytest.mark.parametrize('case', R.WGRAD_CASES, ids=R.case_id)
@@ -259,13 +339,15 @@ def test_pw_wgrad(gpu, case):
     dt, C, K, N, HW = case
     c = R.pw_case(dt, N, C, K, HW)
     R.check_exact_pw(c)
-    x, y = _feat(c['x'], dt, gpu), _f32(c['y'], gpu)
+    _pitch(c['W'], C, dt)
+    x, y = _feat(c['x'], dt, gpu, 'x'), _f32(c['y'], gpu, 'y')
     for acc in (False, True):
         ref = R.pw_wgrad(c['x'], c['y'], c['prior_w'] if acc else None)
         for kc in (True, False):
             prior = c['prior_w'] if kc else c['prior_w'].t().contiguous()
-            dw = _f32(prior, gpu) if acc else torch.full(prior.shape, 777.0, device=gpu)
-            ops.pw_wgrad(x, y, dw, kc, acc)
+            dw = _f32(prior, gpu, 'dw') if acc else G.empty(prior.shape, torch.float32, gpu, 'dw')
+            _run(ops, 'pw_wgrad %s acc=%d kc=%d' % (case, acc, kc), ops.pw_wgrad, x, y, dw, kc, acc)      # workspace: exactly
+            assert G.unwritten(dw) == 0                                                  # mi355_pw_wgrad_workspace bytes
             got = dw.double().cpu()
             assert torch.equal(got if kc else got.t(), ref), (acc, kc)                               # [equal]
 
@@ -276,10 +358,12 @@ def test_hm_rowsum(gpu, case):
     N, K, HW = case
     c = R.rowsum_case(N, K, HW)
     R.check_exact_rowsum(c)
-    y = _f32(c['y'], gpu)
+    _pitch(c['y'].shape[3], 1, 'f32')
+    y = _f32(c['y'], gpu, 'y')
     for acc in (False, True):
-        out = _f32(c['prior'], gpu) if acc else torch.full((K,), 777.0, device=gpu)
-        ops.hm_rowsum(y, out, acc)
+        out = _f32(c['prior'], gpu, 'out') if acc else G.empty((K,), torch.float32, gpu, 'out')
+        _run(ops, 'hm_rowsum %s acc=%d' % (case, acc), ops.hm_rowsum, y, out, acc)       # workspace: exactly N * K * 4 bytes
+        assert G.unwritten(out) == 0
         assert torch.equal(out.double().cpu(), R.hm_rowsum(c['y'], c['prior'] if acc else None)), acc    # [equal]
 
 
@@ -290,15 +374,16 @@ def _sgd_run(ops, gpu, c, nesterov, wd, lowp, off=0, room=0):
     tot = n + room
     sent = 544.0
     P = torch.full((tot,), sent, device=gpu); P[off:off + n] = _f32(c['p'], gpu)
-    G = torch.full((tot,), sent, device=gpu)
     B = torch.full((tot,), sent, device=gpu); B[off:off + n] = 0
-    L = torch.full((tot,), sent, dtype=torch.bfloat16, device=gpu) if lowp else None
-    lr_dev = torch.zeros((), device=gpu)
-    for g, lr in zip(c['g'], R.SGD_LRS):
-        G[off:off + n] = _f32(g, gpu)
+    # the whole buffers sit in guards: with room = 0 the views end where the back flank begins
+    P, B, Gr = G.place(P, 'p'), G.place(B, 'buf'), G.place(torch.full((tot,), sent, device=gpu), 'g')
+    L = G.place(torch.full((tot,), sent, dtype=torch.bfloat16, device=gpu), 'p_lowp') if lowp else None
+    lr_dev = G.place(torch.zeros((), device=gpu), 'lr_dev')
+    for i, (g, lr) in enumerate(zip(c['g'], R.SGD_LRS)):
+        Gr[off:off + n] = _f32(g, gpu)
         lr_dev.fill_(lr)
-        ops.sgd_nesterov(P[off:off + n], G[off:off + n], B[off:off + n], lr_dev, R.SGD_MU, wd, nesterov,
-                         L[off:off + n] if lowp else None)
+        _run(ops, 'sgd_nesterov n=%d step %d' % (n, i), ops.sgd_nesterov, P[off:off + n], Gr[off:off + n], B[off:off + n], lr_dev,
+             R.SGD_MU, wd, nesterov, L[off:off + n] if lowp else None)
     return P, B, L
 
 
@@ -351,10 +436,73 @@ def test_sgd_on_views_at_an_offset(gpu, sgd_refs, n):
 def test_cast_f32(gpu, dt, n):
     ops = _ops()
     src = R.cast_values(n)
-    dst = torch.full((n + 3,), 544.0, dtype=R.TDT[dt], device=gpu)
-    ops.cast_f32(src.to(gpu), dst[:n])
+    dst = G.place(torch.full((n + 3,), 544.0, dtype=R.TDT[dt], device=gpu), 'dst')
+    _run(ops, 'cast_f32 %s n=%d' % (dt, n), ops.cast_f32, G.place(src.to(gpu), 'src'), dst[:n])
+    tight = G.empty((n,), R.TDT[dt], gpu, 'dst, tight')               # ... and a destination that ends at its flank
+    _run(ops, 'cast_f32 tight %s n=%d' % (dt, n), ops.cast_f32, G.place(src.to(gpu), 'src'), tight)
+    assert _written(tight, src)
+    assert R.bits_equal(tight.cpu(), src.to(R.TDT[dt]))                                              # [equal], NaN by position
     assert R.bits_equal(dst[:n].cpu(), src.to(R.TDT[dt]))                                            # [equal], NaN by position
     assert torch.equal(dst[n:].float().cpu(), torch.full((3,), 544.0))                               # [equal]
+
+
+# ================================================================ F. a workspace one byte short: nothing launches
+def _abi_refuses(ops, name, args, ws, out):
+    """The entry point returns the workspace error ahead of its launches: the launch log stays empty, the output and the
+    workspace keep their fill and no flank changes."""
+    import mi355
+    ops.prof_reset(); ops.prof_enable(2)
+    try:
+        rc = getattr(mi355.load(), name)(*args)
+        torch.cuda.synchronize()
+        assert rc == -3                                  # MI355_EWORKSPACE
+        assert 'workspace too small' in mi355.load().mi355_last_error().decode()
+        assert ops.prof_launches() == []
+    finally:
+        ops.prof_enable(0); ops.prof_reset()
+    G.check(name + ', workspace one byte short')
+    assert G.unwritten(out) == out.numel() * 4 and G.unwritten(ws.view(torch.float32)) == ws.numel()
+
+
+@pytest.mark.parametrize('dt', R.DTS)
+def test_pw_wgrad_workspace_one_byte_short(gpu, dt):
+    import mi355
+    from mi355 import dtype_code, ptr, stream_ptr
+    ops = _ops()
+    N, C, K, HW = 3, 24, 21, 64
+    c = R.pw_case(dt, N, C, K, HW)
+    _pitch(c['W'], C, dt)
+    x, y = _feat(c['x'], dt, gpu, 'x'), _f32(c['y'], gpu, 'y')
+    need = mi355.load().mi355_pw_wgrad_workspace(N, HW, C, K)
+    assert need == 3 * K * C * 4                          # three slices of 64 pixels
+    with G.window(ops, 'pw_wgrad ws'):
+        ws = ops.workspace(need, gpu)
+    dw = G.empty((K, C), torch.float32, gpu, 'dw')
+    _abi_refuses(ops, 'mi355_pw_wgrad', (ptr(x), ptr(y), ptr(dw), 1, 0, N, HW, C, K, dtype_code(R.TDT[dt]), ptr(ws), need - 1, stream_ptr()), ws, dw)
+    # ... and with exactly `need` bytes it runs
+    mi355.call('mi355_pw_wgrad', ptr(x), ptr(y), ptr(dw), 1, 0, N, HW, C, K, dtype_code(R.TDT[dt]), ptr(ws), need, stream_ptr())
+    torch.cuda.synchronize()
+    G.check('pw_wgrad, exact workspace')
+    assert G.unwritten(dw) == 0 and torch.equal(dw.double().cpu(), R.pw_wgrad(c['x'], c['y']))     # [equal]
+
+
+def test_hm_rowsum_workspace_one_byte_short(gpu):
+    import mi355
+    from mi355 import ptr, stream_ptr
+    ops = _ops()
+    N, K, HW = 3, 21, 255
+    c = R.rowsum_case(N, K, HW)
+    _pitch(c['y'].shape[3], 1, 'f32')
+    y = _f32(c['y'], gpu, 'y')
+    need = N * K * 4
+    with G.window(ops, 'hm_rowsum ws'):
+        ws = ops.workspace(need, gpu)
+    out = G.empty((K,), torch.float32, gpu, 'out')
+    _abi_refuses(ops, 'mi355_hm_rowsum', (ptr(y), ptr(out), 0, N, K, HW, ptr(ws), need - 1, stream_ptr()), ws, out)
+    mi355.call('mi355_hm_rowsum', ptr(y), ptr(out), 0, N, K, HW, ptr(ws), need, stream_ptr())
+    torch.cuda.synchronize()
+    G.check('hm_rowsum, exact workspace')
+    assert G.unwritten(out) == 0 and torch.equal(out.double().cpu(), R.hm_rowsum(c['y']))          # [equal]
 
 
 # ================================================================ E. wrapper checks: nothing launches

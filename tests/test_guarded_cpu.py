@@ -196,6 +196,80 @@ def test_window_restores_what_it_replaced_after_an_exception():
     assert G._buf_of(t) is None
 
 
+def _like_sources():
+    base = torch.arange(64.0)
+    return {'channels_last': torch.arange(2.0 * 8 * 3 * 5).view(2, 8, 3, 5).contiguous(memory_format=torch.channels_last),
+            'offset': base[4:52].view(4, 12),                      # a dense view that starts 16 bytes into its storage
+            'zero-size': torch.zeros(3, 0, 7)}
+
+
+@pytest.mark.parametrize('what', ['channels_last', 'offset', 'zero-size'])
+def test_empty_like_gives_a_guarded_view_of_the_same_shape_strides_and_dtype(what):
+    ops = _fake_ops()
+    t = _like_sources()[what]
+    with G.window(ops, 'like ' + what):
+        a = torch.empty_like(t)
+        h = torch.empty_like(t, dtype=torch.bfloat16)
+        c = torch.empty_like(t, device='cpu')
+        m = torch.empty_like(t, device='meta')                     # another device type: the real function
+        k = torch.empty_like(t, memory_format=torch.contiguous_format)    # not modelled: the real function
+    assert m.device.type == 'meta' and tuple(m.shape) == tuple(t.shape)
+    assert tuple(k.shape) == tuple(t.shape) and k.is_contiguous() and (t.numel() == 0 or G._buf_of(k) is None)
+    for v, dt in ((a, torch.float32), (h, torch.bfloat16), (c, torch.float32)):
+        assert tuple(v.shape) == tuple(t.shape) and v.stride() == t.stride() and v.dtype == dt and v.device == t.device
+        if t.numel():
+            assert v.data_ptr() % 256 == G.START and G._buf_of(v) is not None
+            assert G.unwritten(v) == t.numel() * v.element_size()                  # nothing but the fill in it
+            assert G._buf_of(v).n == t.numel() * v.element_size()
+    if what == 'channels_last':
+        assert a.permute(0, 2, 3, 1).is_contiguous()
+    G.check()
+    if not t.numel():
+        return
+    # an emulated one-element overrun behind the payload, then one in front of it
+    one = torch.tensor([0, 0, 128, 63], dtype=torch.uint8)          # the bytes of 1.0f
+    for side in ('behind', 'in front'):
+        with G.window(ops, 'like %s, store %s' % (what, side)):
+            y = torch.empty_like(t)
+        raw, start, n = _raw_of(y)
+        assert n == t.numel() * 4
+        y.copy_(t)
+        if side == 'behind':
+            raw[start + n:start + n + 4] = one
+            expect = 'back flank changed, bytes %d .. %d ' % (n, n + 3)
+        else:
+            raw[start - 4:start] = one
+            expect = 'front flank changed, bytes -4 .. -1 '
+        with pytest.raises(G.GuardError) as e:
+            G.check()
+        text = str(e.value)
+        assert expect in text and 'empty_like%s' % (tuple(t.shape),) in text and 'store ' + side in text, text
+        assert torch.equal(y, t)
+        G.check()
+
+
+def test_empty_like_passes_through_what_it_does_not_model_and_is_restored_after_an_exception():
+    ops = _fake_ops()
+    real = torch.empty_like
+    gapped = torch.zeros(4, 16)[:, ::2]                             # a view with holes: torch chooses new strides for it
+    with pytest.raises(RuntimeError):
+        with G.window(ops, 'raises'):
+            assert torch.empty_like is not real
+            g = torch.empty_like(gapped)
+            assert tuple(g.shape) == (4, 8) and G._buf_of(g) is None and g.stride() == real(gapped).stride()
+            r = torch.empty_like(torch.zeros(3), requires_grad=True)
+            assert r.requires_grad and G._buf_of(r) is not None
+            raise RuntimeError('the wrapper refused')
+    assert torch.empty_like is real
+    with G.window(ops, 'outer'):
+        with pytest.raises(ValueError):
+            with G.window(ops, 'inner'):
+                raise ValueError()
+        assert torch.empty_like is not real                         # the outer window is still open
+    assert torch.empty_like is real
+    assert G._buf_of(torch.empty_like(torch.zeros(3, 5))) is None   # outside a window: untouched allocations
+
+
 def test_views_keep_shape_strides_dtype_layout_and_start():
     ops = _fake_ops()
     is_nhwc = lambda x: x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous()

@@ -176,6 +176,7 @@ def _pw_shapes():
             for HW in R.PW_HW:
                 seen.append((dt, N, C, K, HW))
     seen += [(dt, N, C, 21, 100) for dt, C, N in R.K2C_STATS_CASES]
+    seen += [(dt, 2, C, 21, HW) for dt in R.DTS for C in (24, 264) for HW in R.PW_EDGE_HW]       # the statistics at the tile edges
     seen += [(dt, N, C, K, HW) for dt, C, K, N, HW in R.WGRAD_CASES]
     return sorted(set(seen))
 
