@@ -145,6 +145,9 @@ SIGNATURES = {
     'mi355_mixup_pairs': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _I, _P]),
     'mi355_fda_workspace_bytes': (_L, [_I, _I, _I, _I, _I]),
     'mi355_fda_transfer': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
+    'mi355_affine_warp_images': (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    'mi355_affine_unwarp_heatmaps': (_I, [_P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'mi355_mse_heatmap_w': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'mi355_augment_workspace': (_Z, [_I, _I]),
     'mi355_augment': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'mi355_resize_normalize': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P]),

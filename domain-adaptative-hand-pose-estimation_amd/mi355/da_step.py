@@ -286,12 +286,12 @@ class CoordRegression(_Term):
         more = {}
         y_ema = step._kept_c.get('y_t_ema') if step.mt is not None else None      # the MeanTeacher's forward of this very step C
         if y_ema is None:
-            x = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
-            y_ema = self.teacher(step).forward(x)
+            y_ema = step.teacher_forward(self.teacher(step), batch)
             more['y_t_ema'] = y_ema                                               # (kept: step M's teacher labels reuse it)
         kp_ema = soft_argmax(y_ema, self.beta)
         more['kp_t_ema'] = kp_ema
-        return self.crit_t(y_t_grad, kp_ema, batch['w_t'], scale=self.target_weight), more
+        w_t = step.teacher_weights(batch)                                         # (a geometric view: w_t * valid)
+        return self.crit_t(y_t_grad, kp_ema, w_t, scale=self.target_weight), more
 
 
 class CrossDomainMixup:
@@ -323,7 +323,7 @@ class CrossDomainMixup:
         self.draws = 0
         self.lam = None                  # (B,) fp32 on the device, fixed address
         self.lam_host = None             # the coefficients of the last draw
-        self._bufs, self._gen, self._teacher = None, None, None
+        self._bufs, self._gen, self._teacher, self._w_t = None, None, None, None
 
     # ------------------------------------------------------------ coefficients
     def draw(self, B=None, device=None):
@@ -379,8 +379,8 @@ class CrossDomainMixup:
             shared = step.mt is not None or (step.coord is not None and step.coord.target == 'teacher')
             y = step.out.get('y_t_ema') if shared else None                   # step C's teacher forward, when there was one
             if y is None:
-                x = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
-                y = self.teacher(step).forward(x)
+                y = step.teacher_forward(self.teacher(step), batch)
+            self._w_t = step.teacher_weights(batch)                           # (a geometric view: w_t * valid)
         K, H, W = y.shape[1:]
         if self._gen is None or (self._gen.num_keypoints, self._gen.height, self._gen.width) != (K, H, W):
             self._gen = PseudoLabelGenerator(K, H, W)
@@ -389,7 +389,8 @@ class CrossDomainMixup:
     def blend(self, batch, hm_t):
         """mixup_pairs(x_s, label_s, w_s, x_t, hm_t, w_t, lam) into the buffers of this object -> (x_mix, hm_mix, w_mix)."""
         f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-        ops_in = [f32(batch[k]) for k in ('x_s', 'label_s', 'w_s', 'x_t')] + [hm_t, f32(batch['w_t'])]
+        w_t = batch['w_t'] if self.labels == 'student' or self._w_t is None else self._w_t
+        ops_in = [f32(batch[k]) for k in ('x_s', 'label_s', 'w_s', 'x_t')] + [hm_t, f32(w_t)]
         sig = tuple(tuple(t.shape) for t in ops_in)
         if self._bufs is None or self._bufs[0] != sig:
             if torch.cuda.is_current_stream_capturing():
@@ -441,8 +442,13 @@ class DAStep:
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
     def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None,
-                 proto=None, clip=None, mixup=None, fda=None, coord=None):
+                 proto=None, clip=None, mixup=None, fda=None, view=None, coord=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
+        # optional mi355.teacher.GeometricView (may also be assigned after construction): the teacher of the iteration -- one forward,
+        # shared by the MeanTeacher, CoordRegression(target='teacher') and CrossDomainMixup(labels='teacher') -- sees the target batch
+        # rotated, scaled and shifted per sample, and its heat-maps are mapped back before anybody reads them; the maps whose peak it
+        # did not see inside its frame drop out of the three terms.  None: nothing is launched, nothing is drawn.
+        self.view, self._last_teacher = view, None
         # optional mi355.optim.GradClipper (may also be assigned after construction): each of the three updates takes the global
         # gradient norm of everything it steps (A: f and the four heads, B: the adversarial heads, C: f), behind the gradient
         # exchange, and steps on the clipped gradients -- or not at all when the norm is not finite.  None: nothing is launched.
@@ -538,6 +544,29 @@ class DAStep:
             _allreduce_mean(self._grads(keys))
 
     # ------------------------------------------------------------------ the three steps (fwd+bwd, then update)
+    def teacher_forward(self, teacher, batch):
+        """The teacher's heat-maps on its view of the target batch (x_t_ema; x_t itself when the batch has none), in the loader's
+        frame.  With a GeometricView the teacher also keeps the flags (`valid`) and w_t * valid (`w_out`)."""
+        x = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
+        teacher.view, self._last_teacher = self.view, teacher
+        if self.view is None:
+            return teacher.forward(x)
+        return teacher.forward(x, w_in=batch['w_t'])
+
+    def teacher_weights(self, batch):
+        """The joint weights a consumer of the teacher's forward uses: w_t, times the flags of the view when there is one (kept by
+        the teacher that ran this iteration's forward)."""
+        return batch['w_t'] if self.view is None else self._last_teacher.w_out
+
+    def _draw_view(self, batch=None):
+        if self.view is None:
+            return
+        if batch is None:
+            self.view.draw()
+        else:
+            self.view.draw(batch['x_t'].shape[0], batch['x_t'].device, image_size=batch['x_t'].shape[-2:],
+                           heatmap_size=batch['label_s'].shape[-2:])
+
     def terms(self):
         """The optional terms that are on, in the order in which step C adds them and issues their kernels."""
         on = [t for t in (self.mt, self.mmd, self.jfa, self.proto) if t is not None]
@@ -733,6 +762,7 @@ class DAStep:
             self.clip.sync()
         if self.mixup is not None:
             self.mixup.draw(batch['x_s'].shape[0], batch['x_s'].device)
+        self._draw_view(batch)
         self._begin_reduce(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'))
         self._fwdbwd_A(batch)
         self._end_reduce(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'))
@@ -852,6 +882,7 @@ class DAStep:
             self.clip.sync()
         if self.mixup is not None:
             self.mixup.draw()                # the coefficients of this iteration, to their fixed device address
+        self._draw_view()                    # the records of this iteration's teacher views, likewise
 
     def replay(self, batch=None):
         if batch is not None and batch is not self.static:

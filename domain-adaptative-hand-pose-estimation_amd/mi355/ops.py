@@ -1382,6 +1382,163 @@ def fda_transfer(x_s, x_t, beta, mean=MEAN, std=STD, out=None, ws=None):
     return out
 
 
+# ---------------------------------------------------------------- geometric teacher view (csrc/warp.hip)
+VIEW_REC_FLOATS = 18          # mi355_view_rec: img, hm, hm_inv, each a row-major 2 x 3 fp32 matrix
+WARP_MAX_SIDE = 4096
+
+
+def _size_hw(size):
+    if isinstance(size, int):
+        return size, size
+    h, w = size
+    return int(h), int(w)
+
+
+def view_records(angle, scale, shift, image_size, heatmap_size):
+    """The record table of a geometric view as a numpy (B, 18) fp32 array (include/mi355pose.h, mi355_view_rec).  angle: B angles
+    in degrees; scale: B factors > 0; shift: (B, 2) translations (tx, ty) in image pixels; image_size, heatmap_size: (H, W) and
+    (h, w), or one int for a square.  Sample b's view maps p to q = s R(a) (p - c) + c + t, c = ((W-1)/2, (H-1)/2); img = A^-1,
+    hm = A in heat-map pixels, hm_inv = its inverse, each composed in float64 and rounded once.  The strides in x and y must be
+    equal whole numbers; non-finite values and s <= 0 are refused."""
+    import numpy as np
+    who = 'view_records'
+    H, W = _size_hw(image_size)
+    h, w = _size_hw(heatmap_size)
+    if min(H, W, h, w) < 1 or H * w != W * h or W % w != 0:
+        raise Mi355Error('%s: the strides in x and y must be equal whole numbers (image %dx%d, heat-map %dx%d)' % (who, H, W, h, w))
+    stride = W // w
+    a = np.atleast_1d(np.asarray(angle, dtype=np.float64))
+    s = np.atleast_1d(np.asarray(scale, dtype=np.float64))
+    t = np.asarray(shift, dtype=np.float64).reshape(-1, 2)
+    B = a.shape[0]
+    if a.ndim != 1 or s.shape != (B,) or t.shape != (B, 2):
+        raise Mi355Error('%s: %d angles, scales of shape %s, shifts of shape %s' % (who, B, s.shape, t.shape))
+    if not (np.isfinite(a).all() and np.isfinite(s).all() and np.isfinite(t).all()):
+        raise Mi355Error('%s: non-finite angle, scale or shift' % who)
+    if not (s > 0).all():
+        raise Mi355Error('%s: scales must be > 0, got %s' % (who, s.tolist()))
+    out = np.empty((B, VIEW_REC_FLOATS), dtype=np.float32)
+    c = np.array([(W - 1) / 2.0, (H - 1) / 2.0])
+    for b in range(B):
+        r = np.deg2rad(a[b])
+        L = s[b] * np.array([[np.cos(r), -np.sin(r)], [np.sin(r), np.cos(r)]])
+        T = c + t[b] - L @ c
+        Li = np.linalg.inv(L)
+        mats = (np.concatenate([Li, (-Li @ T)[:, None]], axis=1), np.concatenate([L, (T / stride)[:, None]], axis=1),
+                np.concatenate([Li, (-Li @ T / stride)[:, None]], axis=1))
+        out[b] = np.concatenate([m.reshape(-1) for m in mats]).astype(np.float32)
+    return out
+
+
+def _chk_view_recs(who, recs, B, *others):
+    _dense_f32(who, 'recs', recs)
+    if recs.numel() != B * VIEW_REC_FLOATS:
+        raise Mi355Error('%s: the record table holds %d floats, %d samples need %d' % (who, recs.numel(), B, B * VIEW_REC_FLOATS))
+    if any(t.device != recs.device for t in others if t is not None):
+        raise Mi355Error('%s: the operands live on different devices' % who)
+
+
+def _chk_sides(who, H, W):
+    if not (1 <= H <= WARP_MAX_SIDE and 1 <= W <= WARP_MAX_SIDE):
+        raise Mi355Error('%s: a plane of %d x %d is outside 1..%d' % (who, H, W, WARP_MAX_SIDE))
+
+
+def affine_warp_images(x, recs, out=None):
+    """out[b, c] = x[b, c] resampled under the `img` matrix of recs[b] (bilinear, 0 outside; mi355_affine_warp_images).  x: dense
+    fp32 (B, C, H, W); recs: a device tensor of B * 18 floats (view_records).  `out` is allocated only when not given, and never
+    during graph capture."""
+    who = 'affine_warp_images'
+    _dense_f32(who, 'x', x)
+    if x.dim() != 4 or x.numel() == 0:
+        raise Mi355Error('%s: x must be a non-empty (B, C, H, W) batch, got %s' % (who, tuple(x.shape)))
+    B, C, H, W = (int(s) for s in x.shape)
+    _chk_sides(who, H, W)
+    if out is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise Mi355Error('%s: out would be allocated during graph capture; run one eager call first' % who)
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+    _dense_f32(who, 'out', out)
+    if tuple(out.shape) != (B, C, H, W):
+        raise Mi355Error('%s: out has shape %s, the launch writes %s' % (who, tuple(out.shape), (B, C, H, W)))
+    _chk_view_recs(who, recs, B, x, out)
+    call('mi355_affine_warp_images', ptr(x), ptr(recs), ptr(out), B, C, H, W, stream_ptr())
+    return out
+
+
+def affine_unwarp_heatmaps(y, recs, margin, w_in=None, out=None):
+    """The teacher's heat-maps mapped back to the loader's frame: y_hat[b, k] = y[b, k] resampled under the `hm` matrix of recs[b]
+    (mi355_affine_unwarp_heatmaps).  Returns (y_hat, valid, w_out): valid (B, K) is 1.0 where the arg-max of y[b, k] lies at
+    least `margin` pixels inside the teacher's frame and its pre-image lies inside the map, else 0.0; w_out = w_in * valid with
+    w_in's shape ((B, K) or (B, K, 1)), None without w_in.  `out`: the triple (y_hat, valid, w_out) -- w_out None without w_in --
+    to be written in place; allocated only when not given, and never during graph capture."""
+    who = 'affine_unwarp_heatmaps'
+    _dense_f32(who, 'y', y)
+    if y.dim() != 4 or y.numel() == 0:
+        raise Mi355Error('%s: y must be a non-empty (B, K, h, w) batch of heat-maps, got %s' % (who, tuple(y.shape)))
+    B, K, h, w = (int(s) for s in y.shape)
+    _chk_sides(who, h, w)
+    if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not math.isfinite(margin) or margin < 0:
+        raise Mi355Error('%s: margin=%r must be a finite number >= 0' % (who, margin))
+    if w_in is not None:
+        _dense_f32(who, 'w_in', w_in)
+        if w_in.numel() != B * K or w_in.shape[0] != B:
+            raise Mi355Error('%s: w_in %s for %d x %d maps' % (who, tuple(w_in.shape), B, K))
+    if out is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise Mi355Error('%s: the outputs would be allocated during graph capture; run one eager call first' % who)
+        out = (torch.empty((B, K, h, w), dtype=torch.float32, device=y.device), torch.empty((B, K), dtype=torch.float32, device=y.device),
+               None if w_in is None else torch.empty(tuple(w_in.shape), dtype=torch.float32, device=y.device))
+    y_hat, valid, w_out = out
+    if (w_in is None) != (w_out is None):
+        raise Mi355Error('%s: w_in and w_out go together (both or neither)' % who)
+    shapes = ((B, K, h, w), (B, K), None if w_in is None else tuple(w_in.shape))
+    for what, t, s in (('y_hat', y_hat, shapes[0]), ('valid', valid, shapes[1]), ('w_out', w_out, shapes[2])):
+        if t is None:
+            continue
+        _dense_f32(who, what, t)
+        if tuple(t.shape) != s:
+            raise Mi355Error('%s: %s has shape %s, the launch writes %s' % (who, what, tuple(t.shape), s))
+    _chk_view_recs(who, recs, B, y, w_in, y_hat, valid, w_out)
+    call('mi355_affine_unwarp_heatmaps', ptr(y), ptr(recs), float(margin), ptr(w_in), ptr(y_hat), ptr(valid), ptr(w_out), B, K, h, w,
+         stream_ptr())
+    return y_hat, valid, w_out
+
+
+def mse_heatmap_w(pred, target, rec, wmap, want_grad, rows=None, grad=None):
+    """mse_heatmap with a per-map weight: (rows [B,K] = w * the per-map sums of squared differences, unit_grad [B,K,H,W] * w or
+    None).  wmap: B * K fp32 weights on the device; maps with w == 0 or outside the record's mask give exact zeros and are not
+    read.  rec: mse_record().  rows / grad are allocated only when not given, and never during graph capture."""
+    who = 'mse_heatmap_w'
+    for what, t in (('pred', pred), ('target', target), ('wmap', wmap)):
+        _dense_f32(who, what, t)
+    if pred.dim() != 4 or pred.numel() == 0 or tuple(target.shape) != tuple(pred.shape):
+        raise Mi355Error('%s: pred %s vs target %s ((B, K, H, W) of one shape)' % (who, tuple(pred.shape), tuple(target.shape)))
+    B, K, H, W = (int(s) for s in pred.shape)
+    if wmap.numel() != B * K:
+        raise Mi355Error('%s: %d weights for %d x %d maps' % (who, wmap.numel(), B, K))
+    _chk_dev(rec)
+    if rec.dtype != torch.int32:
+        raise Mi355Error('%s: rec must be the int32 pair of mse_record' % who)
+    _chk_room('%s rec' % who, rec, 2)
+    if rows is None or (want_grad and grad is None):
+        if torch.cuda.is_current_stream_capturing():
+            raise Mi355Error('%s: rows / unit_grad would be allocated during graph capture; run one eager call first' % who)
+        if rows is None:
+            rows = torch.empty((B, K), dtype=torch.float32, device=pred.device)
+        if want_grad and grad is None:
+            grad = torch.empty_like(pred)
+    _dense_f32(who, 'rows', rows)
+    _chk_room('%s rows' % who, rows, B * K)
+    if want_grad:
+        _dense_f32(who, 'unit_grad', grad)
+        _chk_room('%s unit_grad' % who, grad, B * K * H * W)
+    if len({t.device for t in (pred, target, wmap, rec, rows) + ((grad,) if want_grad else ())}) != 1:
+        raise Mi355Error('%s: the operands live on different devices' % who)
+    call('mi355_mse_heatmap_w', ptr(pred), ptr(target), ptr(rec), ptr(wmap), ptr(rows), ptr(grad) if want_grad else 0, B, K, H * W,
+         stream_ptr())
+    return rows, (grad if want_grad else None)
+
+
 # ---------------------------------------------------------------- MMD alignment (csrc/mmd.hip)
 MMD_MAX_ROWS, MMD_MAX_KERNELS = 256, 8
 _mmd_ws = {}

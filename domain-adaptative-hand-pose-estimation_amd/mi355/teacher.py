@@ -9,6 +9,9 @@ the ``repack_params`` / cast route for the convs with no BatchNorm behind them. 
 fp32 weights by the packers the host path uses, so they are that path's bits.  A grouped conv is folded in the dense
 block-diagonal form the host path packs: its master is copied onto the diagonal of a zeroed fixed-address buffer first.
 
+``GeometricView`` is what ``DAStep(view=...)`` takes: per sample another rotation, scale and shift of what the teacher sees, and the
+way back for its heat-maps (``csrc/warp.hip``; Kim et al., ECCV 2022 -- not in the reference).
+
 ``MeanTeacher`` is what ``DAStep(mt=...)`` takes: the teacher, the device-resident loss and the per-epoch schedule of its weight
 ``m`` and of the joint curriculum ``k``.
 """
@@ -19,9 +22,145 @@ from . import Mi355Error, ops
 from . import nn as _nn
 
 
+def _pair(size):
+    if isinstance(size, int):
+        return size, size
+    h, w = size
+    return int(h), int(w)
+
+
+class GeometricView:
+    """Another view of the target batch for the teacher: per sample a rotation ``a ~ U(-rot_deg, rot_deg)`` degrees, a scale
+    ``s ~ U(lo, hi)`` and a shift ``t ~ U(-shift, shift) * side`` about the image centre (Kim et al., ECCV 2022).  ``apply(x)`` is the
+    teacher's input (``mi355_affine_warp_images``), ``undo(y, w_in)`` maps its heat-maps back to the loader's frame and flags the
+    maps whose peak the teacher saw at least ``margin`` heat-map pixels inside its frame (``mi355_affine_unwarp_heatmaps``).
+    Forward only: the teacher is detached, nothing is differentiated through either warp; a differentiable warp for a view on the
+    student's side is out of scope.
+
+    The record table lives in device memory at a fixed address and is written from the host before the iteration (``draw``), from
+    an RNG state this object owns -- seeded from ``seed`` and ``rank``; the global RNG is not advanced.  The warped batch, the
+    back-mapped maps, the flags and the masked weights live at fixed addresses too, keyed by the signature of the operands.
+    ``state_dict()`` is what the epoch checkpoint keeps as ``view_state``.  The default ranges are placeholders: their effect on
+    convergence has not been measured."""
+
+    def __init__(self, rot_deg=30.0, scale=(0.75, 1.25), shift=0.1, margin=2.0, seed=0, rank=0, image_size=None, heatmap_size=None):
+        import math
+        lo, hi = (float(v) for v in scale)
+        if not (math.isfinite(rot_deg) and 0.0 <= rot_deg <= 180.0):
+            raise ValueError('GeometricView: rot_deg must lie in 0 .. 180 degrees, got %r' % (rot_deg,))
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+            raise ValueError('GeometricView: the scale range must be finite with 0 < lo <= hi, got %r' % (scale,))
+        if not (math.isfinite(shift) and 0.0 <= shift <= 1.0):
+            raise ValueError('GeometricView: shift is a fraction of the image side in 0 .. 1, got %r' % (shift,))
+        if not (math.isfinite(margin) and margin >= 0.0):
+            raise ValueError('GeometricView: margin must be finite and not negative, got %r' % (margin,))
+        self.rot_deg, self.scale, self.shift, self.margin = float(rot_deg), (lo, hi), float(shift), float(margin)
+        self.seed, self.rank = int(seed or 0), int(rank)
+        self._rng = self._seeded(0)
+        self.draws = 0
+        self.image_size = None if image_size is None else _pair(image_size)
+        self.heatmap_size = None if heatmap_size is None else _pair(heatmap_size)
+        self.recs = None                 # (B * 18,) fp32 on the device, fixed address
+        self.recs_host = None            # the records of the last draw, (B, 18) fp32
+        self.params_host = None          # the last draw: (B, 4) float64 angle (degrees), scale, tx, ty (image pixels)
+        self._bufs = {}
+
+    # ------------------------------------------------------------ draws
+    def draw(self, B=None, device=None, image_size=None, heatmap_size=None):
+        """Draw the views of the coming iteration and write their records to the device (host work: outside graph capture).
+        Returns the (B, 4) draws: angle in degrees, scale, shift in image pixels."""
+        if image_size is not None:
+            self.image_size = _pair(image_size)
+        if heatmap_size is not None:
+            self.heatmap_size = _pair(heatmap_size)
+        if self.recs is None or (B is not None and self.recs.numel() != int(B) * ops.VIEW_REC_FLOATS):
+            if B is None:
+                raise RuntimeError('GeometricView: run one eager iteration before replaying graphs')
+            if torch.device(device).type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise Mi355Error('GeometricView: the record table would be allocated during graph capture; run one eager iteration first')
+            self.recs = torch.zeros(int(B) * ops.VIEW_REC_FLOATS, dtype=torch.float32, device=device)
+        if self.image_size is None or self.heatmap_size is None:
+            raise RuntimeError('GeometricView: draw() needs image_size and heatmap_size the first time')
+        n = self.recs.numel() // ops.VIEW_REC_FLOATS
+        with torch.random.fork_rng(devices=[]):          # the global CPU generator is put back as it was
+            torch.set_rng_state(self._rng)
+            u = torch.rand(n, 4, dtype=torch.float64).numpy()
+            self._rng = torch.get_rng_state()
+        self.draws += 1
+        H, W = self.image_size
+        lo, hi = self.scale
+        p = u.copy()
+        p[:, 0] = (2.0 * u[:, 0] - 1.0) * self.rot_deg
+        p[:, 1] = lo + (hi - lo) * u[:, 1]
+        p[:, 2] = (2.0 * u[:, 2] - 1.0) * self.shift * W
+        p[:, 3] = (2.0 * u[:, 3] - 1.0) * self.shift * H
+        self.params_host = p
+        self.recs_host = ops.view_records(p[:, 0], p[:, 1], p[:, 2:], self.image_size, self.heatmap_size)   # (refuses non-finite, s <= 0)
+        self.recs.copy_(torch.from_numpy(self.recs_host).view(-1), non_blocking=True)
+        return p
+
+    def _seeded(self, draws):
+        """The generator state of a rank that starts (draws = 0) or joins a resumed run whose checkpoint holds another rank's state."""
+        return torch.Generator().manual_seed(self.seed * 1000003 + 7907 * self.rank + 29 + 104723 * int(draws)).get_state()
+
+    def state_dict(self):
+        """The RNG state, the number of draws so far and the last draws (a CPU copy): what the checkpoint keeps."""
+        return {'rng_state': self._rng.clone(), 'draws': self.draws, 'rank': self.rank,
+                'ranges': (self.rot_deg, self.scale, self.shift, self.margin),
+                'params': None if self.params_host is None else torch.from_numpy(self.params_host.copy())}
+
+    def load_state_dict(self, state):
+        """Go on where the saved run was.  The checkpoint is rank 0's: another rank takes the number of draws and a state seeded
+        from (seed, rank, draws), so that the ranks keep drawing different views."""
+        self.draws = int(state.get('draws', 0))
+        if int(state.get('rank', 0)) == self.rank:
+            self._rng = state['rng_state'].clone().to(torch.uint8).cpu()
+        else:
+            self._rng = self._seeded(self.draws)
+
+    # ------------------------------------------------------------ the two warps
+    def _buffers(self, key, shapes, device):
+        got = self._bufs.get(key[0])
+        if got is None or got[0] != key:
+            if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise Mi355Error('GeometricView: the %s buffers would be allocated during graph capture; run one eager iteration first' % key[0])
+            got = self._bufs[key[0]] = (key, tuple(None if s is None else torch.empty(s, dtype=torch.float32, device=device) for s in shapes))
+        return got[1]
+
+    def _check(self, what, t, size, which):
+        if self.recs is None:
+            raise Mi355Error('GeometricView: no records: draw() first')
+        if t.dim() != 4 or t.shape[0] * ops.VIEW_REC_FLOATS != self.recs.numel() or tuple(t.shape[-2:]) != size:
+            raise Mi355Error('GeometricView: %s of shape %s, the records were drawn for %d samples and a %s of %s'
+                             % (what, tuple(t.shape), self.recs.numel() // ops.VIEW_REC_FLOATS, which, size))
+
+    def apply(self, x):
+        """The teacher's input: x (B, C, H, W) under the views of the last draw, in a buffer of this object."""
+        x = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
+        self._check('a batch', x, self.image_size, 'image size')
+        out, = self._buffers(('apply', tuple(x.shape)), (tuple(x.shape),), x.device)
+        return ops.affine_warp_images(x, self.recs, out=out)
+
+    def undo(self, y, w_in=None):
+        """(y_hat, valid, w_out): the teacher's heat-maps y (B, K, h, w) mapped back to the loader's frame, the per-map flags (B, K)
+        and w_in * valid in w_in's shape (None without w_in), in buffers of this object."""
+        f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+        y = f32(y.detach())
+        self._check('heat-maps', y, self.heatmap_size, 'heat-map size')
+        if w_in is not None:
+            w_in = f32(w_in)
+        B, K = y.shape[:2]
+        key = ('undo', tuple(y.shape), None if w_in is None else tuple(w_in.shape))
+        out = self._buffers(key, (tuple(y.shape), (B, K), None if w_in is None else tuple(w_in.shape)), y.device)
+        return ops.affine_unwarp_heatmaps(y, self.recs, self.margin, w_in=w_in, out=out)
+
+
 class InIterationTeacher:
-    def __init__(self, ema):
+    def __init__(self, ema, view=None):
         self.ema, self.model = ema, ema.model_ema
+        # optional GeometricView (may also be assigned later): the teacher runs on view.apply(x) and forward() returns its
+        # heat-maps mapped back (view.undo), keeping the flags in `valid` and the masked weights in `w_out`.  None: x as it is.
+        self.view, self.valid, self.w_out = view, None, None
         self._pairs = None              # [(folded, conv, bn, dtype, deconv, s2d)] in forward order
         self._sig = None
         self._pack_cache = {}
@@ -175,12 +314,19 @@ class InIterationTeacher:
                 ops.cast_f32(m.weight.detach(), cast.buf)
                 cast.key = (_nn._param_version(m.weight), cast.buf.dtype)
 
-    def forward(self, x):
-        """y_t_ema = model_ema(x)[0]: eval mode, running statistics, no_grad (train1.py:364)."""
+    def forward(self, x, w_in=None):
+        """y_t_ema = model_ema(x)[0]: eval mode, running statistics, no_grad (train1.py:364).  With a view: the teacher runs on
+        view.apply(x) and its heat-maps come back mapped to x's frame; `valid` and `w_out` (= w_in * valid) are kept."""
+        if self.view is not None:
+            x = self.view.apply(x)
         if self._pairs is None:
             self._build(x)
             self.refresh()
-        return self._run(x)
+        y = self._run(x)
+        if self.view is None:
+            return y
+        y, self.valid, self.w_out = self.view.undo(y, w_in)
+        return y
 
     __call__ = forward
 
@@ -228,8 +374,10 @@ class MeanTeacher:
 
     def step_c(self, step, batch, f_t, y_t, y_t_grad):
         """m * mt_loss(y_t, teacher(x_t_ema)) with y_t's autograd graph; x_t_ema is x_t itself when the batch has none."""
-        x_t_ema = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
-        y_ema = self.teacher.forward(x_t_ema)
+        y_ema = step.teacher_forward(self.teacher, batch)
         if not torch.cuda.is_current_stream_capturing():
             self.sync(y_t_grad.shape)
-        return self.loss(y_t_grad, y_ema), {'y_t_ema': y_ema}     # (kept: step M's teacher labels reuse this forward)
+        # with a geometric view the maps whose peak the teacher did not see inside its frame are left out (weight 0); weight_t
+        # stays ignored, as in the reference's mt_loss
+        return self.loss(y_t_grad, y_ema, wmap=self.teacher.valid if self.teacher.view is not None else None), \
+            {'y_t_ema': y_ema}                                   # (kept: step M's teacher labels reuse this forward)

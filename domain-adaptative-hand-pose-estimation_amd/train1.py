@@ -18,7 +18,9 @@ and the target batch, with Gaussian pseudo-labels for the target side: the refer
 ``--coord-target-weight`` / ``--coord-beta`` / ``--coord-delta`` (a coordinate loss on the differentiable soft-arg-max of the source
 heat-maps against the un-quantised annotation, and of the target heat-maps against the EMA teacher's: integral regression, not in
 the reference), ``--fda {off,on}`` with ``--fda-beta`` (step A sees the source batch with the low-frequency amplitude of the target batch:
-Fourier Domain Adaptation, not in the reference), ``--clip-grad-norm FLOAT``
+Fourier Domain Adaptation, not in the reference), ``--mt-view {same,geom}`` with ``--view-rot`` / ``--view-scale`` / ``--view-shift`` /
+``--view-margin`` (the EMA teacher sees the target batch rotated, scaled and shifted per sample and its heat-maps are mapped back
+before they are compared: geometric consistency, not in the reference), ``--clip-grad-norm FLOAT``
 (global gradient-norm clipping of each of the three updates with a non-finite step guard, on the device; not in the reference), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
@@ -63,7 +65,7 @@ from mi355 import ops as _ops
 from mi355.ops import FDA_MAX_B, fda_band
 from mi355.da_step import CoordRegression, CrossDomainMixup, FourierStyle, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
 from mi355.optim import EMATeacher, GradClipper, make_optimizer
-from mi355.teacher import MeanTeacher
+from mi355.teacher import GeometricView, MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
 from uda.model.regda_7 import MainOutput, PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
@@ -234,6 +236,10 @@ def main(args):
         # step M behind update C: blends of the two batches through backbone, neck and main head (mi355.da_step.CrossDomainMixup)
         step.mixup = CrossDomainMixup(beta=args.mixup_beta, weight=args.mixup_weight, labels=args.mixup_labels, ema=ema,
                                       seed=args.seed, rank=RANK)
+    if args.mt_view == 'geom':
+        # the teacher's forward of the iteration runs on another view of the target batch (mi355.teacher.GeometricView)
+        step.view = GeometricView(rot_deg=args.view_rot, scale=tuple(args.view_scale), shift=args.view_shift, margin=args.view_margin,
+                                  seed=args.seed, rank=RANK)
     if args.fda == 'on':
         # step A sees the source batch in the style of the target batch (mi355.da_step.FourierStyle); no state, nothing to checkpoint
         step.fda = FourierStyle(beta=args.fda_beta)
@@ -683,6 +689,26 @@ _OPTIONS = [
                               "it for --mixup: 'student' = the model's own y_t of step C; 'teacher' = the EMA teacher's on its view of "
                               "the target batch (needs --ema-update const|warmup; with --mt-loss on the teacher's forward of step C "
                               "is reused)")),
+    (('--mt-view',), dict(default='same', choices=['same', 'geom'], help="what the EMA teacher sees of the target batch: 'same' = the "
+                         "loader's geometry (x_t_ema differs from x_t by colour jitter and blur only); 'geom' = per sample another "
+                         "rotation, scale and shift (--view-rot / --view-scale / --view-shift), its heat-maps mapped back to the "
+                         "loader's frame before --mt-loss on, --coord-loss both and --mixup-labels teacher read them, and the maps "
+                         "whose peak the teacher did not see --view-margin pixels inside its frame left out of all three (Kim et "
+                         "al., ECCV 2022; not in the reference); two kernel launches around the teacher's forward, forward only; the "
+                         "views come from an RNG state of their own, seeded from --seed and the rank, kept in the epoch checkpoint "
+                         "(view_state); needs --ema-update const|warmup and one of the three consumers; 'same': nothing is launched")),
+    (('--view-rot',), dict(default=30.0, type=float, metavar='DEG', help='--mt-view geom: the angle is drawn from U(-DEG, DEG) (0 .. 180; '
+                          'the default is a placeholder: its effect on convergence has not been measured, and cannot be without the '
+                          'data sets)')),
+    (('--view-scale',), dict(default=[0.75, 1.25], type=float, nargs=2, metavar=('LO', 'HI'), help='--mt-view geom: the scale is drawn '
+                            'from U(LO, HI) (0 < LO <= HI; the defaults are placeholders: their effect on convergence has not been '
+                            'measured, and cannot be without the data sets)')),
+    (('--view-shift',), dict(default=0.1, type=float, metavar='FRAC', help='--mt-view geom: the shift is drawn from U(-FRAC, FRAC) times '
+                            'the image side, per axis (0 .. 1; the default is a placeholder: its effect on convergence has not been '
+                            'measured, and cannot be without the data sets)')),
+    (('--view-margin',), dict(default=2.0, type=float, metavar='PX', help="--mt-view geom: a map takes part only when the teacher's "
+                             'arg-max lies at least PX heat-map pixels inside its frame (0 <= PX < half the heat-map side; the default '
+                             'is a placeholder: its effect on convergence has not been measured, and cannot be without the data sets)')),
     (('--fda',), dict(default='off', choices=['off', 'on'], help="Fourier-domain stylisation of the source batch (Fourier Domain "
                      "Adaptation, Yang and Soatto 2020; not in the reference): step A's forward takes every source image with the "
                      "amplitude of its (2b+1)^2 lowest frequencies replaced by that of the target image of the same index, the "
@@ -760,7 +786,24 @@ class _Parser(argparse.ArgumentParser):
             self.error('--mixup-labels teacher needs a moving teacher: add --ema-update const (or warmup)')
         if getattr(args, 'coord_loss', 'off') == 'both' and getattr(args, 'ema_update', 'off') == 'off':
             self.error('--coord-loss both needs a moving teacher: add --ema-update const (or warmup)')
+        if getattr(args, 'mt_view', 'same') == 'geom':
+            if not (getattr(args, 'mt_loss', 'off') == 'on' or getattr(args, 'coord_loss', 'off') == 'both' or
+                    (getattr(args, 'mixup', 'off') == 'on' and getattr(args, 'mixup_labels', 'student') == 'teacher')):
+                self.error("--mt-view geom changes what the teacher's forward sees, and nothing reads that forward: add --mt-loss on, "
+                           "--coord-loss both or --mixup on --mixup-labels teacher")
+            if getattr(args, 'ema_update', 'off') == 'off':
+                self.error('--mt-view geom needs a moving teacher: add --ema-update const (or warmup)')
         try:                                             # (the checks the term classes make, under the flags' names)
+            if getattr(args, 'mt_view', 'same') == 'geom':
+                lo, hi = args.view_scale
+                if not 0.0 <= args.view_rot <= 180.0:
+                    raise ValueError('--view-rot must lie in 0 .. 180 degrees, got %r' % (args.view_rot,))
+                if not (0.0 < lo <= hi < float('inf')):
+                    raise ValueError('--view-scale needs finite 0 < LO <= HI, got %r %r' % (lo, hi))
+                if not 0.0 <= args.view_shift <= 1.0:
+                    raise ValueError('--view-shift is a fraction of the image side in 0 .. 1, got %r' % (args.view_shift,))
+                if not 0.0 <= args.view_margin < 0.5 * float(getattr(args, 'heatmap_size', 64)):
+                    raise ValueError('--view-margin must lie in 0 .. half of --heatmap-size, got %r' % (args.view_margin,))
             if getattr(args, 'mixup', 'off') == 'on':
                 check_positive('--mixup-beta', args.mixup_beta)
                 check_positive('--mixup-weight', args.mixup_weight)

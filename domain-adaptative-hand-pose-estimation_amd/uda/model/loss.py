@@ -172,6 +172,30 @@ class _MSEFn(torch.autograd.Function):
         return ops.scale_by_dev(g, gout.contiguous().float()), None, None, None
 
 
+class _MSEWFn(torch.autograd.Function):
+    """_MSEFn with a per-map weight in device memory (mi355_mse_heatmap_w): loss = (*scale_dev) * sum_r w_r * rows_r; maps with
+    weight 0 are neither read nor given a gradient other than zeros."""
+
+    @staticmethod
+    def forward(ctx, pred, target, rec, scale_dev, wmap):
+        pred, target = ops._hm(pred), ops._hm(target)            # (as mse_heatmap takes them)
+        B, K = pred.shape[:2]
+        rows = torch.empty((B, K), dtype=torch.float32, device=pred.device)
+        g = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        ops.mse_heatmap_w(pred, target, rec, wmap, g is not None, rows=rows, grad=g)
+        ctx.save_for_backward(g)
+        return ops.scale_by_dev(ops.reduce_sum(rows.view(-1)), scale_dev)
+
+    @staticmethod
+    def backward(ctx, gout):
+        g, = ctx.saved_tensors
+        if g is None or gout is None:
+            return None, None, None, None, None
+        if _rt.is_unit_grad(gout):
+            return g, None, None, None, None
+        return ops.scale_by_dev(g, gout.contiguous().float()), None, None, None, None
+
+
 class MeanTeacherLoss:
     """``m * mt_loss(pre, label, weight, k)`` with everything that changes per epoch -- the joint mask, m / n and 2 m / n, n = B *
     |subset| * H * W -- in device memory: ``set()`` rewrites it (outside graph capture), a captured graph that contains the
@@ -197,10 +221,13 @@ class MeanTeacherLoss:
             self.state = state
         return self
 
-    def __call__(self, pre, label):
+    def __call__(self, pre, label, wmap=None):
+        """wmap: optional (B, K) fp32 per-map weights on the device (the flags of a geometric teacher view); n stays B * |subset| * H * W."""
         if self.state is None:
             raise RuntimeError('MeanTeacherLoss: set(m, k, shape) first')
-        return _MSEFn.apply(pre, label.detach(), self.rec, self.scale)
+        if wmap is None:
+            return _MSEFn.apply(pre, label.detach(), self.rec, self.scale)
+        return _MSEWFn.apply(pre, label.detach(), self.rec, self.scale, wmap.detach())
 
 
 _mt_cache = {}

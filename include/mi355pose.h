@@ -749,6 +749,44 @@ long mi355_fda_workspace_bytes(int B, int C, int H, int W, int b);
 int mi355_fda_transfer(const float* x_s, const float* x_t, float* out, const float* mean, const float* std, int B, int C, int H,
                        int W, int b, void* ws, long ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- geometric teacher view (csrc/warp.hip)
+ * The teacher of a consistency term sees another view of the target image -- rotated, scaled, shifted per sample -- and its
+ * heat-maps are mapped back before they are compared (Kim et al., "A Unified Framework for Domain Adaptive Pose Estimation",
+ * ECCV 2022).  The reference has no such function, so there is no file:line to cite; the semantics are stated here.  Forward
+ * only: the teacher is detached, nothing is differentiated through either warp.
+ * The view of sample b maps a point p of the loader's frame to q = A p = s R(a) (p - c) + c + t, c = ((W-1)/2, (H-1)/2).  Its
+ * record holds three row-major 2 x 3 fp32 matrices acting on (column, row, 1), composed on the host in float64 and rounded once:
+ * img = A^-1 (output pixel of the warped image -> input pixel), hm = A in heat-map pixels (image coordinate = stride * heat-map
+ * coordinate: the same linear part, the translation divided by the stride), hm_inv = the inverse of hm.
+ * Arithmetic of both warps, fp32, no FMA contraction, for output pixel (row i, column j) under the matrix m:
+ *   xs = fl(fl(fl(m00 * j) + fl(m01 * i)) + m02), ys likewise with the second row;
+ *   the sample is +0 unless xs > -1 && xs < W && ys > -1 && ys < H, tested before any conversion to an integer (NaN and inf
+ *   coordinates give +0);  x0 = floor(xs), fx = fl(xs - x0);  a tap outside the plane has the value +0;
+ *   horizontally r = (fx == 0) ? v0 : fl(fl(v0 * fl(1 - fx)) + fl(v1 * fx)), vertically the same form on the two row results;
+ *   a tap whose weight is exactly 0 is not read.
+ * So the identity record, integer shifts and exact quarter turns are exact copies, -0, inf and NaN included.  No atomics, the
+ * same bits on every run, eagerly and under graph replay.  Dense fp32 operands, pointers 4-byte aligned; an output must not
+ * overlap an input or another output; sides up to MI355_WARP_MAX_SIDE.  Never allocates; capturable.
+ * affine_warp_images: out[b][c] = x[b][c] sampled under recs[b].img, x and out [B][C][H][W].  Every output pixel is written once;
+ *   a stream whose gathers are served by the caches.  16-byte stores when out is 16-byte aligned and W % 4 == 0, scalar otherwise.
+ * affine_unwarp_heatmaps: out[b][k] = y[b][k] sampled under recs[b].hm, y and out [B][K][h][w], one workgroup per map, the map
+ *   staged in LDS when h * w * 4 <= 65536 (read from global memory otherwise: the same bits).  In the same launch
+ *   valid[b][k] = 1.0f or 0.0f: with u* the arg-max of y[b][k] by mi355_argmax2d's rules (first index on ties, a NaN counts as the
+ *   maximum), 1 iff margin <= u*_x <= (w-1) - margin and margin <= u*_y <= (h-1) - margin (fp32) and p* = hm_inv u* (the order
+ *   above) lies in [0, w-1] x [0, h-1].  The location decides, not the peak's value.  w_out[b][k] = fl(w_in[b][k] * valid[b][k]);
+ *   w_in and w_out are both given or both null.  margin: finite and >= 0.
+ * mse_heatmap_w: mi355_mse_heatmap with a per-map fp32 weight wmap[B * K] in device memory: with s the row sum of
+ *   mi355_mse_heatmap in its order, rows[r] = fl(s * w) and unit_grad[r][j] = fl(fl(fl(p_j - t_j) * grad_scale) * w).  A row with
+ *   w == 0 or outside the joint mask is exact zeros and pred / target are not read for it.  grad_scale is the caller's: n stays
+ *   B * |subset| * H * W whatever the weights are. */
+#define MI355_WARP_MAX_SIDE 4096
+typedef struct mi355_view_rec { float img[6]; float hm[6]; float hm_inv[6]; } mi355_view_rec;
+int mi355_affine_warp_images(const float* x, const mi355_view_rec* recs, float* out, int B, int C, int H, int W, void* stream);
+int mi355_affine_unwarp_heatmaps(const float* y, const mi355_view_rec* recs, float margin, const float* w_in, float* out, float* valid,
+                                 float* w_out, int B, int K, int h, int w, void* stream);
+int mi355_mse_heatmap_w(const float* pred, const float* target, const mi355_mse_rec* rec_dev, const float* wmap, float* rows,
+                        float* unit_grad, int B, int K, int HW, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
