@@ -350,6 +350,86 @@ __global__ __launch_bounds__(256) void coord_heatmap_reg_kernel(const float* __r
   }
 }
 
+// Backward of the soft-arg-max for an arbitrary upstream gradient g_uv (see mi355pose.h): what a loss that couples the joints of a
+// sample (bone.hip) needs, where coord_heatmap_kernel fuses one per-joint loss.  Same m, e_i, s, p_i, u, v as above.  A row whose
+// two upstream components are both exactly 0 is selected out before its map is read (block- / wave-uniform).
+__global__ __launch_bounds__(256) void softargmax_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ g_uv, float beta,
+                                                              float* __restrict__ grad, unsigned HW, unsigned W) {
+  __shared__ float red[4];
+  const int m = blockIdx.x;
+  const size_t base = (size_t)m * HW;
+  const float* row = pred + base;
+  float* g = grad + base;
+  const float gu = g_uv[2 * m], gv = g_uv[2 * m + 1];
+  if (gu == 0.f && gv == 0.f) {
+    for (unsigned i = threadIdx.x; i < HW; i += 256) g[i] = 0.f;
+    return;
+  }
+  float mx = -INFINITY;
+  for (unsigned i = threadIdx.x; i < HW; i += 256) mx = fmaxf(mx, row[i] * beta);
+  mx = block_max<4>(mx, red);
+  float s = 0.f, su = 0.f, sv = 0.f;
+  for (unsigned i = threadIdx.x; i < HW; i += 256) {
+    const float e = expf(row[i] * beta - mx);
+    s += e; su += e * (float)(i % W); sv += e * (float)(i / W);
+  }
+  s = block_sum<4>(s, red); su = block_sum<4>(su, red); sv = block_sum<4>(sv, red);
+  const float u = su / s, v = sv / s;
+  for (unsigned i = threadIdx.x; i < HW; i += 256) {
+    const float p = expf(row[i] * beta - mx) / s;
+    const float t = ((float)(i % W) - u) * gu + ((float)(i / W) - v) * gv;
+    g[i] = beta * p * t;
+  }
+}
+
+template <int NV, bool WPM>
+__global__ __launch_bounds__(256) void softargmax_bwd_reg_kernel(const float* __restrict__ pred, const float* __restrict__ g_uv, float beta,
+                                                                  float* __restrict__ grad, int rows, int W) {
+  using G = RowGeom<NV, WPM>;
+  constexpr int HW = 4 * NV * G::kThreads;
+  __shared__ float red[4];
+  __shared__ float red3[12];
+  const int m = G::map();
+  if (WPM && m >= rows) return;                              // (wave-uniform: a whole wave owns a map)
+  const size_t base = (size_t)m * HW;
+  float4* out = reinterpret_cast<float4*>(grad + base);
+  const float gu = g_uv[2 * m], gv = g_uv[2 * m + 1];
+  if (gu == 0.f && gv == 0.f) {                              // (uniform over the threads of the map: no barrier is left behind)
+#pragma unroll
+    for (int j = 0; j < NV; ++j) out[G::tid() + G::kThreads * j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  float v[4 * NV];
+  row_load<NV, WPM>(pred + base, v);
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < 4 * NV; ++k) mx = fmaxf(mx, v[k] * beta);
+  mx = G::max(mx, red);
+  float s = 0.f, su = 0.f, sv = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = row_index<NV, WPM>(j, e);
+      const float ex = expf(v[4 * j + e] * beta - mx);
+      s += ex; su += ex * (float)(i % W); sv += ex * (float)(i / W);
+      v[4 * j + e] = ex;                                     // (kept for the gradient)
+    }
+  G::sum3(s, su, sv, red3);
+  const float u = su / s, vv = sv / s;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = row_index<NV, WPM>(j, e);
+      const float t = ((float)(i % W) - u) * gu + ((float)(i / W) - vv) * gv;
+      o[e] = beta * (v[4 * j + e] / s) * t;
+    }
+    out[G::tid() + G::kThreads * j] = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
 // row-kernel dispatch: 0 = no register form for this map size (or unaligned pointers): the loop kernels above
 static int row_form(int HW, const void* a, const void* b = nullptr, const void* c = nullptr) {
   static const bool on = !(getenv("MI355_ROW_REG") && atoi(getenv("MI355_ROW_REG")) == 0);      // A/B switch
@@ -606,6 +686,26 @@ extern "C" int mi355_coord_heatmap(const float* pred, const float* coord, const 
     default: hipLaunchKernelGGL(coord_heatmap_kernel, dim3(rows), dim3(256), 0, st, pred, coord, weight, beta, delta, coef, loss_rows, unit_grad, uv, (unsigned)HW, (unsigned)W);
   }
   MI_CHECK_LAUNCH("coord_heatmap");
+  return MI355_OK;
+}
+extern "C" int mi355_softargmax_backward(const float* pred, const float* g_uv, float beta, float* grad, int rows, int H, int W, void* stream) {
+  if (!pred || !g_uv || !grad) MI_FAIL(MI355_EINVAL, "softargmax_backward: null pred, g_uv or grad");
+  if (rows < 1 || H < 1 || W < 1) MI_FAIL(MI355_EINVAL, "softargmax_backward: bad shape (rows=%d H=%d W=%d)", rows, H, W);
+  if ((long)H * (long)W >= (1L << 31)) MI_FAIL(MI355_EINVAL, "softargmax_backward: map too large (H=%d W=%d: H*W must be below 2^31)", H, W);
+  if (!__builtin_isfinite(beta) || !(beta > 0.f)) MI_FAIL(MI355_EINVAL, "softargmax_backward: beta must be finite and positive, got %g", (double)beta);
+  hipStream_t st = as_stream(stream);
+  const int HW = H * W;
+  const int form = row_form(HW, pred, grad);
+  char lab[80];
+  if (prof_on()) snprintf(lab, sizeof(lab), "softargmax_backward rows%d %dx%d form%d", rows, H, W, form);
+  ProfScope ps(st, 0.0, 8.0 * rows * HW + 8.0 * rows, 2, prof_on() ? lab : nullptr);
+  switch (form) {
+    case 1: hipLaunchKernelGGL((softargmax_bwd_reg_kernel<4, false>), dim3(rows), dim3(256), 0, st, pred, g_uv, beta, grad, rows, W); break;
+    case 2: hipLaunchKernelGGL((softargmax_bwd_reg_kernel<4, true>), dim3(cdiv(rows, 4)), dim3(256), 0, st, pred, g_uv, beta, grad, rows, W); break;
+    case 3: hipLaunchKernelGGL((softargmax_bwd_reg_kernel<1, true>), dim3(cdiv(rows, 4)), dim3(256), 0, st, pred, g_uv, beta, grad, rows, W); break;
+    default: hipLaunchKernelGGL(softargmax_bwd_kernel, dim3(rows), dim3(256), 0, st, pred, g_uv, beta, grad, (unsigned)HW, (unsigned)W);
+  }
+  MI_CHECK_LAUNCH("softargmax_backward");
   return MI355_OK;
 }
 extern "C" int mi355_reduce_sum(const float* in, float* out, int n, float scale, void* stream) {

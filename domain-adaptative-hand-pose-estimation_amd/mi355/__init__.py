@@ -112,6 +112,9 @@ SIGNATURES = {
     'mi355_softargmax': (_I, [_P, _P, _I, _I, _I, _F, _F, _P]),
     'mi355_kl_heatmap': (_I, [_P, _P, _P, _F, _P, _P, _I, _I, _F, _P]),
     'mi355_coord_heatmap': (_I, [_P, _P, _P, _F, _F, _F, _P, _P, _P, _I, _I, _I, _P]),
+    'mi355_softargmax_backward': (_I, [_P, _P, _F, _P, _I, _I, _I, _P]),
+    'mi355_bone_prior': (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _I, _I, _I, _P]),
+    'mi355_bone_stats_update': (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P]),
     'mi355_reduce_sum': (_I, [_P, _P, _I, _F, _P]),
     'mi355_scale_by_dev': (_I, [_P, _P, _P, _L, _P]),
     'mi355_scale_feature': (_I, [_P, _P, _P, _L, _I, _P]),

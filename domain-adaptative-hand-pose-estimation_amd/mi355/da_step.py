@@ -294,6 +294,41 @@ class CoordRegression(_Term):
         return self.crit_t(y_t_grad, kp_ema, w_t, scale=self.target_weight), more
 
 
+class KinematicPrior(_Term):
+    """What ``DAStep(bone=...)`` takes: a bone-ratio skeleton prior on the target prediction (``uda.model.loss.BonePriorLoss``; in the
+    family of the bone-length-ratio constraint of Zhou et al., ICCV 2017 -- not in the reference).  Step A blends the bone-length
+    ratios of the source annotations (``batch['kp_s']``, ``batch['w_s']``) into running statistics (``uda.model.loss.BoneStatistics``,
+    one launch; labels, not a network: they cannot drift with the student).  Step C's loss gains ``weight * BonePriorLoss(y_t,
+    batch['w_t'], stats)``: the same ratios of the soft-arg-max of ``softmax(beta * y_t)``, standardised by those statistics,
+    penalised beyond ``margin`` standard deviations, through the main head's graph.  No teacher, no further forward.  The weight
+    rides inside the kernel (``scale=``); the statistics live at fixed addresses, so captured graphs carry them from replay to
+    replay.  With several ranks each rank keeps its own statistics, as with the prototype memories."""
+    key, needs_head_graph = 'bone', True
+
+    def __init__(self, weight=1.0, margin=1.0, momentum=0.01, beta=1.0, eps=1e-4, bones=None):
+        from uda.model.loss import HAND_BONES, BonePriorLoss, BoneStatistics, check_positive
+        check_positive('KinematicPrior: the weight', weight)
+        self.weight = float(weight)
+        self.crit = BonePriorLoss(beta=beta, margin=margin, eps=eps)              # (checks beta, margin and eps)
+        self.stats = BoneStatistics(HAND_BONES if bones is None else bones, momentum)
+
+    def source(self, batch):
+        """Step A's part; a batch without the continuous key points is an error, not an update left out."""
+        if batch.get('kp_s') is None:
+            raise KeyError("KinematicPrior: the batch has no 'kp_s' (the continuous source key points, (B, K, 2) in heat-map pixels)")
+        self.stats.update(batch['kp_s'], batch['w_s'])
+
+    def step_c(self, step, batch, f_t, y_t, y_t_grad):
+        loss = self.crit(y_t_grad, batch['w_t'], self.stats, scale=self.weight)
+        return loss, {'bone_uv_t': self.crit.uv}                  # (kept: the soft-arg-max the prior was taken of)
+
+    def state_dict(self):
+        return self.stats.state_dict()
+
+    def load_state_dict(self, state):
+        self.stats.load_state_dict(state)
+
+
 class CrossDomainMixup:
     """What ``DAStep(mixup=...)`` takes: a fourth stage, step M, behind update C.  The reference's ``mixup`` (uda/model/loss.py:13-24,
     never called there: nothing builds heat-maps for the unlabelled target images) on the batch of the iteration: every source
@@ -442,7 +477,7 @@ class DAStep:
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
     def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None,
-                 proto=None, clip=None, mixup=None, fda=None, view=None, coord=None):
+                 proto=None, clip=None, mixup=None, fda=None, view=None, bone=None, coord=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         # optional mi355.teacher.GeometricView (may also be assigned after construction): the teacher of the iteration -- one forward,
         # shared by the MeanTeacher, CoordRegression(target='teacher') and CrossDomainMixup(labels='teacher') -- sees the target batch
@@ -469,6 +504,9 @@ class DAStep:
         # the target batch (two launches at the head of step A) instead of batch['x_s'], which is only read; steps B, C and M, the
         # teacher views and the mixup blend keep the batch's own tensors.  None: nothing is launched.
         self.fda = fda
+        # optional KinematicPrior (may also be assigned after construction): step A updates the bone-ratio statistics from
+        # batch['kp_s'], and the prior on the target prediction is the last of step C's terms.  None: nothing is launched.
+        self.bone = bone
         self._kept_c = {}
         if mt is not None and self.ema is None:
             self.ema = mt.ema
@@ -572,6 +610,8 @@ class DAStep:
         on = [t for t in (self.mt, self.mmd, self.jfa, self.proto) if t is not None]
         if self.coord is not None and self.coord.target == 'teacher':
             on.append(self.coord)
+        if self.bone is not None:
+            on.append(self.bone)
         return on
 
     def _fwdbwd_A(self, b):
@@ -579,6 +619,8 @@ class DAStep:
         for o in self.opt.values():
             o.zero_grad()
         x_s = b['x_s'] if self.fda is None else self.fda.stylise(b)
+        if self.bone is not None:
+            self.bone.source(b)              # the statistics step C reads: one launch, nothing of the network in it
         with _rt.grouped_wgrads():
             y_s, y_s_adv, y_s_adv2, y_s_adv3, f_s = m(x_s)
             for t in self.terms():
@@ -749,8 +791,8 @@ class DAStep:
     # ------------------------------------------------------------------ eager iteration
     def run(self, batch):
         """batch: dict x_s, label_s, w_s, x_t, w_t (+ optional label_t for the PCK bookkeeping; with `mt`: x_t_ema, the teacher's
-        view of the target batch -- x_t itself when the key is absent; with `coord`: kp_s, the continuous source key points (B, K, 2)
-        in heat-map pixels)."""
+        view of the target batch -- x_t itself when the key is absent; with `coord` or `bone`: kp_s, the continuous source key
+        points (B, K, 2) in heat-map pixels)."""
         if self.graphs is not None:
             return self.replay(batch)
         from uda.model.regda_4 import _CENTRES

@@ -832,6 +832,57 @@ def coord_heatmap(pred, coord, weight, beta=1.0, delta=1.0, coef=1.0, want_grad=
     return rows, g, uv
 
 
+def softargmax_backward(pred, g_uv, beta=1.0):
+    """d loss / d ``pred`` (B, K, H, W) of a loss on the soft-arg-max of ``softmax(beta * pred)``, from ``g_uv`` (B, K, 2) =
+    d loss / d (u, v) (mi355_softargmax_backward).  A joint whose two components are exactly 0 gets a map of zeros unread."""
+    pred = _hm(pred)
+    B, K, H, W = pred.shape
+    if tuple(g_uv.shape) != (B, K, 2):
+        raise Mi355Error('softargmax_backward: pred %s needs a gradient (%d, %d, 2), got %s' % (tuple(pred.shape), B, K, tuple(g_uv.shape)))
+    g_uv = _hm(g_uv)
+    g = torch.empty_like(pred)
+    call('mi355_softargmax_backward', ptr(pred), ptr(g_uv), float(beta), ptr(g), B * K, H, W, stream_ptr())
+    return g
+
+
+def _bone_args(who, uv, weight, bones, mean, var, seen):
+    uv = _hm(uv)
+    if uv.dim() != 3 or uv.shape[2] != 2:
+        raise Mi355Error('%s: the points must be (B, K, 2), got %s' % (who, tuple(uv.shape)))
+    B, K, _ = uv.shape
+    if weight is not None:
+        if weight.numel() != B * K:
+            raise Mi355Error('%s: %d weights for %d joints' % (who, weight.numel(), B * K))
+        weight = _hm(weight.reshape(B, K))
+    if bones.dtype != torch.int32 or bones.dim() != 2 or bones.shape[1] != 2 or not bones.is_contiguous():
+        raise Mi355Error('%s: the bone table must be a contiguous int32 (E, 2) tensor, got %s %s' % (who, bones.dtype, tuple(bones.shape)))
+    E = bones.shape[0]
+    for name, t, dt in (('mean', mean, torch.float32), ('var', var, torch.float32), ('seen', seen, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (E,) or not t.is_contiguous():
+            raise Mi355Error('%s: %s must be a contiguous %s (%d,) tensor, got %s %s' % (who, name, dt, E, t.dtype, tuple(t.shape)))
+        _chk_dev(t)
+    _chk_dev(bones)
+    return uv, weight, B, K, E
+
+
+def bone_prior(uv, weight, bones, mean, var, seen, margin=1.0, eps=1e-4, coef=1.0, want_grad=True):
+    """The bone-ratio prior of ``uv`` (B, K, 2) against the running statistics (mi355_bone_prior).  Returns (loss_rows [B], g_uv
+    [B, K, 2] or None); ``coef`` is the term's coefficient: g_uv = d(coef * mean over B of the rows) / d uv."""
+    uv, weight, B, K, E = _bone_args('bone_prior', uv, weight, bones, mean, var, seen)
+    rows = torch.empty((B,), dtype=torch.float32, device=uv.device)
+    g = torch.empty_like(uv) if want_grad else None
+    call('mi355_bone_prior', ptr(uv), ptr(weight), ptr(bones), ptr(mean), ptr(var), ptr(seen), float(margin), float(eps),
+         float(coef) / B, ptr(rows), ptr(g), B, K, E, stream_ptr())
+    return rows, g
+
+
+def bone_stats_update(kp, weight, bones, mean, var, seen, rho):
+    """Blend the bone-ratio statistics of the batch ``kp`` (B, K, 2) into ``mean`` / ``var`` / ``seen``, in place
+    (mi355_bone_stats_update)."""
+    kp, weight, B, K, E = _bone_args('bone_stats_update', kp, weight, bones, mean, var, seen)
+    call('mi355_bone_stats_update', ptr(kp), ptr(weight), ptr(bones), ptr(mean), ptr(var), ptr(seen), float(rho), B, K, E, stream_ptr())
+
+
 def reduce_sum(v, scale=1.0):
     v = v.contiguous()
     out = torch.empty((), dtype=torch.float32, device=v.device)

@@ -20,7 +20,8 @@ heat-maps against the un-quantised annotation, and of the target heat-maps again
 the reference), ``--fda {off,on}`` with ``--fda-beta`` (step A sees the source batch with the low-frequency amplitude of the target batch:
 Fourier Domain Adaptation, not in the reference), ``--mt-view {same,geom}`` with ``--view-rot`` / ``--view-scale`` / ``--view-shift`` /
 ``--view-margin`` (the EMA teacher sees the target batch rotated, scaled and shifted per sample and its heat-maps are mapped back
-before they are compared: geometric consistency, not in the reference), ``--clip-grad-norm FLOAT``
+before they are compared: geometric consistency, not in the reference), ``--bone-loss {off,on}`` with ``--bone-weight`` / ``--bone-margin`` / ``--bone-momentum`` / ``--bone-beta`` / ``--bone-eps``
+(a bone-ratio skeleton prior on the target prediction against running statistics of the source annotations; not in the reference), ``--clip-grad-norm FLOAT``
 (global gradient-norm clipping of each of the three updates with a non-finite step guard, on the device; not in the reference), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
@@ -63,7 +64,7 @@ import mi355
 import uda.model as models
 from mi355 import ops as _ops
 from mi355.ops import FDA_MAX_B, fda_band
-from mi355.da_step import CoordRegression, CrossDomainMixup, FourierStyle, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
+from mi355.da_step import CoordRegression, KinematicPrior, CrossDomainMixup, FourierStyle, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
 from mi355.optim import EMATeacher, GradClipper, make_optimizer
 from mi355.teacher import GeometricView, MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
@@ -191,8 +192,8 @@ def main(args):
         # host -> HBM copies of the next batch overlap the current step (pinned, double-buffered, side stream)
         # (--mt-loss: meta['image_ema'] of the target batches travels with them instead of as a blocking copy inside the iteration)
         ema_keys = ('image_ema',) if want_ema and not args.synthetic else ()
-        # (--coord-loss: meta['keypoint2d'] of the source batches, the un-quantised key points, travels with them likewise)
-        train_source_iter = DevicePrefetcher(train_source_iter, device, meta_keys=('keypoint2d',) if args.coord_loss != 'off' else ())
+        # (--coord-loss, --bone-loss: meta['keypoint2d'] of the source batches, the un-quantised key points, travels with them likewise)
+        train_source_iter = DevicePrefetcher(train_source_iter, device, meta_keys=('keypoint2d',) if wants_keypoints(args) else ())
         train_target_iter = DevicePrefetcher(train_target_iter, device, meta_keys=ema_keys)
 
     # model (+ the EMA copy the reference builds and checkpoints, train1.py:102-128; frozen unless --ema-update is on)
@@ -245,6 +246,8 @@ def main(args):
         step.fda = FourierStyle(beta=args.fda_beta)
     # step A (and, with 'both', step C against the teacher) gains a loss on the soft-arg-max coordinates
     step.coord = coord_term(args, ema)
+    # step A keeps bone-ratio statistics of the source annotations, step C holds the target prediction to them
+    step.bone = bone_term(args)
     if args.clip_grad_norm > 0:
         # each update clips the global norm of what it steps and skips itself when that norm is not finite (mi355.optim.GradClipper)
         step.clip = GradClipper(args.clip_grad_norm, device)
@@ -370,6 +373,19 @@ def coord_term(args, ema):
                            target='teacher' if args.coord_loss == 'both' else 'off', target_weight=args.coord_target_weight, ema=ema)
 
 
+def bone_term(args):
+    """The ``mi355.da_step.KinematicPrior`` of --bone-loss on; None when the switch is off."""
+    if args.bone_loss == 'off':
+        return None
+    return KinematicPrior(weight=args.bone_weight, margin=args.bone_margin, momentum=args.bone_momentum, beta=args.bone_beta,
+                          eps=args.bone_eps)
+
+
+def wants_keypoints(args):
+    """Does some term read batch['kp_s'], the un-quantised source key points?"""
+    return args.coord_loss != 'off' or args.bone_loss == 'on'
+
+
 def source_keypoints(meta, image_size, heatmap_size, device):
     """batch['kp_s']: ``meta['keypoint2d']`` (B, K, 2) in image pixels -> fp32 heat-map pixels on `device`, un-quantised (the labels
     sit at ``int(. + 0.5)`` of these)."""
@@ -398,7 +414,7 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
         x_t, label_t, weight_t, meta_t = next(train_target_iter)
         to = lambda t: t.to(device, non_blocking=True)
         batch = dict(x_s=to(x_s), label_s=to(label_s), w_s=to(weight_s), x_t=to(x_t), w_t=to(weight_t), label_t=to(label_t))
-        if coord is not None:                            # the un-quantised source key points, image pixels -> heat-map pixels
+        if coord is not None or getattr(step, 'bone', None) is not None:   # the un-quantised source key points, image pixels -> heat-map pixels
             batch['kp_s'] = source_keypoints(meta_s, args.image_size, args.heatmap_size, device)
         if mt is not None or (mixup is not None and mixup.labels == 'teacher') or (coord is not None and coord.target == 'teacher'):   # x_t_ema = meta_t['image_ema'] (train1.py:364); synthetic images have no augmentation
             batch['x_t_ema'] = batch['x_t'] if args.synthetic else to(meta_t['image_ema'])
@@ -736,6 +752,23 @@ _OPTIONS = [
     (('--coord-beta',), dict(default=1.0, type=float, metavar='FLOAT', help='inverse temperature of the softmax under the soft-arg-max '
                             '(positive; 1 = the distribution the KL loss trains the main head towards)')),
     (('--coord-delta',), dict(default=1.0, type=float, metavar='FLOAT', help='threshold of the smooth-L1 in heat-map pixels (0: plain L1)')),
+    (('--bone-loss',), dict(default='off', choices=['off', 'on'], help="bone-ratio skeleton prior on the target batch (in the family "
+                           "of the bone-length-ratio constraint of Zhou et al. 2017; not in the reference): step A blends the bone-length "
+                           "ratios of the un-quantised source annotations (meta['keypoint2d']) into running statistics, step C adds w * "
+                           "the squared excess beyond --bone-margin standard deviations of the same ratios of the target prediction's "
+                           "soft-arg-max; no teacher and no further forward; the statistics travel in the epoch checkpoint (bone_state); "
+                           "'off': nothing is launched")),
+    (('--bone-weight',), dict(default=1.0, type=float, metavar='FLOAT', help='weight w of the bone-ratio prior (constant, positive; the '
+                             'default is a placeholder: its effect on convergence has not been measured, and cannot be without the '
+                             'data sets)')),
+    (('--bone-margin',), dict(default=1.0, type=float, metavar='FLOAT', help='dead zone of the prior in standard deviations of the source '
+                             'ratio (finite, not negative; a placeholder, as the weight)')),
+    (('--bone-momentum',), dict(default=0.01, type=float, metavar='FLOAT', help='weight of a source batch in the running mean and variance '
+                               'of the ratios, in [0, 1] (the first batch is taken whole; a placeholder, as the weight)')),
+    (('--bone-beta',), dict(default=1.0, type=float, metavar='FLOAT', help='inverse temperature of the softmax under the soft-arg-max '
+                           '(positive; a placeholder, as the weight)')),
+    (('--bone-eps',), dict(default=1e-4, type=float, metavar='FLOAT', help='added to the running variance under the square root (positive; '
+                          'a placeholder, as the weight)')),
     (('--clip-grad-norm',), dict(default=0.0, type=_clip_norm, metavar='FLOAT', help="global gradient-norm clipping with a non-finite "
                                 "step guard: each of the updates A, B, C (M with --mixup on; and the pre-training step) clips over everything it steps, as "
                                 "clip_grad_norm_(those parameters, FLOAT) before the optimizers would, in two launches per update and "
@@ -823,6 +856,14 @@ class _Parser(argparse.ArgumentParser):
                 check_positive('--coord-beta', args.coord_beta)
                 if not 0.0 <= args.coord_delta < float('inf'):
                     raise ValueError('--coord-delta must be finite and not negative, got %r' % (args.coord_delta,))
+            if getattr(args, 'bone_loss', 'off') == 'on':
+                check_positive('--bone-weight', args.bone_weight)
+                check_positive('--bone-beta', args.bone_beta)
+                check_positive('--bone-eps', args.bone_eps)
+                if not 0.0 <= args.bone_margin < float('inf'):
+                    raise ValueError('--bone-margin must be finite and not negative, got %r' % (args.bone_margin,))
+                if not 0.0 <= args.bone_momentum <= 1.0:
+                    raise ValueError('--bone-momentum must be in [0, 1], got %r' % (args.bone_momentum,))
             if getattr(args, 'mmd_loss', 'off') == 'on':
                 check_positive('--mmd-weight', args.mmd_weight)
                 check_whole('--mmd-kernels', args.mmd_kernels, 8)

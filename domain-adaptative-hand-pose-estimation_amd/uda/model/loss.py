@@ -134,6 +134,166 @@ def soft_argmax(output, beta=1.0):
     return ops.softargmax(output.detach(), beta, 1.0)
 
 
+# ---------------------------------------------------------------- bone-ratio skeleton prior (not in the reference)
+# (parent, child) pairs of the 21-joint hand of uda/dataset/keypoint_dataset.py:47-57: the wrist and five chains of four joints
+HAND_BONES = tuple((0 if j % 4 == 1 else j - 1, j) for j in range(1, 21))
+
+
+def _check_bones(bones):
+    bones = tuple((int(p), int(c)) for p, c in bones)
+    if not 1 <= len(bones) <= 32:
+        raise ValueError('the bone table needs 1 .. 32 (parent, child) pairs, got %d' % len(bones))
+    for p, c in bones:
+        if p == c or not (0 <= p < 32 and 0 <= c < 32):
+            raise ValueError('a bone joins two different joints in 0 .. 31, got %r' % ((p, c),))
+    return bones
+
+
+class BoneStatistics:
+    """Running mean and variance of the bone-length ratios of the source annotations (mi355_bone_stats_update), per bone of the
+    table ``bones``, and which bones have been seen at all.  ``table`` (E, 2) int32, ``mean`` / ``var`` (E,) fp32 and ``seen``
+    (E,) int32 live at fixed device addresses from the first ``update`` (or ``to``) on, so a captured launch carries them from
+    replay to replay and handles the first batch like any other.  ``momentum``: the weight of a batch in the blend."""
+
+    def __init__(self, bones=HAND_BONES, momentum=0.01, device=None):
+        if not 0.0 <= float(momentum) <= 1.0:
+            raise ValueError('BoneStatistics: the momentum must be in [0, 1], got %r' % (momentum,))
+        self.bones, self.momentum = _check_bones(bones), float(momentum)
+        self.num_joints = 1 + max(max(b) for b in self.bones)
+        self.table = self.mean = self.var = self.seen = None
+        self._pending = None
+        if device is not None:
+            self.to(device)
+
+    def to(self, device):
+        """Allocate the device buffers (outside graph capture); a state loaded earlier is copied in."""
+        if self.table is None:
+            if torch.device(device).type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise _rt.Mi355Error('bone statistics would be allocated during graph capture: warm up first')
+            E = len(self.bones)
+            self.table = torch.tensor(self.bones, dtype=torch.int32).to(device)
+            self.mean = torch.zeros(E, dtype=torch.float32, device=device)
+            self.var = torch.zeros(E, dtype=torch.float32, device=device)
+            self.seen = torch.zeros(E, dtype=torch.int32, device=device)
+            if self._pending is not None:
+                state, self._pending = self._pending, None
+                self.load_state_dict(state)
+        return self
+
+    def update(self, kp, w=None):
+        """Blend the batch ``kp`` (B, K, 2) with joint weights ``w`` (B, K[, 1]) into the statistics: one launch."""
+        self.to(kp.device)
+        if kp.shape[1] < self.num_joints:
+            raise ValueError('BoneStatistics: the table names joint %d, the batch has %d joints' % (self.num_joints - 1, kp.shape[1]))
+        ops.bone_stats_update(kp.detach(), None if w is None else w.detach(), self.table, self.mean, self.var, self.seen, self.momentum)
+
+    def reset(self):
+        self._pending = None
+        if self.table is not None:
+            self.mean.zero_(); self.var.zero_(); self.seen.zero_()
+
+    def state_dict(self):
+        """CPU copies of mean, var and seen (None before first use): what the epoch checkpoint keeps as ``bone_state``."""
+        if self.table is None:
+            return dict(self._pending) if self._pending is not None else {'mean': None, 'var': None, 'seen': None}
+        return {k: getattr(self, k).detach().cpu().clone() for k in ('mean', 'var', 'seen')}
+
+    def load_state_dict(self, state):
+        if state.get('mean') is None:
+            self.reset()
+            return
+        E = len(self.bones)
+        for k in ('mean', 'var', 'seen'):
+            if tuple(state[k].shape) != (E,):
+                raise ValueError('BoneStatistics: %s of the state is %s, the table has %d bones' % (k, tuple(state[k].shape), E))
+        if self.table is None:
+            self._pending = {k: state[k].detach().cpu().clone() for k in ('mean', 'var', 'seen')}
+            return
+        self.mean.copy_(state['mean'].float()); self.var.copy_(state['var'].float())      # (in place: a captured graph keeps the addresses)
+        self.seen.copy_(state['seen'].to(torch.int32))
+
+
+def _bone_check(stats, K):
+    if stats.table is None:
+        raise _rt.Mi355Error('bone_prior: the statistics have no device buffers yet (BoneStatistics.update or .to first)')
+    if K < stats.num_joints:
+        raise ValueError('bone_prior: the table names joint %d, the prediction has %d joints' % (stats.num_joints - 1, K))
+
+
+def _bone_backward(ctx, gout, n_in):
+    g, = ctx.saved_tensors
+    rest = (None,) * (n_in - 1)
+    if g is None or gout is None:
+        return (None,) + rest
+    if _rt.is_unit_grad(gout):
+        return (g,) + rest
+    return (ops.scale_by_dev(g, gout.contiguous().float()),) + rest
+
+
+class _BoneFn(torch.autograd.Function):
+    """loss = coeff * mean(rows) of the bone-ratio prior on coordinates; the kernel writes d loss / d uv in the forward (_KLFn's
+    scheme)."""
+
+    @staticmethod
+    def forward(ctx, uv, weight, stats, margin, eps, coeff):
+        ctx.set_materialize_grads(False)
+        rows, g = ops.bone_prior(uv, weight, stats.table, stats.mean, stats.var, stats.seen, margin, eps, coeff, ctx.needs_input_grad[0])
+        ctx.save_for_backward(g)
+        return ops.reduce_sum(rows, float(coeff) / rows.numel()), rows
+
+    @staticmethod
+    def backward(ctx, gout, grows):
+        return _bone_backward(ctx, gout, 6)
+
+
+def bone_prior(uv, weight, stats, margin=1.0, eps=1e-4, scale=1.0):
+    """The bone-ratio prior of the points ``uv`` (B, K, 2) against ``stats`` (a ``BoneStatistics``), differentiable w.r.t. ``uv``:
+    per sample, the lengths of the present bones (both joints of weight > 0, bone seen in the statistics) divided by their mean
+    are standardised by the running mean and variance, and what exceeds ``margin`` standard deviations is penalised
+    quadratically; the mean over the batch, times ``scale``.  Invariant to rotation, scale and shift of a sample."""
+    _bone_check(stats, uv.shape[1])
+    w = None if weight is None else weight.detach()
+    return _BoneFn.apply(uv, w, stats, float(margin), float(eps), float(scale))[0]
+
+
+class _BoneHeatmapFn(torch.autograd.Function):
+    """The same loss on heat-maps: soft-arg-max -> bone prior -> backward of the soft-arg-max, three launches in the forward."""
+
+    @staticmethod
+    def forward(ctx, pred, weight, stats, beta, margin, eps, coeff):
+        ctx.set_materialize_grads(False)
+        uv = ops.softargmax(pred, beta, 1.0)
+        want = ctx.needs_input_grad[0]
+        rows, g_uv = ops.bone_prior(uv, weight, stats.table, stats.mean, stats.var, stats.seen, margin, eps, coeff, want)
+        ctx.save_for_backward(ops.softargmax_backward(pred, g_uv, beta) if want else None)
+        ctx.mark_non_differentiable(uv)
+        return ops.reduce_sum(rows, float(coeff) / rows.numel()), rows, uv
+
+    @staticmethod
+    def backward(ctx, gout, grows, guv):
+        return _bone_backward(ctx, gout, 7)
+
+
+class BonePriorLoss(nn.Module):
+    """``bone_prior`` on the soft-arg-max of ``softmax(beta * output)`` (B, K, H, W), with its gradient w.r.t. the heat-maps.
+    ``uv`` holds the soft-arg-max of the last call, detached."""
+
+    def __init__(self, beta=1.0, margin=1.0, eps=1e-4):
+        super().__init__()
+        check_positive('BonePriorLoss: beta', beta)
+        check_positive('BonePriorLoss: eps', eps)
+        if not 0.0 <= float(margin) < float('inf'):
+            raise ValueError('BonePriorLoss: the margin must be finite and not negative, got %r' % (margin,))
+        self.beta, self.margin, self.eps = float(beta), float(margin), float(eps)
+        self.uv = None
+
+    def forward(self, output, weight, stats, scale=1.0):
+        _bone_check(stats, output.shape[1])
+        w = None if weight is None else weight.detach()
+        loss, _, self.uv = _BoneHeatmapFn.apply(output, w, stats, self.beta, self.margin, self.eps, float(scale))
+        return loss
+
+
 # ---------------------------------------------------------------- mean-teacher consistency (reference uda/model/loss.py:265-297)
 # the joint curriculum of mt_loss: k < 100 the wrist, then one more joint per finger every 100, all joints from 400 on
 MT_SUBSETS = ((100, (0,)),

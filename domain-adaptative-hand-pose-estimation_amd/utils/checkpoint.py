@@ -2,7 +2,7 @@
 
 Layout (reference train1.py:248-268 plus additive keys): ``<epoch>.pth`` holds ``model``, ``optimizer_f`` / ``_h`` / ``_h_adv`` and their
 ``lr_scheduler_*``, ``epoch`` and ``args``; additive: the same for ``h_adv2`` / ``h_adv3``, ``gl_iter_num``, ``ema_state``, ``proto_state``,
-``mixup_state``, ``view_state`` and -- ``--dtype fp8`` -- ``fp8_state``.  ``model_ema.pth`` beside it holds ``model_ema``.  Every piece is restored into
+``bone_state``, ``mixup_state``, ``view_state`` and -- ``--dtype fp8`` -- ``fp8_state``.  ``model_ema.pth`` beside it holds ``model_ema``.  Every piece is restored into
 objects that have not run an iteration yet: optimizers that are not flat, a teacher without its mirror layout, no graphs.
 """
 import os
@@ -16,7 +16,7 @@ from mi355.optim import check_state_dict_kind
 REFERENCE_KEYS = ('model', 'optimizer_f', 'optimizer_h', 'optimizer_h_adv', 'lr_scheduler_f', 'lr_scheduler_h', 'lr_scheduler_h_adv',
                   'epoch', 'args')
 ADDITIVE_KEYS = ('optimizer_h_adv2', 'optimizer_h_adv3', 'lr_scheduler_h_adv2', 'lr_scheduler_h_adv3', 'gl_iter_num')
-OPTIONAL_KEYS = ('ema_state', 'proto_state', 'mixup_state', 'view_state', 'fp8_state')      # written when the run has the piece of state
+OPTIONAL_KEYS = ('ema_state', 'proto_state', 'bone_state', 'mixup_state', 'view_state', 'fp8_state')      # written when the run has the piece of state
 
 
 def ema_path_beside(path):
@@ -28,6 +28,8 @@ def training_state(epoch, args, model, opts, scheds, step, ema):
     ck_extra = {'ema_state': ema.state_dict()} if ema is not None else {}
     if getattr(step, 'proto', None) is not None:
         ck_extra['proto_state'] = step.proto.state_dict()
+    if getattr(step, 'bone', None) is not None:
+        ck_extra['bone_state'] = step.bone.state_dict()
     if getattr(step, 'mixup', None) is not None:
         ck_extra['mixup_state'] = step.mixup.state_dict()
     if getattr(step, 'view', None) is not None:
@@ -82,6 +84,8 @@ def apply_training_state(ck, path, args, model, model_ema, opts, scheds, step, e
         model_ema.load_state_dict(torch.load(beside, map_location='cpu', weights_only=False)['model_ema'])
     if getattr(step, 'proto', None) is not None and 'proto_state' in ck:
         step.proto.load_state_dict(ck['proto_state'], device)      # both prototype memories and m
+    if getattr(step, 'bone', None) is not None and 'bone_state' in ck:
+        step.bone.load_state_dict(ck['bone_state'])                 # mean, var and seen of the bone-ratio statistics
     if getattr(step, 'mixup', None) is not None and 'mixup_state' in ck:
         step.mixup.load_state_dict(ck['mixup_state'])               # the RNG state of the blend coefficients (rank 0's)
     if getattr(step, 'view', None) is not None and 'view_state' in ck:

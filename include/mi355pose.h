@@ -411,6 +411,45 @@ int mi355_kl_heatmap(const float* pred, const float* target, const float* weight
  * coef not finite. */
 int mi355_coord_heatmap(const float* pred, const float* coord, const float* weight, float beta, float delta, float coef,
                         float* loss_rows, float* unit_grad, float* uv, int rows, int H, int W, void* stream);
+/* Backward of the soft-arg-max for an arbitrary upstream gradient, one launch (NOT in the reference, whose soft-arg-max is
+ * forward-only).  pred [rows][H][W] fp32, g_uv [rows][2] = d loss / d (u, v), grad [rows][H][W].  With m, e_i, s, p_i, u, v
+ * exactly as mi355_coord_heatmap defines them (the forward is mi355_softargmax with out_scale 1):
+ *   grad[r][i] = beta * p_i * ((x_i - u) * g_u + (y_i - v) * g_v)
+ * A row whose g_u and g_v are both exactly 0 is skipped by selection: a row of +0 whatever pred[r] holds (NaN and inf included;
+ * the map is not read).  Elsewhere a NaN of pred[r] or g_uv[r] reaches the whole of grad[r] and no other row.  Same forms as
+ * mi355_coord_heatmap (register-resident with 16-byte stores at 64 x 64, 32 x 32 and 16 x 16 when pred and grad are 16-byte
+ * aligned, a loop form otherwise).  No atomics, fixed summation order, no allocation.
+ * MI355_EINVAL: null pred / g_uv / grad; rows, H or W < 1; H*W >= 2^31; beta not finite or <= 0. */
+int mi355_softargmax_backward(const float* pred, const float* g_uv, float beta, float* grad, int rows, int H, int W, void* stream);
+/* Bone-ratio skeleton prior (NOT in the reference; in the family of the bone-length-ratio constraint of Zhou et al., ICCV 2017:
+ * PAPERS.md).  The skeleton is a table bones = int32 [E][2] of (parent, child) joint indices in device memory; an entry outside
+ * [0, K) is no bone.  uv [B][K][2] fp32, weight [B][K] (nullable: all joints visible), mean / var [E] fp32 and seen [E] int32:
+ * the running statistics of mi355_bone_stats_update.  fp64 arithmetic on the fp32 operands, every product and sum rounded on its
+ * own, every sum in ascending bone order, one rounding to fp32 at each store.  Per sample b:
+ *   bone e = (p, c) is present iff w[p] > 0 && w[c] > 0 && seen[e];  d_e = uv[c] - uv[p];  l_e = sqrt(dx*dx + dy*dy)
+ *   n = number of present bones, S = sum of their l_e.  n < 2 || S == 0: the sample is skipped (loss 0, gradient rows exactly 0)
+ *   lbar = S / n;  r_e = l_e / lbar;  sd_e = sqrt(var_e + eps);  z_e = (r_e - mean_e) / sd_e;  h_e = max(|z_e| - margin, 0)
+ *   loss_rows[b] = (sum_e 0.5 * h_e^2) / n
+ *   q_e = h_e * sign(z_e) / (n * sd_e);  Q = (sum_e q_e * r_e) / n;  gl_e = (q_e - Q) / lbar
+ *   t_e = (coef * gl_e / l_e) * d_e  (nothing for l_e == 0);  g_uv[b][c] += t_e;  g_uv[b][p] -= t_e        (g_uv nullable)
+ * coef = the term's coefficient / B: the scalar loss is mi355_reduce_sum(loss_rows, coef) and g_uv its gradient w.r.t. uv.
+ * The loss does not change under a rotation, a scaling or a shift of the sample's points.  A NaN coordinate of a present bone
+ * reaches that sample's loss and gradient and no other sample's.
+ * MI355_EINVAL: null uv / bones / mean / var / seen / loss_rows; B < 1 or > MI355_BONE_MAX_BATCH; K < 2 or >
+ * MI355_BONE_MAX_JOINTS; E < 1 or > MI355_BONE_MAX_BONES; margin not finite or < 0; eps not finite or <= 0; coef not finite. */
+#define MI355_BONE_MAX_JOINTS 32
+#define MI355_BONE_MAX_BONES 32
+#define MI355_BONE_MAX_BATCH 4096
+int mi355_bone_prior(const float* uv, const float* weight, const int* bones, const float* mean, const float* var, const int* seen,
+                     float margin, float eps, float coef, float* loss_rows, float* g_uv, int B, int K, int E, void* stream);
+/* Running statistics of the bone ratios, one launch of one workgroup, fp64.  kp [B][K][2], weight [B][K] (nullable).  r_e^b as
+ * above, except that presence ignores `seen`; skipped samples are left out.  For every bone that c_e >= 1 samples show: m_e =
+ * the mean and v_e = the biased variance (about m_e) of its ratios, samples in ascending order.  seen[e] == 0: mean = m, var =
+ * v, seen = 1; else mean = (1 - rho) * mean + rho * m and likewise var.  A bone with c_e == 0 is not touched.  All three arrays
+ * are updated in place on the device, so a captured launch handles the first batch like any other.
+ * MI355_EINVAL: null kp / bones / mean / var / seen; shapes as above; rho outside [0, 1] or NaN. */
+int mi355_bone_stats_update(const float* kp, const float* weight, const int* bones, float* mean, float* var, int* seen, float rho,
+                            int B, int K, int E, void* stream);
 /* out[0] = scale * sum(in[0..n)) in a fixed order (deterministic). */
 int mi355_reduce_sum(const float* in, float* out, int n, float scale, void* stream);
 /* out[i] = in[i] * (*g_dev) : backward of the KL loss (upstream scalar gradient on device). */
