@@ -26,6 +26,19 @@ thread_local char g_tag[160] = "";
 thread_local long g_last = -1;      // launch index of the entry this thread opened last (prof_amend_label)
 }
 bool prof_on() { return P().on; }
+
+// row-kernel dispatch of the heat-map row kernels (heatmap_rows.h): 0 = no register form for this map size (or unaligned
+// pointers): the loop kernels
+int row_form(int HW, const void* a, const void* b, const void* c) {
+  static const bool on = !(getenv("MI355_ROW_REG") && atoi(getenv("MI355_ROW_REG")) == 0);      // A/B switch
+  if (!on) return 0;
+  if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) return 0;
+  if (HW == 4096) return 1;       // block per map, 16 floats per thread (a wave per 64 x 64 map, 64 floats per lane, measured slower:
+                                  // arg-max 9.5 vs 6.5 us, soft-arg-max 12.4 vs 8.7, KL 22.5 vs 18.1 on the 64 x 21 x 64 x 64 tensor)
+  if (HW == 1024) return 2;       // wave per map, 16 floats per lane
+  if (HW == 256) return 3;        // wave per map, 4 floats per lane
+  return 0;
+}
 void prof_set_tag(const char* fmt, ...) {
   if (!P().on) return;
   va_list ap; va_start(ap, fmt); vsnprintf(g_tag, sizeof(g_tag), fmt, ap); va_end(ap);

@@ -477,7 +477,7 @@ class DAStep:
     h_adv3 (FusedSGD or any torch optimizer), ``criteria`` = dict with keys kl, rd (x6), rd2 (x5), rd1 (x1)."""
 
     def __init__(self, model, optimizers, criteria, trade_off=1.0, skip_discarded=True, track_accuracy=True, ema=None, mt=None, mmd=None, jfa=None,
-                 proto=None, clip=None, mixup=None, fda=None, view=None, bone=None, coord=None):
+                 proto=None, clip=None, mixup=None, fda=None, view=None, bone=None, occlude=None, teacher_conf=0.0, conf_beta=1.0, coord=None):
         self.model, self.opt, self.crit = model, optimizers, criteria
         # optional mi355.teacher.GeometricView (may also be assigned after construction): the teacher of the iteration -- one forward,
         # shared by the MeanTeacher, CoordRegression(target='teacher') and CrossDomainMixup(labels='teacher') -- sees the target batch
@@ -507,6 +507,19 @@ class DAStep:
         # optional KinematicPrior (may also be assigned after construction): step A updates the bone-ratio statistics from
         # batch['kp_s'], and the prior on the target prediction is the last of step C's terms.  None: nothing is launched.
         self.bone = bone
+        # optional mi355.teacher.KeypointOcclusion (may also be assigned after construction): the teacher's one forward of the
+        # iteration moves to the head of step B, and the student's forwards of the target batch (step B's; step C's own one with
+        # skip_discarded=False) read a copy of batch['x_t'] with a patch around confident teacher key points blanked.  batch['x_t']
+        # is only read: the teacher, step M's blend and FDA keep the loader's images.  None: nothing is launched, nothing is drawn.
+        # teacher_conf > 0 (with or without occlusion): a teacher map counts for the MeanTeacher, CoordRegression(target='teacher')
+        # and CrossDomainMixup(labels='teacher') only when the peak of softmax(conf_beta * y) reaches it (the occlusion's own beta
+        # when there is one) -- `conf` multiplies in wherever the view's `valid` flags do; it is also the occlusion's candidate
+        # threshold.  0: no gate.
+        import math
+        if not (isinstance(teacher_conf, (int, float)) and math.isfinite(teacher_conf) and teacher_conf >= 0.0):
+            raise ValueError('DAStep: teacher_conf must be finite and not negative, got %r' % (teacher_conf,))
+        self.occlude, self.teacher_conf, self.conf_beta = occlude, float(teacher_conf), float(conf_beta)
+        self._gate, self._occ_teacher, self._y_ema_iter, self._x_student = None, None, None, None
         self._kept_c = {}
         if mt is not None and self.ema is None:
             self.ema = mt.ema
@@ -585,16 +598,84 @@ class DAStep:
     def teacher_forward(self, teacher, batch):
         """The teacher's heat-maps on its view of the target batch (x_t_ema; x_t itself when the batch has none), in the loader's
         frame.  With a GeometricView the teacher also keeps the flags (`valid`) and w_t * valid (`w_out`)."""
+        sel = self._selector()
+        if sel is not None and self._y_ema_iter is not None:
+            return self._y_ema_iter                      # this iteration's one forward: every later caller reads the same maps
         x = batch['x_t_ema'] if batch.get('x_t_ema') is not None else batch['x_t']
         teacher.view, self._last_teacher = self.view, teacher
         if self.view is None:
-            return teacher.forward(x)
-        return teacher.forward(x, w_in=batch['w_t'])
+            y = teacher.forward(x)
+        else:
+            y = teacher.forward(x, w_in=batch['w_t'])
+        if sel is not None:
+            # the confidence of every map (of the maps as the consumers read them: mapped back under a view, whose flags enter
+            # as the gate) and, with occlusion, the boxes: two launches behind the forward
+            S = batch['x_t'].shape[-1]
+            if sel.n > 0 and batch['x_t'].shape[-2] != S:
+                raise _rt.Mi355Error('DAStep: key-point occlusion needs square target images, got %s' % (tuple(batch['x_t'].shape),))
+            sel.select(y, self.teacher_conf, S, gate_in=teacher.valid if self.view is not None else None, w_in=batch['w_t'])
+            self._y_ema_iter = y
+            self.out.update(conf_share=sel.stats[1])
+            if sel.n > 0:
+                self.out.update(occ_boxes=sel.stats[0])
+        return y
+
+    def _selector(self):
+        """The KeypointOcclusion whose select() follows the teacher's forward: the step's occlusion, else -- for teacher_conf > 0
+        alone -- a gate of the step's own with no boxes; None when both are off."""
+        if self.occlude is not None:
+            return self.occlude
+        if self.teacher_conf > 0.0:
+            if self._gate is None:
+                from .teacher import KeypointOcclusion
+                self._gate = KeypointOcclusion(n=0, beta=self.conf_beta)
+            return self._gate
+        return None
+
+    def _iteration_teacher(self):
+        """The in-iteration teacher of the hoisted forward: the one the consumers of this step would use, else one of the step's own."""
+        if self.mt is not None:
+            return self.mt.teacher
+        if self.coord is not None and self.coord.target == 'teacher':
+            return self.coord.teacher(self)
+        if self.mixup is not None and self.mixup.labels == 'teacher':
+            return self.mixup.teacher(self)
+        if self._occ_teacher is None:
+            if self.ema is None:
+                raise ValueError('key-point occlusion needs an EMATeacher (--ema-update const|warmup)')
+            from .teacher import InIterationTeacher
+            self._occ_teacher = InIterationTeacher(self.ema)
+        return self._occ_teacher
+
+    def _student_input(self, batch):
+        """What the student's forwards of the target batch read: batch['x_t'], or -- with occlusion -- its occluded copy, behind the
+        teacher's forward of the iteration at the head of step B."""
+        if self.occlude is None or self.occlude.n == 0:
+            return batch['x_t']
+        self.teacher_forward(self._iteration_teacher(), batch)
+        return self.occlude.apply(batch['x_t'])
 
     def teacher_weights(self, batch):
         """The joint weights a consumer of the teacher's forward uses: w_t, times the flags of the view when there is one (kept by
-        the teacher that ran this iteration's forward)."""
+        the teacher that ran this iteration's forward), times the confidence flags with teacher_conf > 0."""
+        if self.teacher_conf > 0.0:
+            return self._selector().w_out                # w_t * conf; conf holds the view's flags
         return batch['w_t'] if self.view is None else self._last_teacher.w_out
+
+    def teacher_map_weights(self, teacher):
+        """The per-map weight of the MeanTeacher's loss: the confidence flags with teacher_conf > 0 (they hold the view's), else the
+        view's flags, else None."""
+        if self.teacher_conf > 0.0:
+            return self._selector().conf
+        return teacher.valid if teacher.view is not None else None
+
+    def _draw_occlusion(self, batch=None):
+        if self.occlude is None:
+            return
+        if batch is None:
+            self.occlude.draw()
+        else:
+            self.occlude.draw(batch['x_t'].shape[0], batch['x_t'].device)
 
     def _draw_view(self, batch=None):
         if self.view is None:
@@ -618,6 +699,7 @@ class DAStep:
         m, c = self.model, self.crit
         for o in self.opt.values():
             o.zero_grad()
+        self._y_ema_iter = None                  # (a new iteration: the teacher's forward of the last one is not this one's)
         x_s = b['x_s'] if self.fda is None else self.fda.stylise(b)
         if self.bone is not None:
             self.bone.source(b)              # the statistics step C reads: one launch, nothing of the network in it
@@ -658,9 +740,10 @@ class DAStep:
         m, c, to = self.model, self.crit, self.trade_off
         for k in ('h_adv', 'h_adv2', 'h_adv3'):
             self.opt[k].zero_grad()
+        x_t = self._x_student = self._student_input(b)
         if self.skip:
             with _rt.bn_updates(2):               # this forward also stands for step C's (identical) one
-                f_t = m.features(b['x_t'])
+                f_t = m.features(x_t)
                 y_t_grad = m.head(f_t)
                 y_t = y_t_grad.detach()           # only ever used detached (pseudo-labels) in B and C ...
                 if not any(t.needs_head_graph for t in self.terms()):
@@ -668,7 +751,7 @@ class DAStep:
             self._shared = (f_t, y_t, y_t_grad)
             y_t_adv, y_t_adv2, y_t_adv3 = m.adv_heads(f_t.detach())
         else:
-            y_t, y_t_adv, y_t_adv2, y_t_adv3, _ = m(b['x_t'])
+            y_t, y_t_adv, y_t_adv2, y_t_adv3, _ = m(x_t)
         loss1 = c['rd1'](y_t, y_t_adv3, b['w_t'], mode='max', scale=0.3 * to)
         H = y_t.shape[-1]
         target5 = ops.bilinear_up(y_t_adv3.detach(), H, 0.5)               # 0.5 * up(y_adv3) ...
@@ -697,7 +780,7 @@ class DAStep:
                 self._shared = None
                 y_t_adv, y_t_adv2, y_t_adv3 = m.adv_heads(f_t)
             else:
-                y_t, y_t_adv, y_t_adv2, y_t_adv3, f_t = m(b['x_t'])
+                y_t, y_t_adv, y_t_adv2, y_t_adv3, f_t = m(self._x_student)
                 y_t_grad = y_t
             loss1 = c['rd2'](y_t, y_t_adv2, None, b['w_t'], mode='min', scale=0.3 * to)
             loss2 = c['rd'](y_t, y_t_adv, None, b['w_t'], mode='min', scale=to)
@@ -734,6 +817,8 @@ class DAStep:
                 self.mixup._teacher.refresh()    # (labels='teacher' without a MeanTeacher: the mixup's own in-iteration teacher)
             if self.coord is not None and self.coord._teacher is not None:
                 self.coord._teacher.refresh()    # (target='teacher' without a MeanTeacher, likewise)
+            if self._occ_teacher is not None:
+                self._occ_teacher.refresh()      # (occlusion with no consumer of the teacher's forward: the step's own teacher)
 
     KM = ('f', 'h')                              # what update M steps
 
@@ -805,6 +890,7 @@ class DAStep:
         if self.mixup is not None:
             self.mixup.draw(batch['x_s'].shape[0], batch['x_s'].device)
         self._draw_view(batch)
+        self._draw_occlusion(batch)
         self._begin_reduce(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'))
         self._fwdbwd_A(batch)
         self._end_reduce(('f', 'h', 'h_adv', 'h_adv2', 'h_adv3'))
@@ -925,6 +1011,7 @@ class DAStep:
         if self.mixup is not None:
             self.mixup.draw()                # the coefficients of this iteration, to their fixed device address
         self._draw_view()                    # the records of this iteration's teacher views, likewise
+        self._draw_occlusion()               # the draws of this iteration's occlusion boxes, likewise
 
     def replay(self, batch=None):
         if batch is not None and batch is not self.static:

@@ -1590,6 +1590,115 @@ def mse_heatmap_w(pred, target, rec, wmap, want_grad, rows=None, grad=None):
     return rows, (grad if want_grad else None)
 
 
+# ---------------------------------------------------------------- adaptive occlusion, teacher confidence (csrc/occlude.hip)
+OCC_MAX_BOXES, OCC_MAX_JOINTS = 8, 64
+
+
+def _occ_out(who, out, specs, device):
+    """The outputs of one launch: `out` as given, or fresh tensors -- never during graph capture.  specs: (name, shape, dtype) or
+    None for an output the call does not have; each given tensor must be dense, of that shape and dtype, on `device`."""
+    if out is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise Mi355Error('%s: the outputs would be allocated during graph capture; run one eager call first' % who)
+        out = tuple(None if s is None else torch.empty(s[1], dtype=s[2], device=device) for s in specs)
+    if len(out) != len(specs):
+        raise Mi355Error('%s: out must hold %d tensors, got %d' % (who, len(specs), len(out)))
+    for t, s in zip(out, specs):
+        if (t is None) != (s is None):
+            raise Mi355Error('%s: out has %s where the call %s' % (who, 'nothing' if t is None else 'a tensor',
+                                                                    'writes ' + s[0] if s is not None else 'writes nothing'))
+        if t is None:
+            continue
+        _chk_dev(t)
+        if t.dtype != s[2] or tuple(t.shape) != tuple(s[1]) or not t.is_contiguous() or t.device != device:
+            raise Mi355Error('%s: %s must be a dense %s tensor of shape %s on %s, got %s %s strides %s on %s'
+                             % (who, s[0], s[2], tuple(s[1]), device, t.dtype, tuple(t.shape), t.stride(), t.device))
+    return out
+
+
+def peak_prob(hm, beta=1.0, out=None):
+    """(idx int32 (B, K), xy fp32 (B, K, 2), p fp32 (B, K)) of the heat-maps hm (B, K, H, W), dense fp32: mi355_argmax2d's index and
+    coordinates and the peak of softmax(beta * hm) per map (mi355_peak_prob); p is NaN for a map that holds a NaN or an inf.
+    `out`: that triple, written in place; allocated only when not given, and never during graph capture."""
+    who = 'peak_prob'
+    _dense_f32(who, 'hm', hm)
+    if hm.dim() != 4 or hm.numel() == 0:
+        raise Mi355Error('%s: hm must be a non-empty (B, K, H, W) batch of heat-maps, got %s' % (who, tuple(hm.shape)))
+    B, K, H, W = (int(s) for s in hm.shape)
+    idx, xy, p = _occ_out(who, out, (('idx', (B, K), torch.int32), ('xy', (B, K, 2), torch.float32), ('p', (B, K), torch.float32)), hm.device)
+    call('mi355_peak_prob', ptr(hm), float(beta), ptr(idx), ptr(xy), ptr(p), B * K, H, W, stream_ptr())
+    return idx, xy, p
+
+
+def teacher_select(p, xy=None, u=None, tau=0.0, prob=0.0, n=0, lo=1, hi=1, image_side=1, heatmap_size=(1, 1), gate_in=None, w_in=None,
+                   out=None, stats=None):
+    """The confidence gate and the occlusion boxes of a batch (mi355_teacher_select).  p (B, K): peak_prob's; xy (B, K, 2) in
+    heat-map pixels; u (B, 1 + 2n) uniform draws on the device; gate_in (B, K) optional (the flags of a geometric view); w_in
+    (B, K) or (B, K, 1) optional.  Returns (conf (B, K), w_out (w_in's shape, None without w_in), boxes int32 (B, n, 4) as
+    (x0, y0, x1, y1) in image pixels, count int32 (B,)); boxes and count are None when n == 0 (the gate alone).  `stats`: an
+    optional fp32 tensor of two elements, which receives the mean number of boxes per sample and the mean of conf.  `out`: the
+    quadruple, written in place; allocated only when not given, and never during graph capture."""
+    who = 'teacher_select'
+    _dense_f32(who, 'p', p)
+    if p.dim() != 2 or p.numel() == 0:
+        raise Mi355Error('%s: p must be a non-empty (B, K) tensor, got %s' % (who, tuple(p.shape)))
+    B, K = (int(s) for s in p.shape)
+    n = int(n)
+    if not 0 <= n <= OCC_MAX_BOXES:
+        raise Mi355Error('%s: N=%d boxes per sample, 0..%d' % (who, n, OCC_MAX_BOXES))
+    H, W = _size_hw(heatmap_size)
+    others = [p]
+    for what, t, shape in (('xy', xy, (B, K, 2)), ('u', u, (B, 1 + 2 * n)), ('gate_in', gate_in, (B, K))):
+        if t is None:
+            if n > 0 and what != 'gate_in':
+                raise Mi355Error('%s: %s is needed to draw boxes (N=%d)' % (who, what, n))
+            continue
+        _dense_f32(who, what, t)
+        if tuple(t.shape) != shape:
+            raise Mi355Error('%s: %s has shape %s, the launch indexes %s' % (who, what, tuple(t.shape), shape))
+        others.append(t)
+    if w_in is not None:
+        _dense_f32(who, 'w_in', w_in)
+        if w_in.numel() != B * K or w_in.shape[0] != B:
+            raise Mi355Error('%s: w_in %s for %d x %d maps' % (who, tuple(w_in.shape), B, K))
+        others.append(w_in)
+    if stats is not None:
+        _dense_f32(who, 'stats', stats)
+        _chk_room('%s stats' % who, stats, 2)
+        others.append(stats)
+    conf, w_out, boxes, count = _occ_out(who, out, (('conf', (B, K), torch.float32),
+                                                    None if w_in is None else ('w_out', tuple(w_in.shape), torch.float32),
+                                                    None if n == 0 else ('boxes', (B, n, 4), torch.int32),
+                                                    None if n == 0 else ('count', (B,), torch.int32)), p.device)
+    if any(t.device != p.device for t in others):
+        raise Mi355Error('%s: the operands live on different devices' % who)
+    call('mi355_teacher_select', ptr(p), ptr(xy) if n else 0, ptr(gate_in), ptr(w_in), ptr(u) if n else 0, float(tau), float(prob), n,
+         int(lo), int(hi), int(image_side), H, W, ptr(conf), ptr(w_out), ptr(boxes), ptr(count), ptr(stats), B, K, stream_ptr())
+    return conf, w_out, boxes, count
+
+
+def occlude_images(x, boxes, out=None):
+    """x (B, C, H, W), dense fp32, with every pixel inside any box of its sample set to +0.0 in all channels; every other word
+    is copied bit for bit (mi355_occlude_images).  boxes: int32 (B, N, 4) on the device, (x0, y0, x1, y1) half-open, N <= 8.  x is
+    only read.  `out` is allocated only when not given, and never during graph capture."""
+    who = 'occlude_images'
+    _dense_f32(who, 'x', x)
+    if x.dim() != 4 or x.numel() == 0:
+        raise Mi355Error('%s: x must be a non-empty (B, C, H, W) batch, got %s' % (who, tuple(x.shape)))
+    B, C, H, W = (int(s) for s in x.shape)
+    _chk_dev(boxes)
+    if boxes.dtype != torch.int32 or boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 4 or not boxes.is_contiguous():
+        raise Mi355Error('%s: boxes must be a dense int32 (%d, N, 4) tensor, got %s %s strides %s' % (who, B, boxes.dtype, tuple(boxes.shape), boxes.stride()))
+    N = int(boxes.shape[1])
+    if N > OCC_MAX_BOXES:
+        raise Mi355Error('%s: N=%d boxes per sample, 0..%d' % (who, N, OCC_MAX_BOXES))
+    out, = _occ_out(who, None if out is None else (out,), (('out', (B, C, H, W), torch.float32),), x.device)
+    if boxes.device != x.device:
+        raise Mi355Error('%s: the operands live on different devices' % who)
+    call('mi355_occlude_images', ptr(x), ptr(boxes) if N else 0, N, ptr(out), B, C, H, W, stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------- MMD alignment (csrc/mmd.hip)
 MMD_MAX_ROWS, MMD_MAX_KERNELS = 256, 8
 _mmd_ws = {}

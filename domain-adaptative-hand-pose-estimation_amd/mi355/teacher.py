@@ -155,6 +155,141 @@ class GeometricView:
         return ops.affine_unwarp_heatmaps(y, self.recs, self.margin, w_in=w_in, out=out)
 
 
+class KeypointOcclusion:
+    """What ``DAStep(occlude=...)`` takes: the student's view of the target batch with a square patch around up to ``n`` of the key
+    points the teacher is sure of set to the data-set mean (0 in normalised space), with probability ``prob`` per sample (the
+    adaptive occlusion of Kim et al., ECCV 2022; the patch rule is this project's -- PAPERS.md).  ``size`` = (lo, hi) are the
+    smallest and the largest side of a patch as fractions of the image side.  A joint is a candidate when the peak of
+    ``softmax(beta * y)`` of the teacher's map reaches the step's ``teacher_conf`` (and, under a geometric view, the map is valid,
+    and its weight is positive).  ``select(y, ...)`` is ``mi355_peak_prob`` + ``mi355_teacher_select``, ``apply(x)``
+    ``mi355_occlude_images``; with ``n = 0`` it only gates (``DAStep(teacher_conf=...)`` without occlusion).
+
+    The draw table lives in device memory at a fixed address and is written from the host before the iteration (``draw``), from an
+    RNG state this object owns -- seeded from ``seed`` and ``rank``; the global RNG is not advanced.  The peaks, the flags, the
+    boxes, the counts and the occluded batch live at fixed addresses too, keyed by the signature of the operands.
+    ``state_dict()`` is what the epoch checkpoint keeps as ``occlude_state``.  Every default is a placeholder: its effect on
+    convergence has not been measured."""
+
+    def __init__(self, prob=0.5, n=1, size=(0.08, 0.16), beta=1.0, seed=0, rank=0):
+        import math
+        lo, hi = (float(v) for v in size)
+        if not (isinstance(prob, (int, float)) and 0.0 <= prob <= 1.0):
+            raise ValueError('KeypointOcclusion: prob must lie in 0 .. 1, got %r' % (prob,))
+        if isinstance(n, bool) or int(n) != n or not 0 <= n <= ops.OCC_MAX_BOXES:
+            raise ValueError('KeypointOcclusion: n must be a whole number in 0 .. %d, got %r' % (ops.OCC_MAX_BOXES, n))
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi <= 1.0):
+            raise ValueError('KeypointOcclusion: the size range is given as fractions of the image side, 0 < lo <= hi <= 1, got %r' % (size,))
+        if not (math.isfinite(beta) and beta > 0.0):
+            raise ValueError('KeypointOcclusion: beta must be finite and positive, got %r' % (beta,))
+        self.prob, self.n, self.size, self.beta = float(prob), int(n), (lo, hi), float(beta)
+        self.seed, self.rank = int(seed or 0), int(rank)
+        self._rng = self._seeded(0)
+        self.draws = 0
+        self.u = None                    # (B, 1 + 2n) fp32 on the device, fixed address
+        self.u_host = None               # the table of the last draw
+        self.stats = None                # two fp32 on the device: mean boxes per sample, mean of conf
+        self.p = self.xy = self.conf = self.w_out = self.boxes = self.count = self.x_occ = None
+        self._bufs = {}
+
+    def sides(self, S):
+        """(lo, hi) in pixels of an image of side S: the fractions rounded to whole pixels, at least one pixel."""
+        lo, hi = (max(1, min(int(S), int(round(f * S)))) for f in self.size)
+        return lo, max(lo, hi)
+
+    # ------------------------------------------------------------ draws
+    def draw(self, B=None, device=None):
+        """Draw the table of the coming iteration and write it to the device (host work: outside graph capture).  Returns the
+        (B, 1 + 2n) float32 draws; nothing is drawn with n = 0."""
+        if self.n == 0:
+            return None
+        if self.u is None or (B is not None and self.u.shape[0] != int(B)):
+            if B is None:
+                raise RuntimeError('KeypointOcclusion: run one eager iteration before replaying graphs')
+            if torch.device(device).type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise Mi355Error('KeypointOcclusion: the draw table would be allocated during graph capture; run one eager iteration first')
+            self.u = torch.zeros(int(B), 1 + 2 * self.n, dtype=torch.float32, device=device)
+        with torch.random.fork_rng(devices=[]):          # the global CPU generator is put back as it was
+            torch.set_rng_state(self._rng)
+            u = torch.rand(tuple(self.u.shape), dtype=torch.float32)      # in [0, 1): at most 1 - 2^-24
+            self._rng = torch.get_rng_state()
+        self.draws += 1
+        self.u_host = u
+        self.u.copy_(u, non_blocking=True)
+        return u
+
+    def _seeded(self, draws):
+        """The generator state of a rank that starts (draws = 0) or joins a resumed run whose checkpoint holds another rank's state."""
+        return torch.Generator().manual_seed(self.seed * 1000003 + 7927 * self.rank + 41 + 104743 * int(draws)).get_state()
+
+    def state_dict(self):
+        """The RNG state and the number of draws so far, what the run goes on from; `ranges` = (prob, n, size, beta), which
+        load_state_dict compares with this object's; `u`, the last table (a CPU copy), is a record for whoever reads the checkpoint
+        and is not read back: the next draw replaces it."""
+        return {'rng_state': self._rng.clone(), 'draws': self.draws, 'rank': self.rank,
+                'ranges': (self.prob, self.n, self.size, self.beta),
+                'u': None if self.u_host is None else self.u_host.clone()}
+
+    def load_state_dict(self, state):
+        """Go on where the saved run was.  The checkpoint is rank 0's: another rank takes the number of draws and a state seeded
+        from (seed, rank, draws), so that the ranks keep drawing different boxes.  A checkpoint written with another prob, n, size
+        or beta is loaded with a warning: the run goes on, but not as the saved one would have (another n is another table shape,
+        so other draws from the same RNG state)."""
+        saved, mine = state.get('ranges'), (self.prob, self.n, self.size, self.beta)
+        if saved is not None and (float(saved[0]), int(saved[1]), tuple(float(v) for v in saved[2]), float(saved[3])) != mine:
+            import warnings
+            warnings.warn('KeypointOcclusion: the checkpoint was written with (prob, n, size, beta) = %r, this run has %r: the resumed '
+                          'run will not draw the boxes the saved run would have' % (tuple(saved), mine))
+        self.draws = int(state.get('draws', 0))
+        if int(state.get('rank', 0)) == self.rank:
+            self._rng = state['rng_state'].clone().to(torch.uint8).cpu()
+        else:
+            self._rng = self._seeded(self.draws)
+
+    # ------------------------------------------------------------ the three launches
+    def _buffers(self, key, specs, device):
+        got = self._bufs.get(key[0])
+        if got is None or got[0] != key:
+            if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise Mi355Error('KeypointOcclusion: the %s buffers would be allocated during graph capture; run one eager iteration first' % key[0])
+            got = self._bufs[key[0]] = (key, tuple(None if s is None else torch.empty(s[0], dtype=s[1], device=device) for s in specs))
+        return got[1]
+
+    def select(self, y, tau, image_side, gate_in=None, w_in=None):
+        """The gate and the boxes from the teacher's heat-maps y (B, K, H, W): sets and returns (conf, w_out); `boxes` and `count`
+        are kept for apply().  tau: the confidence threshold; gate_in: the flags of a geometric view; w_in: the joint weights."""
+        f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+        y = f32(y.detach())
+        B, K = y.shape[:2]
+        if w_in is not None:
+            w_in = f32(w_in)
+        if gate_in is not None:
+            gate_in = f32(gate_in)
+        n = self.n
+        if n > 0 and (self.u is None or self.u.shape[0] != B):
+            raise Mi355Error('KeypointOcclusion: no draws for a batch of %d: draw() first' % B)
+        i32 = torch.int32
+        key = ('select', tuple(y.shape), None if w_in is None else tuple(w_in.shape), n)
+        bufs = self._buffers(key, (((B, K), i32), ((B, K, 2), torch.float32), ((B, K), torch.float32), ((B, K), torch.float32),
+                                   None if w_in is None else (tuple(w_in.shape), torch.float32),
+                                   None if n == 0 else ((B, n, 4), i32), None if n == 0 else ((B,), i32), ((2,), torch.float32)), y.device)
+        idx, self.xy, self.p, conf, w_out, boxes, count, self.stats = bufs
+        ops.peak_prob(y, self.beta, out=(idx, self.xy, self.p))
+        lo, hi = self.sides(image_side) if n > 0 else (1, 1)
+        self.conf, self.w_out, self.boxes, self.count = ops.teacher_select(
+            self.p, self.xy, self.u if n > 0 else None, tau, self.prob, n, lo, hi, int(image_side) if n > 0 else 1, tuple(y.shape[-2:]),
+            gate_in=gate_in, w_in=w_in, out=(conf, w_out, boxes, count), stats=self.stats)
+        return self.conf, self.w_out
+
+    def apply(self, x):
+        """The student's input: x (B, C, S, S) with the boxes of the last select() blanked, in a buffer of this object."""
+        if self.boxes is None:
+            raise Mi355Error('KeypointOcclusion: no boxes: select() first (n = %d)' % self.n)
+        x = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
+        out, = self._buffers(('apply', tuple(x.shape)), ((tuple(x.shape), torch.float32),), x.device)
+        self.x_occ = ops.occlude_images(x, self.boxes, out=out)
+        return self.x_occ
+
+
 class InIterationTeacher:
     def __init__(self, ema, view=None):
         self.ema, self.model = ema, ema.model_ema
@@ -377,7 +512,7 @@ class MeanTeacher:
         y_ema = step.teacher_forward(self.teacher, batch)
         if not torch.cuda.is_current_stream_capturing():
             self.sync(y_t_grad.shape)
-        # with a geometric view the maps whose peak the teacher did not see inside its frame are left out (weight 0); weight_t
-        # stays ignored, as in the reference's mt_loss
-        return self.loss(y_t_grad, y_ema, wmap=self.teacher.valid if self.teacher.view is not None else None), \
+        # with a geometric view the maps whose peak the teacher did not see inside its frame are left out (weight 0), with
+        # teacher_conf > 0 those the teacher is not sure of; weight_t stays ignored, as in the reference's mt_loss
+        return self.loss(y_t_grad, y_ema, wmap=step.teacher_map_weights(self.teacher)), \
             {'y_t_ema': y_ema}                                   # (kept: step M's teacher labels reuse this forward)

@@ -21,7 +21,10 @@ the reference), ``--fda {off,on}`` with ``--fda-beta`` (step A sees the source b
 Fourier Domain Adaptation, not in the reference), ``--mt-view {same,geom}`` with ``--view-rot`` / ``--view-scale`` / ``--view-shift`` /
 ``--view-margin`` (the EMA teacher sees the target batch rotated, scaled and shifted per sample and its heat-maps are mapped back
 before they are compared: geometric consistency, not in the reference), ``--bone-loss {off,on}`` with ``--bone-weight`` / ``--bone-margin`` / ``--bone-momentum`` / ``--bone-beta`` / ``--bone-eps``
-(a bone-ratio skeleton prior on the target prediction against running statistics of the source annotations; not in the reference), ``--clip-grad-norm FLOAT``
+(a bone-ratio skeleton prior on the target prediction against running statistics of the source annotations; not in the reference),
+``--occlude {off,keypoint}`` with ``--occlude-p`` / ``--occlude-n`` / ``--occlude-size`` and ``--teacher-conf`` / ``--conf-beta`` (the student sees the
+target batch with a patch around key points the EMA teacher is sure of blanked, and the teacher-driven terms leave out the maps
+the teacher is not sure of: adaptive occlusion, not in the reference), ``--clip-grad-norm FLOAT``
 (global gradient-norm clipping of each of the three updates with a non-finite step guard, on the device; not in the reference), ``--metrics {pck,full}`` with ``--decode {argmax,upsample,quarter,taylor}`` and
 ``--auc-max-px`` (validation also reports key points in image pixels: end-point error, PCK curve and AUC; the reference's
 unused ``compute_uv_from_heatmaps2``, ``accuracy_2d`` and the curve of ``accuracy_3d``, utils/keypoint_detection.py:95-205; the
@@ -66,7 +69,7 @@ from mi355 import ops as _ops
 from mi355.ops import FDA_MAX_B, fda_band
 from mi355.da_step import CoordRegression, KinematicPrior, CrossDomainMixup, FourierStyle, JointFeatureAlign, MMDAlign, PrototypeAlign, build_training, broadcast_module, _allreduce_mean
 from mi355.optim import EMATeacher, GradClipper, make_optimizer
-from mi355.teacher import GeometricView, MeanTeacher
+from mi355.teacher import GeometricView, KeypointOcclusion, MeanTeacher
 from uda.model.loss import JointsKLLoss, check_blend_weight, check_positive, check_whole
 from uda.model.pose_resnet2 import Upsampling, PoseResNet
 from uda.model.regda_7 import MainOutput, PoseResNetx9 as RegDAPoseResNetx1, PoseResNetx10 as RegDAPoseResNetx2
@@ -182,7 +185,8 @@ def main(args):
     print("Source test:", len(val_source_loader)); print("Target test:", len(val_target_loader))
     train_source_iter, train_target_iter = ForeverDataIterator(train_source_loader), ForeverDataIterator(train_target_loader)
     # who reads the teacher's view of the target batch (meta['image_ema']): the consistency term, and mixup labelled by the teacher
-    want_ema = args.mt_loss == 'on' or (args.mixup == 'on' and args.mixup_labels == 'teacher') or args.coord_loss == 'both'
+    want_ema = args.mt_loss == 'on' or (args.mixup == 'on' and args.mixup_labels == 'teacher') or args.coord_loss == 'both' or \
+        args.occlude == 'keypoint'
     if args.device_augment and not args.synthetic:
         # packed sources -> HBM, augmentation and heat-map labels on the GPU (mi355.augment, utils.labels)
         dev_aug = lambda it, ema=False: DeviceAugmentIterator(it, device, args.image_size, args.heatmap_size, want_ema=ema)
@@ -241,6 +245,13 @@ def main(args):
         # the teacher's forward of the iteration runs on another view of the target batch (mi355.teacher.GeometricView)
         step.view = GeometricView(rot_deg=args.view_rot, scale=tuple(args.view_scale), shift=args.view_shift, margin=args.view_margin,
                                   seed=args.seed, rank=RANK)
+    if args.occlude == 'keypoint':
+        # the student's forwards of the target batch read it with patches around confident teacher key points blanked
+        # (mi355.teacher.KeypointOcclusion); the teacher's forward moves to the head of step B
+        step.occlude = KeypointOcclusion(prob=args.occlude_p, n=args.occlude_n, size=tuple(args.occlude_size), beta=args.conf_beta,
+                                         seed=args.seed, rank=RANK)
+    # a teacher map counts for the teacher-driven terms only when the peak of its softmax reaches --teacher-conf (0: no gate)
+    step.teacher_conf, step.conf_beta = float(args.teacher_conf), float(args.conf_beta)
     if args.fda == 'on':
         # step A sees the source batch in the style of the target batch (mi355.da_step.FourierStyle); no state, nothing to checkpoint
         step.fda = FourierStyle(beta=args.fda_beta)
@@ -401,7 +412,11 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
         mt.set_epoch(epoch)                              # m and k are functions of the epoch (train1.py:351-353)
     keys = (['coord'] if coord is not None else []) + [t.key for t in terms] + (['mix'] if mixup is not None else [])
     names, fmts = names + ['Loss (%s)' % k for k in keys], fmts + [':.2e'] * len(keys)
-    clip, n_fixed = step.clip, 9 + len(keys)
+    # device scalars of the occlusion and the confidence gate: mean boxes per sample, share of confident teacher maps
+    occluding = getattr(step, 'occlude', None) is not None and step.occlude.n > 0
+    gauges = ([('Occl', 'occ_boxes')] if occluding else []) + ([('Conf', 'conf_share')] if occluding or getattr(step, 'teacher_conf', 0.0) > 0 else [])
+    names, fmts = names + [n for n, _ in gauges], fmts + [':4.2f'] * len(gauges)
+    clip, n_fixed = step.clip, 9 + len(keys) + len(gauges)
     if clip is not None:                                 # the gradient norms of the updates, read when a line is printed
         if mixup is not None:
             clip.ensure_slot('m')                        # update M's record
@@ -416,7 +431,7 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
         batch = dict(x_s=to(x_s), label_s=to(label_s), w_s=to(weight_s), x_t=to(x_t), w_t=to(weight_t), label_t=to(label_t))
         if coord is not None or getattr(step, 'bone', None) is not None:   # the un-quantised source key points, image pixels -> heat-map pixels
             batch['kp_s'] = source_keypoints(meta_s, args.image_size, args.heatmap_size, device)
-        if mt is not None or (mixup is not None and mixup.labels == 'teacher') or (coord is not None and coord.target == 'teacher'):   # x_t_ema = meta_t['image_ema'] (train1.py:364); synthetic images have no augmentation
+        if mt is not None or (mixup is not None and mixup.labels == 'teacher') or (coord is not None and coord.target == 'teacher') or occluding:   # x_t_ema = meta_t['image_ema'] (train1.py:364); synthetic images have no augmentation
             batch['x_t_ema'] = batch['x_t'] if args.synthetic else to(meta_t['image_ema'])
         meters[1].update(time.time() - end)
         # HIP-graph replay once this process has run three eager iterations (whatever epoch it resumed at).  With several
@@ -453,6 +468,9 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
                 a, c = _pck(out[k]); m.update(a, c)
             for m, k in zip(meters[9:], keys):
                 m.update(float(out['loss_' + k]), args.batch_size)
+            for m, (_, k) in zip(meters[9 + len(keys):], gauges):
+                if k in out:                             # (conf_share appears with the first teacher forward that is gated)
+                    m.update(float(out[k]), args.batch_size)
             if clip is not None:
                 norms = clip.read()[0]
                 for m, s in zip(meters[n_fixed:], clip.SLOTS):
@@ -769,6 +787,31 @@ _OPTIONS = [
                            '(positive; a placeholder, as the weight)')),
     (('--bone-eps',), dict(default=1e-4, type=float, metavar='FLOAT', help='added to the running variance under the square root (positive; '
                           'a placeholder, as the weight)')),
+    (('--occlude',), dict(default='off', choices=['off', 'keypoint'], help="adaptive key-point occlusion of the student's target input "
+                         "(Kim et al. 2022; not in the reference): the EMA teacher's forward moves to the head of step B; with "
+                         "probability --occlude-p per sample, square patches around up to --occlude-n key points the teacher is sure "
+                         "of (peak of softmax(--conf-beta * y) >= --teacher-conf; valid under --mt-view geom; weight > 0) are set to the "
+                         "data-set mean in the copy of the target batch the student's forwards read -- the teacher, step M's blend and "
+                         "--fda keep the loader's images, and the training 'Acc (t)' meter then describes the occluded input.  The boxes "
+                         "come from an RNG state of their own, seeded from --seed and the rank, kept in the epoch checkpoint "
+                         "(occlude_state); needs --ema-update const|warmup; 'off': nothing is launched, nothing is drawn")),
+    (('--occlude-p',), dict(default=0.5, type=float, metavar='FLOAT', help='--occlude keypoint: probability that a sample is occluded at all '
+                           '(0 .. 1; the default is a placeholder: its effect on convergence has not been measured, and cannot be '
+                           'without the data sets)')),
+    (('--occlude-n',), dict(default=1, type=int, metavar='N', help='--occlude keypoint: at most N patches per occluded sample, around '
+                           'distinct key points (1 .. 8; a placeholder, as the probability)')),
+    (('--occlude-size',), dict(default=[0.08, 0.16], type=float, nargs=2, metavar=('LO', 'HI'), help='--occlude keypoint: the side of a patch '
+                              'is drawn uniformly from LO .. HI times --image-size, in whole pixels (0 < LO <= HI <= 1; a placeholder, as '
+                              'the probability)')),
+    (('--teacher-conf',), dict(default=0.0, type=float, metavar='TAU', help="a teacher map counts for --mt-loss, --coord-loss both and "
+                              "--mixup-labels teacher only when the peak of softmax(--conf-beta * y) reaches TAU (the flags multiply in "
+                              "where the flags of --mt-view geom do); also the candidate threshold of --occlude keypoint.  A perfect "
+                              "sigma = 2 label has a peak of 1 / (8 pi) = 0.0398.  0: no gate, nothing is launched (the default; any "
+                              "other value is a placeholder: its effect on convergence has not been measured, and cannot be without "
+                              "the data sets)")),
+    (('--conf-beta',), dict(default=1.0, type=float, metavar='FLOAT', help='inverse temperature of the softmax whose peak is the '
+                           "teacher's confidence (positive; 1 = the distribution the KL loss trains the main head towards; a "
+                           'placeholder, as the threshold)')),
     (('--clip-grad-norm',), dict(default=0.0, type=_clip_norm, metavar='FLOAT', help="global gradient-norm clipping with a non-finite "
                                 "step guard: each of the updates A, B, C (M with --mixup on; and the pre-training step) clips over everything it steps, as "
                                 "clip_grad_norm_(those parameters, FLOAT) before the optimizers would, in two launches per update and "
@@ -826,7 +869,30 @@ class _Parser(argparse.ArgumentParser):
                            "--coord-loss both or --mixup on --mixup-labels teacher")
             if getattr(args, 'ema_update', 'off') == 'off':
                 self.error('--mt-view geom needs a moving teacher: add --ema-update const (or warmup)')
+        consumer = getattr(args, 'mt_loss', 'off') == 'on' or getattr(args, 'coord_loss', 'off') == 'both' or \
+            (getattr(args, 'mixup', 'off') == 'on' and getattr(args, 'mixup_labels', 'student') == 'teacher')
+        if getattr(args, 'occlude', 'off') == 'keypoint' and getattr(args, 'ema_update', 'off') == 'off':
+            self.error('--occlude keypoint needs a moving teacher: add --ema-update const (or warmup)')
+        if getattr(args, 'teacher_conf', 0.0) > 0 and not (consumer or getattr(args, 'occlude', 'off') == 'keypoint'):
+            self.error("--teacher-conf gates the teacher's maps, and nothing reads them: add --mt-loss on, --coord-loss both, "
+                       "--mixup on --mixup-labels teacher or --occlude keypoint")
         try:                                             # (the checks the term classes make, under the flags' names)
+            if getattr(args, 'teacher_conf', None) is not None:
+                if not 0.0 <= args.teacher_conf < float('inf'):
+                    raise ValueError('--teacher-conf must be finite and not negative, got %r' % (args.teacher_conf,))
+                if not 0.0 < args.conf_beta < float('inf'):
+                    raise ValueError('--conf-beta must be finite and positive, got %r' % (args.conf_beta,))
+            if getattr(args, 'occlude', 'off') == 'keypoint':
+                lo, hi = args.occlude_size
+                if not 0.0 <= args.occlude_p <= 1.0:
+                    raise ValueError('--occlude-p must lie in 0 .. 1, got %r' % (args.occlude_p,))
+                if not 1 <= args.occlude_n <= 8:
+                    raise ValueError('--occlude-n must lie in 1 .. 8, got %r' % (args.occlude_n,))
+                if not (0.0 < lo <= hi <= 1.0):
+                    raise ValueError('--occlude-size needs 0 < LO <= HI <= 1 (fractions of --image-size), got %r %r' % (lo, hi))
+                if int(args.image_size) % int(getattr(args, 'heatmap_size', 64)) != 0:
+                    raise ValueError('--occlude keypoint needs --image-size to be a multiple of --heatmap-size, got %r and %r'
+                                     % (args.image_size, getattr(args, 'heatmap_size', 64)))
             if getattr(args, 'mt_view', 'same') == 'geom':
                 lo, hi = args.view_scale
                 if not 0.0 <= args.view_rot <= 180.0:

@@ -134,6 +134,17 @@ def soft_argmax(output, beta=1.0):
     return ops.softargmax(output.detach(), beta, 1.0)
 
 
+def peak_confidence(y, beta=1.0):
+    """(xy, p) of heat-maps ``y`` (B, K, H, W), detached: the arg-max (B, K, 2) in heat-map pixels, (x, y), and the peak (B, K) of
+    ``softmax(beta * y)`` over each map (``mi355_peak_prob``) -- the confidence ``DAStep(teacher_conf=...)`` thresholds.  The raw
+    maximum of a map is an unbounded logit; the peak of the softmax lies in (0, 1], and a perfect sigma = 2 label has 1 / (8 pi).
+    A map that holds a NaN or an inf has p = NaN, which passes no threshold."""
+    y = y.detach()
+    y = y if (y.dtype == torch.float32 and y.is_contiguous()) else y.float().contiguous()
+    _, xy, p = ops.peak_prob(y, beta)
+    return xy, p
+
+
 # ---------------------------------------------------------------- bone-ratio skeleton prior (not in the reference)
 # (parent, child) pairs of the 21-joint hand of uda/dataset/keypoint_dataset.py:47-57: the wrist and five chains of four joints
 HAND_BONES = tuple((0 if j % 4 == 1 else j - 1, j) for j in range(1, 21))

@@ -2,7 +2,7 @@
 
 Layout (reference train1.py:248-268 plus additive keys): ``<epoch>.pth`` holds ``model``, ``optimizer_f`` / ``_h`` / ``_h_adv`` and their
 ``lr_scheduler_*``, ``epoch`` and ``args``; additive: the same for ``h_adv2`` / ``h_adv3``, ``gl_iter_num``, ``ema_state``, ``proto_state``,
-``bone_state``, ``mixup_state``, ``view_state`` and -- ``--dtype fp8`` -- ``fp8_state``.  ``model_ema.pth`` beside it holds ``model_ema``.  Every piece is restored into
+``bone_state``, ``mixup_state``, ``view_state``, ``occlude_state`` and -- ``--dtype fp8`` -- ``fp8_state``.  ``model_ema.pth`` beside it holds ``model_ema``.  Every piece is restored into
 objects that have not run an iteration yet: optimizers that are not flat, a teacher without its mirror layout, no graphs.
 """
 import os
@@ -16,7 +16,7 @@ from mi355.optim import check_state_dict_kind
 REFERENCE_KEYS = ('model', 'optimizer_f', 'optimizer_h', 'optimizer_h_adv', 'lr_scheduler_f', 'lr_scheduler_h', 'lr_scheduler_h_adv',
                   'epoch', 'args')
 ADDITIVE_KEYS = ('optimizer_h_adv2', 'optimizer_h_adv3', 'lr_scheduler_h_adv2', 'lr_scheduler_h_adv3', 'gl_iter_num')
-OPTIONAL_KEYS = ('ema_state', 'proto_state', 'bone_state', 'mixup_state', 'view_state', 'fp8_state')      # written when the run has the piece of state
+OPTIONAL_KEYS = ('ema_state', 'proto_state', 'bone_state', 'mixup_state', 'view_state', 'occlude_state', 'fp8_state')      # written when the run has the piece of state
 
 
 def ema_path_beside(path):
@@ -34,6 +34,8 @@ def training_state(epoch, args, model, opts, scheds, step, ema):
         ck_extra['mixup_state'] = step.mixup.state_dict()
     if getattr(step, 'view', None) is not None:
         ck_extra['view_state'] = step.view.state_dict()
+    if getattr(step, 'occlude', None) is not None:
+        ck_extra['occlude_state'] = step.occlude.state_dict()
     fp8 = fp8_state_dict(model) if mi355.fp8_convs() else None
     if fp8 is not None:
         ck_extra['fp8_state'] = fp8                     # the delayed-scaling records of --dtype fp8 (mi355.nn.fp8_state_dict)
@@ -90,6 +92,8 @@ def apply_training_state(ck, path, args, model, model_ema, opts, scheds, step, e
         step.mixup.load_state_dict(ck['mixup_state'])               # the RNG state of the blend coefficients (rank 0's)
     if getattr(step, 'view', None) is not None and 'view_state' in ck:
         step.view.load_state_dict(ck['view_state'])                 # the RNG state of the teacher's geometric views (rank 0's)
+    if getattr(step, 'occlude', None) is not None and 'occlude_state' in ck:
+        step.occlude.load_state_dict(ck['occlude_state'])           # the RNG state of the occlusion boxes (rank 0's)
     if ck.get('fp8_state') is not None and mi355.fp8_convs():
         try:                                         # --dtype fp8: the scaling records, to the layers that owned them
             load_fp8_state_dict(model, ck['fp8_state'], device)

@@ -826,6 +826,45 @@ int mi355_affine_unwarp_heatmaps(const float* y, const mi355_view_rec* recs, flo
 int mi355_mse_heatmap_w(const float* pred, const float* target, const mi355_mse_rec* rec_dev, const float* wmap, float* rows,
                         float* unit_grad, int B, int K, int HW, void* stream);
 
+/* ---------------------------------------------------------------- adaptive occlusion, teacher confidence (csrc/occlude.hip)
+ * The student of a consistency term sees the target image with a patch around a key point the teacher is sure of blanked out,
+ * and the teacher-driven terms weigh a map by whether the teacher is sure of it (Kim et al., "A Unified Framework for Domain
+ * Adaptive Pose Estimation", ECCV 2022; the patch rule is this project's, the paper's is not quoted: PAPERS.md).  The reference has
+ * no such function, so there is no file:line to cite; the semantics are stated here.  Forward only.  No atomics; the same bits on
+ * every run, eagerly and under graph replay.  Dense operands, pointers 4-byte aligned.  Never allocates; capturable.  Every
+ * refusal is MI355_EINVAL before any launch, the message naming the argument.
+ * peak_prob: per map of hm [rows][H][W] fp32, idx[rows] and xy[rows][2] are mi355_argmax2d's bit for bit (first index on ties, a
+ *   NaN counts as the maximum, xy = 0 unless the maximum is > 0) and p[rows] = 1 / s rounded once to fp32, s = the fp64 sum over the
+ *   map of exp((double)v * beta - (double)max * beta) in a fixed order: the peak of softmax(beta * y), this project's stand-in for the paper's
+ *   normalised activation (the main head is trained with a KL against normalised Gaussians, so the raw maximum is an unbounded
+ *   logit; a perfect sigma = 2 label has p = 1 / (8 pi)).  A map that holds a NaN or +-inf has p = NaN.  Forms as mi355_softargmax:
+ *   register-resident at 64 x 64, 32 x 32, 16 x 16 for a 16-byte-aligned hm (the map is read once), the loop form otherwise
+ *   (walked twice).  beta: finite and > 0; H * W below 2^31.
+ * teacher_select: one thread per sample.  pass[b][k] = p >= tau && (gate_in null || gate_in > 0); conf[b][k] = 1.0f or 0.0f (a NaN p
+ *   never passes); with w_in (and w_out; both or neither) w_out = fl(w_in * conf).  N > 0: the candidates of sample b are its joints
+ *   with pass and (w_in null || w_in > 0) in ascending order, m of them.  u[b][1 + 2N] are uniform draws in [0, 1).  u[b][0] >= prob:
+ *   no box.  Otherwise for slot i < min(N, m), with mm = m - i candidates left: j = min(int(fl(u[b][1+2i] * mm)), mm - 1) (fp32
+ *   product, truncated) is taken out of the list; side = min(lo + int(fl(u[b][2+2i] * (hi - lo + 1))), hi); with (x, y) = xy[b][k]
+ *   clamped to the map (NaN -> 0), cx = int(x) * (S / W) + (S / W) / 2, cy = int(y) * (S / H) + (S / H) / 2; the box is
+ *   x0 = cx - side / 2, x1 = x0 + side, likewise in y, clipped to [0, S]: boxes[b][i] = (x0, y0, x1, y1), half-open.  Unused slots
+ *   are (0, 0, 0, 0); count[b] = boxes drawn.  N == 0: gate only (xy, u, boxes, count may be null).  stats (nullable): two floats,
+ *   the mean of count over B and the mean of conf over B * K, from integer sums.  tau finite; prob in [0, 1]; N in 0 ..
+ *   MI355_OCC_MAX_BOXES; 1 <= lo <= hi <= S; S a multiple of H and of W; K up to MI355_OCC_MAX_JOINTS.
+ * occlude_images: out = x [B][C][H][W] with every pixel inside any of the N boxes of its sample (all channels) set to +0.0 -- 0
+ *   is the data-set mean in normalised space -- and every other word copied bit for bit (NaN payloads, -0.0).  x is only read,
+ *   every word of out is written exactly once, out is never read.  boxes [B][N][4] int32 (x0, y0, x1, y1), half-open, any values
+ *   (they are only compared with); a sample's records are read once per workgroup.  A stream: 16-byte accesses when W % 4 == 0
+ *   and x and out are 16-byte aligned, 4-byte otherwise.  out must not overlap x or boxes; C * H * W below 2^31. */
+#define MI355_OCC_MAX_BOXES 8
+#define MI355_OCC_MAX_JOINTS 64
+#define MI355_OCC_MAX_BATCH 65535
+#define MI355_OCC_MAX_SIDE 4096
+int mi355_peak_prob(const float* hm, float beta, int32_t* idx, float* xy, float* p, int rows, int H, int W, void* stream);
+int mi355_teacher_select(const float* p, const float* xy, const float* gate_in, const float* w_in, const float* u, float tau,
+                         float prob, int N, int lo, int hi, int S, int H, int W, float* conf, float* w_out, int32_t* boxes,
+                         int32_t* count, float* stats, int B, int K, void* stream);
+int mi355_occlude_images(const float* x, const int32_t* boxes, int N, float* out, int B, int C, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
