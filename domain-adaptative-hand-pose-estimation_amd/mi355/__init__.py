@@ -154,6 +154,8 @@ SIGNATURES = {
     'mi355_peak_prob': (_I, [_P, _F, _P, _P, _P, _I, _I, _I, _P]),
     'mi355_teacher_select': (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     'mi355_occlude_images': (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'mi355_hand_rec_size': (_Z, []),
+    'mi355_render_hands': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
     'mi355_augment_workspace': (_Z, [_I, _I]),
     'mi355_augment': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'mi355_resize_normalize': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P]),

@@ -7,6 +7,8 @@ are contiguous NCHW fp32.  Nothing here falls back to torch math.
 import ctypes
 import math
 
+import numpy as _np
+
 import torch
 
 from . import (BnBwdSrc, ConvDesc, FP8, Mi355Error, WgradItem, call, compute_dtype, dtype_code, load, ptr, stream_ptr, workspace)
@@ -1696,6 +1698,70 @@ def occlude_images(x, boxes, out=None):
     if boxes.device != x.device:
         raise Mi355Error('%s: the operands live on different devices' % who)
     call('mi355_occlude_images', ptr(x), ptr(boxes) if N else 0, N, ptr(out), B, C, H, W, stream_ptr())
+    return out
+
+
+# ---------------------------------------------------------------- rendered hands (csrc/render.hip)
+# include/mi355pose.h mi355_hand_rec, field for field
+HAND_REC_DTYPE = _np.dtype([('jx', '<f4', 21), ('jy', '<f4', 21), ('jz', '<f4', 21), ('radius', '<f4', 20), ('skin', '<f4', 3),
+                            ('light', '<f4', 3), ('ambient', '<f4'), ('bg0', '<f4', 3), ('bg1', '<f4', 3), ('grad', '<f4', 2),
+                            ('grad_off', '<f4'), ('noise_amp', '<f4'), ('noise_inv_cell', '<f4'), ('noise_seed', '<u4'),
+                            ('occ_a', '<f4', 2), ('occ_b', '<f4', 2), ('occ_r', '<f4'), ('occ_z', '<f4'), ('occ_col', '<f4', 3),
+                            ('sensor_sigma', '<f4'), ('sensor_seed', '<u4'), ('gain', '<f4', 3), ('bias', '<f4', 3), ('reserved', '<u4')])
+assert HAND_REC_DTYPE.itemsize == 480
+RENDER_SIDES = tuple(range(16, 513, 16))
+
+
+def render_norm(mean=None, std=None):
+    """(mean3, inv_std3) as the fp32 values the kernel subtracts and multiplies by: 1 / std formed in double, rounded once."""
+    mean = _np.asarray(MEAN if mean is None else mean, dtype=_np.float64)
+    std = _np.asarray(STD if std is None else std, dtype=_np.float64)
+    if mean.shape != (3,) or std.shape != (3,) or not (_np.isfinite(mean).all() and _np.isfinite(std).all() and (std > 0).all()):
+        raise Mi355Error('render_hands: mean and std must be three finite values each, std > 0')
+    return mean.astype(_np.float32), (1.0 / std).astype(_np.float32)
+
+
+def render_hands(recs, image_size, out=None, out_ema=None, ids=None, mean=None, std=None):
+    """The images of a batch of hand records (mi355_render_hands): recs is a dense device tensor holding B records of
+    HAND_REC_DTYPE (any element type; B = its bytes / 480), image_size = S, a multiple of 16 from 16 to 512.  Returns `out`
+    (B, 3, S, S) fp32, normalised with mean / std (the loaders' by default); out_ema, when given, receives the same scene with gain 1,
+    bias 0 and no sensor noise, and ids (B, S, S) uint8 the front-most primitive at each pixel centre (0 background, 1 .. 20 bone
+    index + 1, 21 the occluder).  `out` is allocated only when not given, and never during graph capture.  Every check raises
+    before anything is launched."""
+    who = 'render_hands'
+    _chk_dev(recs, out, out_ema, ids)
+    S = int(image_size)
+    if S != image_size or S not in RENDER_SIDES:
+        raise Mi355Error('%s: image_size=%r is not a multiple of 16 from 16 to 512' % (who, image_size))
+    nbytes = recs.numel() * recs.element_size()
+    if not recs.is_contiguous() or nbytes == 0 or nbytes % HAND_REC_DTYPE.itemsize:
+        raise Mi355Error('%s: recs must be a dense tensor of whole %d-byte records, got %s %s strides %s' % (
+            who, HAND_REC_DTYPE.itemsize, recs.dtype, tuple(recs.shape), recs.stride()))
+    B = nbytes // HAND_REC_DTYPE.itemsize
+    if out is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise Mi355Error('%s: out would be allocated during graph capture; run one eager call first' % who)
+        out = torch.empty((B, 3, S, S), dtype=torch.float32, device=recs.device)
+    for what, t, shape, dt, align in (('recs', recs, None, None, 16), ('out', out, (B, 3, S, S), torch.float32, 16),
+                                      ('out_ema', out_ema, (B, 3, S, S), torch.float32, 16), ('ids', ids, (B, S, S), torch.uint8, 4)):
+        if t is None:
+            continue
+        if shape is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise Mi355Error('%s: %s must be a dense %s tensor of shape %s, got %s %s strides %s' % (who, what, dt, shape, t.dtype, tuple(t.shape), t.stride()))
+        if t.data_ptr() % align:
+            raise Mi355Error('%s: %s must be %d-byte aligned (offset %d)' % (who, what, align, t.data_ptr() % align))
+        if t.device != recs.device:
+            raise Mi355Error('%s: the operands live on different devices' % who)
+    spans = [(what, t.data_ptr(), t.numel() * t.element_size()) for what, t in (('recs', recs), ('out', out), ('out_ema', out_ema), ('ids', ids))
+             if t is not None]
+    for u in range(len(spans)):
+        for v in range(u + 1, len(spans)):
+            (na, pa, la), (nb, pb, lb) = spans[u], spans[v]
+            if pa < pb + lb and pb < pa + la:
+                raise Mi355Error('%s: %s and %s overlap' % (who, na, nb))
+    m3, s3 = render_norm(mean, std)
+    fl = ctypes.c_float * 3
+    call('mi355_render_hands', ptr(recs), ptr(out), ptr(out_ema), ptr(ids), B, S, fl(*m3.tolist()), fl(*s3.tolist()), stream_ptr())
     return out
 
 

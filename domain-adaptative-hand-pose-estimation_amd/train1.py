@@ -2,7 +2,8 @@
 """Domain-adaptive hand-pose training on the MI355X kernels — same command line, log / checkpoint layout and
 training schedule as the reference's ``train1.py`` (main :37-275, pretrain :278-325, train :328-492,
 validate :495-536, CLI :591-675).  Additive flags: ``--synthetic`` (seeded synthetic data instead of the
-out-of-scope CPU dataset layer), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--mx-eval``, ``--no-graph``, ``--device-augment`` (the training
+out-of-scope CPU dataset layer), ``--synthetic-hands`` with ``--render-gap`` / ``--render-train-size`` / ``--render-val-size`` (a rendered
+two-domain hand data set drawn on the GPU from per-sample records, with exact key points: utils/rendered_dataset.py), ``--dtype {bf16,f32,fp8,mxfp8}``, ``--mx-eval``, ``--no-graph``, ``--device-augment`` (the training
 augmentation chain, the validation resize and the labels of both on the GPU), ``--ema-update {off,const,warmup}`` (keep the
 EMA teacher ``model_ema`` up to date: the reference's commented-out call at train1.py:461), ``--mt-loss {off,on}`` with
 ``--mt-weight`` / ``--mt-k`` (the mean-teacher consistency term on the target batch: the reference's unused ``x_t_ema``, ``m`` and
@@ -118,6 +119,9 @@ def replicas_in_sync(model):
     return float(cs)
 
 
+RENDERED_LABEL_EPSILON = 1e-12        # JointsKLLoss.epsilon under --synthetic-hands (main(): labels of joints outside the frame)
+
+
 def build_datasets(args):
     image_size, heatmap_size = (args.image_size,) * 2, (args.heatmap_size,) * 2
     if args.synthetic:
@@ -125,6 +129,12 @@ def build_datasets(args):
         mk = lambda n, seed: SyntheticHand21(n, image_size, heatmap_size, seed=seed)
         n = args.batch_size * max(args.iters_per_epoch, 1)
         return mk(n, 11), mk(4 * args.batch_size, 12), mk(n, 13), mk(4 * args.batch_size, 14)
+    if getattr(args, 'synthetic_hands', False):
+        # rendered hands: 'cg' source and 'photo' target, both validation sets labelled (as H3D's is), seeds disjoint from training
+        from utils.rendered_dataset import RenderedHand21
+        mk = lambda n, seed, domain: RenderedHand21(n, image_size, heatmap_size, seed=seed, domain=domain, gap=args.render_gap)
+        return (mk(args.render_train_size, 21, 'cg'), mk(args.render_val_size, 22, 'cg'),
+                mk(args.render_train_size, 23, 'photo'), mk(args.render_val_size, 24, 'photo'))
     import uda.dataset as datasets                   # RHD / H3D / STB readers + key-point aware augmentation (PIL + numpy)
     import uda.dataset.keypoint_detection as T
     normalize = T.Normalize([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])
@@ -151,6 +161,9 @@ def make_loader(ds, args, train):
     ragged = getattr(args, 'device_augment', False) and not args.synthetic
     collate = ragged_collate if ragged else None
     val_workers = args.workers if ragged else 0
+    if getattr(args, 'synthetic_hands', False):          # records, packed per batch (utils.data.record_collate); the GPU draws them
+        from utils.data import record_collate
+        collate, val_workers = record_collate, args.workers
     if WORLD == 1:
         return DataLoader(ds, batch_size=args.batch_size, shuffle=train, num_workers=args.workers if train else val_workers,
                           pin_memory=True, drop_last=train, collate_fn=collate)
@@ -187,7 +200,13 @@ def main(args):
     # who reads the teacher's view of the target batch (meta['image_ema']): the consistency term, and mixup labelled by the teacher
     want_ema = args.mt_loss == 'on' or (args.mixup == 'on' and args.mixup_labels == 'teacher') or args.coord_loss == 'both' or \
         args.occlude == 'keypoint'
-    if args.device_augment and not args.synthetic:
+    if args.synthetic_hands:
+        # records -> HBM, the images (with --mt-loss etc. also the teacher's meta['image_ema']) and the labels on the GPU
+        from utils.data import RenderedHandIterator
+        rend = lambda it, ema=False, kp=False: RenderedHandIterator(it, device, args.image_size, args.heatmap_size, want_ema=ema,
+                                                                    want_keypoints=kp or args.debug)
+        train_source_iter, train_target_iter = rend(train_source_iter, kp=wants_keypoints(args)), rend(train_target_iter, want_ema)
+    elif args.device_augment and not args.synthetic:
         # packed sources -> HBM, augmentation and heat-map labels on the GPU (mi355.augment, utils.labels)
         dev_aug = lambda it, ema=False: DeviceAugmentIterator(it, device, args.image_size, args.heatmap_size, want_ema=ema)
         # (--mt-loss: the target batches also carry meta['image_ema'], the geometry-only image the teacher sees)
@@ -217,12 +236,21 @@ def main(args):
                                         lr_gamma=args.lr_gamma, lr_decay=args.lr_decay, trade_off=args.trade_off,
                                         num_keypoints=num_keypoints, optimizer=args.optimizer, adam_betas=tuple(args.adam_betas),
                                         adam_eps=args.adam_eps)
-    if args.synthetic:
+    if args.synthetic or args.synthetic_hands:
         # noise images make the target predictions collapse within a few dozen iterations; the reference's per-map
         # max-normalisation then divides 0 by 0 (regda_7.py:3623-3625).  Synthetic runs keep such maps at zero instead.
+        # (rendered hands: an untrained model can still emit an all-zero ground-false map, so the guard stays on)
         for c in step.crit.values():
             if hasattr(c, 'guard_empty_maps'):
                 c.guard_empty_maps = True
+    if args.synthetic_hands:
+        # a rendered joint may lie outside the frame: its label is an all-zero map with weight 0, and the KL loss normalises a label
+        # by its sum -- 0 / 0, a NaN that the zero weight does not remove (uda/model/loss.py:145-158; the noise data set keeps every
+        # joint in frame).  The loss's own epsilon makes such a label uniform, its row exactly 0; at 1e-12 a labelled map keeps its
+        # bits where it is not zero (1 + 1e-12 rounds to 1) and its zero pixels become about 1e-13 of the mass.
+        for c in [criterion] + list(step.crit.values()):
+            if isinstance(c, JointsKLLoss):
+                c.epsilon = RENDERED_LABEL_EPSILON
     ema = None
     if args.ema_update != 'off':
         # the teacher follows the model after every iteration (uda/model/loss.py:252-261 at train1.py:461), on the device
@@ -264,7 +292,7 @@ def main(args):
         step.clip = GradClipper(args.clip_grad_norm, device)
     start_epoch = 0
     if args.resume is None:
-        if args.pretrain is None or (args.synthetic and not os.path.exists(args.pretrain)):
+        if args.pretrain is None or ((args.synthetic or args.synthetic_hands) and not os.path.exists(args.pretrain)):
             print("Pretraining the model on source domain.")
             args.pretrain = logger.get_checkpoint_path('pretrain')
             pre = PoseResNet(backbone, upsampling, 256, num_keypoints, True).to(device)
@@ -309,7 +337,7 @@ def main(args):
     for epoch in range(start_epoch, args.epochs):
         logger.set_epoch(epoch)
         print(*[scheds[k].get_last_lr() for k in ('f', 'h', 'h_adv', 'h_adv2')])
-        train(train_source_iter, train_target_iter, step, scheds, epoch, args)
+        train(train_source_iter, train_target_iter, step, scheds, epoch, args, logger=logger)
         if step.clip is not None:
             print('skipped steps: %d' % step.clip.read()[1])       # (a count since the start of this process: not checkpointed)
         s_acc = validate(val_source_loader, model, criterion, args)
@@ -404,7 +432,7 @@ def source_keypoints(meta, image_size, heatmap_size, device):
     return (kp.float() / (float(image_size) / float(heatmap_size))).contiguous()
 
 
-def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
+def train(train_source_iter, train_target_iter, step, scheds, epoch, args, logger=None):
     names = ['Time', 'Data', 'Loss (s)', 'Loss (t, false)', 'Loss (t, truth)', 'Acc (s)', 'Acc (t)', 'Acc (s, adv)', 'Acc (t, adv)']
     fmts = [':4.2f', ':3.1f', ':.2e', ':.2e', ':.2e', ':3.2f', ':3.2f', ':3.2f', ':3.2f']
     mt, terms, mixup, coord = step.mt, step.terms(), step.mixup, step.coord
@@ -477,7 +505,26 @@ def train(train_source_iter, train_target_iter, step, scheds, epoch, args):
                     m.update(norms[s][0], 1)
             meters[0].update(time.time() - end)
             progress.display(i)
+            if args.debug and getattr(args, 'synthetic_hands', False) and logger is not None and RANK == 0:
+                debug_images(batch, out, meta_s, meta_t, logger, i)      # (outside the captured graphs; one device read)
         end = time.time()
+
+
+def debug_images(batch, out, meta_s, meta_t, logger, i):
+    """--debug under --synthetic-hands: sample 0 of the source and of the target batch, de-normalised, with the predicted (red) and
+    the labelled (green) skeleton, written to the logger's visualize/ directory.  Everything needed travels in one device read."""
+    from utils.visualize import visualize
+    S, K = batch['x_s'].shape[-1], out['y_s'].shape[1]
+    parts = []
+    for x, y, meta in ((batch['x_s'], out['y_s'], meta_s), (batch['x_t'], out['y_t'], meta_t)):
+        pred = get_max_preds_device(y[:1])[0].reshape(-1).float() * (float(S) / float(y.shape[-1]))
+        parts += [x[0].reshape(-1).float(), pred, meta['keypoint2d'][0].reshape(-1).float()]
+    flat = torch.cat(parts).cpu().numpy()
+    n, o = 3 * S * S, 0
+    for name in ('source', 'target'):
+        image, pred, label = flat[o:o + n].reshape(3, S, S), flat[o + n:o + n + 2 * K].reshape(K, 2), flat[o + n + 2 * K:o + n + 4 * K].reshape(K, 2)
+        visualize(image, pred, label, logger.get_image_path('%s_%d.jpg' % (name, i)))
+        o += n + 4 * K
 
 
 def validate_batch_metrics(y, label, weight, criterion):
@@ -523,6 +570,11 @@ def validate(val_loader, model, criterion, args, dump=None):
         # DeviceResize data set: packed sources -> HBM, resize + normalisation and the heat-map labels on the GPU
         batches = DeviceAugmentIterator(val_loader, device, dataset.image_size[0], dataset.heatmap_size[0], dataset.sigma,
                                         geometry_only=True)
+    if getattr(dataset, 'records_on_device', False):
+        # RenderedHand21: records -> HBM, the images and the heat-map labels on the GPU; meta['keypoint2d'] is the model's own joints
+        from utils.data import RenderedHandIterator
+        batches = RenderedHandIterator(val_loader, device, dataset.image_size[0], dataset.heatmap_size[0], dataset.sigma,
+                                       want_keypoints=True)
     pending = []                             # (loss, pred, label pred, batch size, heat-map h, w) of the batches not yet metered
     pose = PoseMetrics(dataset.num_keypoints, args.auc_max_px, device=device) if full else None
     kept = []                                # --dump-preds: (pred, gt, visible, maxval) of every batch, on the device
@@ -661,10 +713,22 @@ _OPTIONS = [
     (('--seed',), dict(default=1, type=int)),
     (('--log',), dict(type=str, default='logs/mt', help='run directory (logs, checkpoints, images)')),
     (('--phase',), dict(type=str, default='train', choices=['train', 'test'])),
-    (('--debug',), dict(action='store_true', help='accepted for CLI parity (visualisation is out of scope)')),
+    (('--debug',), dict(action='store_true', help='with --synthetic-hands: at every print interval, write sample 0 of the source and of '
+                       'the target batch with the predicted and the labelled skeleton to <log>/visualize/<epoch>/; otherwise accepted '
+                       'for CLI parity and ignored')),
     (('--ema-decay',), dict(default=0.999, type=float, metavar='ALPHA', help='decay m of the EMA teacher (--ema-update): v_ema = v_ema * m + (1 - m) * v')),
     # additive
     (('--synthetic',), dict(action='store_true', help='seeded synthetic batches instead of the CPU dataset layer')),
+    (('--synthetic-hands',), dict(action='store_true', help="a rendered two-domain hand data set instead of the data sets on disk "
+                                 "(utils/rendered_dataset.py): a procedural articulated hand drawn on the GPU from per-sample records, "
+                                 "'cg' renders as the source and 'photo' renders (cluttered background, occluder, sensor noise, colour "
+                                 "jitter) as the target, both with exact key points; the data roots are ignored, as under --synthetic, "
+                                 "which it excludes")),
+    (('--render-gap',), dict(default=1.0, type=float, metavar='FLOAT', help="--synthetic-hands: how far the 'photo' distributions lie from the "
+                            "'cg' ones, 0 (the same distribution) .. 1 (the full gap)")),
+    (('--render-train-size',), dict(default=65536, type=int, metavar='N', help='--synthetic-hands: training items per domain')),
+    (('--render-val-size',), dict(default=512, type=int, metavar='N', help='--synthetic-hands: validation items per domain (seeds '
+                                 'disjoint from the training sets)')),
     (('--dtype',), dict(default='bf16', choices=['bf16', 'f32', 'fp8', 'mxfp8'], help="compute dtype of activations / packed weights ('fp8': bf16 storage, fp8 operands in the K-heavy conv GEMMs; 'mxfp8': the same convs and the neck's transposed convs on block-scaled MX e4m3 operands)")),
     (('--mx-eval',), dict(action='store_true', help='validation / test forwards: the BatchNorm-folded 3x3 / 4x4 convs and transposed convs '
                           'on block-scaled MX e4m3 operands (opt-in, any --dtype with bf16 activations; also MI355_MX_EVAL=1)')),
@@ -855,6 +919,18 @@ class _Parser(argparse.ArgumentParser):
 
     def parse_args(self, *a, **kw):
         args = super().parse_args(*a, **kw)
+        if getattr(args, 'synthetic_hands', False):
+            if getattr(args, 'synthetic', False):
+                self.error('--synthetic and --synthetic-hands exclude each other: noise batches or rendered hands, not both')
+            if getattr(args, 'device_augment', False):
+                self.error('--device-augment with --synthetic-hands: the rendered records already are the device path '
+                           '(images and labels are made on the GPU); drop --device-augment')
+            if min(args.render_train_size, args.render_val_size) < 1:
+                self.error('--render-train-size and --render-val-size must be at least 1')
+            if args.image_size % 16 != 0 or not 16 <= args.image_size <= 512:
+                self.error('--synthetic-hands renders sides that are multiples of 16 from 16 to 512, got --image-size %d' % args.image_size)
+        if not 0.0 <= getattr(args, 'render_gap', 1.0) <= 1.0:
+            self.error('--render-gap must lie in 0 .. 1, got %r' % (args.render_gap,))
         if getattr(args, 'mt_loss', 'off') == 'on' and getattr(args, 'ema_update', 'off') == 'off':
             self.error('--mt-loss on needs a moving teacher: add --ema-update const (or warmup)')
         if getattr(args, 'mixup', 'off') == 'on' and getattr(args, 'mixup_labels', 'student') == 'teacher' and \

@@ -198,3 +198,99 @@ class DeviceAugmentIterator:
         target, weight = generate_target_device(kp, visible.to(self.device, non_blocking=True), self.heatmap_size, self.sigma,
                                                 self.image_size)
         return x, target, weight, meta
+
+
+# ---------------------------------------------------------------- rendered hands (train1.py --synthetic-hands)
+HAND_KEYPOINTS = 21
+
+
+def record_collate(samples):
+    """Collate of ``RenderedHand21``: (record, key points (21, 2) float32, visibility (21, 1) float32) per sample -> ONE uint8 tensor
+    [B records | B x 21 x 2 key points | B x 21 visibilities], so that a batch is a single pinned buffer and a single copy (the
+    default collate does not take numpy structured scalars).  A record is 480 bytes, so all three parts start 8-byte aligned."""
+    import numpy as np
+    recs = np.stack([s[0] for s in samples])
+    kp = np.stack([s[1] for s in samples]).astype(np.float32, copy=False)
+    vis = np.stack([s[2] for s in samples]).astype(np.float32, copy=False)
+    return torch.from_numpy(np.concatenate([recs.view(np.uint8).reshape(-1), kp.view(np.uint8).reshape(-1), vis.view(np.uint8).reshape(-1)]))
+
+
+class RenderedHandIterator:
+    """Batches of ``record_collate`` -> the ``(x, target, weight, meta)`` batches the training and validation loops consume, on the
+    GPU: the packed batch is copied from pinned host memory on a side stream while the previous one is consumed (two staging slots,
+    as ``DevicePrefetcher``), ``mi355.ops.render_hands`` draws x -- and, with want_ema, ``meta['image_ema']``, the same scene without
+    gain, bias and sensor noise, in the same launch -- and ``utils.labels.generate_target_device`` makes the heat-maps from the key
+    points: two launches of the library per batch.  With want_keypoints ``meta['keypoint2d']`` holds the un-quantised key points
+    (B, 21, 2), image pixels, on the device."""
+
+    def __init__(self, iterator, device, image_size=256, heatmap_size=64, sigma=2, want_ema=False, want_keypoints=False):
+        from mi355.ops import HAND_REC_DTYPE
+        self.source = iterator
+        self.it = iter(iterator)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ValueError('RenderedHandIterator renders on a GPU; there is no CPU path')
+        self.image_size, self.heatmap_size, self.sigma = int(image_size), int(heatmap_size), sigma
+        self.want_ema, self.want_keypoints = bool(want_ema), bool(want_keypoints)
+        self.rec_bytes = HAND_REC_DTYPE.itemsize
+        self.sample_bytes = self.rec_bytes + HAND_KEYPOINTS * 12
+        self.stream = torch.cuda.Stream(self.device)
+        self._staging, self._slot_free, self._slot = [dict(), dict()], [None, None], 0
+        self._ready = None
+        self._preload()
+
+    def __iter__(self):
+        return self
+
+    def __len__(self):
+        return len(self.source)
+
+    def _preload(self):
+        try:
+            host = next(self.it)
+        except StopIteration:
+            self._ready = None
+            return
+        if host.dtype != torch.uint8 or host.dim() != 1 or host.numel() == 0 or host.numel() % self.sample_bytes:
+            raise ValueError('RenderedHandIterator: a batch must be the flat uint8 tensor of record_collate, got %s %s' % (host.dtype, tuple(host.shape)))
+        slot = self._slot
+        self._slot = 1 - slot
+        if self._slot_free[slot] is not None:
+            self._slot_free[slot].synchronize()                 # the staging buffer of this slot is about to be rewritten
+        if not host.is_pinned():
+            buf = self._staging[slot].get(host.numel())
+            if buf is None:
+                buf = self._staging[slot][host.numel()] = torch.empty(host.numel(), dtype=torch.uint8, pin_memory=True)
+            buf.copy_(host)
+            host = buf
+        with torch.cuda.stream(self.stream):
+            dev = host.to(self.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self._slot_free[slot] = ev
+        self._ready = (dev, ev)
+
+    def __next__(self):
+        from mi355 import ops
+        from utils.labels import generate_target_device
+        if self._ready is None:
+            raise StopIteration
+        dev, ev = self._ready
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ev)
+        dev.record_stream(cur)
+        self._preload()
+        B, S = dev.numel() // self.sample_bytes, self.image_size
+        recs = dev[:B * self.rec_bytes]
+        kp = dev[B * self.rec_bytes:B * (self.rec_bytes + HAND_KEYPOINTS * 8)].view(torch.float32).view(B, HAND_KEYPOINTS, 2)
+        vis = dev[B * (self.rec_bytes + HAND_KEYPOINTS * 8):].view(torch.float32).view(B, HAND_KEYPOINTS, 1)
+        x = torch.empty((B, 3, S, S), dtype=torch.float32, device=self.device)
+        ema = torch.empty_like(x) if self.want_ema else None
+        ops.render_hands(recs, S, out=x, out_ema=ema)
+        target, weight = generate_target_device(kp, vis, self.heatmap_size, self.sigma, S)
+        meta = {}
+        if self.want_keypoints:
+            meta['keypoint2d'] = kp
+        if self.want_ema:
+            meta['image_ema'] = ema
+        return x, target, weight, meta

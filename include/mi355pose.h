@@ -865,6 +865,55 @@ int mi355_teacher_select(const float* p, const float* xy, const float* gate_in, 
                          int32_t* count, float* stats, int B, int K, void* stream);
 int mi355_occlude_images(const float* x, const int32_t* boxes, int N, float* out, int B, int C, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------- rendered hands (csrc/render.hip)
+ * A batch of S x S RGB images drawn from one fixed-size record per sample: 20 bone capsules between 21 projected joints, one
+ * optional occluder capsule, a two-colour gradient background with value noise, Lambert shading, sensor noise and a photometric
+ * gain / bias (utils/rendered_dataset.py fills the records; the reference has no such function).  The arithmetic, restated in numpy
+ * by tests/render_ref.py: fp32, only + - * / sqrt, every operation rounded on its own, no FMA contraction, sums left to right.
+ *   Primitive k = 0 .. 19 is bone k of the hand (parent a = joint (k % 4 == 0 ? 0 : k), child b = joint k + 1; x, y in pixels, z a
+ *   depth in pixels, smaller is nearer) with radius[k]; primitive 20 is the occluder (occ_a, occ_b, occ_r, depth occ_z at both
+ *   ends).  A primitive is VALID iff ax, ay, az, bx, by, bz and r all have a magnitude <= MI355_RENDER_MAX_COORD (which a NaN and
+ *   an infinity fail) and r > 0; one that is not covers nothing.
+ *   At a point p = (px, py): e = b - a; ee = ex*ex + ey*ey; d = p - a; q = (dx*ex + dy*ey) / ee when ee > 0, else 0 -- chosen by
+ *   selection, the quotient is not formed; t = q < 0 ? 0 : (q > 1 ? 1 : q); c = a + t*e; w = p - c; d2 = wx*wx + wy*wy; r2 = r*r;
+ *   p is covered iff d2 <= r2; depth = (az + t*(bz - az)) - sqrt(r2 - d2).  The front-most primitive is the covered one of
+ *   strictly smallest depth below +inf, the lower index on ties.
+ *   Colour there: n = (wx / r, wy / r, sqrt(1 - d2 / r2)); lam = n.x*l.x + n.y*l.y + n.z*l.z, 0 unless > 0;
+ *   shade = ambient + (1 - ambient) * lam; colour[c] = base[c] * shade, base = skin, or occ_col for the occluder.
+ *   Background: g = (px*grad[0] + py*grad[1]) + grad_off clamped to [0, 1] as t is; colour[c] = bg0[c] + g*(bg1[c] - bg0[c]); when
+ *   noise_amp > 0 and 0 < noise_inv_cell <= 1 (else no noise): u = (px + 1)*inv_cell, v = (py + 1)*inv_cell, ix = floor(u),
+ *   fx = u - ix, sx = (fx*fx)*(3 - 2*fx), likewise y; with L(i, j) = H(noise_seed, i, j) the lattice values,
+ *   top = L(ix,iy) + sx*(L(ix+1,iy) - L(ix,iy)), bot likewise on iy + 1, val = top + sy*(bot - top), and amp*(val - 0.5) is added
+ *   to each channel.  H(s, a, b) = float(h >> 8) * 2^-24 in [0, 1) with, on uint32, h = s ^ a*0x9E3779B1; h ^= h >> 16;
+ *   h *= 0x85EBCA6B; h ^= b*0xC2B2AE35; h ^= h >> 13; h *= 0x27D4EB2F; h ^= h >> 16.
+ *   Pixel (row i, column j), channel c: m[c] = 0.25 * (((s0 + s1) + s2) + s3) over the colours at (j - .25, i - .25),
+ *   (j + .25, i - .25), (j - .25, i + .25), (j + .25, i + .25);  out_ema = (m[c] - mean[c]) * inv_std[c];
+ *   out = ((m[c]*gain[c] + bias[c] + noise) - mean[c]) * inv_std[c], noise = sensor_sigma * ((((u0 + u1) + u2) + u3) - 2) with
+ *   uk = H(sensor_seed ^ (4c + k + 1)*0x632BE5AB, i, j) when sensor_sigma > 0, else absent;  ids = 1 + the front-most
+ *   primitive at the pixel centre (j, i), 0 for background.
+ * out, out_ema (nullable) [B][3][S][S] fp32, ids (nullable) [B][S][S] uint8; mean3, inv_std3: HOST pointers to three floats.  S: a
+ * multiple of 16 from 16 to 512.  recs, out, out_ema 16-byte aligned, ids 4-byte.  No output may overlap recs or another output.
+ * One launch: one workgroup per 32 x 32 tile of one sample, the record staged in LDS, the primitives culled against the tile by
+ * float comparisons only (nothing in a record is ever converted to an index except the noise lattice coordinate, whose range
+ * the inv_cell test bounds); the culling never changes the image.  No atomics: the same bits on every run, eagerly and under
+ * graph replay.  Never allocates; capturable.  Every refusal is MI355_EINVAL before any launch, naming the argument. */
+#define MI355_RENDER_MAX_COORD 1048576.0f
+#define MI355_RENDER_MAX_SIDE 512
+typedef struct mi355_hand_rec {
+  float jx[21], jy[21], jz[21];      /* projected joints: pixels, depth in pixels */
+  float radius[20];                  /* per bone, pixels */
+  float skin[3], light[3], ambient;  /* base colour, unit light direction (z towards the camera), ambient share */
+  float bg0[3], bg1[3], grad[2], grad_off;
+  float noise_amp, noise_inv_cell; uint32_t noise_seed;
+  float occ_a[2], occ_b[2], occ_r, occ_z, occ_col[3];     /* occ_r = 0: no occluder */
+  float sensor_sigma; uint32_t sensor_seed;
+  float gain[3], bias[3];
+  uint32_t reserved;                 /* pads the record to 480 bytes, a multiple of 16 */
+} mi355_hand_rec;
+size_t mi355_hand_rec_size(void);
+int mi355_render_hands(const mi355_hand_rec* recs, float* out, float* out_ema, unsigned char* ids, int B, int S,
+                       const float* mean3, const float* inv_std3, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
