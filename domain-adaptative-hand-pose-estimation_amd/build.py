@@ -25,7 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libmi355pose.so')
-SOURCES = ['api.hip', 'igemm.hip', 'pgemm.hip', 'igemm_fp8.hip', 'mx_fp8.hip', 'wgrad_fp8.hip', 'bn.hip', 'pool_layout.hip', 'pw21.hip', 'heatmap.hip', 'optim.hip', 'augment.hip', 'teacher.hip', 'eval.hip', 'mmd.hip', 'jfa.hip', 'proto.hip', 'mixup.hip', 'fda.hip', 'warp.hip', 'bone.hip', 'occlude.hip', 'render.hip']
+SOURCES = ['api.hip', 'igemm.hip', 'pgemm.hip', 'igemm_fp8.hip', 'mx_fp8.hip', 'wgrad_fp8.hip', 'bn.hip', 'pool_layout.hip', 'pw21.hip', 'heatmap.hip', 'optim.hip', 'augment.hip', 'teacher.hip', 'eval.hip', 'mmd.hip', 'jfa.hip', 'proto.hip', 'mixup.hip', 'fda.hip', 'warp.hip', 'bone.hip', 'occlude.hip', 'render.hip', 'track.hip']
 HEADERS = ['common.h', 'conv_plan.h', 'igemm_common.h', 'fp8_common.h', 'joint_pool.h', 'adam_slice.h', 'heatmap_rows.h']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 LLVM_BIN = os.environ.get('MI355_LLVM_BIN', '/opt/rocm/lib/llvm/bin')

@@ -40,6 +40,13 @@ class BnBwdSrc(ctypes.Structure):
                 ('save_mean', ctypes.c_void_p), ('save_invstd', ctypes.c_void_p), ('relu', ctypes.c_int)]
 
 
+class TrackParams(ctypes.Structure):
+    """mi355_track_params: the box rule of mi355_track_update, passed by value."""
+    _fields_ = [('tau', ctypes.c_float), ('min_joints', ctypes.c_int32), ('scale', ctypes.c_float), ('alpha', ctypes.c_float),
+                ('grow', ctypes.c_float), ('max_lost', ctypes.c_int32), ('min_side', ctypes.c_float), ('Wf', ctypes.c_int32),
+                ('Hf', ctypes.c_int32), ('S', ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/mi355pose.h one to one
 _P, _I, _L, _F, _Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_size_t
 _D = ctypes.POINTER(ConvDesc)
@@ -156,6 +163,8 @@ SIGNATURES = {
     'mi355_occlude_images': (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
     'mi355_hand_rec_size': (_Z, []),
     'mi355_render_hands': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    'mi355_roi_crop_normalize': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    'mi355_track_update': (_I, [_P, _P, _P, TrackParams, _P, _P, _P, _P, _I, _I, _P]),
     'mi355_augment_workspace': (_Z, [_I, _I]),
     'mi355_augment': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'mi355_resize_normalize': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _P, _P, _P]),

@@ -1765,6 +1765,113 @@ def render_hands(recs, image_size, out=None, out_ema=None, ids=None, mean=None, 
     return out
 
 
+# ---------------------------------------------------------------- hand tracking (csrc/track.hip)
+# include/mi355pose.h mi355_track_rec, field for field
+TRACK_REC_DTYPE = _np.dtype([('frame', '<i4'), ('x0', '<f4'), ('y0', '<f4'), ('side', '<f4'), ('mirror', '<i4'), ('live', '<i4'),
+                             ('lost', '<i4'), ('reserved', '<i4')])
+assert TRACK_REC_DTYPE.itemsize == 32
+TRACK_MAX_COORD, TRACK_MAX_FRAME, TRACK_MAX_JOINTS, TRACK_MAX_SIDE = 1048576.0, 4096, 64, 512      # include/mi355pose.h MI355_TRACK_*
+TRACK_SIDES = tuple(range(16, TRACK_MAX_SIDE + 1, 16))
+# tau, min_joints, alpha, grow, max_lost and min_side are PLACEHOLDERS: their effect has not been measured.  scale = 1.5 is the data
+# sets' crop (scale_box(get_bounding_box(keypoint2d), w, h, 1.5)).
+TRACK_DEFAULTS = dict(tau=0.02, min_joints=8, scale=1.5, alpha=1.0, grow=1.25, max_lost=5, min_side=16.0)
+
+
+def track_records(n, frame=0, x0=0.0, y0=0.0, side=1.0, mirror=0, live=0, lost=0):
+    """A numpy structured array of n records (TRACK_REC_DTYPE); every argument is a scalar or a sequence of n values."""
+    rec = _np.zeros(int(n), TRACK_REC_DTYPE)
+    for name, v in (('frame', frame), ('x0', x0), ('y0', y0), ('side', side), ('mirror', mirror), ('live', live), ('lost', lost)):
+        rec[name] = v
+    return rec
+
+
+def pack_track_records(rec, device=None, out=None):
+    """The (N, 8) int32 tensor that holds the records `rec` (a TRACK_REC_DTYPE array) word for word: new on `device`, or `out`
+    rewritten in place (a tracker's records stay at their address)."""
+    rec = _np.ascontiguousarray(rec, dtype=TRACK_REC_DTYPE).reshape(-1)
+    host = torch.from_numpy(rec.view(_np.int32).reshape(-1, 8).copy())
+    if out is None:
+        return host.to(device)
+    if out.dtype != torch.int32 or tuple(out.shape) != tuple(host.shape) or not out.is_contiguous():
+        raise Mi355Error('pack_track_records: out must be a dense int32 %s tensor, got %s %s' % (tuple(host.shape), out.dtype, tuple(out.shape)))
+    out.copy_(host)
+    return out
+
+
+def unpack_track_records(recs):
+    """The records of an (N, 8) int32 tensor as a TRACK_REC_DTYPE array on the host (a device tensor is read back: synchronises)."""
+    a = _np.ascontiguousarray(recs.detach().cpu().numpy()).reshape(-1, 8)
+    if a.dtype != _np.int32:
+        raise Mi355Error('unpack_track_records: the records are an int32 (N, 8) tensor, got %s' % (a.dtype,))
+    return a.view(TRACK_REC_DTYPE).reshape(-1)
+
+
+def _chk_track_recs(who, what, recs):
+    _chk_dev(recs)
+    if recs.dtype != torch.int32 or recs.dim() != 2 or recs.shape[1] != 8 or recs.shape[0] < 1 or not recs.is_contiguous():
+        raise Mi355Error('%s: %s must be a dense int32 (N, 8) tensor of records, got %s %s strides %s' % (who, what, recs.dtype, tuple(recs.shape), recs.stride()))
+    return int(recs.shape[0])
+
+
+def roi_crop_normalize(frames, recs, S, out=None, mean=MEAN, std=STD):
+    """out (N, 3, S, S) fp32: the square of every record of `recs` (int32 (N, 8) on the device, pack_track_records) cut out of the
+    uint8 (F, Hf, Wf, 3) RGB device tensor `frames`, resized to S x S, mirrored where the record says so and normalised
+    (mi355_roi_crop_normalize).  The records are read on the device only; an unusable one gives an image of zeros.  `out` is
+    allocated only when not given, and never during graph capture.  Every check raises before anything is launched."""
+    who = 'roi_crop_normalize'
+    _chk_dev(frames, out)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0 or not frames.is_contiguous():
+        raise Mi355Error('%s: frames must be a dense uint8 (F, Hf, Wf, 3) tensor, got %s %s strides %s' % (who, frames.dtype, tuple(frames.shape), frames.stride()))
+    F, Hf, Wf = (int(s) for s in frames.shape[:3])
+    N = _chk_track_recs(who, 'recs', recs)
+    if int(S) != S or S not in TRACK_SIDES:
+        raise Mi355Error('%s: S=%r is not a multiple of 16 from 16 to %d' % (who, S, TRACK_MAX_SIDE))
+    S = int(S)
+    out, = _occ_out(who, None if out is None else (out,), (('out', (N, 3, S, S), torch.float32),), frames.device)
+    if recs.device != frames.device:
+        raise Mi355Error('%s: the operands live on different devices' % who)
+    norm = _np.array(list(mean) + list(std), dtype=_np.float32)
+    call('mi355_roi_crop_normalize', ptr(frames), F, Hf, Wf, ptr(recs), N, S, norm.ctypes.data, ptr(out), stream_ptr())
+    return out
+
+
+def track_params(frame_shape, S, **kw):
+    """The mi355_track_params of a frame (Hf, Wf) and crop side S; keywords override TRACK_DEFAULTS."""
+    from . import TrackParams
+    unknown = sorted(set(kw) - set(TRACK_DEFAULTS))
+    if unknown:
+        raise Mi355Error('track_update: unknown parameter(s) %s (known: %s)' % (', '.join(unknown), ', '.join(sorted(TRACK_DEFAULTS))))
+    p = dict(TRACK_DEFAULTS, **kw)
+    Hf, Wf = _size_hw(frame_shape)
+    return TrackParams(float(p['tau']), int(p['min_joints']), float(p['scale']), float(p['alpha']), float(p['grow']), int(p['max_lost']),
+                       float(p['min_side']), Wf, Hf, int(S))
+
+
+def track_update(recs, xy, conf, params, out=None, rec_out=None):
+    """Key points back to the frame and the next box of every hand (mi355_track_update).  recs: int32 (N, 8) records on the device;
+    xy (N, K, 2) fp32 key points in crop pixels; conf (N, K) fp32; params: track_params(...).  Returns (kp (N, K, 2) in frame pixels,
+    vis (N, K) 1.0 / 0.0, score (N,), rec_out); `rec_out` defaults to `recs` itself (updated in place).  `out`: the triple (kp, vis,
+    score), written in place; allocated only when not given, and never during graph capture."""
+    who = 'track_update'
+    N = _chk_track_recs(who, 'recs', recs)
+    _dense_f32(who, 'xy', xy)
+    _dense_f32(who, 'conf', conf)
+    if xy.dim() != 3 or xy.shape[0] != N or xy.shape[2] != 2 or xy.shape[1] < 1:
+        raise Mi355Error('%s: xy must be (%d, K, 2), got %s' % (who, N, tuple(xy.shape)))
+    K = int(xy.shape[1])
+    if conf.numel() != N * K or conf.shape[0] != N:
+        raise Mi355Error('%s: conf %s for %d x %d joints' % (who, tuple(conf.shape), N, K))
+    if rec_out is None:
+        rec_out = recs
+    elif _chk_track_recs(who, 'rec_out', rec_out) != N:
+        raise Mi355Error('%s: rec_out holds %d records, recs %d' % (who, rec_out.shape[0], N))
+    kp, vis, score = _occ_out(who, out, (('kp', (N, K, 2), torch.float32), ('vis', (N, K), torch.float32), ('score', (N,), torch.float32)), recs.device)
+    if any(t.device != recs.device for t in (xy, conf, rec_out)):
+        raise Mi355Error('%s: the operands live on different devices' % who)
+    call('mi355_track_update', ptr(recs), ptr(xy), ptr(conf), params, ptr(kp), ptr(vis), ptr(score), ptr(rec_out), N, K, stream_ptr())
+    return kp, vis, score, rec_out
+
+
 # ---------------------------------------------------------------- MMD alignment (csrc/mmd.hip)
 MMD_MAX_ROWS, MMD_MAX_KERNELS = 256, 8
 _mmd_ws = {}

@@ -8,7 +8,11 @@ probability, sensor noise and per-channel gain / bias jitter.  ``gap`` in [0, 1]
 one (0) to the full one (1); it does nothing to 'cg'.
 
 Item i is a pure function of (seed, i, domain, gap): nothing needs checkpointing and a resumed run sees the same items.
-Everything that needs sin, cos, exp or log is computed here and carried in the record."""
+Everything that needs sin, cos, exp or log is computed here and carried in the record.
+
+Sequence mode (``hand_sequence`` / ``render_sequence``, predict.py --synthetic-hands-video): two drawn hands interpolated linearly in
+joint positions, depths and radii over N frames of one 'photo' scene, rendered and converted to uint8 HWC frames on the device, so
+that the key points of every frame of a video are exact as well."""
 import numpy as np
 from torch.utils.data import Dataset
 
@@ -114,3 +118,48 @@ class RenderedHand21(Dataset):
 
     def group_accuracy(self, accuracies):
         return {name: sum(accuracies[i] for i in ks) / len(ks) for name, ks in self.keypoints_group.items()}
+
+
+def hand_sequence(n_frames, frame_size=256, seed=1, hand_share=0.45, travel=0.18, gap=1.0):
+    """(records (n_frames,) of HAND_REC_DTYPE, key points (n_frames, 21, 2) fp32 in frame pixels) of a hand that moves and changes
+    pose across a frame_size x frame_size frame.  Items 0 and 1 of RenderedHand21(domain='photo', seed) give the two poses: each
+    is shrunk to `hand_share` of the frame about its centre and moved `travel` of the side away from it, one up and to the left,
+    the other down and to the right; frame t interpolates joint positions, depths and radii linearly between them.  The scene
+    (skin, light, background, gain and bias) is item 0's in every frame, without an occluder; the sensor noise is drawn anew per frame."""
+    n_frames, S = int(n_frames), int(frame_size)
+    if n_frames < 1:
+        raise ValueError('hand_sequence: n_frames must be at least 1, got %r' % (n_frames,))
+    ds = RenderedHand21(length=2, image_size=S, domain='photo', seed=seed, gap=gap)
+    ends = []
+    for i, sign in ((0, -1.0), (1, 1.0)):
+        rec = ds[i][0]
+        c = (S - 1) / 2.0
+        shift = sign * travel * S * np.array([1.0, 0.6])
+        ends.append((c + hand_share * (rec['jx'].astype(np.float64) - c) + shift[0], c + hand_share * (rec['jy'].astype(np.float64) - c) + shift[1],
+                     hand_share * rec['jz'].astype(np.float64), hand_share * rec['radius'].astype(np.float64)))
+    recs = np.zeros(n_frames, dtype=HAND_REC_DTYPE)
+    recs[:] = ds[0][0]
+    for t in range(n_frames):
+        a = t / (n_frames - 1) if n_frames > 1 else 0.0
+        for name, v0, v1 in zip(('jx', 'jy', 'jz', 'radius'), ends[0], ends[1]):
+            recs[name][t] = (1.0 - a) * v0 + a * v1
+    recs['occ_r'] = 0.0
+    recs['sensor_seed'] = (int(recs['sensor_seed'][0]) + np.arange(n_frames, dtype=np.uint64) * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)
+    return recs, np.stack([recs['jx'], recs['jy']], axis=2).astype(np.float32)
+
+
+def render_sequence(recs, frame_size, device, chunk=16):
+    """The uint8 (n, frame_size, frame_size, 3) RGB frames of `recs` on `device`: mi355_render_hands, de-normalised, rounded and
+    laid out HWC by device operations (the host sees no pixel)."""
+    import torch
+    from mi355 import ops
+    from mi355.augment import MEAN, STD
+    S = int(frame_size)
+    mean, std = (torch.tensor(v, dtype=torch.float32, device=device).view(1, 3, 1, 1) for v in (MEAN, STD))
+    out = torch.empty((len(recs), S, S, 3), dtype=torch.uint8, device=device)
+    for at in range(0, len(recs), chunk):
+        part = np.ascontiguousarray(recs[at:at + chunk])
+        r_d = torch.from_numpy(part.view(np.uint8).reshape(len(part), -1).copy()).to(device)
+        x = ops.render_hands(r_d, S)
+        out[at:at + len(part)] = ((x * std + mean).clamp_(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).permute(0, 2, 3, 1)
+    return out

@@ -22,12 +22,30 @@ def visualize(image, pred, label, filename, bones=None):
     canvas = Image.fromarray(denormalize(image), 'RGB')
     draw = ImageDraw.Draw(canvas)
     for pts, colour in ((label, LABEL_COLOUR), (pred, PRED_COLOUR)):
-        if pts is None:
-            continue
-        pts = np.nan_to_num(np.asarray(pts, dtype=np.float64), nan=-1.0e4, posinf=1.0e4, neginf=-1.0e4)
-        for a, b in bones:
-            draw.line([tuple(int(v) for v in pts[a]), tuple(int(v) for v in pts[b])], fill=colour, width=1)
-        for x, y in pts:
-            draw.ellipse([int(x) - 1, int(y) - 1, int(x) + 1, int(y) + 1], outline=colour)
+        if pts is not None:
+            _skeleton(draw, pts, colour, bones)
+    canvas.save(filename)
+    return filename
+
+
+def _skeleton(draw, pts, colour, bones):
+    pts = np.nan_to_num(np.asarray(pts, dtype=np.float64), nan=-1.0e4, posinf=1.0e4, neginf=-1.0e4)
+    for a, b in bones:
+        draw.line([tuple(int(v) for v in pts[a]), tuple(int(v) for v in pts[b])], fill=colour, width=1)
+    for x, y in pts:
+        draw.ellipse([int(x) - 1, int(y) - 1, int(x) + 1, int(y) + 1], outline=colour)
+
+
+def overlay(frame, preds, filename, labels=None, bones=None):
+    """Save the uint8 (H, W, 3) RGB `frame` with the skeleton of every hand in `preds` (a list of (K, 2) arrays, frame pixels) in
+    red on top of those of `labels` (optional, likewise) in green: the per-frame picture of predict.py --overlay."""
+    from PIL import Image, ImageDraw
+    if bones is None:
+        from uda.model.loss import HAND_BONES as bones
+    canvas = Image.fromarray(np.ascontiguousarray(frame, dtype=np.uint8), 'RGB')
+    draw = ImageDraw.Draw(canvas)
+    for group, colour in ((labels, LABEL_COLOUR), (preds, PRED_COLOUR)):
+        for pts in group or ():
+            _skeleton(draw, pts, colour, bones)
     canvas.save(filename)
     return filename

@@ -914,6 +914,73 @@ size_t mi355_hand_rec_size(void);
 int mi355_render_hands(const mi355_hand_rec* recs, float* out, float* out_ema, unsigned char* ids, int B, int S,
                        const float* mean3, const float* inv_std3, void* stream);
 
+/* ---------------------------------------------------------------- hand tracking (csrc/track.hip)
+ * From a camera frame and a rough hand box to key points in that frame, and from those to the next frame's box, without the host:
+ * the boxes are records in DEVICE memory that one kernel crops by and the other rewrites.  Tracking a hand by the box of its
+ * previous key points is the common practice of hand-pose pipelines; the box rule below is this project's.  The
+ * reference has no such function, so there is no file:line to cite; the semantics are stated here and restated in numpy by
+ * tests/track_ref.py.  Forward only.  No atomics: the same bits on every run, eagerly and under graph replay.  Never allocates;
+ * capturable.  fp32 throughout, every operation rounded on its own, no FMA contraction.
+ * The record: (x0, y0) is the left / upper EDGE of a square of `side` frame pixels -- PIL's crop box, the convention of
+ * uda/dataset/keypoint_detection.crop -- in frame `frame` of the batch; mirror != 0 flips the crop along W (a left hand shown to
+ * a right-hand network); live == 0 is an empty slot; lost counts the frames since the hand was last seen.  The host never reads
+ * a record before a launch, so both kernels are safe for ANY bit pattern in it.  A record is USABLE iff live != 0 and
+ * 0 <= frame < F and |x0| <= MI355_TRACK_MAX_COORD and |y0| <= MI355_TRACK_MAX_COORD (a NaN and an infinity fail) and
+ * 1 <= side <= 4 S (mi355_track_update has no F: there `frame` is not tested).  Every test on a float is a float comparison made
+ * before any conversion to an integer; no address is formed from an unbounded value.
+ * roi_crop_normalize: out[n] [3][S][S] fp32 = the square of record n resized to S x S and normalised; frames [F][Hf][Wf][3] uint8 RGB,
+ *   dense, 1 <= Hf, Wf <= MI355_TRACK_MAX_FRAME (the row pitch 3 Wf need not be a multiple of 4); norm: HOST pointer to six floats,
+ *   mean[3] then std[3] (std > 0, all finite).  An unusable record writes +0.0 to its whole image and reads no pixel.  Otherwise
+ *     value of a byte p in channel c: T[c][p] = fl(fl((float)p / 255.0f - mean[c]) / std[c]), what mi355_resize_normalize writes for
+ *       it; a tap outside the frame has the value +0 (the data-set mean), chosen by selection, nothing is read;
+ *     step = fl(side / (float)S); n = 1 if side <= S, 2 if side <= 2 S, 3 if side <= 3 S, else 4 sub-samples per axis;
+ *     off_a = fl(((float)a + 0.5f) / (float)n), a = 0 .. n-1; for output column j: jj = mirror ? S - 1 - j : j and
+ *       xs = fl(fl(x0 + fl(fl((float)jj + off_a) * step)) - 0.5f); ys likewise from y0 and the row i (never mirrored);
+ *     one sample at (xs, ys), per channel, by the rule stated above for mi355_affine_warp_images on the Hf x Wf plane of T-values:
+ *       +0 unless xs > -1 && xs < Wf && ys > -1 && ys < Hf; x0i = floor(xs), fx = fl(xs - x0i); horizontally
+ *       r = (fx == 0) ? v0 : fl(fl(v0 * fl(1 - fx)) + fl(v1 * fx)), vertically the same form on the two row results with fy; with
+ *       fx == 0 (fy == 0) the second tap (row) is not read -- the only skipped read: when fx rounds to 1 the first tap is read
+ *       with weight 0, inside the frame like every read;
+ *     the pixel = fl(sum / (float)(n n)), sum = the n n samples added left to right starting from the first, sub-sample rows
+ *       ascending and columns ascending within a row.
+ *   So an integer box with side == S is mi355_resize_normalize of that square bit for bit, and mirror is that image flipped.
+ *   One workgroup per 32 x 32 output tile of one hand; the record is read once per workgroup and T is built in LDS.  16-byte stores
+ *   when out is 16-byte aligned, 4-byte stores otherwise; out and recs need 4-byte alignment, frames none.  S: a multiple of 16 from
+ *   16 to MI355_TRACK_MAX_SIDE.  out must not overlap frames or recs.
+ * track_update: one thread per hand, joints in ascending order.  xy [N][K][2] key points in crop pixels (as the decoders write
+ *   them), conf [N][K]; kp [N][K][2], vis [N][K], score [N] are written; rec_out may be rec_in itself (a thread reads its record
+ *   completely before it writes) and may not overlap it otherwise.  With Sf = (float)S, Wff = (float)Wf, Hff = (float)Hf of params:
+ *   unusable record: kp, vis, score = +0 and rec_out = rec_in with live = 0.  Otherwise
+ *     st = fl(side / Sf); xm = mirror ? fl(fl(Sf - 1.0f) - x) : x; kx = fl(x0 + fl(xm * st)), ky = fl(y0 + fl(y * st));
+ *     vis[k] = 1.0f iff conf[k] >= tau (a NaN fails) and kx and ky are finite, else 0.0f; kp[k] = (kx, ky), or (+0, +0) when either
+ *     is not finite.  m = the visible joints; score = fl(sum / (float)m), sum = their conf added left to right from +0; 0 when m = 0.
+ *     cap = min(min(Wff, Hff), 4 Sf); clamp(s) = (t = s < min_side ? min_side : s; t > cap ? cap : t); hx = fl(side * 0.5f);
+ *     cx = fl(x0 + hx), cy = fl(y0 + hx) the old centre.
+ *     m >= min_joints: over the visible kp, (lx, ux) = (min, max) of kx, (ly, uy) of ky; e = max(fl(ux - lx), fl(uy - ly));
+ *       sn = clamp(fl(scale * e)); nx = fl(fl(lx + ux) * 0.5f), ny likewise; cx' = fl(cx + fl(alpha * fl(nx - cx))), cy' likewise,
+ *       side' = clamp(fl(side + fl(alpha * fl(sn - side)))); lost' = 0.
+ *     else: lost' = lost < 0 ? 1 : (lost >= max_lost ? max_lost + 1 : lost + 1).  lost' > max_lost: live' = 0 and x0, y0, side are
+ *       kept as they are.  Otherwise cx' = cx, cy' = cy, side' = (t = fl(side * grow); t > cap ? cap : t).
+ *     In every case but the dead one: x0' = shift(fl(cx' - fl(side' * 0.5f)), Wff), y0' = shift(fl(cy' - fl(side' * 0.5f)), Hff),
+ *       shift(v, L) = (t = v < 0 ? 0 : v; h = fl(L - side'); t > h ? h : t), the rule of uda/dataset/util.scale_box without its
+ *       rounding to whole pixels.  frame and mirror are copied, reserved is written as 0, live' = 1 unless dead.
+ *   params, checked on the host: tau finite; 1 <= min_joints <= K; scale finite and > 0; 0 <= alpha <= 1; grow finite and >= 1;
+ *   0 <= max_lost <= 2^30; min_side finite and >= 1; 1 <= Wf, Hf <= MI355_TRACK_MAX_FRAME; S as above.  1 <= K <= MI355_TRACK_MAX_JOINTS.
+ *   Pointers 4-byte aligned; no output may overlap an input (rec_out == rec_in apart) or another output.
+ * Every refusal is MI355_EINVAL before any launch, the message naming the argument. */
+#define MI355_TRACK_MAX_COORD 1048576.0f
+#define MI355_TRACK_MAX_FRAME 4096
+#define MI355_TRACK_MAX_SIDE 512
+#define MI355_TRACK_MAX_JOINTS 64
+typedef struct mi355_track_rec { int32_t frame; float x0, y0, side; int32_t mirror, live, lost, reserved; } mi355_track_rec;
+typedef struct mi355_track_params {
+  float tau; int32_t min_joints; float scale, alpha, grow; int32_t max_lost; float min_side; int32_t Wf, Hf, S;
+} mi355_track_params;
+int mi355_roi_crop_normalize(const unsigned char* frames, int F, int Hf, int Wf, const mi355_track_rec* recs, int N, int S,
+                             const float* norm, float* out, void* stream);
+int mi355_track_update(const mi355_track_rec* rec_in, const float* xy, const float* conf, mi355_track_params params, float* kp,
+                       float* vis, float* score, mi355_track_rec* rec_out, int N, int K, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation (csrc/augment.hip)
  * The reference's per-sample CPU chain (train1.py:54-66: RandomRotation, RandomResizedCrop, ColorJitter(0.25, 0.25, 0.25),
  * GaussianBlur, ToTensor, Normalize, plus the image_ema copy of uda/dataset/keypoint_detection.py:171-181) on a batch of B
